@@ -7,7 +7,7 @@ synthetic 10-species x 5-genome x 5 Mbp set (BASELINE.json north_star / SURVEY.m
 (steps 3-4), group sets (step 6), across-group union-sum + histogram (steps 7-8).
 Inputs (cleaned sequence text, 1 byte per base) are resident in HBM before the timed region.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 N > 1: one process per GPU; every rank owns its own 10 species (weak scaling); steps 1-6 need
@@ -43,7 +43,30 @@ def parse_args():
     ap.add_argument("--k", type=int, default=31)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-species", type=int, default=0, help="species in the CPU baseline sample (0 = all)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the arrays the last timed step returned as DIR/<name>.npy (float64)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, res, rank, world):
+    """The last timed step's results, as a caller of exp1_run / dist.exp1_step receives them (histogram bins and
+    distinct counts, exact in float64).  Inputs are seeded (khoice_amd/synth.py), so two builds run with the same
+    arguments can be compared file by file.  At N > 1 each rank writes its own arrays under a rank prefix."""
+    arrays = {name: np.asarray(res[name], dtype=np.float64)
+              for name in ("within_hist", "across_hist", "distinct_per_seq") if res.get(name) is not None}
+    total = sum(a.nbytes for a in arrays.values()) * world
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes over the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    prefix = f"rank{rank}_" if world > 1 else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), a)
 
 
 def source_hash() -> str:
@@ -191,6 +214,8 @@ def main():
     dt = time.perf_counter() - t1
     st = eng.stats()          # collects the HIP events recorded on the engine's stream
     eng.profile(False)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, res, rank, world)
 
     distinct_local = int(res["distinct_per_seq"].sum())
     if world > 1:

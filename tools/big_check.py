@@ -6,7 +6,7 @@ form and the key-array form of kh_exp1_run must agree on every histogram and dis
     python tools/big_check.py          (on the GPU box)
 """
 import os, sys, time
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 from khoice_amd import engine as E, synth
 items = synth.species_set(12, 5, 8_000_000)

@@ -1,7 +1,8 @@
 #!/bin/bash
 # Run ON THE GPU BOX: SQ counters of the bench kernels (one pass, 8 SQ slots).  tools/pmc_sq.sh TAG [bench args]
 TAG=${1:-sq}; shift || true
-cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
+cd /tmp && export TMPDIR=/tmp && cd "$ROOT"
 OUT=gpurun_out/pmc_$TAG
 rm -rf $OUT && mkdir -p $OUT
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_INSTS_VALU SQ_INSTS_LDS --kernel-trace --output-format csv -d $OUT/a -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline "$@" > $OUT/a.log 2>&1
