@@ -64,7 +64,8 @@ void kh_debug_set_stamps_skm(u64* p) { (void)hipMemcpyToSymbol(HIP_SYMBOL(g_skm_
 
 size_t kh_skm_scatter_lds_bytes(u32 nb1) {
     const u32 nbk = (nb1 + 3) & ~3u;
-    return flush_lds_bytes<SKM_CAP>(nbk) + (size_t)SKM_CW * 4 + (((size_t)SKM_CW * 2 + 15) & ~(size_t)15) + 64 * 4 + 4 * 32 * 4 + 64;
+    return flush_lds_bytes<SKM_CAP>(nbk) + (size_t)SKM_CW * 4 + (((size_t)SKM_CW * 2 + 15) & ~(size_t)15) + 64 * 4 + 4 * 32 * 4 +
+           (size_t)SKM_NT * 8 + 64;
 }
 size_t kh_skm_regroup_lds_bytes(u32 S) { return flush_lds_bytes<SKM_RG_CAP>((S + 3) & ~3u) + (size_t)((S + 3) & ~3u) * 4 + 64; }
 
@@ -82,6 +83,7 @@ __global__ __launch_bounds__(SKM_NT, KH_TUNE_SKM_SCATTER_WAVES) void k_skm_scatt
     u16* bad16 = reinterpret_cast<u16*>(p);                   p += ((size_t)SKM_CW * 2 + 15) & ~(size_t)15;
     u32* tailh = reinterpret_cast<u32*>(p);                   p += 64 * 4;       // hashes of positions SUB .. SUB + 63
     u32* xch = reinterpret_cast<u32*>(p);                     p += 4 * 32 * 4;   // [wave][j]: hashes of the wave's first thread
+    uint2* lrun = reinterpret_cast<uint2*>(p);                p += (size_t)SKM_NT * 8;   // [thread]: {cont, ext}, read by the record builders
     u32* misc = reinterpret_cast<u32*>(p);                    // [1] valid k-mers of the tile, [2] scratch, [4..] scan scratch
 
     const u32 tid = threadIdx.x, lane = lane_id(), wid = tid >> 6;
@@ -172,16 +174,13 @@ __global__ __launch_bounds__(SKM_NT, KH_TUNE_SKM_SCATTER_WAVES) void k_skm_scatt
             bm |= bm >> ((u32)k - cover);
             vm = ~(u32)bm;
         }
-        // ---- slots; runs of valid positions with one slot become records
+        // ---- runs of valid positions with one minimizer become records
         // (the hash is a bijection: equal minimizer hashes = one minimizer = one slot; the slot itself is
-        // worked out once per record)
-        u32 sl[SKM_PPT];
+        // worked out once per record, by the thread that builds it)
         u32 cont = 0;
 #pragma unroll
-        for (int j = 0; j < (int)SKM_PPT; ++j) {
-            sl[j] = cur[j];
-            if (j && cur[j] == cur[j - 1]) cont |= 1u << j;
-        }
+        for (int j = 1; j < (int)SKM_PPT; ++j)
+            if (cur[j] == cur[j - 1]) cont |= 1u << j;
         cont &= vm & (vm << 1);
         // A run may go on into the NEXT thread of the wave (not past the wave's 2048 positions, not over more than
         // one boundary, not beyond nmax k-mers): then its record belongs to the thread it starts in, and the next
@@ -195,18 +194,29 @@ __global__ __launch_bounds__(SKM_NT, KH_TUNE_SKM_SCATTER_WAVES) void k_skm_scatt
         const bool merge_in = lane != 0 && p_tr != 0 && (vm & 1u) && p_min == cur[0] && p_tr + lead <= nmax;
         const u32 ext = next_lane(merge_in ? lead : 0u, 0u);   // k-mers of the next thread that join my last run
         const u32 starts = (vm & ~cont) & ~(merge_in ? 1u : 0u);
-        auto run_len = [&](u32 s) -> u32 {
-            const u32 len = 1u + (u32)__builtin_ctzll(~((u64)cont >> (s + 1)));
-            return s + len == SKM_PPT ? len + ext : len;
+        auto run_len = [&](u32 c, u32 e, u32 s) -> u32 {
+            const u32 len = 1u + (u32)__builtin_ctzll(~((u64)c >> (s + 1)));
+            return s + len == SKM_PPT ? len + e : len;
         };
-        u32 nrec = 0;
+        lrun[tid] = make_uint2(cont, ext);
+        // One record per start, unless a run is longer than nmax k-mers, i.e. cont holds nmax consecutive ones.
+        // (A run joined by the next thread is never cut: the join asks for tr + lead <= nmax.)  Such threads
+        // ("split") count and describe their records one start at a time; they are rare (tandem repeats).
+        bool split;
         {
+            u32 y = cont, c = 1;
+            while (2 * c <= nmax) { y &= y >> c; c <<= 1; }
+            split = (y & (y >> (nmax - c))) != 0u;
+        }
+        const bool any_split = __ballot(split) != 0;   // uniform
+        u32 nrec = (u32)__popc(starts);
+        if (any_split && split) {
+            nrec = 0;
             u32 st = starts;
             while (st) {
                 const u32 s = (u32)__builtin_ctz(st);
                 st &= st - 1;
-                const u32 len = run_len(s);
-                nrec += (len + nmax - 1) / nmax;
+                nrec += (run_len(cont, ext, s) + nmax - 1) / nmax;
             }
         }
         {   // valid k-mer instances of the tile
@@ -215,9 +225,12 @@ __global__ __launch_bounds__(SKM_NT, KH_TUNE_SKM_SCATTER_WAVES) void k_skm_scatt
         }
         if (stamp) SKM_STAMP(3);
         // ---- append to the staging array; a full array is flushed (a prefix of the threads fits).
-        // (Measured and not kept: descriptors first, then records built by all threads evenly — the same
-        // 0.77 ms, more registers.)
+        // Two steps: every thread writes one descriptor {thread, start, n or 0, minimizer} into the first 8 bytes of
+        // the staging entry each of its records will occupy; then the wave's records (contiguous) are built by its
+        // 64 lanes in turn, each from the sub-tile's code words in LDS, and overwrite their descriptors.  The
+        // divergent per-thread loop over starts it replaces ran as often as the busiest lane of the wave.
         if (stamp) SKM_STAMP(4);
+        uint2* const dsc = reinterpret_cast<uint2*>(L.stage);   // descriptor of staging entry i: dsc[2 * i]
         bool done = false, first_round = true;
         while (true) {
             const u32 mine = done ? 0u : nrec;
@@ -232,36 +245,68 @@ __global__ __launch_bounds__(SKM_NT, KH_TUNE_SKM_SCATTER_WAVES) void k_skm_scatt
             }
             if (first_round) { tile_recs += total; first_round = false; }
             const bool fits = staged + excl + mine <= SKM_CAP;
+            const bool wrote = !done && fits;
             if (stamp) SKM_STAMP(9);
-            if (!done && fits) {
-                u32 at = staged + excl;
-                u32 st = starts;
-                while (st) {
-                    const u32 s = (u32)__builtin_ctz(st);
-                    st &= st - 1;
-                    u32 len = run_len(s);
-                    const u32 slot = slot_of(pick32(sl, s), nslots);
-                    const u32 coarse = (u32)(((u64)slot * smagic) >> 40), fine = slot - coarse * S;
-                    for (u32 s2 = s; len; ) {
-                        const u32 n = len < nmax ? len : nmax;
-                        const u64 w0 = ((u64)cw[1] << 32) | cw[0], w1 = ((u64)cw[3] << 32) | cw[2], w2 = ((u64)cw[5] << 32) | cw[4];
-                        const u32 sh = 2 * s2;
-                        u64 rlo = sh ? (w0 >> sh) | ((w1 << 1) << (63 - sh)) : w0;
-                        u64 rhi = sh ? (w1 >> sh) | ((w2 << 1) << (63 - sh)) : w1;
-                        const u32 bits = 2 * (n + (u32)k - 1);
-                        if (bits < 64) { rlo &= (1ull << bits) - 1ull; rhi = 0; }
-                        else rhi &= kh_mask((int)bits - 64);
-                        rhi |= ((u64)fine << 44) | ((u64)rtag << 53) | ((u64)n << 59);
-                        L.stage[at] = make_uint4((u32)rlo, (u32)(rlo >> 32), (u32)rhi, (u32)(rhi >> 32));
-                        L.sid[at] = (u16)coarse;
-                        atomicAdd(&L.bcnt[coarse], 1u);
-                        ++at;
-                        s2 += n;
-                        len -= n;
+            if (wrote) {
+                const u32 at = staged + excl;
+                if (!split) {   // predicated compaction over the 32 positions: no run-time register index
+                    u32 sv = starts, tb = tid << 5;
+                    asm volatile("" : "+v"(sv), "+v"(tb));   // (keeps 32 ranks / 32 tags from being hoisted out of the loops as live registers)
+#pragma unroll
+                    for (int j = 0; j < (int)SKM_PPT; ++j)
+                        if (sv & (1u << j))
+                            dsc[2 * (at + (u32)__popc(sv & ((1u << j) - 1u)))] = make_uint2(tb | (u32)j, cur[j]);
+                } else {
+                    u32 sl[SKM_PPT];
+#pragma unroll
+                    for (int j = 0; j < (int)SKM_PPT; ++j) sl[j] = cur[j];
+                    u32 a = at, st = starts;
+                    while (st) {
+                        const u32 s = (u32)__builtin_ctz(st);
+                        st &= st - 1;
+                        const u32 minv = pick32(sl, s);
+                        for (u32 s2 = s, len = run_len(cont, ext, s); len; ) {
+                            const u32 n = len < nmax ? len : nmax;
+                            dsc[2 * a++] = make_uint2((n << 16) | (tid << 5) | s2, minv);
+                            s2 += n;
+                            len -= n;
+                        }
                     }
                 }
-                done = true;
             }
+            // The lanes that wrote are consecutive, and those before them in the wave wrote in an earlier round
+            // (mine = 0 now): the wave's new records are staging entries base .. base + cnt - 1.
+            const u64 wm = __ballot(wrote);
+            if (wm) {   // uniform
+                const u32 base = staged + (u32)__builtin_amdgcn_readlane((int)excl, 0);
+                const u32 cnt = (u32)__builtin_amdgcn_readlane((int)incl, 63 - __builtin_clzll(wm));
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+                for (u32 r = lane; r < cnt; r += KH_WAVE) {
+                    const u32 at = base + r;
+                    const uint2 d = dsc[2 * at];
+                    const u32 src = (d.x >> 5) & (SKM_NT - 1), s = d.x & 31u;
+                    const uint2 li = lrun[src];
+                    const u32 n = (d.x >> 16) ? (d.x >> 16) : run_len(li.x, li.y, s);
+                    const u32 slot = slot_of(d.y, nslots);
+                    const u32 coarse = (u32)(((u64)slot * smagic) >> 40), fine = slot - coarse * S;
+                    // bases src * 32 + s .. + n + k - 2 (at most 31 + 54 < 96: inside the thread's window)
+                    const u32 bp = src * SKM_PPT + s, sh = 2 * (bp & 15u);
+                    const u32* cq = code + (bp >> 4);
+                    const u32 c0 = cq[0], c1 = cq[1], c2 = cq[2], c3 = cq[3], c4 = cq[4];
+                    const int bits = 2 * ((int)n + k - 1);   // 2k .. 108
+                    auto keep = [](u32 x, int b) -> u32 { return b >= 32 ? x : (b <= 0 ? 0u : x & ((1u << b) - 1u)); };
+                    const u32 x0 = __builtin_amdgcn_alignbit(c1, c0, sh);
+                    const u32 x1 = keep(__builtin_amdgcn_alignbit(c2, c1, sh), bits - 32);
+                    const u32 x2 = keep(__builtin_amdgcn_alignbit(c3, c2, sh), bits - 64);
+                    const u32 x3 = keep(__builtin_amdgcn_alignbit(c4, c3, sh), bits - 96) | (fine << 12) | (rtag << 21) | (n << 27);
+                    L.stage[at] = make_uint4(x0, x1, x2, x3);
+                    L.sid[at] = (u16)coarse;
+                    atomicAdd(&L.bcnt[coarse], 1u);
+                }
+            }
+            if (wrote) done = true;
             // records appended in this round: those of the fitting prefix of threads
             if (stamp) SKM_STAMP(5);
             const u32 room = SKM_CAP - staged;
