@@ -128,6 +128,18 @@ struct Tmp {
         if (!(tmp).b) return kh_fail(KH_E_NOMEM, "device allocation of %zu bytes failed", \
                                      (size_t)(bytes));                                    \
     } while (0)
+// scoped pinned host staging (kh_ctx::pin_alloc / pin_release)
+struct Pinned {
+    kh_ctx* c;
+    void* p = nullptr;
+    size_t n = 0;
+    ~Pinned() { if (p) c->pin_release(p, n); }
+};
+#define PIN_ALLOC(pin, bytes)                                                               \
+    do {                                                                                    \
+        (pin).p = (pin).c->pin_alloc(bytes, &(pin).n);                                      \
+        if (!(pin).p) return kh_fail(KH_E_NOMEM, "pinned host allocation failed");         \
+    } while (0)
 
 void* kh_ctx::pin_alloc(size_t bytes, size_t* got) {
     bytes = (bytes + 4095) & ~(size_t)4095;
@@ -543,17 +555,13 @@ static int build_once(kh_ctx* c, int nseq, const uint8_t* const* seqs, const uin
     // Start order of pass C (KhBucketWork): buckets of up to 64 consecutive segments are
     // interleaved (bucket 0 of each, bucket 1 of each, ...), every segment writes into its own
     // output region [out_base, out_base + npos) and runs its own look-back chain.
-    struct Pin {
-        kh_ctx* c; void* p = nullptr; size_t bytes = 0;
-        ~Pin() { if (p) c->pin_release(p, bytes); }
-    } plan_pin{c};
+    Pinned plan_pin{c};
     // the launch sequence's small tables — output bases, start ranks, segments, tiles — travel in ONE upload
     // (three separate copies, two of them from pageable vectors, were a sixth of a single-genome build)
     const size_t up_rank = 8 * (size_t)nseq, up_segs = (up_rank + 4 * (size_t)nb_total + 7) & ~(size_t)7,
                  up_tiles = up_segs + sizeof(KhSeg) * (size_t)nseq,
                  up_bytes = up_tiles + sizeof(KhTile) * (size_t)std::max<u32>(1, ntiles);
-    plan_pin.p = c->pin_alloc(up_bytes, &plan_pin.bytes);
-    if (!plan_pin.p) return kh_fail(KH_E_NOMEM, "pinned host allocation failed");
+    PIN_ALLOC(plan_pin, up_bytes);
     u64* h_out_base = static_cast<u64*>(plan_pin.p);
     u32* h_rank = reinterpret_cast<u32*>(h_out_base + nseq);
     memcpy(static_cast<u8*>(plan_pin.p) + up_segs, segs.data(), sizeof(KhSeg) * (size_t)nseq);
@@ -653,16 +661,15 @@ static int build_once(kh_ctx* c, int nseq, const uint8_t* const* seqs, const uin
         buf_ref(okeys); grid->okeys = okeys;
         buf_ref(d_bstart.b); grid->bstart = d_bstart.b;
         buf_ref(d_lb.b); grid->lb = d_lb.b;
-        grid->pin = plan_pin.p; grid->pin_bytes = plan_pin.bytes;
+        grid->pin = plan_pin.p; grid->pin_bytes = plan_pin.n;
         plan_pin.p = nullptr;
         return KH_OK;
     }
 
     // ---- read back set boundaries
     if (g_trace) g_t_build_submitted = now_ms();
-    Pin pin{c};
-    pin.p = c->pin_alloc(8 * (size_t)nb_total + 64 + 8, &pin.bytes);
-    if (!pin.p) return kh_fail(KH_E_NOMEM, "pinned host allocation failed");
+    Pinned pin{c};
+    PIN_ALLOC(pin, 8 * (size_t)nb_total + 64 + 8);
     u64* desc = static_cast<u64*>(pin.p);
     u64& nvalid = desc[(size_t)nb_total + 8];
     HIPCHK(hipMemcpyAsync(desc, d_lb.b->p, 8 * (u64)nb_total + 64, hipMemcpyDeviceToHost, st));
@@ -896,7 +903,7 @@ static int setop_bounds(SetopJob& j) {
 }
 
 // slot bounds of several planned operations (same k) in ONE launch
-static int setop_bounds_batch(kh_ctx* c, std::vector<SetopJob>& jobs, Tmp& d_jobs, void** pin, size_t* pin_bytes) {
+static int setop_bounds_batch(kh_ctx* c, std::vector<SetopJob>& jobs, Tmp& d_jobs, Pinned& pin) {
     std::vector<KhBoundsJob> hb;
     u64 max_threads = 0;
     int W = 1, k = 0;
@@ -908,11 +915,10 @@ static int setop_bounds_batch(kh_ctx* c, std::vector<SetopJob>& jobs, Tmp& d_job
         k = j.k;
     }
     if (hb.empty()) return KH_OK;
-    *pin = c->pin_alloc(sizeof(KhBoundsJob) * hb.size(), pin_bytes);
-    if (!*pin) return kh_fail(KH_E_NOMEM, "pinned host allocation failed");
-    memcpy(*pin, hb.data(), sizeof(KhBoundsJob) * hb.size());
+    PIN_ALLOC(pin, sizeof(KhBoundsJob) * hb.size());
+    memcpy(pin.p, hb.data(), sizeof(KhBoundsJob) * hb.size());
     TMP_ALLOC(d_jobs, c, sizeof(KhBoundsJob) * hb.size());
-    HIPCHK(hipMemcpyAsync(d_jobs.b->p, *pin, sizeof(KhBoundsJob) * hb.size(), hipMemcpyHostToDevice, c->st));
+    HIPCHK(hipMemcpyAsync(d_jobs.b->p, pin.p, sizeof(KhBoundsJob) * hb.size(), hipMemcpyHostToDevice, c->st));
     c->prof_begin(KC_RANGE_BOUNDS);
     kh_launch_range_bounds_batch(W, d_jobs.as<KhBoundsJob>(), (u32)hb.size(), max_threads, k, c->st);
     c->prof_end();
@@ -1476,18 +1482,17 @@ extern "C" int kh_sets_partition_bounds(kh_ctx* c, const kh_set* const* sets, in
 // its genomes are built in sub-waves, each summed into a running union that carries counters
 // (no saturation until the end), so the memory in flight is one sub-wave + the union.  The
 // final pass applies `cs` and takes the histogram.  Same result as the one-wave path.
+struct SetsGuard {
+    std::vector<kh_set*>& v;
+    ~SetsGuard() { for (auto* s : v) kh_set_free(s); }
+};
 static int group_union_incremental(kh_ctx* c, const std::vector<int>& members, const uint8_t* const* seqs,
                                    const uint64_t* lens, int on_device, int k, u32 cs, u64 budget,
                                    uint64_t* hist, u32 hist_len, uint64_t* distinct_per_seq,
                                    kh_set** out_union) {
     kh_set* running = nullptr;
     std::vector<kh_set*> wsets;
-    auto cleanup = [&]() {
-        for (auto* s : wsets) kh_set_free(s);
-        wsets.clear();
-        kh_set_free(running);
-        running = nullptr;
-    };
+    SetsGuard free_wsets{wsets};
     size_t i0 = 0;
     while (i0 < members.size()) {
         size_t i1 = i0;
@@ -1501,7 +1506,7 @@ static int group_union_incremental(kh_ctx* c, const std::vector<int>& members, c
         for (size_t j = i0; j < i1; ++j) { wseqs[j - i0] = seqs[members[j]]; wlens[j - i0] = lens[members[j]]; }
         int r = kh_build_batch(c, (int)(i1 - i0), wseqs.data(), wlens.data(), on_device, k, 1, KH_NO_MAX,
                                KH_KMC_DEFAULT_CS, 0, wsets.data());
-        if (r != KH_OK) { cleanup(); return r; }
+        if (r != KH_OK) { kh_set_free(running); return r; }
         std::vector<const kh_set*> in;
         if (running) in.push_back(running);
         for (size_t j = i0; j < i1; ++j) {
@@ -1510,7 +1515,7 @@ static int group_union_incremental(kh_ctx* c, const std::vector<int>& members, c
         }
         kh_set* next = nullptr;
         r = run_setop(c, in, KH_OP_UNION, KH_OC_SUM, 0x7fffffffu, &next, nullptr, 0);
-        if (r != KH_OK) { cleanup(); return r; }
+        if (r != KH_OK) { kh_set_free(running); return r; }
         for (auto* s : wsets) kh_set_free(s);
         wsets.clear();
         kh_set_free(running);
@@ -1518,11 +1523,90 @@ static int group_union_incremental(kh_ctx* c, const std::vector<int>& members, c
         i0 = i1;
     }
     std::vector<const kh_set*> in{running};
-    int r = run_setop(c, in, KH_OP_UNION, KH_OC_SUM, cs, out_union, hist, hist_len);
-    cleanup();
+    const int r = run_setop(c, in, KH_OP_UNION, KH_OC_SUM, cs, out_union, hist, hist_len);
+    kh_set_free(running);
     return r;
 }
 
+struct Exp1In {   // the arguments of kh_exp1_run that every form reads
+    int nseq; const uint8_t* const* seqs; const uint64_t* lens; int on_device;
+    const int* group_of; int ngroups, k; u32 cs, hist_len;
+};
+// The operands of a tagged union (exp1_skm, exp1_fused) in group-major order: the genomes of a group are consecutive
+// bits of the mask.  Bins: per group one per count of its operands, then one per count of groups (across).  by_group:
+// the operands are the GROUPS (every record carries its genome's group number): only the across-group histogram comes
+// out — the second pass of a run over more than 64 genomes, whose batches have answered the within-group questions.
+struct TagLayout {
+    int nseq = 0, ngroups = 0;
+    bool by_group = false;
+    std::vector<int> gsize, gstart, perm;   // perm[i]: the caller's sequence that is operand i
+    std::vector<u32> bin0;                  // first bin of a group
+    u32 abase = 0, nbins = 0;               // first across-group bin, bins in all
+    u32 fan = 1;                            // genomes of the largest group
+    // [64] ginfo words; by_group: [nseq] the tag (group) of every operand
+    void words(u32* h_ginfo, u8* h_tags, const int* group_of) const {
+        memset(h_ginfo, 0, 256);
+        if (by_group) {
+            for (int g = 0; g < ngroups; ++g) h_ginfo[g] = (u32)g | (1u << 8) | (bin0[g] << 16);
+            for (int i = 0; i < nseq; ++i) h_tags[i] = (u8)group_of[perm[i]];
+        } else {
+            for (int g = 0; g < ngroups; ++g)
+                for (int j = 0; j < gsize[g]; ++j)
+                    h_ginfo[gstart[g] + j] = (u32)gstart[g] | ((u32)gsize[g] << 8) | (bin0[g] << 16);
+        }
+    }
+    void add_bins(std::vector<u64>& bins, const u64* h_hist, u32 reps) const {   // the kernels' per-workgroup copies
+        for (u32 r = 0; r < reps; ++r)
+            for (u32 b = 0; b < nbins; ++b) bins[b] += h_hist[(size_t)r * nbins + b];
+    }
+    void fold(kh_ctx* c, const std::vector<u64>& bins, uint64_t* within_hist, uint64_t* across_hist, u32 hist_len) const {
+        if (within_hist && !by_group) {
+            memset(within_hist, 0, 8 * (size_t)ngroups * hist_len);
+            for (int g = 0; g < ngroups; ++g)
+                for (int cnt = 1; cnt <= gsize[g]; ++cnt)
+                    within_hist[(size_t)g * hist_len + std::min<u32>((u32)cnt, hist_len - 1)] += bins[bin0[g] + cnt];
+        }
+        u64 across_n = 0;
+        for (int cnt = 1; cnt <= ngroups; ++cnt) across_n += bins[abase + cnt];
+        c->stat.setop_out += across_n;
+        if (across_hist) {
+            memset(across_hist, 0, 8 * (size_t)hist_len);
+            for (int cnt = 1; cnt <= ngroups; ++cnt)
+                across_hist[std::min<u32>((u32)cnt, hist_len - 1)] += bins[abase + cnt];
+        }
+    }
+};
+static int tag_layout(TagLayout* L, int nseq, const int* group_of, int ngroups, bool by_group) {
+    L->nseq = nseq;
+    L->ngroups = ngroups;
+    L->by_group = by_group;
+    L->gsize.assign(ngroups, 0);
+    L->gstart.assign(ngroups + 1, 0);
+    L->perm.resize(nseq);
+    L->bin0.resize(ngroups);
+    for (int i = 0; i < nseq; ++i) L->gsize[group_of[i]]++;
+    for (int g = 0; g < ngroups; ++g) {
+        if (!L->gsize[g]) return kh_fail(KH_E_ARG, "group %d has no sequences", g);
+        L->gstart[g + 1] = L->gstart[g] + L->gsize[g];
+        L->bin0[g] = L->nbins;
+        L->nbins += (by_group ? 1u : (u32)L->gsize[g]) + 1;   // by_group: every operand is a group of its own
+        L->fan = std::max<u32>(L->fan, (u32)L->gsize[g]);
+    }
+    L->abase = L->nbins;
+    L->nbins += (u32)ngroups + 1;
+    std::vector<int> at(L->gstart.begin(), L->gstart.end() - 1);
+    for (int i = 0; i < nseq; ++i) L->perm[at[group_of[i]]++] = i;
+    return KH_OK;
+}
+static u64 kmer_positions(int n, const uint64_t* lens, int k, u64* bases = nullptr) {
+    u64 pos = 0, b = 0;
+    for (int i = 0; i < n; ++i) {
+        pos += lens[i] >= (u64)k ? lens[i] - k + 1 : 0;
+        b += lens[i];
+    }
+    if (bases) *bases = b;
+    return pos;
+}
 // The super-k-mer form of the fused path (kh_skm.hip): bases -> 16-byte records of consecutive k-mers that
 // share their minimizer slot -> two counting-sort levels (coarse bucket, slot) -> one LDS hash set per
 // slot.  Takes what the key-array form below takes when k is in [KH_SKM_MIN_K, KH_SKM_MAX_K], nothing is
@@ -1540,166 +1624,155 @@ static int skm_minimizer_len(int k) {
     const int m15w = k - 15 + 1;                                   // m-mers per k-mer with m = 15
     return (m15w > 1 && ((m15w - 1) & (m15w - 2)) == 0) ? 16 : 15;
 }
-// by_group: the operands of the union are the GROUPS (every record carries its genome's group number): only the
-// across-group histogram comes out — the second pass of a run over more than 64 genomes, whose batches of
-// whole groups have answered the within-group questions.
-// records_only (the exchange form of the multi-GPU step): stop behind the regroup and hand the records by slot out —
-// with force_slots slots, the number all ranks agreed on (slots are a global function of the minimizer).
-struct SkmRecords {
-    u32 force_slots = 0;
-    DevBuf* reg2 = nullptr;     // out: [nslots][cap2] records
-    DevBuf* ws = nullptr;       // out: workspace that holds cur2
-    const u32* cur2 = nullptr;  // out: [nslots] records per slot
-    u32 nslots = 0, cap2 = 0;
-    u64 records = 0;            // out: records written
-    u32 fan_hint = 0;           // in: genomes whose copies of a locus arrive together (tags of ONE group: the sub-batch size)
-    std::vector<u64>* inst = nullptr;   // out (if set): k-mer instances per sequence, in the caller's order
-    bool want_spill = false;    // in: records that did not fit their slot's region are handed out too (else: a failure)
-    DevBuf* spill = nullptr;    // out: [spill_cap] records, then [spill_cap] u32 slots
-    u32 spill_n = 0, spill_cap = 0;
-    ~SkmRecords() { buf_unref(reg2); buf_unref(ws); buf_unref(spill); }
+static bool skm_form_k(int k) {
+    // k = 17 .. 19 on the headline shape: 3.75 / 3.6 / 3.3 ms against 4.4 with key arrays; k = 16 and 15 (windows of 5
+    // or 6 over 11 bases: too many overfull slots; over 12: twice the coarse buckets) 5.2 / 6.7 ms: below 17 the key
+    // arrays stay (KHOICE_SKM_MIN_K: experiments and tests, the kernels take k >= 15)
+    int min_k = KH_SKM_MIN_K;
+    if (const char* e = getenv("KHOICE_SKM_MIN_K")) min_k = std::max(15, atoi(e));
+    if (k < min_k || k > KH_SKM2_MAX_K || getenv("KHOICE_NO_SKM")) return false;
+    return k <= KH_SKM_MAX_K || !getenv("KHOICE_NO_SKM2");   // two-word keys: 32-byte records, kh_skm2.hip
+}
+// records per k-mer: a run of k-mers with one minimizer is (w + 1) / 2 long on average; cuts at the waves' 2048
+// positions, at boundaries a run may not cross (a second thread boundary, nmax) and at invalid bases add
+// a little (measured: 0.120 records per k-mer at w = 16, 0.27 at w = 7)
+static double skm_per_kmer(u32 w) { return 2.0 / (double)(w + 1) + 1.0 / 48.0; }
+// k-mer instances that land in a slot together (the copies of a locus in the `fan` genomes of a group: skm_plan)
+static double skm_clump(u32 w, u32 fan) { return 0.5 * (double)(w + 1) * (double)fan; }
+// a slot's records vary like its instances: sigma / mean = sqrt(clump / mean) (12 % at k = 31 with groups of five,
+// 36 % with ten genomes per group and two-word keys): five sigma, at least 1.7
+static double skm_region_slack(double clump, double mean) { return std::max(1.7, 1.0 + 5.0 * std::sqrt(clump / mean)); }
+// records of one part of the exchange form: the piece's records over nparts, 30 % to spare
+static u64 skm_part_cap(u64 positions, double per_kmer, int nparts) {
+    return ((u64)((double)positions * per_kmer * 1.3 / nparts) + 8192 + 63) & ~63ull;
+}
+struct SkmGeometry {
+    bool two = false;               // two-word keys
+    int m = 0;                      // minimizer length
+    u32 w = 0, nmax = 0;            // m-mers per k-mer, k-mers per record at most
+    u64 positions = 0;              // k-mer positions of the input
+    u32 nslots = 0, S = 0, nb1 = 0; // slots, slots per coarse bucket, coarse buckets
+    u32 cap1 = 0, cap2 = 0;         // records a coarse bucket's / a slot's region holds
+    u32 ugrid = 0;                  // workgroups of the persistent union
 };
-static int exp1_skm(kh_ctx* c, int nseq, const uint8_t* const* seqs, const uint64_t* lens, int on_device,
-                    const int* group_of, int ngroups, int k, u32 cs, uint64_t* within_hist,
-                    uint64_t* across_hist, u32 hist_len, uint64_t* distinct_per_seq, bool* done, bool by_group = false,
-                    SkmRecords* rec_out = nullptr) {
-    *done = false;
-    {
-        // k = 17 .. 19 on the headline shape: 3.75 / 3.6 / 3.3 ms against 4.4 with key arrays; k = 16 and 15 (windows of 5
-        // or 6 over 11 bases: too many overfull slots; over 12: twice the coarse buckets) 5.2 / 6.7 ms: below 17 the key
-        // arrays stay (KHOICE_SKM_MIN_K: experiments and tests, the kernels take k >= 15)
-        int min_k = KH_SKM_MIN_K;
-        if (const char* e = getenv("KHOICE_SKM_MIN_K")) min_k = std::max(15, atoi(e));
-        if (k < min_k || k > KH_SKM2_MAX_K || getenv("KHOICE_NO_SKM")) return KH_OK;
-    }
-    const bool two = k > KH_SKM_MAX_K;   // two-word keys: 32-byte records, kh_skm2.hip
-    if (two && getenv("KHOICE_NO_SKM2")) return KH_OK;
-    if ((!by_group && nseq > KH_TAG_MAX_OPS) || ngroups > KH_TAG_MAX_OPS) return KH_OK;
-    std::vector<int> gsize(ngroups, 0), gstart(ngroups + 1, 0), perm(nseq);
-    for (int i = 0; i < nseq; ++i) gsize[group_of[i]]++;
-    u32 nbins = 0;
-    std::vector<u32> bin0(ngroups);
-    for (int g = 0; g < ngroups; ++g) {
-        if (!gsize[g]) return kh_fail(KH_E_ARG, "group %d has no sequences", g);
-        gstart[g + 1] = gstart[g] + gsize[g];
-        bin0[g] = nbins;
-        nbins += (by_group ? 1u : (u32)gsize[g]) + 1;   // by_group: every operand is a group of its own
-    }
-    const u32 abase = nbins;
-    nbins += (u32)ngroups + 1;
-    if (nbins > (u32)KH_TAG_MAX_BINS) return KH_OK;
-    {
-        std::vector<int> at(gstart.begin(), gstart.end() - 1);
-        for (int i = 0; i < nseq; ++i) perm[at[group_of[i]]++] = i;
-    }
-    // ---- geometry: minimizer length, slots, regions
-    int m;
-    u32 w, nmax;
-    if (!two) {
-        m = skm_minimizer_len(k);
-        if (const char* e = getenv("KHOICE_SKM_M")) m = std::min(16, std::max(2, atoi(e)));   // experiments
-        if (m >= k) return KH_OK;
-        w = (u32)(k - m + 1);
-        nmax = (u32)std::min(31, 55 - k);
-        if (!kh_skm_supports_w(w)) return KH_OK;
+// The slot geometry for `positions` k-mer positions whose largest group has `fan` genomes; force_slots: the number of
+// slots all ranks agreed on (slots are a global function of the minimizer).  false: the form does not apply.
+static bool skm_plan(int k, u64 positions, u32 fan, u32 force_slots, int cus, SkmGeometry* out) {
+    if (!skm_form_k(k)) return false;
+    SkmGeometry g;
+    g.two = k > KH_SKM_MAX_K;
+    if (!g.two) {
+        g.m = skm_minimizer_len(k);
+        if (const char* e = getenv("KHOICE_SKM_M")) g.m = std::min(16, std::max(2, atoi(e)));   // experiments
+        if (g.m >= k) return false;
+        g.w = (u32)(k - g.m + 1);
+        g.nmax = (u32)std::min(31, 55 - k);
+        if (!kh_skm_supports_w(g.w)) return false;
     } else {   // the scatter exists for every third window width: one of m = 16, 15, 14 fits
-        m = 16;
-        if (const char* e = getenv("KHOICE_SKM2_M")) m = std::min(16, std::max(10, atoi(e)));   // experiments: the first length tried
-        const int m_lo = m - 2;
-        while (m >= m_lo && !kh_skm2_supports_w((u32)(k - m + 1))) --m;
-        if (m < m_lo) return KH_OK;
-        w = (u32)(k - m + 1);
-        nmax = (u32)std::min(63, 118 - k);
+        g.m = 16;
+        while (g.m >= 14 && !kh_skm2_supports_w((u32)(k - g.m + 1))) --g.m;
+        if (g.m < 14) return false;
+        g.w = (u32)(k - g.m + 1);
+        g.nmax = (u32)std::min(63, 118 - k);
     }
-    u64 total_pos = 0, bases = 0, seq_bytes = 0;
-    for (int i = 0; i < nseq; ++i) {
-        total_pos += lens[i] >= (u64)k ? lens[i] - k + 1 : 0;
-        bases += lens[i];
-    }
-    if (!total_pos) return KH_OK;
+    if (!positions) return false;
+    g.positions = positions;
     // k-mer instances per slot: the hash set takes T = 4096 (2048 for two-word keys) per round.  The genomes of a
     // group put their copies of a locus in the same slot, a minimizer run at a time: clumps of c = (w + 1) / 2 x
     // (largest group) instances, so sigma = sqrt(mean x c); mean + 2.5 sigma = T  (measured: 2500 / 2900 / 3200 /
     // 3500 / 3800 at k = 31 with groups of five: union 1.96 / 1.81 / 1.75 / 1.80 / 1.94 ms; the rule gives 3180)
-    // entries of the union's hash set (one-word keys): 4096 with 1024 threads (two workgroups per CU) or 2048 with 512
-    // (four per CU, half-size slots)
-    u32 table = 4096;
-    if (const char* e = getenv("KHOICE_SKM_TABLE")) table = atoi(e) == 2048 ? 2048u : (atoi(e) == 2560 ? 2560u : 4096u);
-    u32 mean;
-    double clump = 1.0;   // instances that land in a slot together
-    {
-        u32 fan = 1;
-        for (int g = 0; g < ngroups; ++g) fan = std::max<u32>(fan, (u32)gsize[g]);
-        if (rec_out && rec_out->fan_hint) fan = std::max(fan, rec_out->fan_hint);
-        const double T = two ? (double)kh_skm2_table() : (double)table, cl = 0.5 * (double)(w + 1) * (double)fan;
-        const double r = 0.5 * (-2.5 * std::sqrt(cl) + std::sqrt(6.25 * cl + 4.0 * T));
-        mean = (u32)std::max(256.0, r * r);
-        clump = cl;
-    }
+    const double clump = skm_clump(g.w, fan);
+    const double T = g.two ? (double)kh_skm2_table() : 4096.0;   // (one-word keys: k_skm_union's 4096 entries)
+    const double r = 0.5 * (-2.5 * std::sqrt(clump) + std::sqrt(6.25 * clump + 4.0 * T));
+    u32 mean = (u32)std::max(256.0, r * r);
     if (const char* e = getenv("KHOICE_SKM_MEAN")) mean = std::max<u32>(64, (u32)strtoul(e, nullptr, 10));
-    // records: a run of k-mers with one minimizer is (w + 1) / 2 long on average; cuts at the waves' 2048
-    // positions, at boundaries a run may not cross (a second thread boundary, nmax) and at invalid bases add
-    // a little (measured: 0.120 records per k-mer at w = 16, 0.27 at w = 7)
-    const double per_kmer = 2.0 / (double)(w + 1) + 1.0 / 48.0;
-    // a slot's records vary like its instances: sigma / mean = sqrt(clump / mean) (12 % at k = 31 with groups of five,
-    // 36 % with ten genomes per group and two-word keys): five sigma, at least 1.7
+    const double per_kmer = skm_per_kmer(g.w);
     double slack1 = 1.25, slack2 = 1.7;
-    const u32 max_cap2 = two ? kh_skm2_max_cap2() : kh_skm_union_max_cap2(table);
+    const u32 max_cap2 = g.two ? kh_skm2_max_cap2() : kh_skm_union_max_cap2();
     for (int it = 0; it < 8; ++it) {   // short windows (k = 20 .. 22: 3.5 k-mers per record): fewer instances per slot so that its records fit
-        slack2 = std::max(1.7, 1.0 + 5.0 * std::sqrt(clump / (double)mean));
+        slack2 = skm_region_slack(clump, (double)mean);
         const double c2 = (double)mean * per_kmer * slack2 + 96 + 16;
         if (c2 <= (double)max_cap2 || mean <= 256) break;
         mean = std::max<u32>(256, (u32)((double)mean * (double)max_cap2 / c2 * 0.98));
     }
-    u64 nslots64 = rec_out && rec_out->force_slots ? rec_out->force_slots : std::max<u64>(1, (total_pos + mean - 1) / mean);
+    u64 nslots64 = force_slots ? force_slots : std::max<u64>(1, (positions + mean - 1) / mean);
     // One-word keys a little above 256 x 512 slots (short windows on the headline shape: k = 20): 512 coarse buckets
     // double the scatter's cursors and LDS (k = 20: scatter 2.3 ms against 1.0 at k = 21).  Since a slot's region may
     // overflow (side list, k_skm_big) its slack can be cut instead: stay at 256 x 512 slots with slack down to 1.4.
-    if (!two && !(rec_out && rec_out->force_slots) && nslots64 > (u64)KH_SKM_MAX_COARSE * KH_SKM_MAX_FINE) {
-        const u64 lim = (u64)KH_SKM_MAX_COARSE * KH_SKM_MAX_FINE;
-        const double per_slot = (double)total_pos * per_kmer / (double)lim;
+    // Two-word keys a little above 512 x 1024 slots (configs[2] at k = 41, the pass by group over 500 M positions):
+    // the same cut, up to what the union's table takes in one go on average.
+    const u64 lim = g.two ? (u64)KH_SKM2_MAX_COARSE * KH_SKM2_MAX_FINE : (u64)KH_SKM_MAX_COARSE * KH_SKM_MAX_FINE;
+    if (!force_slots && nslots64 > lim) {
+        const double per_slot = (double)positions * per_kmer / (double)lim;
         const double s2 = ((double)max_cap2 - 112.0) / per_slot;
-        double s2_min = 1.4;
-        if (const char* e = getenv("KHOICE_SKM_MIN_SLACK")) s2_min = std::max(1.0, atof(e));   // experiments
-        if (s2 >= s2_min) { nslots64 = lim; slack2 = std::min(slack2, s2); }
-    }
-    // two-word keys a little above 512 x 1024 slots (configs[2] at k = 41, the pass by group over 500 M positions):
-    // the same cut, up to what the union's table takes in one go on average
-    if (two && !(rec_out && rec_out->force_slots) && nslots64 > (u64)KH_SKM2_MAX_COARSE * KH_SKM2_MAX_FINE) {
-        const u64 lim = (u64)KH_SKM2_MAX_COARSE * KH_SKM2_MAX_FINE;
-        const double per_slot = (double)total_pos * per_kmer / (double)lim;
-        const double s2 = ((double)max_cap2 - 112.0) / per_slot;
-        if (s2 >= 1.4 && (double)total_pos / (double)lim <= 0.75 * (double)kh_skm2_table()) { nslots64 = lim; slack2 = std::min(slack2, s2); }
+        if (s2 >= 1.4 && (!g.two || (double)positions / (double)lim <= 0.75 * (double)kh_skm2_table())) {
+            nslots64 = lim;
+            slack2 = std::min(slack2, s2);
+        }
     }
     // coarse buckets: 256 keep the scatter's runs long; inputs past 256 x 512 slots (> 400 M k-mers) take 512
-    const u32 max_coarse = (two || nslots64 > (u64)KH_SKM_MAX_COARSE * KH_SKM_MAX_FINE) ? KH_SKM2_MAX_COARSE : KH_SKM_MAX_COARSE;
-    if (nslots64 > (u64)max_coarse * (two ? KH_SKM2_MAX_FINE : KH_SKM_MAX_FINE)) return KH_OK;
-    const u32 nslots = (u32)nslots64;
-    const u32 S = std::max<u32>(1, (nslots + max_coarse - 1) / max_coarse);
-    const u32 nb1 = (nslots + S - 1) / S;
-    const double recs = (double)total_pos * per_kmer;
+    const u32 max_coarse = (g.two || nslots64 > (u64)KH_SKM_MAX_COARSE * KH_SKM_MAX_FINE) ? KH_SKM2_MAX_COARSE : KH_SKM_MAX_COARSE;
+    if (nslots64 > (u64)max_coarse * (g.two ? KH_SKM2_MAX_FINE : KH_SKM_MAX_FINE)) return false;
+    g.nslots = (u32)nslots64;
+    g.S = std::max<u32>(1, (g.nslots + max_coarse - 1) / max_coarse);
+    g.nb1 = (g.nslots + g.S - 1) / g.S;
+    const double recs = (double)positions * per_kmer;
     if (const char* e = getenv("KHOICE_SKM_SLACK")) slack1 = slack2 = std::max(0.01, atof(e));   // below 1: tests of the overflow fall-back
-    const u64 cap1_64 = ((u64)(recs / nb1 * slack1) + 2048 + 63) & ~63ull;
-    u64 cap2_64 = ((u64)(recs / nslots * slack2) + 96 + 15) & ~15ull;
-    if (cap2_64 > max_cap2 && !(rec_out && rec_out->force_slots)) {
+    const u64 cap1_64 = ((u64)(recs / g.nb1 * slack1) + 2048 + 63) & ~63ull;
+    u64 cap2_64 = ((u64)(recs / g.nslots * slack2) + 96 + 15) & ~15ull;
+    if (cap2_64 > max_cap2 && !force_slots) {
         // Large groups: the copies of a locus (one record per genome of the group) arrive in a slot together, so the
         // five-sigma region is larger than the union takes.  The region is cut to what it takes and the slots with a
         // locus too many go the side-list way (k_skm_big); only when there are more of those than the side list
         // holds is the call given to the key arrays.  (Models of how many there will be — loci per slot Poisson, the
         // group's genomes as one clump — were off by 10 x in both directions on synthetic sets: it is tried.)
-        u32 fan = 1;
-        for (int g = 0; g < ngroups; ++g) fan = std::max<u32>(fan, (u32)gsize[g]);
-        if ((double)fan + recs / (double)nslots <= (double)max_cap2 - 112.0) cap2_64 = max_cap2 & ~15u;
+        if ((double)fan + recs / (double)g.nslots <= (double)max_cap2 - 112.0) cap2_64 = max_cap2 & ~15u;
     }
-    if (cap2_64 > max_cap2 || cap1_64 > 0x7fffffffull) return KH_OK;
-    const u32 cap1 = (u32)cap1_64, cap2 = (u32)cap2_64;
-    const size_t rec_bytes = two ? 32 : 16;
-    const size_t reg1_bytes = rec_bytes * (size_t)nb1 * cap1, reg2_bytes = rec_bytes * (size_t)nslots * cap2;
+    if (cap2_64 > max_cap2 || cap1_64 > 0x7fffffffull) return false;
+    g.cap1 = (u32)cap1_64;
+    g.cap2 = (u32)cap2_64;
+    // the union is persistent (as many workgroups as fit the chip, each with a histogram of its own)
+    g.ugrid = std::min<u32>(g.nslots, (g.two ? kh_skm2_union_per_cu() : kh_skm_union_per_cu()) * (u32)std::max(1, cus));
+    *out = g;
+    return true;
+}
+// A pass of the super-k-mer form between the regroup and the union: its device buffers and pinned staging.
+struct SkmStage {
+    TagLayout L;
+    SkmGeometry g;
+    KhSkmJob job;
+    Tmp d_seq, d_ws, d_reg1, d_reg2, d_spill;
+    Pinned pin;
+    u8* h_down = nullptr;           // pinned read-back of the workspace's [hist .. dup], laid out as on the device
+    u32 ntiles = 0;
+    u64 bases = 0;
+    bool staged = false;            // false: the form does not apply (k, operands, geometry, memory)
+    // one-word keys: what a slot's region cannot hold goes to a side list, the slot to a kernel of its own
+    static constexpr u32 spill_cap = 1u << 20, big_cap = 16384u;
+#ifdef KH_STAMPS
+    Tmp d_stamps;
+#endif
+    explicit SkmStage(kh_ctx* c) : pin{c} {}
+};
+// (a) + (b): the geometry, then the input staged, scattered and regrouped by slot
+static int skm_prepare(kh_ctx* c, int nseq, const uint8_t* const* seqs, const uint64_t* lens, int on_device,
+                       const int* group_of, int ngroups, int k, bool by_group, u32 force_slots, u32 fan_hint, SkmStage* s) {
+    TagLayout* L = &s->L;
+    if (!skm_form_k(k)) return KH_OK;
+    if ((!by_group && nseq > KH_TAG_MAX_OPS) || ngroups > KH_TAG_MAX_OPS) return KH_OK;
+    KHCHK(tag_layout(L, nseq, group_of, ngroups, by_group));
+    if (L->nbins > (u32)KH_TAG_MAX_BINS) return KH_OK;
+    const u64 positions = kmer_positions(nseq, lens, k, &s->bases);
+    // (fan_hint: genomes whose copies of a locus arrive together although they are tags of ONE group)
+    if (!skm_plan(k, positions, std::max(L->fan, fan_hint), force_slots, c->cus, &s->g)) return KH_OK;
+    const SkmGeometry& g = s->g;
+    const size_t rec_bytes = g.two ? 32 : 16;
+    const size_t reg1_bytes = rec_bytes * (size_t)g.nb1 * g.cap1, reg2_bytes = rec_bytes * (size_t)g.nslots * g.cap2;
     HIPCHK(hipSetDevice(c->dev));
     {
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess &&
-            reg1_bytes + reg2_bytes + bases + (64u << 20) > free_b + c->pool.cached_bytes)
+            reg1_bytes + reg2_bytes + s->bases + (64u << 20) > free_b + c->pool.cached_bytes)
             return KH_OK;   // the key-range waves of the key-array form handle what does not fit
     }
     hipStream_t st = c->st;
@@ -1708,15 +1781,16 @@ static int exp1_skm(kh_ctx* c, int nseq, const uint8_t* const* seqs, const uint6
     u32 tile_pos = KH_TILE;
     {
         const u64 want_tiles = 8ull * (u64)std::max(1, c->cus);
-        while (tile_pos > (u32)KH_SUBTILE && (total_pos + tile_pos - 1) / tile_pos < want_tiles) tile_pos >>= 1;
+        while (tile_pos > (u32)KH_SUBTILE && (positions + tile_pos - 1) / tile_pos < want_tiles) tile_pos >>= 1;
     }
     std::vector<KhSeg> segs(nseq);
     std::vector<u64> pack_off(nseq);
     std::vector<KhTile> tiles;
+    u64 seq_bytes = 0;
     for (int i = 0; i < nseq; ++i) {
         KhSeg& sg = segs[i];
         memset(&sg, 0, sizeof sg);
-        const u64 len = lens[perm[i]];
+        const u64 len = lens[L->perm[i]];
         pack_off[i] = seq_bytes;
         sg.len = len;
         sg.npos = len >= (u64)k ? len - k + 1 : 0;
@@ -1727,70 +1801,52 @@ static int exp1_skm(kh_ctx* c, int nseq, const uint8_t* const* seqs, const uint6
     }
     seq_bytes += 256;
     const u32 ntiles = (u32)tiles.size();
-    // the union is persistent (as many workgroups as fit the chip, each with a histogram of its own)
-    const u32 ugrid = std::min<u32>(nslots, (two ? kh_skm2_union_per_cu() : kh_skm_union_per_cu(table)) * (u32)std::max(1, c->cus));
-    const u32 reps = ugrid;
-    const size_t hist_words = (size_t)reps * nbins;
+    const u32 reps = g.ugrid;
+    const size_t hist_words = (size_t)reps * L->nbins;
     // workspace: [hist][ctl: 8 u32][inst: nseq u64][dup: 64 u64][cur1: nb1 u32][cur2: nslots u32] (zeroed) [ginfo: 64 u32]
     const size_t off_ctl = 8 * hist_words, off_inst = off_ctl + 32, off_dup = off_inst + 8 * (size_t)nseq,
-                 off_cur1 = off_dup + 8 * 64, off_cur2 = off_cur1 + 4 * (size_t)KH_SKM_CUR1_STRIDE * nb1,
-                 off_ginfo = off_cur2 + 4 * (size_t)((nslots + 3) & ~3u), off_tags = off_ginfo + 256,
+                 off_cur1 = off_dup + 8 * 64, off_cur2 = off_cur1 + 4 * (size_t)KH_SKM_CUR1_STRIDE * g.nb1,
+                 off_ginfo = off_cur2 + 4 * (size_t)((g.nslots + 3) & ~3u), off_tags = off_ginfo + 256,
                  off_segs = off_tags + (((size_t)nseq + 15) & ~(size_t)15), off_tiles = off_segs + sizeof(KhSeg) * nseq,
                  ws_bytes = off_tiles + sizeof(KhTile) * (size_t)std::max<u32>(1, ntiles);   // [ginfo .. tiles]: one upload
-    Tmp d_seq, d_ws, d_reg1, d_reg2, d_spill;
-    // one-word keys: what a slot's region cannot hold goes to a side list, the slot to a kernel of its own
-    const u32 spill_cap = 1u << 20, big_cap = 16384u;
+    const u32 spill_cap = SkmStage::spill_cap;
     bool need_pack = false;
     for (int i = 0; i < nseq; ++i)
-        if (!(on_device && (reinterpret_cast<uintptr_t>(seqs[perm[i]]) & 15) == 0)) need_pack = true;
-    TMP_ALLOC(d_seq, c, need_pack ? seq_bytes : 256);
-    TMP_ALLOC(d_ws, c, ws_bytes);
-    TMP_ALLOC(d_reg1, c, reg1_bytes);
-    TMP_ALLOC(d_reg2, c, reg2_bytes);
-    if (spill_cap) TMP_ALLOC(d_spill, c, (size_t)spill_cap * (rec_bytes + 4) + (size_t)big_cap * 4);
-    struct PinG { kh_ctx* c; void* p = nullptr; size_t n = 0; ~PinG() { if (p) c->pin_release(p, n); } } pin{c};
+        if (!(on_device && (reinterpret_cast<uintptr_t>(seqs[L->perm[i]]) & 15) == 0)) need_pack = true;
+    TMP_ALLOC(s->d_seq, c, need_pack ? seq_bytes : 256);
+    TMP_ALLOC(s->d_ws, c, ws_bytes);
+    TMP_ALLOC(s->d_reg1, c, reg1_bytes);
+    TMP_ALLOC(s->d_reg2, c, reg2_bytes);
+    TMP_ALLOC(s->d_spill, c, (size_t)spill_cap * (rec_bytes + 4) + (size_t)SkmStage::big_cap * 4);
     // pinned staging: [segs][tiles][ginfo] up, [hist .. dup] down
     const size_t up_bytes = ws_bytes - off_ginfo;   // the upload, laid out as on the device
     const size_t down_bytes = off_cur1;
-    pin.p = c->pin_alloc(up_bytes + down_bytes + 64, &pin.n);
-    if (!pin.p) return kh_fail(KH_E_NOMEM, "pinned host allocation failed");
-    u8* h_up = static_cast<u8*>(pin.p);
-    u8* h_down = h_up + ((up_bytes + 63) & ~(size_t)63);
+    PIN_ALLOC(s->pin, up_bytes + down_bytes + 64);
+    u8* h_up = static_cast<u8*>(s->pin.p);
+    s->h_down = h_up + ((up_bytes + 63) & ~(size_t)63);
     c->prof_begin(KC_COPY_IN);
     for (int i = 0; i < nseq; ++i) {
-        const uint8_t* src = seqs[perm[i]];
+        const uint8_t* src = seqs[L->perm[i]];
         if (on_device && (reinterpret_cast<uintptr_t>(src) & 15) == 0) { segs[i].seq = src; continue; }
-        segs[i].seq = d_seq.as<u8>() + pack_off[i];
+        segs[i].seq = s->d_seq.as<u8>() + pack_off[i];
         if (!segs[i].len) continue;
-        HIPCHK(hipMemcpyAsync(d_seq.as<u8>() + pack_off[i], src, segs[i].len,
+        HIPCHK(hipMemcpyAsync(s->d_seq.as<u8>() + pack_off[i], src, segs[i].len,
                               on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
     }
-    u32* h_ginfo = reinterpret_cast<u32*>(h_up);
-    u8* h_tags = h_up + (off_tags - off_ginfo);
-    KhSeg* h_segs = reinterpret_cast<KhSeg*>(h_up + (off_segs - off_ginfo));
-    KhTile* h_tiles = reinterpret_cast<KhTile*>(h_up + (off_tiles - off_ginfo));
-    memcpy(h_segs, segs.data(), sizeof(KhSeg) * nseq);
-    if (ntiles) memcpy(h_tiles, tiles.data(), sizeof(KhTile) * (size_t)ntiles);
-    memset(h_ginfo, 0, 256);
-    if (by_group) {
-        for (int g = 0; g < ngroups; ++g) h_ginfo[g] = (u32)g | (1u << 8) | (bin0[g] << 16);
-        for (int i = 0; i < nseq; ++i) h_tags[i] = (u8)group_of[perm[i]];
-    } else {
-        for (int g = 0; g < ngroups; ++g)
-            for (int j = 0; j < gsize[g]; ++j)
-                h_ginfo[gstart[g] + j] = (u32)gstart[g] | ((u32)gsize[g] << 8) | (bin0[g] << 16);
-    }
-    u8* wsp = d_ws.as<u8>();
+    memcpy(h_up + (off_segs - off_ginfo), segs.data(), sizeof(KhSeg) * nseq);
+    if (ntiles) memcpy(h_up + (off_tiles - off_ginfo), tiles.data(), sizeof(KhTile) * (size_t)ntiles);
+    L->words(reinterpret_cast<u32*>(h_up), h_up + (off_tags - off_ginfo), group_of);
+    u8* wsp = s->d_ws.as<u8>();
     HIPCHK(hipMemsetAsync(wsp, 0, off_ginfo, st));
     HIPCHK(hipMemcpyAsync(wsp + off_ginfo, h_up, up_bytes, hipMemcpyHostToDevice, st));
     c->prof_end();
 
-    KhSkmJob job;
+    KhSkmJob& job = s->job;
     job.seg_tag = by_group ? wsp + off_tags : nullptr;
     job.segs = reinterpret_cast<const KhSeg*>(wsp + off_segs);
     job.tiles = reinterpret_cast<const KhTile*>(wsp + off_tiles);
-    job.reg1 = d_reg1.as<uint4>();
-    job.reg2 = d_reg2.as<uint4>();
+    job.reg1 = s->d_reg1.as<uint4>();
+    job.reg2 = s->d_reg2.as<uint4>();
     job.cur1 = reinterpret_cast<u32*>(wsp + off_cur1);
     job.cur2 = reinterpret_cast<u32*>(wsp + off_cur2);
     job.inst = reinterpret_cast<unsigned long long*>(wsp + off_inst);
@@ -1799,86 +1855,64 @@ static int exp1_skm(kh_ctx* c, int nseq, const uint8_t* const* seqs, const uint6
     job.hist = reinterpret_cast<unsigned long long*>(wsp);
     job.ctl = reinterpret_cast<u32*>(wsp + off_ctl);
     job.tile_pos = tile_pos;
-    job.k = k; job.m = m; job.w = w; job.nmax = nmax;
-    job.nslots = nslots; job.S = S; job.nb1 = nb1; job.cap1 = cap1; job.cap2 = cap2;
-    job.nbins = nbins; job.abase = abase; job.reps = reps; job.nops = by_group ? (u32)ngroups : (u32)nseq;
-    job.table = table;
-    job.spill_rec = spill_cap ? d_spill.as<uint4>() : nullptr;
-    job.spill_slot = spill_cap ? reinterpret_cast<u32*>(d_spill.as<u8>() + (size_t)spill_cap * rec_bytes) : nullptr;
-    job.big_list = spill_cap ? reinterpret_cast<u32*>(d_spill.as<u8>() + (size_t)spill_cap * (rec_bytes + 4)) : nullptr;
+    job.k = k; job.m = g.m; job.w = g.w; job.nmax = g.nmax;
+    job.nslots = g.nslots; job.S = g.S; job.nb1 = g.nb1; job.cap1 = g.cap1; job.cap2 = g.cap2;
+    job.nbins = L->nbins; job.abase = L->abase; job.reps = reps; job.nops = by_group ? (u32)ngroups : (u32)nseq;
+    job.spill_rec = s->d_spill.as<uint4>();
+    job.spill_slot = reinterpret_cast<u32*>(s->d_spill.as<u8>() + (size_t)spill_cap * rec_bytes);
+    job.big_list = reinterpret_cast<u32*>(s->d_spill.as<u8>() + (size_t)spill_cap * (rec_bytes + 4));
     job.spill_cap = spill_cap;
-    job.big_cap = big_cap;
+    job.big_cap = SkmStage::big_cap;
+    s->ntiles = ntiles;
 #ifdef KH_STAMPS
-    Tmp d_stamps;
-    const u64 nst = std::max<u64>(ntiles, nslots);
-    TMP_ALLOC(d_stamps, c, 128 * nst);
-    HIPCHK(hipMemsetAsync(d_stamps.b->p, 0, 128 * nst, st));
-    kh_debug_set_stamps_skm(d_stamps.as<u64>());
+    const u64 nst = std::max<u64>(ntiles, g.nslots);
+    TMP_ALLOC(s->d_stamps, c, 128 * nst);
+    HIPCHK(hipMemsetAsync(s->d_stamps.b->p, 0, 128 * nst, st));
+    kh_debug_set_stamps_skm(s->d_stamps.as<u64>());
 #endif
     c->prof_begin(KC_SKM_SCATTER);
-    if (two) kh_launch_skm2_scatter(job, ntiles, st);
+    if (g.two) kh_launch_skm2_scatter(job, ntiles, st);
     else kh_launch_skm_scatter(job, ntiles, st);
     c->prof_end();
 #ifdef KH_STAMPS
-    report_stamps(c, "skm_scatter (second sub-tile: codes / hashes / minima / slots+count / - / append / barrier / -)", d_stamps.b, ntiles);
-    HIPCHK(hipMemsetAsync(d_stamps.b->p, 0, 128 * nst, st));
+    report_stamps(c, "skm_scatter (second sub-tile: codes / hashes / minima / slots+count / - / append / barrier / -)", s->d_stamps.b, ntiles);
+    HIPCHK(hipMemsetAsync(s->d_stamps.b->p, 0, 128 * nst, st));
     kh_debug_set_stamps_skm(nullptr);
 #endif
     c->prof_begin(KC_SKM_REGROUP);
-    if (two) kh_launch_skm2_regroup(job, st);
+    if (g.two) kh_launch_skm2_regroup(job, st);
     else kh_launch_skm_regroup(job, st);
     c->prof_end();
 #ifdef KH_STAMPS
-    kh_debug_set_stamps_skm(d_stamps.as<u64>());
+    kh_debug_set_stamps_skm(s->d_stamps.as<u64>());
 #endif
-    if (rec_out) {   // the records by slot are what the caller wants
-        HIPCHK(hipGetLastError());
-        u32 h_ctl[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        HIPCHK(hipMemcpyAsync(h_ctl, job.ctl, 32, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        if (getenv("KHOICE_SKM_DEBUG"))
-            fprintf(stderr, "[skm records] k=%d positions=%llu nb1=%u S=%u nslots=%u cap1 %u cap2 %u | records %u errors %u spilled %u\n", k,
-                    (unsigned long long)total_pos, nb1, S, nslots, cap1, cap2, h_ctl[2], h_ctl[0], h_ctl[5]);
-        // (records on the side list: handed out to a caller that asked for them, a failure otherwise)
-        if ((h_ctl[0] & (KH_ERR_CAPACITY | KH_ERR_ORDER)) || (h_ctl[5] && (!rec_out->want_spill || two || h_ctl[5] > spill_cap))) {
-            c->stat.retries++;
-            return KH_OK;
-        }
-        if (h_ctl[5]) {
-            rec_out->spill = d_spill.b; d_spill.b = nullptr;
-            rec_out->spill_n = h_ctl[5];
-            rec_out->spill_cap = spill_cap;
-        }
-        c->stat.skm_records += h_ctl[2];
-        if (rec_out->inst) {
-            std::vector<u64> hi(nseq);
-            HIPCHK(hipMemcpyAsync(hi.data(), job.inst, 8 * (size_t)nseq, hipMemcpyDeviceToHost, st));
-            HIPCHK(hipStreamSynchronize(st));
-            rec_out->inst->assign(nseq, 0);
-            for (int i = 0; i < nseq; ++i) (*rec_out->inst)[perm[i]] = hi[i];
-        }
-        rec_out->records = h_ctl[2];
-        rec_out->reg2 = d_reg2.b; d_reg2.b = nullptr;
-        rec_out->ws = d_ws.b; d_ws.b = nullptr;
-        rec_out->cur2 = job.cur2;
-        rec_out->nslots = nslots;
-        rec_out->cap2 = cap2;
-        *done = true;
-        return KH_OK;
-    }
+    s->staged = true;
+    return KH_OK;
+}
+// (a) + (b) + (c): the union over the staged records (and k_skm_big for the slots it left out), then the read-out
+static int exp1_skm(kh_ctx* c, const Exp1In& in, uint64_t* within_hist, uint64_t* across_hist, uint64_t* distinct_per_seq,
+                    bool* done, bool by_group = false) {
+    *done = false;
+    SkmStage s(c);
+    KHCHK(skm_prepare(c, in.nseq, in.seqs, in.lens, in.on_device, in.group_of, in.ngroups, in.k, by_group, 0, 0, &s));
+    if (!s.staged) return KH_OK;
+    const TagLayout& L = s.L;
+    const SkmGeometry& g = s.g;
+    const KhSkmJob& job = s.job;
+    hipStream_t st = c->st;
     c->prof_begin(KC_SKM_UNION);
-    if (two) kh_launch_skm2_union(job, cs, ugrid, st);
-    else kh_launch_skm_union(job, cs, ugrid, st);
+    if (g.two) kh_launch_skm2_union(job, in.cs, g.ugrid, st);
+    else kh_launch_skm_union(job, in.cs, g.ugrid, st);
     c->prof_end();
     HIPCHK(hipGetLastError());
 #ifdef KH_STAMPS
-    report_stamps(c, "skm_union (scan barrier / owner / expand / insert / barrier / read-out / barrier / flush)", d_stamps.b, nslots);
+    report_stamps(c, "skm_union (scan barrier / owner / expand / insert / barrier / read-out / barrier / flush)", s.d_stamps.b, g.nslots);
     kh_debug_set_stamps_skm(nullptr);
 #endif
     if (getenv("KHOICE_SKM_DEBUG")) {   // diagnostics: how full the regions are
-        std::vector<u32> h1(nb1), h2(nslots);
-        HIPCHK(hipMemcpy2DAsync(h1.data(), 4, job.cur1, 4 * (size_t)KH_SKM_CUR1_STRIDE, 4, nb1, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(h2.data(), job.cur2, 4 * (size_t)nslots, hipMemcpyDeviceToHost, st));
+        std::vector<u32> h1(g.nb1), h2(g.nslots);
+        HIPCHK(hipMemcpy2DAsync(h1.data(), 4, job.cur1, 4 * (size_t)KH_SKM_CUR1_STRIDE, 4, g.nb1, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(h2.data(), job.cur2, 4 * (size_t)g.nslots, hipMemcpyDeviceToHost, st));
         u32 hc[8];
         HIPCHK(hipMemcpyAsync(hc, job.ctl, 32, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
@@ -1888,69 +1922,58 @@ static int exp1_skm(kh_ctx* c, int nseq, const uint8_t* const* seqs, const uint6
         for (u32 v : h2) { t2 += v; m2 = std::max(m2, v); }
         fprintf(stderr, "[skm] k=%d m=%d w=%u nmax=%u positions=%llu records=%llu (%.2f k-mers each) nb1=%u S=%u nslots=%u | "
                         "coarse: mean %.0f max %u cap %u | slot: mean %.1f max %u cap %u | tiles %u x %u | expanded: %u k-mers | errors %u spilled %u overfull slots %u\n",
-                k, m, w, nmax, (unsigned long long)total_pos, (unsigned long long)t1, (double)total_pos / std::max<u64>(1, t1),
-                nb1, S, nslots, (double)t1 / nb1, m1, cap1, (double)t2 / nslots, m2, cap2, ntiles, tile_pos, hc[3], hc[0], hc[5], hc[6]);
+                in.k, g.m, g.w, g.nmax, (unsigned long long)g.positions, (unsigned long long)t1, (double)g.positions / std::max<u64>(1, t1),
+                g.nb1, g.S, g.nslots, (double)t1 / g.nb1, m1, g.cap1, (double)t2 / g.nslots, m2, g.cap2, s.ntiles, job.tile_pos, hc[3], hc[0], hc[5], hc[6]);
     }
+    u8* h_down = s.h_down;
+    u8* wsp = s.d_ws.as<u8>();
+    auto down = [&](const void* d) { return h_down + (static_cast<const u8*>(d) - wsp); };   // the host copy of a workspace field
+    const size_t down_bytes = down(job.cur1) - h_down;
     HIPCHK(hipMemcpyAsync(h_down, wsp, down_bytes, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     const u64* h_hist = reinterpret_cast<const u64*>(h_down);
-    const u32* h_ctl = reinterpret_cast<const u32*>(h_down + off_ctl);
+    const u32* h_ctl = reinterpret_cast<const u32*>(down(job.ctl));
     if (h_ctl[6] && !(h_ctl[0] & (KH_ERR_CAPACITY | KH_ERR_ORDER))) {
         // overfull slots (skewed input: a minimizer shared by far more k-mers than a hash predicts): the union left
         // them out; one workgroup each now, and the read-back again — only these slots are done twice, not the call
-        if (h_ctl[5] > spill_cap || h_ctl[6] > big_cap) { c->stat.retries++; return KH_OK; }   // too many: the key-array form
+        if (h_ctl[5] > SkmStage::spill_cap || h_ctl[6] > SkmStage::big_cap) { c->stat.retries++; return KH_OK; }   // too many: the key-array form
         c->stat.big_slots += h_ctl[6];
         c->prof_begin(KC_SKM_BIG);
-        if (two) kh_launch_skm2_big(job, cs, h_ctl[6], st);
-        else kh_launch_skm_big(job, cs, h_ctl[6], st);
+        if (g.two) kh_launch_skm2_big(job, in.cs, h_ctl[6], st);
+        else kh_launch_skm_big(job, in.cs, h_ctl[6], st);
         c->prof_end();
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(h_down, wsp, down_bytes, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
     }
-    const u64* h_inst = reinterpret_cast<const u64*>(h_down + off_inst);
-    const u64* h_dup = reinterpret_cast<const u64*>(h_down + off_dup);
+    const u64* h_inst = reinterpret_cast<const u64*>(down(job.inst));
+    const u64* h_dup = reinterpret_cast<const u64*>(down(job.dup));
     if (h_ctl[0] & (KH_ERR_CAPACITY | KH_ERR_ORDER)) {
         c->stat.retries++;
         return KH_OK;   // a region or a slot overflowed: the key-array form takes over
     }
     c->stat.skm_records += h_ctl[2];
-    if (!by_group) {
-        c->stat.bases += bases;
-        c->stat.builds += nseq;
+    if (!L.by_group) {
+        c->stat.bases += s.bases;
+        c->stat.builds += L.nseq;
         u64 inst = 0, dsum = 0;
-        for (int i = 0; i < nseq; ++i) {
+        for (int i = 0; i < L.nseq; ++i) {
             const u64 d = h_inst[i] - h_dup[i];
             inst += h_inst[i];
             dsum += d;
-            if (distinct_per_seq) distinct_per_seq[perm[i]] = d;
+            if (distinct_per_seq) distinct_per_seq[L.perm[i]] = d;
         }
         c->stat.kmers += inst;
         c->stat.distinct += dsum;
         c->stat.setop_in += dsum;
     }
     c->stat.setops++;
-    std::vector<u64> bins(nbins, 0);
-    for (u32 r = 0; r < reps; ++r)
-        for (u32 b = 0; b < nbins; ++b) bins[b] += h_hist[(size_t)r * nbins + b];
-    if (within_hist && !by_group) {
-        memset(within_hist, 0, 8 * (size_t)ngroups * hist_len);
-        for (int g = 0; g < ngroups; ++g)
-            for (int cnt = 1; cnt <= gsize[g]; ++cnt)
-                within_hist[(size_t)g * hist_len + std::min<u32>((u32)cnt, hist_len - 1)] += bins[bin0[g] + cnt];
-    }
-    u64 across_n = 0;
-    for (int cnt = 1; cnt <= ngroups; ++cnt) across_n += bins[abase + cnt];
-    c->stat.setop_out += across_n;
-    if (across_hist) {
-        memset(across_hist, 0, 8 * (size_t)hist_len);
-        for (int cnt = 1; cnt <= ngroups; ++cnt)
-            across_hist[std::min<u32>((u32)cnt, hist_len - 1)] += bins[abase + cnt];
-    }
+    std::vector<u64> bins(L.nbins, 0);
+    L.add_bins(bins, h_hist, job.reps);
+    L.fold(c, bins, within_hist, across_hist, in.hist_len);
     *done = true;
     return KH_OK;
 }
-
 // The fused form of steps 1-8 (no per-genome / per-group database is handed out): ONE batched build
 // in grid mode, ONE tagged union over all genomes, ONE host synchronisation.  *done == false on
 // return means "not applicable or a slot overflowed": the caller takes the general path.
@@ -1962,45 +1985,28 @@ static int exp1_fused(kh_ctx* c, int nseq, const uint8_t* const* seqs, const uin
     if (want_scale) *want_scale = 0.0;
     const int W = k <= 32 ? 1 : 2;
     if (nseq > KH_TAG_MAX_OPS || ngroups > KH_TAG_MAX_OPS) return KH_OK;
-    // operands in group-major order: the genomes of a group are consecutive bits of the mask
-    std::vector<int> gsize(ngroups, 0), gstart(ngroups + 1, 0), perm(nseq);
-    for (int i = 0; i < nseq; ++i) gsize[group_of[i]]++;
-    u32 fan = 1, nbins = 0;
-    std::vector<u32> bin0(ngroups);
-    for (int g = 0; g < ngroups; ++g) {
-        if (!gsize[g]) return kh_fail(KH_E_ARG, "group %d has no sequences", g);
-        gstart[g + 1] = gstart[g] + gsize[g];
-        bin0[g] = nbins;
-        nbins += (u32)gsize[g] + 1;
-        fan = std::max<u32>(fan, (u32)gsize[g]);
-    }
-    const u32 abase = nbins;
-    nbins += (u32)ngroups + 1;
-    if (nbins > (u32)KH_TAG_MAX_BINS) return KH_OK;
-    {
-        std::vector<int> at(gstart.begin(), gstart.end() - 1);
-        for (int i = 0; i < nseq; ++i) perm[at[group_of[i]]++] = i;
-    }
+    TagLayout L;
+    KHCHK(tag_layout(&L, nseq, group_of, ngroups, false));
+    if (L.nbins > (u32)KH_TAG_MAX_BINS) return KH_OK;
     const u32 mean = k <= 32 ? KH_BUCKET_MEAN_W1 : KH_BUCKET_MEAN_W2;
     std::vector<const uint8_t*> pseq(nseq);
     std::vector<uint64_t> plen(nseq);
     for (int i = 0; i < nseq; ++i) {
-        pseq[i] = seqs[perm[i]];
-        plen[i] = lens[perm[i]];
+        pseq[i] = seqs[L.perm[i]];
+        plen[i] = lens[L.perm[i]];
         // longer than one segment's bucket table: the general path cuts such sequences into chunks
-        if (lens[perm[i]] >= (u64)k && lens[perm[i]] - k + 1 > (u64)(KH_MAX_BUCKETS_PER_SEG / 4) * mean) return KH_OK;
+        if (lens[L.perm[i]] >= (u64)k && lens[L.perm[i]] - k + 1 > (u64)(KH_MAX_BUCKETS_PER_SEG / 4) * mean) return KH_OK;
     }
     HIPCHK(hipSetDevice(c->dev));
     hipStream_t st = c->st;
 
-    std::vector<u64> bins(nbins, 0), dist_acc(nseq, 0);
+    std::vector<u64> bins(L.nbins, 0), dist_acc(nseq, 0);
     const bool emit = across_set != nullptr;
     std::vector<kh_set*> wave_sets;   // emitted across-group sets, one per wave (disjoint, ascending key ranges)
-    auto drop_sets = [&]() { for (auto* s : wave_sets) kh_set_free(s); wave_sets.clear(); };
-    struct SetsGuard { std::vector<kh_set*>& v; ~SetsGuard() { for (auto* s : v) kh_set_free(s); } } sets_guard{wave_sets};
+    SetsGuard sets_guard{wave_sets};
     for (u32 wave = 0; wave < nwaves; ++wave) {
     GridBuild gb;
-    gb.fan = std::max(fan, fan_hint);   // (fan_hint: genomes that are related although every one is a group of its own here)
+    gb.fan = std::max(L.fan, fan_hint);   // (fan_hint: genomes that are related although every one is a group of its own here)
     gb.wave = wave;
     gb.nwaves = nwaves;
     gb.s_scale = s_scale;
@@ -2011,7 +2017,7 @@ static int exp1_fused(kh_ctx* c, int nseq, const uint8_t* const* seqs, const uin
     {
         const int br = build_once(c, nseq, pseq.data(), plen.data(), on_device, k, 1, KH_NO_MAX, KH_KMC_DEFAULT_CS, 0, mean,
                                   nullptr, &cap_hit, &again, &gb);
-        if (br != KH_OK) { drop_sets(); return br; }
+        if (br != KH_OK) return br;
     }
 
     // ---- tagged union queued behind the build
@@ -2019,26 +2025,21 @@ static int exp1_fused(kh_ctx* c, int nseq, const uint8_t* const* seqs, const uin
     const u32 grid = nslots;
     const u32 reps = std::min<u32>(256, std::max<u32>(1, grid));
     // workspace: [hist: reps x nbins u64][ctl: 8 u32][out_n u64][ginfo: 64 u32][descriptors: nslots u64 when emitting]
-    const size_t hist_words = (size_t)reps * nbins;
+    const size_t hist_words = (size_t)reps * L.nbins;
     const size_t ws_bytes = 8 * hist_words + 32 + 8 + 256 + (emit ? 8 * (size_t)nslots : 0);
     Tmp d_ws;
     TMP_ALLOC(d_ws, c, ws_bytes);
     u8* wsp = d_ws.as<u8>();
-    struct PinG { kh_ctx* c; void* p = nullptr; size_t n = 0; ~PinG() { if (p) c->pin_release(p, n); } } pin{c};
+    Pinned pin{c};
     // pinned staging: [ginfo upload: 64 u32][hist read-back][ctl + out_n: 40 B][distinct: nseq u64][pass C tail: 64 B][nvalid u64]
-    const size_t pin_need = 256 + 8 * hist_words + 40 + 8 * (size_t)nseq + 64 + 8;
-    pin.p = c->pin_alloc(pin_need, &pin.n);
-    if (!pin.p) return kh_fail(KH_E_NOMEM, "pinned host allocation failed");
+    PIN_ALLOC(pin, 256 + 8 * hist_words + 40 + 8 * (size_t)nseq + 64 + 8);
     u32* h_ginfo = static_cast<u32*>(pin.p);
     u64* h_hist = reinterpret_cast<u64*>(h_ginfo + 64);
     u32* h_ctl = reinterpret_cast<u32*>(h_hist + hist_words);
     u64* h_distinct = reinterpret_cast<u64*>(h_ctl + 10);
     u64* h_ctail = h_distinct + nseq;
     u64* h_nvalid = h_ctail + 8;
-    memset(h_ginfo, 0, 256);
-    for (int g = 0; g < ngroups; ++g)
-        for (int j = 0; j < gsize[g]; ++j)
-            h_ginfo[gstart[g] + j] = (u32)gstart[g] | ((u32)gsize[g] << 8) | (bin0[g] << 16);
+    L.words(h_ginfo, nullptr, group_of);
     HIPCHK(hipMemsetAsync(wsp, 0, 8 * hist_words + 40, st));
     HIPCHK(hipMemcpyAsync(wsp + 8 * hist_words + 40, h_ginfo, 256, hipMemcpyHostToDevice, st));
     if (emit) HIPCHK(hipMemsetAsync(wsp + 8 * hist_words + 40 + 256, 0, 8 * (size_t)nslots, st));
@@ -2056,7 +2057,7 @@ static int exp1_fused(kh_ctx* c, int nseq, const uint8_t* const* seqs, const uin
     job.ginfo = reinterpret_cast<const u32*>(wsp + 8 * hist_words + 40);
     job.hist = reinterpret_cast<unsigned long long*>(wsp);
     job.ctl = reinterpret_cast<u32*>(wsp + 8 * hist_words);
-    job.nb = gb.nb; job.S = gb.S; job.nops = (u32)nseq; job.nbins = nbins; job.abase = abase;
+    job.nb = gb.nb; job.S = gb.S; job.nops = (u32)nseq; job.nbins = L.nbins; job.abase = L.abase;
     job.ngroups = (u32)ngroups; job.reps = reps;
     job.nbv = gb.nb * nwaves;
     job.binmul = (1u << 26) / ((KH_FINE_BINS + gb.S - 1) / gb.S);
@@ -2089,7 +2090,6 @@ static int exp1_fused(kh_ctx* c, int nseq, const uint8_t* const* seqs, const uin
     const u32 uerr = h_ctl[0];
     if ((cerr | uerr) & (KH_ERR_CAPACITY | KH_ERR_SPIN_TIMEOUT | KH_ERR_ORDER)) {
         c->stat.retries++;
-        drop_sets();
         // a slot of the union held more records than fit (keys shared by many genomes, repeats): the
         // kernel recorded its fullest slot, the caller may try again with that many more sub-ranges
         if (want_scale && !(cerr & KH_ERR_CAPACITY) && (uerr & KH_ERR_CAPACITY) && !(uerr & KH_ERR_ORDER) && h_ctl[1] > gb.cap)
@@ -2106,8 +2106,7 @@ static int exp1_fused(kh_ctx* c, int nseq, const uint8_t* const* seqs, const uin
     }
     c->stat.distinct += dsum;
     c->stat.setop_in += dsum;
-    for (u32 r = 0; r < reps; ++r)
-        for (u32 b = 0; b < nbins; ++b) bins[b] += h_hist[(size_t)r * nbins + b];
+    L.add_bins(bins, h_hist, reps);
     if (emit) {
         const u64 n = *reinterpret_cast<const u64*>(h_ctl + 8);
         buf_ref(okeys);
@@ -2116,37 +2115,334 @@ static int exp1_fused(kh_ctx* c, int nseq, const uint8_t* const* seqs, const uin
     }
     }   // waves
     if (distinct_per_seq)
-        for (int i = 0; i < nseq; ++i) distinct_per_seq[perm[i]] = dist_acc[i];
-    if (within_hist) {
-        memset(within_hist, 0, 8 * (size_t)ngroups * hist_len);
-        for (int g = 0; g < ngroups; ++g)
-            for (int cnt = 1; cnt <= gsize[g]; ++cnt)
-                within_hist[(size_t)g * hist_len + std::min<u32>((u32)cnt, hist_len - 1)] += bins[bin0[g] + cnt];
-    }
-    u64 across_n = 0;
-    for (int cnt = 1; cnt <= ngroups; ++cnt) across_n += bins[abase + cnt];
-    c->stat.setop_out += across_n;
-    if (across_hist) {
-        memset(across_hist, 0, 8 * (size_t)hist_len);
-        for (int cnt = 1; cnt <= ngroups; ++cnt)
-            across_hist[std::min<u32>((u32)cnt, hist_len - 1)] += bins[abase + cnt];
-    }
+        for (int i = 0; i < nseq; ++i) distinct_per_seq[L.perm[i]] = dist_acc[i];
+    L.fold(c, bins, within_hist, across_hist, hist_len);
     if (across_set) {
         if (wave_sets.size() == 1) {
             *across_set = wave_sets[0];
             wave_sets.clear();
         } else {   // the waves' sets cover disjoint key ranges: their union is their concatenation
-            const int r = kh_union_sum(c, wave_sets.data(), (int)wave_sets.size(), cs, across_set, nullptr, 0);
-            drop_sets();
-            if (r != KH_OK) return r;
+            KHCHK(kh_union_sum(c, wave_sets.data(), (int)wave_sets.size(), cs, across_set, nullptr, 0));
         }
     }
     *done = true;
     return KH_OK;
 }
+// ---- experiment 1: the forms and their dispatch
+// Groups are run in waves that fit a device memory budget.  A base in flight costs ~8W bytes in the partition array +
+// 8W (+4) in the output arrays + its share of the group union: budget = 1/64 (W=1) or 1/96 (W=2) of the free HBM, in
+// bases.  (Free memory depends on what the pool holds at the time: it is asked again where a plan is made.)
+static u64 exp1_wave_bases(kh_ctx* c, int k) {
+    u64 budget = 4ull << 30;
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess)
+        budget = std::max<u64>(1u << 20, (free_b + c->pool.cached_bytes) / (k <= 32 ? 64 : 96));
+    if (const char* e = getenv("KHOICE_WAVE_BASES")) budget = std::max<u64>(1, strtoull(e, nullptr, 10));
+    return budget;
+}
+// a batch whose bases exceed the budget: key-range waves (HBM-spill partitioning of BASELINE
+// configs[4]) — every wave re-extracts the batch's bases but keeps one slice of the key space,
+// so the memory in flight is 1/waves of the keys and the histograms of the waves add up
+static u32 exp1_waves(u64 bases, u64 budget) { return (u32)std::max<u64>(1, (bases + budget - 1) / budget); }
 
+// Some of the caller's sequences as the forms take them, groups numbered from 0; `dist` receives their distinct k-mers,
+// scatter() hands them back in the caller's order.
+struct SubBatch {
+    std::vector<int> idx;                   // the caller's numbers of the sequences
+    std::vector<const uint8_t*> seqs;
+    std::vector<uint64_t> lens, dist;
+    std::vector<int> group;
+    int ngroups = 0;
+    u64 bases = 0;
+    int n() const { return (int)idx.size(); }
+    void add(const Exp1In& in, int i, int g) {
+        idx.push_back(i);
+        seqs.push_back(in.seqs[i]);
+        lens.push_back(in.lens[i]);
+        dist.push_back(0);
+        group.push_back(g);
+        bases += in.lens[i];
+    }
+    Exp1In view(const Exp1In& in) const {   // as the forms take the whole input
+        return Exp1In{n(), seqs.data(), lens.data(), in.on_device, group.data(), ngroups, in.k, in.cs, in.hist_len};
+    }
+    void scatter(uint64_t* distinct_per_seq) const {
+        if (distinct_per_seq)
+            for (size_t j = 0; j < idx.size(); ++j) distinct_per_seq[idx[j]] = dist[j];
+    }
+};
+static SubBatch groups_batch(const Exp1In& in, int g0, int g1) {   // the sequences of groups [g0, g1)
+    SubBatch b;
+    b.ngroups = g1 - g0;
+    for (int i = 0; i < in.nseq; ++i)
+        if (in.group_of[i] >= g0 && in.group_of[i] < g1) b.add(in, i, in.group_of[i] - g0);
+    return b;
+}
+// A fast form that is abandoned part-way (a later batch or wave overflows) has already counted its earlier
+// batches: the statistics of an attempt are kept only when the attempt succeeds — its retries and order
+// fallbacks stay counted.
+struct StatCheckpoint {
+    kh_ctx* c;
+    Stats at = c->stat;
+    void rollback() const {
+        const u64 retries = c->stat.retries, order_fallbacks = c->stat.order_fallbacks;
+        c->stat = at;
+        c->stat.retries = retries;
+        c->stat.order_fallbacks = order_fallbacks;
+    }
+};
+// exp1_fused, and once more with the finer slots an overflowing union asked for; cp: failed attempts are rolled back
+static int exp1_fused_rescaled(kh_ctx* c, const Exp1In& in, SubBatch& b, u32 cs, uint64_t* within_hist, uint64_t* across_hist,
+                               kh_set** across_set, u32 nwaves, u32 fan_hint, const StatCheckpoint* cp, bool* done) {
+    double scale = 0.0;
+    KHCHK(exp1_fused(c, b.n(), b.seqs.data(), b.lens.data(), in.on_device, b.group.data(), b.ngroups, in.k, cs, within_hist,
+                     across_hist, in.hist_len, b.dist.data(), across_set, done, nwaves, 1.0, &scale, fan_hint));
+    if (*done) return KH_OK;
+    if (cp) cp->rollback();
+    if (scale > 1.0 && scale < 16.0) {
+        KHCHK(exp1_fused(c, b.n(), b.seqs.data(), b.lens.data(), in.on_device, b.group.data(), b.ngroups, in.k, cs, within_hist,
+                         across_hist, in.hist_len, b.dist.data(), across_set, done, nwaves, scale, nullptr, fan_hint));
+        if (!*done && cp) cp->rollback();
+    }
+    return KH_OK;
+}
 static int exp1_big_group_skm(kh_ctx* c, int n, const uint8_t* const* seqs, const uint64_t* lens, int on_device, int k, u32 cs,
                               uint64_t* whist, u32 hist_len, uint64_t* dist, bool* done);
+// One group of more than 64 genomes (exp_type_1.smk:36-61 lists whatever data/dataset_N holds): sub-batches of
+// up to 64 genomes, each a fused build + tagged union in which every genome is a group of its own, so that the
+// set a sub-batch emits carries "in how many of its genomes"; one counter-summing union of those sets is the
+// group's step_3 database (its histogram fused: step_4).
+static int exp1_big_group(kh_ctx* c, const Exp1In& in, int g, u64 budget, uint64_t* whist, uint64_t* dist_out /* [nseq] or null */,
+                          kh_set** group_set, bool* done) {
+    *done = false;
+    SubBatch all = groups_batch(in, g, g + 1);
+    if (!group_set && whist) {   // histogram and distinct counts only: the super-k-mer form in phases
+        const StatCheckpoint cp{c};
+        KHCHK(exp1_big_group_skm(c, all.n(), all.seqs.data(), all.lens.data(), in.on_device, in.k, in.cs, whist, in.hist_len,
+                                 all.dist.data(), done));
+        if (*done) {
+            all.scatter(dist_out);
+            return KH_OK;
+        }
+        cp.rollback();
+    }
+    std::vector<kh_set*> subs;
+    SetsGuard guard{subs};
+    for (size_t i0 = 0; i0 < all.idx.size(); i0 += KH_TAG_MAX_OPS) {
+        const size_t m = std::min<size_t>(KH_TAG_MAX_OPS, all.idx.size() - i0);
+        SubBatch b;   // every genome a group of its own
+        for (size_t j = i0; j < i0 + m; ++j) b.add(in, all.idx[j], b.ngroups++);
+        kh_set* aset = nullptr;
+        bool d = false;
+        KHCHK(exp1_fused_rescaled(c, in, b, 0x7fffffffu, nullptr, nullptr, &aset, exp1_waves(b.bases, budget), (u32)m, nullptr, &d));
+        if (!d) return KH_OK;
+        subs.push_back(aset);
+        b.scatter(dist_out);
+    }
+    if (group_set) KHCHK(kh_union_sum(c, subs.data(), (int)subs.size(), in.cs, group_set, whist, whist ? in.hist_len : 0));
+    else if (whist) KHCHK(kh_union_histogram(c, subs.data(), (int)subs.size(), in.cs, whist, in.hist_len));
+    *done = true;
+    return KH_OK;
+}
+// Batches of whole groups for the fused forms: a batch holds at most 64 genomes — the width of the genome mask; a
+// group of more than 64 genomes is a batch of its own (big, exp1_big_group).  false: a group without genomes.
+struct Exp1Batch { int g0, g1; bool big; };
+static bool exp1_batches(const Exp1In& in, u64 budget, std::vector<Exp1Batch>* batches) {
+    std::vector<u64> gbases(in.ngroups, 0);
+    std::vector<int> gcount(in.ngroups, 0);
+    for (int i = 0; i < in.nseq; ++i) { gbases[in.group_of[i]] += in.lens[i]; gcount[in.group_of[i]]++; }
+    u64 acc_b = 0;
+    int acc_n = 0, acc_g = 0, acc_bins = 0, g0 = 0;
+    auto close = [&](int g1, bool big) {
+        batches->push_back(Exp1Batch{g0, g1, big});
+        g0 = g1;
+        acc_b = 0; acc_n = acc_g = acc_bins = 0;
+    };
+    for (int g = 0; g < in.ngroups; ++g) {
+        if (gcount[g] == 0) return false;
+        if (gcount[g] > KH_TAG_MAX_OPS) {   // wider than the genome mask: a batch of its own, taken in sub-batches
+            if (acc_n) close(g, false);
+            close(g + 1, true);
+            continue;
+        }
+        // (a batch above the memory budget is run as key-range waves, see exp1_waves: groups are
+        // only split into batches by the width of the genome mask)
+        const bool fits = acc_n + gcount[g] <= KH_TAG_MAX_OPS && acc_g + 1 <= KH_TAG_MAX_OPS &&
+                          acc_bins + gcount[g] + 1 + (acc_g + 2) <= KH_TAG_MAX_BINS &&
+                          (acc_b + gbases[g] <= budget || acc_n == 0);
+        if (!fits) close(g, false);
+        acc_b += gbases[g]; acc_n += gcount[g]; acc_g += 1; acc_bins += gcount[g] + 1;
+    }
+    if (acc_n || batches->empty()) close(in.ngroups, false);
+    return true;
+}
+// Histograms only, more than 64 genomes: every batch in the super-k-mer form for the within-group
+// questions, then ONE more pass over all genomes whose records carry the group number for the
+// across-group one.  Anything it cannot take (a region overflow, k outside its range) -> the key arrays.
+static int exp1_two_pass(kh_ctx* c, const Exp1In& in, const std::vector<Exp1Batch>& batches, u64 budget, uint64_t* within_hist,
+                         uint64_t* across_hist, uint64_t* distinct_per_seq, bool* done) {
+    const StatCheckpoint cp{c};
+    std::vector<uint64_t> wtmp(within_hist ? (size_t)in.ngroups * in.hist_len : 0), dtmp(in.nseq, 0), atmp(in.hist_len, 0);
+    bool ok = true;
+    for (const Exp1Batch& bt : batches) {
+        uint64_t* wh = within_hist ? wtmp.data() + (size_t)bt.g0 * in.hist_len : nullptr;
+        if (bt.big) {
+            KHCHK(exp1_big_group(c, in, bt.g0, budget, wh, dtmp.data(), nullptr, &ok));
+        } else {
+            SubBatch b = groups_batch(in, bt.g0, bt.g1);
+            KHCHK(exp1_skm(c, b.view(in), wh, nullptr, b.dist.data(), &ok));
+            if (ok) b.scatter(dtmp.data());
+        }
+        if (!ok) break;
+    }
+    if (ok) KHCHK(exp1_skm(c, in, nullptr, atmp.data(), nullptr, &ok, /*by_group=*/true));
+    if (!ok) {
+        cp.rollback();
+        return KH_OK;
+    }
+    if (within_hist) memcpy(within_hist, wtmp.data(), 8 * wtmp.size());
+    memcpy(across_hist, atmp.data(), 8 * (size_t)in.hist_len);
+    if (distinct_per_seq) memcpy(distinct_per_seq, dtmp.data(), 8 * (size_t)in.nseq);
+    *done = true;
+    return KH_OK;
+}
+// Several batches, each in a fused form, and the union of their across-group sets (see kh_exp1_run)
+static int exp1_batched(kh_ctx* c, const Exp1In& in, const std::vector<Exp1Batch>& batches, u64 budget, uint64_t* within_hist,
+                        uint64_t* across_hist, uint64_t* distinct_per_seq, kh_set** across_set, bool* done) {
+    const StatCheckpoint cp{c};
+    const bool want_across = across_hist || across_set;
+    std::vector<kh_set*> asets;
+    SetsGuard guard{asets};
+    for (const Exp1Batch& bt : batches) {
+        uint64_t* wh = within_hist ? within_hist + (size_t)bt.g0 * in.hist_len : nullptr;
+        bool d = false;
+        if (bt.big) {   // its across-group set: the group's k-mers, each counted once
+            kh_set* gs = nullptr;
+            KHCHK(exp1_big_group(c, in, bt.g0, budget, wh, distinct_per_seq, want_across ? &gs : nullptr, &d));
+            if (d && gs) {
+                kh_set* one = nullptr;
+                const int r = kh_set_counts(c, gs, 1, &one);
+                kh_set_free(gs);
+                KHCHK(r);
+                asets.push_back(one);
+            }
+        } else {
+            SubBatch b = groups_batch(in, bt.g0, bt.g1);
+            kh_set* aset = nullptr;
+            if (!want_across)   // steps 1-4 only (more than 64 genomes, no across-group step): the batches are independent
+                KHCHK(exp1_skm(c, b.view(in), wh, nullptr, b.dist.data(), &d));
+            if (!d)
+                KHCHK(exp1_fused(c, b.n(), b.seqs.data(), b.lens.data(), in.on_device, b.group.data(), b.ngroups, in.k, in.cs, wh,
+                                 nullptr, in.hist_len, b.dist.data(), want_across ? &aset : nullptr, &d, exp1_waves(b.bases, budget)));
+            if (d) {
+                if (aset) asets.push_back(aset);
+                b.scatter(distinct_per_seq);
+            }
+        }
+        if (!d) {
+            cp.rollback();
+            return KH_OK;
+        }
+    }
+    *done = true;
+    if (across_set) return kh_union_sum(c, asets.data(), (int)asets.size(), in.cs, across_set, across_hist, in.hist_len);
+    if (across_hist) return kh_union_histogram(c, asets.data(), (int)asets.size(), in.cs, across_hist, in.hist_len);
+    return KH_OK;
+}
+// The general path: per-genome sets, per-group unions (steps 1-6), then steps 7+8 over the group sets.
+static int exp1_general(kh_ctx* c, const Exp1In& in, uint64_t* within_hist, uint64_t* across_hist, uint64_t* distinct_per_seq,
+                        kh_set** group_sets, kh_set** across_set) {
+    const int nseq = in.nseq, ngroups = in.ngroups, k = in.k;
+    const u32 cs = in.cs, hist_len = in.hist_len;
+    std::vector<kh_set*> gsets(nseq, nullptr), unions(ngroups, nullptr), usets(ngroups, nullptr);
+    SetsGuard free_usets{usets}, free_unions{unions}, free_gsets{gsets};
+    // Groups are independent until step 7, so they are processed in waves that fit a device
+    // memory budget (all groups at once for the benchmark sizes; wave by wave for inputs whose
+    // k-mers would not fit HBM together): per wave, steps 1+2 build every genome of the wave as
+    // a plain set in ONE batched launch sequence, steps 3+4+6 enqueue the wave's group unions
+    // back to back before the host waits once; the genome sets are released before the next wave.
+    const u64 budget = exp1_wave_bases(c, k);
+    std::vector<u64> group_bases(ngroups, 0);
+    for (int i = 0; i < nseq; ++i) group_bases[in.group_of[i]] += in.lens[i];
+    int r = KH_OK;
+    const double t_begin = g_trace ? now_ms() : 0;
+    double t_unions_submitted = 0, t_unions_synced = 0, t_groups_done = 0;
+    for (int g0 = 0; g0 < ngroups;) {
+        if (group_bases[g0] > budget) {             // one group larger than a wave: sub-waves of genomes
+            r = group_union_incremental(c, groups_batch(in, g0, g0 + 1).idx, in.seqs, in.lens, in.on_device, k, cs, budget,
+                                        within_hist ? within_hist + (size_t)g0 * hist_len : nullptr, hist_len,
+                                        distinct_per_seq, &unions[g0]);
+            if (r == KH_OK) r = kh_set_counts(c, unions[g0], 1, &usets[g0]);
+            if (r != KH_OK) return r;
+            ++g0;
+            continue;
+        }
+        int g1 = g0;
+        u64 acc = 0;
+        while (g1 < ngroups && acc + group_bases[g1] <= budget) acc += group_bases[g1++];
+        const SubBatch b = groups_batch(in, g0, g1);
+        const std::vector<int>& idx = b.idx;
+        std::vector<kh_set*> wsets(idx.size(), nullptr);
+        KHCHK(kh_build_batch(c, b.n(), b.seqs.data(), b.lens.data(), in.on_device, k, 1, KH_NO_MAX,
+                             KH_KMC_DEFAULT_CS, 0, wsets.data()));
+        for (size_t j = 0; j < idx.size(); ++j) {
+            gsets[idx[j]] = wsets[j];
+            if (distinct_per_seq) distinct_per_seq[idx[j]] = wsets[j]->n;
+        }
+        std::vector<SetopJob> jobs(g1 - g0);
+        for (int g = g0; g < g1; ++g) {
+            SetopJob& j = jobs[g - g0];
+            j.c = c; j.op = KH_OP_UNION; j.mode = KH_OC_SUM; j.cs = cs;
+            j.hist = within_hist ? within_hist + (size_t)g * hist_len : nullptr;
+            j.hist_len = hist_len;
+            for (int i : idx)
+                if (in.group_of[i] == g) j.in.push_back(gsets[i]);
+            if (j.in.empty()) return kh_fail(KH_E_ARG, "group %d has no sequences", g);
+            if ((int)j.in.size() > KH_MAX_INPUT_SETS) {   // beyond one launch's fan-in: the general path
+                KHCHK(kh_union_sum(c, j.in.data(), (int)j.in.size(), cs, &unions[g], j.hist, hist_len));
+                j.in.clear();
+                continue;
+            }
+            r = setop_prepare(j);
+            if (r == KH_OK) r = setop_plan(j);
+            if (r != KH_OK) return r;
+        }
+        // the slot bounds of all unions of the wave in one launch, then the unions back to back
+        Tmp d_bjobs;
+        Pinned bpin{c};
+        r = setop_bounds_batch(c, jobs, d_bjobs, bpin);
+        if (r == KH_OK) {
+            std::vector<SetopJob*> run;
+            for (auto& j : jobs) run.push_back(&j);
+            r = setop_run_batch(c, run.data(), run.size());
+        }
+        if (r != KH_OK) return r;
+        if (g_trace) t_unions_submitted = now_ms();
+        if (hipStreamSynchronize(c->st) != hipSuccess) return kh_fail(KH_E_HIP, "stream sync failed");
+        if (g_trace) t_unions_synced = now_ms();
+        for (int g = g0; g < g1; ++g) {
+            if (!jobs[g - g0].in.empty()) KHCHK(setop_finish(jobs[g - g0], &unions[g]));
+        }
+        jobs.clear();
+        for (int g = g0; g < g1; ++g) KHCHK(kh_set_counts(c, unions[g], 1, &usets[g]));
+        for (int i : idx) { kh_set_free(gsets[i]); gsets[i] = nullptr; }   // genome sets of this wave
+        g0 = g1;
+    }
+    // steps 7+8 (skipped when the caller wants neither output: the multi-GPU path does them
+    // after exchanging the group sets, khoice_amd/dist.py)
+    if (g_trace) t_groups_done = now_ms();
+    if (across_set) KHCHK(kh_union_sum(c, usets.data(), ngroups, cs, across_set, across_hist, hist_len));   // (nothing fails after it)
+    else if (across_hist) KHCHK(kh_union_histogram(c, usets.data(), ngroups, cs, across_hist, hist_len));
+    if (g_trace)
+        fprintf(stderr, "[khoice trace] build submit %.3f wait %.3f | unions submit %.3f wait %.3f finish %.3f | "
+                        "across %.3f | total %.3f ms\n",
+                g_t_build_submitted - t_begin, g_t_build_synced - g_t_build_submitted,
+                t_unions_submitted - g_t_build_synced, t_unions_synced - t_unions_submitted,
+                t_groups_done - t_unions_synced, now_ms() - t_groups_done, now_ms() - t_begin);
+    if (group_sets)
+        for (int g = 0; g < ngroups; ++g) { group_sets[g] = unions[g]; unions[g] = nullptr; }
+    return KH_OK;
+}
 extern "C" int kh_exp1_run(kh_ctx* c, int nseq, const uint8_t* const* seqs, const uint64_t* lens,
                            int on_device, const int* group_of, int ngroups, int k, uint32_t cs,
                            uint64_t* within_hist, uint64_t* across_hist, uint32_t hist_len,
@@ -2159,359 +2455,39 @@ extern "C" int kh_exp1_run(kh_ctx* c, int nseq, const uint8_t* const* seqs, cons
             return kh_fail(KH_E_ARG, "group_of[%d]=%d outside [0,%d)", i, group_of[i], ngroups);
     KHCHK(check_k(k));
     if (cs < 1) return kh_fail(KH_E_ARG, "cs must be >= 1");
+    const Exp1In in{nseq, seqs, lens, on_device, group_of, ngroups, k, cs, hist_len};
     // No per-group database wanted: the fused form (one build in grid mode + one tagged union per
     // BATCH of whole groups; a batch holds at most 64 genomes — the width of the genome mask — and
     // fits the memory budget).  One batch: its histograms are the answer.  Several: each batch also
     // emits its across-group set (counter = groups of the batch holding the k-mer) and one
     // counter-summing union of those sets gives step 7/8.  Anything the fused form cannot take
-    // (a group of more than 64 genomes, a slot overflow) falls through to the general path below.
-    // A fast form that is abandoned part-way (a later batch or wave overflows) has already counted its earlier
-    // batches: the statistics of an attempt are kept only when the attempt succeeds.
-    const Stats stat_at_entry = c->stat;
-    auto forget_attempt = [&]() {
-        const u64 retries = c->stat.retries, order_fallbacks = c->stat.order_fallbacks;
-        c->stat = stat_at_entry;
-        c->stat.retries = retries;
-        c->stat.order_fallbacks = order_fallbacks;
-    };
+    // (a group of more than 64 genomes, a slot overflow) falls through to the general path.
     if (!group_sets && !getenv("KHOICE_NO_FUSED")) {
-        u64 fbudget = 4ull << 30;
-        size_t free_b = 0, total_b = 0;
         HIPCHK(hipSetDevice(c->dev));
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess)
-            fbudget = std::max<u64>(1u << 20, (free_b + c->pool.cached_bytes) / (k <= 32 ? 64 : 96));
-        if (const char* e = getenv("KHOICE_WAVE_BASES")) fbudget = std::max<u64>(1, strtoull(e, nullptr, 10));
-        std::vector<u64> gbases(ngroups, 0);
-        std::vector<int> gcount(ngroups, 0);
-        for (int i = 0; i < nseq; ++i) { gbases[group_of[i]] += lens[i]; gcount[group_of[i]]++; }
-        std::vector<int> batch_end;      // group index one past each batch
-        std::vector<char> batch_big;     // the batch is ONE group of more than 64 genomes (exp1_big_group)
-        bool applicable = true;
-        {
-            u64 acc_b = 0;
-            int acc_n = 0, acc_g = 0, acc_bins = 0;
-            for (int g = 0; g < ngroups && applicable; ++g) {
-                if (gcount[g] == 0) { applicable = false; break; }
-                if (gcount[g] > KH_TAG_MAX_OPS) {   // wider than the genome mask: a batch of its own, taken in sub-batches
-                    if (acc_n) { batch_end.push_back(g); batch_big.push_back(0); acc_b = 0; acc_n = acc_g = acc_bins = 0; }
-                    batch_end.push_back(g + 1);
-                    batch_big.push_back(1);
-                    continue;
+        const u64 budget = exp1_wave_bases(c, k);
+        std::vector<Exp1Batch> batches;
+        bool done = false;
+        if (exp1_batches(in, budget, &batches)) {
+            if (batches.size() == 1 && !batches[0].big) {   // all groups in one batch
+                const StatCheckpoint cp{c};
+                if (!across_set) {   // histograms and distinct counts only: the super-k-mer form
+                    KHCHK(exp1_skm(c, in, within_hist, across_hist, distinct_per_seq, &done));
+                    if (!done) cp.rollback();
                 }
-                // (a batch above the memory budget is run as key-range waves, see below: groups are
-                // only split into batches by the width of the genome mask)
-                const bool fits = acc_n + gcount[g] <= KH_TAG_MAX_OPS && acc_g + 1 <= KH_TAG_MAX_OPS &&
-                                  acc_bins + gcount[g] + 1 + (acc_g + 2) <= KH_TAG_MAX_BINS &&
-                                  (acc_b + gbases[g] <= fbudget || acc_n == 0);
-                if (!fits) { batch_end.push_back(g); batch_big.push_back(0); acc_b = 0; acc_n = acc_g = acc_bins = 0; }
-                acc_b += gbases[g]; acc_n += gcount[g]; acc_g += 1; acc_bins += gcount[g] + 1;
+                if (!done) {   // the key arrays, with one more try with finer slots before the general path
+                    SubBatch b = groups_batch(in, 0, ngroups);
+                    KHCHK(exp1_fused_rescaled(c, in, b, cs, within_hist, across_hist, across_set, exp1_waves(b.bases, budget), 0, &cp, &done));
+                    if (done) b.scatter(distinct_per_seq);
+                }
+            } else {
+                if (!across_set && across_hist && ngroups <= KH_TAG_MAX_OPS && !getenv("KHOICE_NO_SKM_TWO_PASS"))
+                    KHCHK(exp1_two_pass(c, in, batches, budget, within_hist, across_hist, distinct_per_seq, &done));
+                if (!done) KHCHK(exp1_batched(c, in, batches, budget, within_hist, across_hist, distinct_per_seq, across_set, &done));
             }
-            if (acc_n || batch_end.empty()) { batch_end.push_back(ngroups); batch_big.push_back(0); }
         }
-        // a batch whose bases exceed the budget: key-range waves (HBM-spill partitioning of BASELINE
-        // configs[4]) — every wave re-extracts the batch's bases but keeps one slice of the key space,
-        // so the memory in flight is 1/waves of the keys and the histograms of the waves add up
-        auto waves_for = [&](u64 bases) -> u32 { return (u32)std::max<u64>(1, (bases + fbudget - 1) / fbudget); };
-        // One group of more than 64 genomes (exp_type_1.smk:36-61 lists whatever data/dataset_N holds): sub-batches of
-        // up to 64 genomes, each a fused build + tagged union in which every genome is a group of its own, so that the
-        // set a sub-batch emits carries "in how many of its genomes"; one counter-summing union of those sets is the
-        // group's step_3 database (its histogram fused: step_4).
-        auto big_group = [&](int g, uint64_t* whist, uint64_t* dist_out /* [nseq] or null */, kh_set** group_set, bool* done) -> int {
-            *done = false;
-            std::vector<int> members;
-            for (int i = 0; i < nseq; ++i)
-                if (group_of[i] == g) members.push_back(i);
-            if (!group_set && whist) {   // histogram and distinct counts only: the super-k-mer form in phases
-                std::vector<const uint8_t*> ms(members.size());
-                std::vector<uint64_t> ml(members.size()), md(members.size(), 0);
-                for (size_t j = 0; j < members.size(); ++j) { ms[j] = seqs[members[j]]; ml[j] = lens[members[j]]; }
-                const Stats before = c->stat;
-                KHCHK(exp1_big_group_skm(c, (int)members.size(), ms.data(), ml.data(), on_device, k, cs, whist, hist_len, md.data(), done));
-                if (*done) {
-                    if (dist_out)
-                        for (size_t j = 0; j < members.size(); ++j) dist_out[members[j]] = md[j];
-                    return KH_OK;
-                }
-                const u64 tries = c->stat.retries;   // (work counted by an attempt that was given up is forgotten, the attempt is not)
-                c->stat = before;
-                c->stat.retries = tries;
-            }
-            std::vector<kh_set*> subs;
-            struct G { std::vector<kh_set*>& v; ~G() { for (auto* x : v) kh_set_free(x); } } guard{subs};
-            for (size_t i0 = 0; i0 < members.size(); i0 += KH_TAG_MAX_OPS) {
-                const size_t m = std::min<size_t>(KH_TAG_MAX_OPS, members.size() - i0);
-                std::vector<const uint8_t*> bs(m);
-                std::vector<uint64_t> bl(m), bd(m, 0);
-                std::vector<int> bg(m);
-                u64 sb = 0;
-                for (size_t j = 0; j < m; ++j) { bs[j] = seqs[members[i0 + j]]; bl[j] = lens[members[i0 + j]]; bg[j] = (int)j; sb += bl[j]; }
-                kh_set* aset = nullptr;
-                bool d = false;
-                double scale = 0.0;
-                KHCHK(exp1_fused(c, (int)m, bs.data(), bl.data(), on_device, bg.data(), (int)m, k, 0x7fffffffu, nullptr, nullptr,
-                                 hist_len, bd.data(), &aset, &d, waves_for(sb), 1.0, &scale, (u32)m));
-                if (!d && scale > 1.0 && scale < 16.0)   // one more try with finer slots
-                    KHCHK(exp1_fused(c, (int)m, bs.data(), bl.data(), on_device, bg.data(), (int)m, k, 0x7fffffffu, nullptr, nullptr,
-                                     hist_len, bd.data(), &aset, &d, waves_for(sb), scale, nullptr, (u32)m));
-                if (!d) return KH_OK;
-                subs.push_back(aset);
-                if (dist_out)
-                    for (size_t j = 0; j < m; ++j) dist_out[members[i0 + j]] = bd[j];
-            }
-            if (group_set) KHCHK(kh_union_sum(c, subs.data(), (int)subs.size(), cs, group_set, whist, whist ? hist_len : 0));
-            else if (whist) KHCHK(kh_union_histogram(c, subs.data(), (int)subs.size(), cs, whist, hist_len));
-            *done = true;
-            return KH_OK;
-        };
-        if (applicable && batch_end.size() == 1 && !batch_big[0]) {
-            u64 all_bases = 0;
-            for (int g = 0; g < ngroups; ++g) all_bases += gbases[g];
-            bool done = false;
-            double scale = 0.0;
-            if (!across_set) {   // histograms and distinct counts only: the super-k-mer form
-                KHCHK(exp1_skm(c, nseq, seqs, lens, on_device, group_of, ngroups, k, cs, within_hist, across_hist,
-                               hist_len, distinct_per_seq, &done));
-                if (done) return KH_OK;
-                forget_attempt();
-            }
-            KHCHK(exp1_fused(c, nseq, seqs, lens, on_device, group_of, ngroups, k, cs, within_hist, across_hist,
-                             hist_len, distinct_per_seq, across_set, &done, waves_for(all_bases), 1.0, &scale));
-            if (done) return KH_OK;
-            forget_attempt();
-            if (scale > 1.0 && scale < 16.0) {   // one more try with finer slots before the general path
-                KHCHK(exp1_fused(c, nseq, seqs, lens, on_device, group_of, ngroups, k, cs, within_hist, across_hist,
-                                 hist_len, distinct_per_seq, across_set, &done, waves_for(all_bases), scale, nullptr));
-                if (done) return KH_OK;
-                forget_attempt();
-            }
-        } else if (applicable) {
-            const bool want_across = across_hist || across_set;
-            // Histograms only, more than 64 genomes: every batch in the super-k-mer form for the within-group
-            // questions, then ONE more pass over all genomes whose records carry the group number for the
-            // across-group one.  Anything it cannot take (a region overflow, k outside its range) -> the key arrays.
-            if (!across_set && across_hist && ngroups <= KH_TAG_MAX_OPS && !getenv("KHOICE_NO_SKM_TWO_PASS")) {
-                bool ok2 = true;
-                int g0b = 0;
-                std::vector<uint64_t> wtmp(within_hist ? (size_t)ngroups * hist_len : 0), dtmp(nseq, 0), atmp(hist_len, 0);
-                for (size_t b = 0; b < batch_end.size() && ok2; ++b) {
-                    const int g1b = batch_end[b];
-                    if (batch_big[b]) {
-                        bool done = false;
-                        KHCHK(big_group(g0b, within_hist ? wtmp.data() + (size_t)g0b * hist_len : nullptr, dtmp.data(), nullptr, &done));
-                        if (!done) { ok2 = false; break; }
-                        g0b = g1b;
-                        continue;
-                    }
-                    std::vector<int> idx;
-                    for (int i = 0; i < nseq; ++i)
-                        if (group_of[i] >= g0b && group_of[i] < g1b) idx.push_back(i);
-                    std::vector<const uint8_t*> bs(idx.size());
-                    std::vector<uint64_t> bl(idx.size()), bd(idx.size(), 0);
-                    std::vector<int> bg(idx.size());
-                    for (size_t j = 0; j < idx.size(); ++j) { bs[j] = seqs[idx[j]]; bl[j] = lens[idx[j]]; bg[j] = group_of[idx[j]] - g0b; }
-                    bool done = false;
-                    KHCHK(exp1_skm(c, (int)idx.size(), bs.data(), bl.data(), on_device, bg.data(), g1b - g0b, k, cs,
-                                   within_hist ? wtmp.data() + (size_t)g0b * hist_len : nullptr, nullptr, hist_len, bd.data(), &done));
-                    if (!done) { ok2 = false; break; }
-                    for (size_t j = 0; j < idx.size(); ++j) dtmp[idx[j]] = bd[j];
-                    g0b = g1b;
-                }
-                if (ok2) {
-                    bool done = false;
-                    KHCHK(exp1_skm(c, nseq, seqs, lens, on_device, group_of, ngroups, k, cs, nullptr, atmp.data(), hist_len, nullptr,
-                                   &done, /*by_group=*/true));
-                    ok2 = done;
-                }
-                if (ok2) {
-                    if (within_hist) memcpy(within_hist, wtmp.data(), 8 * wtmp.size());
-                    memcpy(across_hist, atmp.data(), 8 * (size_t)hist_len);
-                    if (distinct_per_seq) memcpy(distinct_per_seq, dtmp.data(), 8 * (size_t)nseq);
-                    return KH_OK;
-                }
-                forget_attempt();
-            }
-            std::vector<kh_set*> asets;
-            auto drop = [&]() { for (auto* s : asets) kh_set_free(s); asets.clear(); };
-            bool ok = true;
-            int g0 = 0;
-            for (size_t b = 0; b < batch_end.size() && ok; ++b) {
-                const int g1 = batch_end[b];
-                if (batch_big[b]) {   // its across-group set: the group's k-mers, each counted once
-                    kh_set* gs = nullptr;
-                    bool done = false;
-                    int r = big_group(g0, within_hist ? within_hist + (size_t)g0 * hist_len : nullptr, distinct_per_seq,
-                                      want_across ? &gs : nullptr, &done);
-                    if (r == KH_OK && done && gs) {
-                        kh_set* one = nullptr;
-                        r = kh_set_counts(c, gs, 1, &one);
-                        kh_set_free(gs);
-                        if (r == KH_OK) asets.push_back(one);
-                    }
-                    if (r != KH_OK) { drop(); return r; }
-                    if (!done) { ok = false; break; }
-                    g0 = g1;
-                    continue;
-                }
-                std::vector<int> idx;
-                for (int i = 0; i < nseq; ++i)
-                    if (group_of[i] >= g0 && group_of[i] < g1) idx.push_back(i);
-                std::vector<const uint8_t*> bs(idx.size());
-                std::vector<uint64_t> bl(idx.size()), bd(idx.size(), 0);
-                std::vector<int> bg(idx.size());
-                for (size_t j = 0; j < idx.size(); ++j) { bs[j] = seqs[idx[j]]; bl[j] = lens[idx[j]]; bg[j] = group_of[idx[j]] - g0; }
-                kh_set* aset = nullptr;
-                bool done = false;
-                u64 bbases = 0;
-                for (int g = g0; g < g1; ++g) bbases += gbases[g];
-                int r = KH_OK;
-                if (!want_across)   // steps 1-4 only (more than 64 genomes, no across-group step): the batches are independent
-                    r = exp1_skm(c, (int)idx.size(), bs.data(), bl.data(), on_device, bg.data(), g1 - g0, k, cs,
-                                 within_hist ? within_hist + (size_t)g0 * hist_len : nullptr, nullptr, hist_len, bd.data(), &done);
-                if (r == KH_OK && !done)
-                    r = exp1_fused(c, (int)idx.size(), bs.data(), bl.data(), on_device, bg.data(), g1 - g0, k, cs,
-                                   within_hist ? within_hist + (size_t)g0 * hist_len : nullptr, nullptr, hist_len,
-                                   bd.data(), want_across ? &aset : nullptr, &done, waves_for(bbases));
-                if (r != KH_OK) { drop(); return r; }
-                if (!done) { ok = false; break; }
-                if (aset) asets.push_back(aset);
-                if (distinct_per_seq)
-                    for (size_t j = 0; j < idx.size(); ++j) distinct_per_seq[idx[j]] = bd[j];
-                g0 = g1;
-            }
-            if (ok) {
-                int r = KH_OK;
-                if (across_set) r = kh_union_sum(c, asets.data(), (int)asets.size(), cs, across_set, across_hist, hist_len);
-                else if (across_hist) r = kh_union_histogram(c, asets.data(), (int)asets.size(), cs, across_hist, hist_len);
-                drop();
-                return r;
-            }
-            drop();
-            forget_attempt();
-        }
+        if (done) return KH_OK;
     }
-    std::vector<kh_set*> gsets(nseq, nullptr), unions(ngroups, nullptr), usets(ngroups, nullptr);
-    kh_set* across = nullptr;
-    auto cleanup = [&]() {
-        for (auto* s : gsets) kh_set_free(s);
-        for (auto* s : unions) kh_set_free(s);
-        for (auto* s : usets) kh_set_free(s);
-        kh_set_free(across);
-    };
-    // Groups are independent until step 7, so they are processed in waves that fit a device
-    // memory budget (all groups at once for the benchmark sizes; wave by wave for inputs whose
-    // k-mers would not fit HBM together): per wave, steps 1+2 build every genome of the wave as
-    // a plain set in ONE batched launch sequence, steps 3+4+6 enqueue the wave's group unions
-    // back to back before the host waits once; the genome sets are released before the next wave.
-    // A base in flight costs ~8W bytes in the partition array + 8W (+4) in the output arrays +
-    // its share of the group union: budget = 1/64 (W=1) or 1/96 (W=2) of the free HBM, in bases.
-    u64 budget = 4ull << 30;
-    {
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess)
-            budget = std::max<u64>(1u << 20, (free_b + c->pool.cached_bytes) / (k <= 32 ? 64 : 96));
-    }
-    if (const char* e = getenv("KHOICE_WAVE_BASES")) budget = std::max<u64>(1, strtoull(e, nullptr, 10));
-    std::vector<u64> group_bases(ngroups, 0);
-    for (int i = 0; i < nseq; ++i) group_bases[group_of[i]] += lens[i];
-    int r = KH_OK;
-    const double t_begin = g_trace ? now_ms() : 0;
-    double t_unions_submitted = 0, t_unions_synced = 0, t_groups_done = 0;
-    for (int g0 = 0; g0 < ngroups;) {
-        if (group_bases[g0] > budget) {             // one group larger than a wave: sub-waves of genomes
-            std::vector<int> members;
-            for (int i = 0; i < nseq; ++i)
-                if (group_of[i] == g0) members.push_back(i);
-            r = group_union_incremental(c, members, seqs, lens, on_device, k, cs, budget,
-                                        within_hist ? within_hist + (size_t)g0 * hist_len : nullptr, hist_len,
-                                        distinct_per_seq, &unions[g0]);
-            if (r == KH_OK) r = kh_set_counts(c, unions[g0], 1, &usets[g0]);
-            if (r != KH_OK) { cleanup(); return r; }
-            ++g0;
-            continue;
-        }
-        int g1 = g0;
-        u64 acc = 0;
-        while (g1 < ngroups && acc + group_bases[g1] <= budget) acc += group_bases[g1++];
-        std::vector<int> idx;                       // sequences of groups [g0, g1)
-        for (int i = 0; i < nseq; ++i)
-            if (group_of[i] >= g0 && group_of[i] < g1) idx.push_back(i);
-        std::vector<const uint8_t*> wseqs(idx.size());
-        std::vector<uint64_t> wlens(idx.size());
-        std::vector<kh_set*> wsets(idx.size(), nullptr);
-        for (size_t j = 0; j < idx.size(); ++j) { wseqs[j] = seqs[idx[j]]; wlens[j] = lens[idx[j]]; }
-        r = kh_build_batch(c, (int)idx.size(), wseqs.data(), wlens.data(), on_device, k, 1, KH_NO_MAX,
-                           KH_KMC_DEFAULT_CS, 0, wsets.data());
-        if (r != KH_OK) { cleanup(); return r; }
-        for (size_t j = 0; j < idx.size(); ++j) {
-            gsets[idx[j]] = wsets[j];
-            if (distinct_per_seq) distinct_per_seq[idx[j]] = wsets[j]->n;
-        }
-        std::vector<SetopJob> jobs(g1 - g0);
-        for (int g = g0; g < g1; ++g) {
-            SetopJob& j = jobs[g - g0];
-            j.c = c; j.op = KH_OP_UNION; j.mode = KH_OC_SUM; j.cs = cs;
-            j.hist = within_hist ? within_hist + (size_t)g * hist_len : nullptr;
-            j.hist_len = hist_len;
-            for (int i : idx)
-                if (group_of[i] == g) j.in.push_back(gsets[i]);
-            if (j.in.empty()) { cleanup(); return kh_fail(KH_E_ARG, "group %d has no sequences", g); }
-            if ((int)j.in.size() > KH_MAX_INPUT_SETS) {   // beyond one launch's fan-in: the general path
-                r = kh_union_sum(c, j.in.data(), (int)j.in.size(), cs, &unions[g], j.hist, hist_len);
-                if (r != KH_OK) { cleanup(); return r; }
-                j.in.clear();
-                continue;
-            }
-            r = setop_prepare(j);
-            if (r == KH_OK) r = setop_plan(j);
-            if (r != KH_OK) { cleanup(); return r; }
-        }
-        // the slot bounds of all unions of the wave in one launch, then the unions back to back
-        Tmp d_bjobs;
-        struct PinGuard { kh_ctx* c; void* p = nullptr; size_t n = 0; ~PinGuard() { if (p) c->pin_release(p, n); } } bpin{c};
-        r = setop_bounds_batch(c, jobs, d_bjobs, &bpin.p, &bpin.n);
-        if (r == KH_OK) {
-            std::vector<SetopJob*> run;
-            for (auto& j : jobs) run.push_back(&j);
-            r = setop_run_batch(c, run.data(), run.size());
-        }
-        if (r != KH_OK) { cleanup(); return r; }
-        if (g_trace) t_unions_submitted = now_ms();
-        if (hipStreamSynchronize(c->st) != hipSuccess) { cleanup(); return kh_fail(KH_E_HIP, "stream sync failed"); }
-        if (g_trace) t_unions_synced = now_ms();
-        for (int g = g0; g < g1; ++g) {
-            if (jobs[g - g0].in.empty()) continue;
-            r = setop_finish(jobs[g - g0], &unions[g]);
-            if (r != KH_OK) { cleanup(); return r; }
-        }
-        jobs.clear();
-        for (int g = g0; g < g1; ++g) {
-            r = kh_set_counts(c, unions[g], 1, &usets[g]);
-            if (r != KH_OK) { cleanup(); return r; }
-        }
-        for (int i : idx) { kh_set_free(gsets[i]); gsets[i] = nullptr; }   // genome sets of this wave
-        g0 = g1;
-    }
-    // steps 7+8 (skipped when the caller wants neither output: the multi-GPU path does them
-    // after exchanging the group sets, khoice_amd/dist.py)
-    if (g_trace) t_groups_done = now_ms();
-    if (across_set) {
-        r = kh_union_sum(c, usets.data(), ngroups, cs, &across, across_hist, hist_len);
-        if (r != KH_OK) { cleanup(); return r; }
-    } else if (across_hist) {
-        r = kh_union_histogram(c, usets.data(), ngroups, cs, across_hist, hist_len);
-        if (r != KH_OK) { cleanup(); return r; }
-    }
-    if (g_trace)
-        fprintf(stderr, "[khoice trace] build submit %.3f wait %.3f | unions submit %.3f wait %.3f finish %.3f | "
-                        "across %.3f | total %.3f ms\n",
-                g_t_build_submitted - t_begin, g_t_build_synced - g_t_build_submitted,
-                t_unions_submitted - g_t_build_synced, t_unions_synced - t_unions_submitted,
-                t_groups_done - t_unions_synced, now_ms() - t_groups_done, now_ms() - t_begin);
-    if (group_sets)
-        for (int g = 0; g < ngroups; ++g) { group_sets[g] = unions[g]; unions[g] = nullptr; }
-    if (across_set) { *across_set = across; across = nullptr; }
-    cleanup();
-    return KH_OK;
+    return exp1_general(c, in, within_hist, across_hist, distinct_per_seq, group_sets, across_set);
 }
 
 // ------------------------------------------------------------------------------ exchange form of steps 7-8
@@ -2527,20 +2503,16 @@ static bool skm_exchange_geometry(int k, uint64_t positions_max, int nparts, u32
                                   double eff_parts = 0.0 /* pieces that share most k-mers count as fewer; 0: nparts */) {
     const int m = skm_minimizer_len(k);
     const u32 w = (u32)(k - m + 1);
-    // k-mer instances per slot and rank: the pack kernel takes 1024 records of a slot; the owner's table (4096 entries)
-    // has to hold the slot's distinct k-mers of ALL ranks — sized for unrelated groups: nparts x the per-rank mean
-    // below three quarters of it
-    const double per_kmer = 2.0 / (double)(w + 1) + 1.0 / 48.0;
+    const double per_kmer = skm_per_kmer(w);
     // k-mer instances per slot and rank.  The owner's table (4096 entries) takes ~3000 instances per round: with
     // groups of related genomes about 0.55 of a rank's instances survive the merge of identical records, so
     // 2600 / (0.55 x nparts) per rank keeps the owner at one round (unrelated genomes: two).  A rank's slot must also
     // fit the pack kernel's 1024 records, and the two partition levels give 512 x 512 slots at most (beyond: the
     // slots grow and the owner takes more rounds).
-    // The regions of a rank's slots are sized as exp1_skm sizes them: the mean with the slack of five sigma, where the
-    // `fan` genomes of a group bring their copies of a locus together (at least 1.7): that must stay below the pack
+    // The regions of a rank's slots are sized as exp1_skm sizes them (skm_region_slack): they must stay below the pack
     // kernel's 1024 records.
-    const double clump = 0.5 * (double)(w + 1) * (double)std::max<u32>(1, fan);
-    auto region = [&](double mean) { return mean * per_kmer * std::max(1.7, 1.0 + 5.0 * std::sqrt(clump / mean)) + 128.0; };
+    const double clump = skm_clump(w, std::max<u32>(1, fan));
+    auto region = [&](double mean) { return mean * per_kmer * skm_region_slack(clump, mean) + 128.0; };
     if (eff_parts <= 0.0) eff_parts = (double)nparts;
     double mean = std::min(2600.0 / (0.55 * eff_parts), (1024.0 - 128.0) / (1.7 * per_kmer));
     while (mean > 64.0 && region(mean) > 1008.0) mean *= 0.95;
@@ -2562,29 +2534,24 @@ extern "C" int kh_skm_exchange_plan(kh_ctx* c, int k, uint64_t positions_max, ui
         return kh_fail(KH_E_CAPACITY, "too many k-mers per rank for the exchange form (%llu positions)", (unsigned long long)positions_max);
     *nslots = (u32)ns;
     *slots_per_part = (u32)((ns + nparts - 1) / nparts);
-    *part_cap = ((u64)((double)positions_max * per_kmer * 1.3 / nparts) + 8192 + 63) & ~63ull;
+    *part_cap = skm_part_cap(positions_max, per_kmer, nparts);
     return KH_OK;
 }
 
-// fan_hint / inst_out / dup_out: the one-GPU use (a group of more than 64 genomes in sub-batches, exp1_big_group_skm):
-// the tags are genomes of ONE group, their instance counts and the repeats under one tag are wanted.  soft: what does
-// not fit is *done = false instead of an error.
+// The one-GPU use of kh_skm_pack (a group of more than 64 genomes in sub-batches, exp1_big_group_skm): the tags are
+// genomes of ONE group, whose copies of a locus arrive together.
+struct SkmPackLocal {
+    std::vector<u64> inst;   // out: k-mer instances per sequence, in the caller's order
+    u64 dup[32] = {};        // out: instances whose (k-mer, tag) pair was seen before
+    Tmp spill;               // out: records that did not fit their slot's region: [SkmStage::spill_cap] records, then as many u32 slots
+    u32 spill_n = 0;
+    bool done = false;       // what does not fit: false instead of an error
+};
+// The records by slot, (a) + (b) with the slots all ranks agreed on, packed by the part that owns their slot
 static int skm_pack_impl(kh_ctx* c, int nseq, const uint8_t* const* seqs, const uint64_t* lens, int on_device,
                          const int* tag_of, int k, uint32_t nslots, int nparts, uint64_t part_cap, void* rec_out,
-                         uint32_t* mask_out, uint32_t* count_out, uint32_t* off_out, uint64_t* part_n, u32 fan_hint,
-                         std::vector<u64>* inst_out, u64* dup_out /* [32] host */, bool* soft_done, u32 nsub = 1,
-                         SkmRecords* keep = nullptr /* the caller's: asks for and receives the side list */);
-extern "C" int kh_skm_pack(kh_ctx* c, int nseq, const uint8_t* const* seqs, const uint64_t* lens, int on_device,
-                           const int* tag_of, int k, uint32_t nslots, int nparts, uint64_t part_cap, void* rec_out,
-                           uint32_t* mask_out, uint32_t* count_out, uint32_t* off_out, uint64_t* part_n) {
-    return skm_pack_impl(c, nseq, seqs, lens, on_device, tag_of, k, nslots, nparts, part_cap, rec_out, mask_out, count_out, off_out,
-                         part_n, 0, nullptr, nullptr, nullptr);
-}
-static int skm_pack_impl(kh_ctx* c, int nseq, const uint8_t* const* seqs, const uint64_t* lens, int on_device,
-                         const int* tag_of, int k, uint32_t nslots, int nparts, uint64_t part_cap, void* rec_out,
-                         uint32_t* mask_out, uint32_t* count_out, uint32_t* off_out, uint64_t* part_n, u32 fan_hint,
-                         std::vector<u64>* inst_out, u64* dup_out, bool* soft_done, u32 nsub, SkmRecords* keep) {
-    if (soft_done) *soft_done = false;
+                         uint32_t* mask_out, uint32_t* count_out, uint32_t* off_out, uint64_t* part_n, SkmPackLocal* loc) {
+    if (loc) loc->done = false;
     if (!c || !seqs || !lens || !tag_of || nseq <= 0 || nparts < 1 || !rec_out || !mask_out || !count_out || !off_out || !part_n)
         return kh_fail(KH_E_ARG, "kh_skm_pack: bad argument");
     if (!skm_exchange_k(k)) return kh_fail(KH_E_ARG, "the exchange form takes k = %d .. %d", KH_SKM_MIN_K, KH_SKM_MAX_K);
@@ -2595,30 +2562,51 @@ static int skm_pack_impl(kh_ctx* c, int nseq, const uint8_t* const* seqs, const 
     }
     HIPCHK(hipSetDevice(c->dev));
     hipStream_t st = c->st;
-    SkmRecords own;
-    SkmRecords& rec = keep ? *keep : own;
-    rec.force_slots = nslots;
-    rec.fan_hint = fan_hint;
-    rec.inst = inst_out;
-    rec.want_spill = keep != nullptr;
-    bool done = false;
     {   // every tag needs a sequence for the geometry code (groups without genomes are refused there): tags are dense here
         std::vector<int> seen(ntags, 0);
         for (int i = 0; i < nseq; ++i) seen[tag_of[i]] = 1;
         for (int t = 0; t < ntags; ++t)
             if (!seen[t]) return kh_fail(KH_E_ARG, "kh_skm_pack: tag %d has no sequence", t);
     }
-    KHCHK(exp1_skm(c, nseq, seqs, lens, on_device, tag_of, ntags, k, 1, nullptr, nullptr, 2, nullptr, &done, /*by_group=*/true, &rec));
-    if (!done) {
-        if (soft_done) return KH_OK;
+    SkmStage s(c);
+    KHCHK(skm_prepare(c, nseq, seqs, lens, on_device, tag_of, ntags, k, /*by_group=*/true, nslots, loc ? (u32)nseq : 0u, &s));
+    u32 h_ctl[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (s.staged) {
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(h_ctl, s.job.ctl, 32, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (getenv("KHOICE_SKM_DEBUG"))
+            fprintf(stderr, "[skm records] k=%d positions=%llu nb1=%u S=%u nslots=%u cap1 %u cap2 %u | records %u errors %u spilled %u\n", k,
+                    (unsigned long long)s.g.positions, s.g.nb1, s.g.S, s.g.nslots, s.g.cap1, s.g.cap2, h_ctl[2], h_ctl[0], h_ctl[5]);
+        // (records on the side list: handed out to a caller that asked for them, a failure otherwise)
+        if ((h_ctl[0] & (KH_ERR_CAPACITY | KH_ERR_ORDER)) || (h_ctl[5] && (!loc || s.g.two || h_ctl[5] > SkmStage::spill_cap))) {
+            c->stat.retries++;
+            s.staged = false;
+        }
+    }
+    if (!s.staged) {
+        if (loc) return KH_OK;
         return kh_fail(KH_E_CAPACITY, "kh_skm_pack: the records did not fit their regions (low-complexity input?)");
     }
-    const u32 spp = (rec.nslots + (u32)nparts - 1) / (u32)nparts;
+    if (h_ctl[5]) {
+        loc->spill.b = s.d_spill.b; s.d_spill.b = nullptr;
+        loc->spill_n = h_ctl[5];
+    }
+    c->stat.skm_records += h_ctl[2];
+    if (loc) {
+        std::vector<u64> hi(nseq);
+        HIPCHK(hipMemcpyAsync(hi.data(), s.job.inst, 8 * (size_t)nseq, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        loc->inst.assign(nseq, 0);
+        for (int i = 0; i < nseq; ++i) loc->inst[s.L.perm[i]] = hi[i];
+    }
+    for (Tmp* t : {&s.d_seq, &s.d_reg1, &s.d_spill}) { buf_unref(t->b); t->b = nullptr; }   // from here on: the records by slot
+    const u32 spp = (s.g.nslots + (u32)nparts - 1) / (u32)nparts;
     Tmp d_ctl;
-    nsub = std::max<u32>(1, nsub);
+    u32 nsub = loc ? 64u : 1u;   // (the one-GPU use: 64 cursors into its one part, which does not travel)
     // The caller wants every part without gaps (it travels): packed through 64 cursors into a buffer of our own and
     // moved together afterwards — one cursor per part is a queue of returning atomics (78 K slots: 0.8 ms).
-    const bool compact = nsub == 1 && spp >= 2048 && !getenv("KHOICE_SKM_PACK_ONE_CURSOR");
+    const bool compact = nsub == 1 && spp >= 2048;
     if (compact) nsub = 64;
     const size_t off_pn = (64 + 4 * (size_t)nparts * nsub + 7) & ~(size_t)7, off_dup = off_pn + ((4 * (size_t)nparts + 7) & ~(size_t)7),
                  ctl_bytes = off_dup + 8 * 32;
@@ -2629,18 +2617,18 @@ static int skm_pack_impl(kh_ctx* c, int nseq, const uint8_t* const* seqs, const 
     HIPCHK(hipMemsetAsync(count_out, 0, 4 * (size_t)spp * nparts, st));   // (slots past the last one: nothing)
     HIPCHK(hipMemsetAsync(off_out, 0, 4 * (size_t)spp * nparts, st));
     KhSkmPackJob job;
-    job.reg2 = reinterpret_cast<const uint4*>(rec.reg2->p);
-    job.cur2 = rec.cur2;
+    job.reg2 = s.d_reg2.as<uint4>();
+    job.cur2 = s.job.cur2;
     job.out_rec = compact ? d_tmp.as<uint4>() : static_cast<uint4*>(rec_out);
     job.out_mask = compact ? reinterpret_cast<u32*>(d_tmp.as<u8>() + 16 * (size_t)nparts * part_cap) : mask_out;
     job.part_cursor = reinterpret_cast<u32*>(d_ctl.as<u8>() + 64);
     job.slot_count = count_out;
     job.slot_off = off_out;
     job.ctl = d_ctl.as<u32>();
-    job.dup = dup_out ? reinterpret_cast<unsigned long long*>(d_ctl.as<u8>() + off_dup) : nullptr;
+    job.dup = loc ? reinterpret_cast<unsigned long long*>(d_ctl.as<u8>() + off_dup) : nullptr;
     job.part_cap = part_cap;
-    job.cap2 = rec.cap2;
-    job.nslots = rec.nslots;
+    job.cap2 = s.g.cap2;
+    job.nslots = s.g.nslots;
     job.spp = spp;
     job.nsub = nsub;
     c->prof_begin(KC_SKM_PACK);
@@ -2655,7 +2643,7 @@ static int skm_pack_impl(kh_ctx* c, int nseq, const uint8_t* const* seqs, const 
         cj.slot_off = off_out;
         cj.part_n = reinterpret_cast<u32*>(d_ctl.as<u8>() + off_pn);
         cj.part_cap = part_cap;
-        cj.nslots = rec.nslots;
+        cj.nslots = s.g.nslots;
         cj.spp = spp;
         cj.nsub = nsub;
         cj.nparts = (u32)nparts;
@@ -2668,39 +2656,44 @@ static int skm_pack_impl(kh_ctx* c, int nseq, const uint8_t* const* seqs, const 
     HIPCHK(hipStreamSynchronize(st));
     if (h[0] & KH_ERR_ORDER) return kh_fail(KH_E_INTERNAL, "kh_skm_pack: a record carried a tag above 31");
     if (h[0] & KH_ERR_CAPACITY) {
-        if (soft_done) return KH_OK;
+        if (loc) return KH_OK;
         return kh_fail(KH_E_CAPACITY, "kh_skm_pack: a slot or a part overflowed");
     }
     for (int p = 0; p < nparts; ++p) {   // (with several cursors per part: the records, which then lie with gaps)
         part_n[p] = 0;
         for (u32 q = 0; q < nsub; ++q) part_n[p] += h[16 + (size_t)p * nsub + q];
     }
-    if (dup_out) memcpy(dup_out, reinterpret_cast<const u8*>(h.data()) + off_dup, 8 * 32);
-    if (soft_done) *soft_done = true;
+    if (loc) {
+        memcpy(loc->dup, reinterpret_cast<const u8*>(h.data()) + off_dup, 8 * 32);
+        loc->done = true;
+    }
     return KH_OK;
 }
-
-static int skm_phased_impl(kh_ctx* c, int k, int npieces, const void* const* recs, const uint32_t* const* masks,
-                           const uint32_t* const* counts, const uint32_t* const* offs, uint32_t nslots, uint32_t cs,
-                           uint64_t* hist, uint32_t hist_len, u64* dup_out /* [npieces][32] host or null */, bool* soft_done,
-                           const u32* dup_row = nullptr, const u32* join_next = nullptr, u32 share_q8 = 256);
-extern "C" int kh_skm_phased_histogram(kh_ctx* c, int k, int npieces, const void* const* recs, const uint32_t* const* masks,
-                                       const uint32_t* const* counts, const uint32_t* const* offs, uint32_t nslots, uint32_t cs,
-                                       uint64_t* hist, uint32_t hist_len) {
-    return skm_phased_impl(c, k, npieces, recs, masks, counts, offs, nslots, cs, hist, hist_len, nullptr, nullptr);
+extern "C" int kh_skm_pack(kh_ctx* c, int nseq, const uint8_t* const* seqs, const uint64_t* lens, int on_device,
+                           const int* tag_of, int k, uint32_t nslots, int nparts, uint64_t part_cap, void* rec_out,
+                           uint32_t* mask_out, uint32_t* count_out, uint32_t* off_out, uint64_t* part_n) {
+    return skm_pack_impl(c, nseq, seqs, lens, on_device, tag_of, k, nslots, nparts, part_cap, rec_out, mask_out, count_out, off_out,
+                         part_n, nullptr);
 }
+
+// The one-GPU use of kh_skm_phased_histogram (exp1_big_group_skm): the pieces are the phases of one group.
+struct SkmPhases {
+    std::vector<u32> row, join;   // per piece: its phase (the row of `dup` it counts into), "the next piece goes on in the same phase"
+    u32 share_q8 = 256;           // share of a piece's instances that are new to its phase, x 256
+    std::vector<u64> dup;         // out [pieces][32]: repeats under one tag
+    bool done = false;            // an overfilled table: false instead of an error
+};
 static int skm_phased_impl(kh_ctx* c, int k, int npieces, const void* const* recs, const uint32_t* const* masks,
                            const uint32_t* const* counts, const uint32_t* const* offs, uint32_t nslots, uint32_t cs,
-                           uint64_t* hist, uint32_t hist_len, u64* dup_out, bool* soft_done, const u32* dup_row, const u32* join_next,
-                           u32 share_q8) {
-    if (soft_done) *soft_done = false;
+                           uint64_t* hist, uint32_t hist_len, SkmPhases* ph) {
+    if (ph) ph->done = false;
     if (!c || npieces < 1 || !recs || !masks || !counts || !offs || !hist || hist_len < 2 || cs < 1)
         return kh_fail(KH_E_ARG, "kh_skm_phased_histogram: bad argument");
     if (!skm_exchange_k(k)) return kh_fail(KH_E_ARG, "the exchange form takes k = %d .. %d", KH_SKM_MIN_K, KH_SKM_MAX_K);
     HIPCHK(hipSetDevice(c->dev));
     hipStream_t st = c->st;
     const size_t off_pieces = 64, off_hist = (off_pieces + sizeof(KhSkmPiece) * (size_t)npieces + 63) & ~(size_t)63;
-    const size_t off_pdup = off_hist + 8 * (size_t)hist_len, ws_bytes = off_pdup + (dup_out ? 8 * 32 * (size_t)npieces : 0);
+    const size_t off_pdup = off_hist + 8 * (size_t)hist_len, ws_bytes = off_pdup + (ph ? 8 * 32 * (size_t)npieces : 0);
     Tmp d_ws;
     TMP_ALLOC(d_ws, c, ws_bytes);
     std::vector<u8> up(off_hist, 0);
@@ -2710,8 +2703,8 @@ static int skm_phased_impl(kh_ctx* c, int k, int npieces, const void* const* rec
         hp[i].mask = masks[i];
         hp[i].count = counts[i];
         hp[i].off = offs[i];
-        hp[i].dup_row = dup_row ? dup_row[i] : (u32)i;
-        hp[i].join_next = join_next ? join_next[i] : 0u;
+        hp[i].dup_row = ph ? ph->row[i] : (u32)i;
+        hp[i].join_next = ph ? ph->join[i] : 0u;
     }
     HIPCHK(hipMemsetAsync(d_ws.b->p, 0, ws_bytes, st));
     HIPCHK(hipMemcpyAsync(d_ws.b->p, up.data(), off_hist, hipMemcpyHostToDevice, st));
@@ -2719,9 +2712,9 @@ static int skm_phased_impl(kh_ctx* c, int k, int npieces, const void* const* rec
     job.pieces = reinterpret_cast<const KhSkmPiece*>(d_ws.as<u8>() + off_pieces);
     job.hist = reinterpret_cast<unsigned long long*>(d_ws.as<u8>() + off_hist);
     job.ctl = d_ws.as<u32>();
-    job.dup = dup_out ? reinterpret_cast<unsigned long long*>(d_ws.as<u8>() + off_pdup) : nullptr;
+    job.dup = ph ? reinterpret_cast<unsigned long long*>(d_ws.as<u8>() + off_pdup) : nullptr;
     job.npieces = (u32)npieces;
-    job.share_q8 = std::min<u32>(256, std::max<u32>(1, share_q8));
+    job.share_q8 = std::min<u32>(256, std::max<u32>(1, ph ? ph->share_q8 : 256u));
     job.nslots = nslots;
     job.hist_len = hist_len;
     job.cs = cs;
@@ -2733,15 +2726,23 @@ static int skm_phased_impl(kh_ctx* c, int k, int npieces, const void* const* rec
     u32 h_ctl[4];
     HIPCHK(hipMemcpyAsync(h_ctl, d_ws.b->p, 16, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(hist, d_ws.as<u8>() + off_hist, 8 * (size_t)hist_len, hipMemcpyDeviceToHost, st));
-    if (dup_out) HIPCHK(hipMemcpyAsync(dup_out, d_ws.as<u8>() + off_pdup, 8 * 32 * (size_t)npieces, hipMemcpyDeviceToHost, st));
+    if (ph) {
+        ph->dup.assign(32 * (size_t)npieces, 0);
+        HIPCHK(hipMemcpyAsync(ph->dup.data(), d_ws.as<u8>() + off_pdup, 8 * 32 * (size_t)npieces, hipMemcpyDeviceToHost, st));
+    }
     HIPCHK(hipStreamSynchronize(st));
     if (h_ctl[0] & KH_ERR_CAPACITY) {
-        if (soft_done) return KH_OK;
+        if (ph) return KH_OK;
         return kh_fail(KH_E_CAPACITY, "kh_skm_phased_histogram: a slot held more k-mers than its table");
     }
     c->stat.setops++;
-    if (soft_done) *soft_done = true;
+    if (ph) ph->done = true;
     return KH_OK;
+}
+extern "C" int kh_skm_phased_histogram(kh_ctx* c, int k, int npieces, const void* const* recs, const uint32_t* const* masks,
+                                       const uint32_t* const* counts, const uint32_t* const* offs, uint32_t nslots, uint32_t cs,
+                                       uint64_t* hist, uint32_t hist_len) {
+    return skm_phased_impl(c, k, npieces, recs, masks, counts, offs, nslots, cs, hist, hist_len, nullptr);
 }
 
 // One group of more than 64 genomes in the super-k-mer form (one-word keys): sub-batches of up to 32 genomes, each
@@ -2762,7 +2763,7 @@ static int exp1_big_group_skm(kh_ctx* c, int n, const uint8_t* const* seqs, cons
     u64 pos_max = 0;
     std::vector<u64> pos(P, 0);
     for (int p = 0; p < P; ++p) {
-        for (int i = first[p]; i < first[p + 1]; ++i) pos[p] += lens[i] >= (u64)k ? lens[i] - k + 1 : 0;
+        pos[p] = kmer_positions(first[p + 1] - first[p], lens + first[p], k);
         pos_max = std::max(pos_max, pos[p]);
     }
     if (!pos_max) return KH_OK;
@@ -2789,12 +2790,20 @@ static int exp1_big_group_skm(kh_ctx* c, int n, const uint8_t* const* seqs, cons
     std::vector<std::unique_ptr<Tmp>> bufs;
     std::vector<const void*> recs;
     std::vector<const uint32_t*> masks, counts, offs;
-    std::vector<u32> rows, joins;   // per piece: the sub-batch it belongs to, "the next piece goes on in the same phase"
+    SkmPhases ph;
+    auto add_piece = [&](const u8* b, size_t off_mask, size_t off_count, size_t off_off, u32 row, u32 join) {
+        recs.push_back(b);
+        masks.push_back(reinterpret_cast<const u32*>(b + off_mask));
+        counts.push_back(reinterpret_cast<const u32*>(b + off_count));
+        offs.push_back(reinterpret_cast<const u32*>(b + off_off));
+        ph.row.push_back(row);
+        ph.join.push_back(join);
+    };
     std::vector<u64> inst_all(n, 0), dup_all(n, 0);
     hipStream_t st = c->st;
     for (int p = 0; p < P; ++p) {
         const int m = first[p + 1] - first[p];
-        const u64 cap = ((u64)((double)pos[p] * per_kmer * 1.3) + 8192 + 63) & ~63ull;
+        const u64 cap = skm_part_cap(pos[p], per_kmer, 1);
         const size_t off_mask = 16 * (size_t)cap, off_count = off_mask + 4 * (size_t)cap, off_off = off_count + 4 * (size_t)((nslots + 3) & ~3u),
                      bytes = off_off + 4 * (size_t)((nslots + 3) & ~3u);
         bufs.emplace_back(new Tmp);
@@ -2802,35 +2811,28 @@ static int exp1_big_group_skm(kh_ctx* c, int n, const uint8_t* const* seqs, cons
         u8* base = bufs.back()->as<u8>();
         std::vector<int> tag(m);
         for (int j = 0; j < m; ++j) tag[j] = j;
-        std::vector<u64> inst;
-        u64 dup[32], part_n = 0;
-        bool ok = false;
-        SkmRecords keep;
+        u64 part_n = 0;
+        SkmPackLocal loc;
         KHCHK(skm_pack_impl(c, m, seqs + first[p], lens + first[p], on_device, tag.data(), k, nslots, 1, cap, base,
                             reinterpret_cast<u32*>(base + off_mask), reinterpret_cast<u32*>(base + off_count),
-                            reinterpret_cast<u32*>(base + off_off), &part_n, (u32)m, &inst, dup, &ok, 64, &keep));
-        if (!ok) {
+                            reinterpret_cast<u32*>(base + off_off), &part_n, &loc));
+        if (!loc.done) {
             if (dbg) fprintf(stderr, "[skm phased] phase %d: the records did not fit\n", p);
             return KH_OK;
         }
         if (dbg) fprintf(stderr, "[skm phased] phase %d: %llu records travel (cap %llu), %u on the side list\n", p, (unsigned long long)part_n,
-                         (unsigned long long)cap, keep.spill_n);
-        recs.push_back(base);
-        masks.push_back(reinterpret_cast<const u32*>(base + off_mask));
-        counts.push_back(reinterpret_cast<const u32*>(base + off_count));
-        offs.push_back(reinterpret_cast<const u32*>(base + off_off));
-        rows.push_back((u32)p);
-        joins.push_back(0);
-        for (int j = 0; j < m; ++j) { inst_all[first[p] + j] = inst[j]; dup_all[first[p] + j] = dup[j]; }
-        if (keep.spill_n) {
+                         (unsigned long long)cap, loc.spill_n);
+        add_piece(base, off_mask, off_count, off_off, (u32)p, 0);
+        for (int j = 0; j < m; ++j) { inst_all[first[p] + j] = loc.inst[j]; dup_all[first[p] + j] = loc.dup[j]; }
+        if (loc.spill_n) {
             // Overfull slots (low-complexity sequence): what the regions could not hold is on the side list, unmerged and
             // in no order.  It joins the sub-batch's phase as extra pieces — sorted by slot on the host (rare, small),
             // at most 1024 records of a slot per piece.
-            const u32 ns = keep.spill_n;
+            const u32 ns = loc.spill_n;
             std::vector<uint4> hrec(ns);
             std::vector<u32> hslot(ns), order(ns);
-            HIPCHK(hipMemcpyAsync(hrec.data(), keep.spill->p, 16 * (size_t)ns, hipMemcpyDeviceToHost, st));
-            HIPCHK(hipMemcpyAsync(hslot.data(), static_cast<const u8*>(keep.spill->p) + 16 * (size_t)keep.spill_cap, 4 * (size_t)ns,
+            HIPCHK(hipMemcpyAsync(hrec.data(), loc.spill.b->p, 16 * (size_t)ns, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpyAsync(hslot.data(), static_cast<const u8*>(loc.spill.b->p) + 16 * (size_t)SkmStage::spill_cap, 4 * (size_t)ns,
                                   hipMemcpyDeviceToHost, st));
             HIPCHK(hipStreamSynchronize(st));
             for (u32 i = 0; i < ns; ++i) {
@@ -2842,7 +2844,7 @@ static int exp1_big_group_skm(kh_ctx* c, int n, const uint8_t* const* seqs, cons
             u32 longest = 0;
             for (u32 i = 0; i < ns; ++i) longest = std::max(longest, ++run[hslot[i]]);
             const u32 extra = (longest + 1023u) / 1024u;
-            joins.back() = 1;
+            ph.join.back() = 1;
             for (u32 e = 0; e < extra; ++e) {
                 std::vector<uint4> prec;
                 std::vector<u32> pmask, pcount(nslots, 0), poff(nslots, 0);
@@ -2871,27 +2873,21 @@ static int exp1_big_group_skm(kh_ctx* c, int n, const uint8_t* const* seqs, cons
                 HIPCHK(hipMemcpyAsync(eb + e_count, pcount.data(), 4 * (size_t)nslots, hipMemcpyHostToDevice, st));
                 HIPCHK(hipMemcpyAsync(eb + e_off, poff.data(), 4 * (size_t)nslots, hipMemcpyHostToDevice, st));
                 HIPCHK(hipStreamSynchronize(st));   // (the host vectors go out of scope)
-                recs.push_back(eb);
-                masks.push_back(reinterpret_cast<const u32*>(eb + e_mask));
-                counts.push_back(reinterpret_cast<const u32*>(eb + e_count));
-                offs.push_back(reinterpret_cast<const u32*>(eb + e_off));
-                rows.push_back((u32)p);
-                joins.push_back(e + 1 < extra ? 1u : 0u);
+                add_piece(eb, e_mask, e_count, e_off, (u32)p, e + 1 < extra ? 1u : 0u);
             }
             c->stat.big_slots += (u64)std::count_if(run.begin(), run.end(), [](u32 v) { return v != 0; });
         }
     }
-    std::vector<u64> pdup((size_t)recs.size() * 32, 0), hist(hist_len, 0);
-    bool ok = false;
-    KHCHK(skm_phased_impl(c, k, (int)recs.size(), recs.data(), masks.data(), counts.data(), offs.data(), nslots, cs, hist.data(), hist_len,
-                          pdup.data(), &ok, rows.data(), joins.data(), share_q8));
-    if (!ok && share_q8 < 256) {   // a table overfilled: the genomes share less than assumed — rounds for unrelated pieces
+    std::vector<u64> hist(hist_len, 0);
+    ph.share_q8 = share_q8;
+    KHCHK(skm_phased_impl(c, k, (int)recs.size(), recs.data(), masks.data(), counts.data(), offs.data(), nslots, cs, hist.data(), hist_len, &ph));
+    if (!ph.done && share_q8 < 256) {   // a table overfilled: the genomes share less than assumed — rounds for unrelated pieces
         if (dbg) fprintf(stderr, "[skm phased] a table overfilled with rounds sized for shared k-mers: once more\n");
         c->stat.retries++;
-        KHCHK(skm_phased_impl(c, k, (int)recs.size(), recs.data(), masks.data(), counts.data(), offs.data(), nslots, cs, hist.data(),
-                              hist_len, pdup.data(), &ok, rows.data(), joins.data(), 256));
+        ph.share_q8 = 256;
+        KHCHK(skm_phased_impl(c, k, (int)recs.size(), recs.data(), masks.data(), counts.data(), offs.data(), nslots, cs, hist.data(), hist_len, &ph));
     }
-    if (!ok) {
+    if (!ph.done) {
         if (dbg) fprintf(stderr, "[skm phased] the phased union overflowed\n");
         return KH_OK;
     }
@@ -2899,7 +2895,7 @@ static int exp1_big_group_skm(kh_ctx* c, int n, const uint8_t* const* seqs, cons
     u64 bases = 0, isum = 0, dsum = 0;
     for (int p = 0; p < P; ++p)
         for (int i = first[p]; i < first[p + 1]; ++i) {
-            const u64 d = inst_all[i] - dup_all[i] - pdup[(size_t)p * 32 + (i - first[p])];
+            const u64 d = inst_all[i] - dup_all[i] - ph.dup[(size_t)p * 32 + (i - first[p])];
             if (dist) dist[i] = d;
             bases += lens[i]; isum += inst_all[i]; dsum += d;
         }

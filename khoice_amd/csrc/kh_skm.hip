@@ -410,8 +410,8 @@ __global__ __launch_bounds__(SKM_RG_NT, 4) void k_skm_regroup(const KhSkmJob jb)
 //    turns its own entries into histogram bins (popcount per group / number of groups).  Nobody scans the table,
 //    no key is read again, waves without chunks have nothing to do.
 //
-// Geometry <NT, T>: threads and table entries of a workgroup.  <1024, 4096>: 79 KB of LDS, two workgroups per CU;
-// <512, 2048>: 40 KB, four per CU (half-size slots: twice as many independent barrier chains per CU).
+// Geometry <NT, T>: threads and table entries of a workgroup.  <1024, 4096>: 79 KB of LDS, two workgroups per CU.
+// (<512, 2048> with four per CU and <640, 2560> with three were measured slower: DESIGN.md §3, §8.)
 // ------------------------------------------------------------------------------------------
 #ifndef KH_TUNE_SKM_UE
 #define KH_TUNE_SKM_UE 2
@@ -421,20 +421,19 @@ constexpr u32 SKM_OB = SKM_UE == 2 ? 4 : 3;           // bits of a chunk's numbe
 constexpr u32 SKM_PASSES = SKM_UE == 2 ? 3 : 2;       // chunks of a slot: at most SKM_PASSES per thread
 constexpr u32 SKM_HSTRIPE_WORDS = 288;                // histogram copies in LDS: 4 / 2 / 1 per bin for <= 72 / 144 / 255 bins
 template <u32 NT, u32 T> struct SkmUnionGeo {
-    static constexpr u32 T2 = T >= 4096 ? 128 : 64;   // second table (a power of two; the main one need not be)
+    static constexpr u32 T2 = 128;                    // second table
     static constexpr u32 MAXREC = NT;                 // records of a slot (cap2 <= this): one per thread
     static constexpr u32 MAXCH = SKM_PASSES * NT;     // chunks of a slot (after the merge of identical records)
     static constexpr size_t LDS = (size_t)T * 16 + (size_t)T2 * 16 + 1024 + 128 + 256 + (size_t)SKM_HSTRIPE_WORDS * 4 +
                                   (size_t)MAXCH * 2 + (size_t)MAXREC * 4;
     static_assert(MAXREC * 16 <= T * 4, "records are staged in the first half of the key plane");
     static_assert(T2 <= NT && T % 4 == 0, "table planes are cleared 16 bytes at a time");
+    static_assert((T & (T - 1u)) == 0u, "table indices wrap by a mask");
 };
-u32 kh_skm_union_threads(u32 table) { return table == 2048 ? 512u : (table == 2560 ? 640u : 1024u); }
-u32 kh_skm_union_max_cap2(u32 table) { return kh_skm_union_threads(table); }
-u32 kh_skm_union_per_cu(u32 table) { return table == 4096 ? 2u : 3u; }
-size_t kh_skm_union_lds_bytes(u32 table) {
-    return table == 2048 ? SkmUnionGeo<512, 2048>::LDS : (table == 2560 ? SkmUnionGeo<640, 2560>::LDS : SkmUnionGeo<1024, 4096>::LDS);
-}
+using SkmUnion = SkmUnionGeo<1024, 4096>;
+u32 kh_skm_union_max_cap2() { return SkmUnion::MAXREC; }
+u32 kh_skm_union_per_cu() { return 2u; }
+size_t kh_skm_union_lds_bytes() { return SkmUnion::LDS; }
 
 __device__ __forceinline__ u32 key_hash2(u32 lo, u32 hi) { return (lo ^ hi) * 0x9E3779B1u; }
 
@@ -459,8 +458,7 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs) 
     extern __shared__ __attribute__((aligned(16))) u8 lds_raw[];
     using G = SkmUnionGeo<NT, T>;
     constexpr u32 T2 = G::T2, NW = NT / 64;
-    constexpr u32 T2SH = T2 == 128 ? 25 : 26;   // 32 - log2(T2)
-    constexpr bool TPOW2 = (T & (T - 1u)) == 0u;   // (a power of two wraps by a mask; 2560 by compare)
+    constexpr u32 T2SH = 25;   // 32 - log2(T2)
     constexpr int E = (int)SKM_UE;
     constexpr u64 EMPTY = ~0ull;   // never a canonical key: the reverse complement of the all-T k-mer is 0
     // Table planes: keys (8-byte stride), low and high halves of the genome masks (4-byte stride).
@@ -609,7 +607,7 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs) 
                             }
                             pend = false;
                         } else {
-                            hp = TPOW2 ? ((hp + 1u) & (T - 1u)) : (hp + 1u == T ? 0u : hp + 1u);
+                            hp = (hp + 1u) & (T - 1u);
                         }
                     }
                 }
@@ -747,7 +745,7 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs) 
                                 act &= ~(1u << e);
                                 if (fresh) mk |= 1u << e;
                             } else {
-                                slot_[e] = TPOW2 ? ((slot_[e] + 1u) & (T - 1u)) : (slot_[e] + 1u == T ? 0u : slot_[e] + 1u);
+                                slot_[e] = (slot_[e] + 1u) & (T - 1u);
                             }
                         }
                     }
@@ -785,12 +783,12 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs) 
                                 if (level == 1 && probes >= 8u) {   // a crowded second table: on in the main one
                                     level = 2; probes = 0;
                                     S = (u32)(((u64)H * T) >> 32) + (u32)KH_TUNE_SKM_FULL_ROUNDS;
-                                    S = TPOW2 ? (S & (T - 1u)) : (S >= T ? S - T : S);
+                                    S = S & (T - 1u);
                                 } else if (level == 2 && probes >= T) {
                                     atomicOr(jb.ctl, KH_ERR_CAPACITY);   // cannot happen: a round holds at most T keys
                                     mine = false;
                                 } else {
-                                    S = level == 1 ? ((S + 1u) & (T2 - 1u)) : (TPOW2 ? ((S + 1u) & (T - 1u)) : (S + 1u == T ? 0u : S + 1u));
+                                    S = level == 1 ? ((S + 1u) & (T2 - 1u)) : ((S + 1u) & (T - 1u));
                                 }
                             }
                         }
@@ -1572,17 +1570,9 @@ void kh_launch_skm_regroup(const KhSkmJob& job, hipStream_t st) {
     hipLaunchKernelGGL(k_skm_regroup, dim3(job.nb1), dim3(SKM_RG_NT), lds, st, job);
 }
 void kh_launch_skm_union(const KhSkmJob& job, u32 cs, u32 grid, hipStream_t st) {
-    const size_t lds = kh_skm_union_lds_bytes(job.table);
-    if (job.table == 2048) {
-        skm_allow_lds(k_skm_union<512, 2048>, lds);
-        hipLaunchKernelGGL((k_skm_union<512, 2048>), dim3(grid), dim3(512), lds, st, job, cs);
-    } else if (job.table == 2560) {
-        skm_allow_lds(k_skm_union<640, 2560>, lds);
-        hipLaunchKernelGGL((k_skm_union<640, 2560>), dim3(grid), dim3(640), lds, st, job, cs);
-    } else {
-        skm_allow_lds(k_skm_union<1024, 4096>, lds);
-        hipLaunchKernelGGL((k_skm_union<1024, 4096>), dim3(grid), dim3(1024), lds, st, job, cs);
-    }
+    const size_t lds = kh_skm_union_lds_bytes();
+    skm_allow_lds(k_skm_union<1024, 4096>, lds);
+    hipLaunchKernelGGL((k_skm_union<1024, 4096>), dim3(grid), dim3(1024), lds, st, job, cs);
 }
 void kh_launch_skm_pack(const KhSkmPackJob& job, hipStream_t st) {
     if (!job.nslots) return;
