@@ -253,7 +253,8 @@ void kh_unmix_host(int k, const uint64_t *key_words, uint64_t *out_words);
  * kh_skm_pack: this rank's genomes -> minimizer records tagged with the LOCAL group number tag_of[i] (0..31), identical
  *   records merged, packed by owner of their slot into CALLER-ALLOCATED device buffers: rec_out [nparts][part_cap] x 16
  *   bytes, mask_out [nparts][part_cap], count_out / off_out [nparts][slots_per_part] (records of a slot and where they
- *   start in their part); part_n[p] (host) = records for part p.
+ *   start in their part); part_n[p] (host) = records for part p.  A rank without k-mers (nseq = 0, or every sequence
+ *   shorter than k) gets zero counts, offsets and part_n.
  * kh_skm_phased_histogram: on the owner, the pieces received (one per source rank, device pointers) -> hist[c] = number of
  *   distinct k-mers of this rank's slots that occur in c groups of all ranks (c saturating at cs). */
 int kh_skm_exchange_plan(kh_ctx *ctx, int k, uint64_t positions_max, uint32_t fan_max, int nparts, uint32_t *nslots,

@@ -2552,7 +2552,8 @@ static int skm_pack_impl(kh_ctx* c, int nseq, const uint8_t* const* seqs, const 
                          const int* tag_of, int k, uint32_t nslots, int nparts, uint64_t part_cap, void* rec_out,
                          uint32_t* mask_out, uint32_t* count_out, uint32_t* off_out, uint64_t* part_n, SkmPackLocal* loc) {
     if (loc) loc->done = false;
-    if (!c || !seqs || !lens || !tag_of || nseq <= 0 || nparts < 1 || !rec_out || !mask_out || !count_out || !off_out || !part_n)
+    if (!c || nseq < 0 || (nseq && (!seqs || !lens || !tag_of)) || nparts < 1 || !nslots || !rec_out || !mask_out || !count_out ||
+        !off_out || !part_n)
         return kh_fail(KH_E_ARG, "kh_skm_pack: bad argument");
     if (!skm_exchange_k(k)) return kh_fail(KH_E_ARG, "the exchange form takes k = %d .. %d", KH_SKM_MIN_K, KH_SKM_MAX_K);
     int ntags = 0;
@@ -2567,6 +2568,15 @@ static int skm_pack_impl(kh_ctx* c, int nseq, const uint8_t* const* seqs, const 
         for (int i = 0; i < nseq; ++i) seen[tag_of[i]] = 1;
         for (int t = 0; t < ntags; ++t)
             if (!seen[t]) return kh_fail(KH_E_ARG, "kh_skm_pack: tag %d has no sequence", t);
+    }
+    const u32 spp = (nslots + (u32)nparts - 1) / (u32)nparts;
+    if (!loc && !kmer_positions(nseq, lens, k)) {
+        // a rank without k-mers (no sequences, or all shorter than k) still sends its parts: all empty
+        HIPCHK(hipMemsetAsync(count_out, 0, 4 * (size_t)spp * nparts, st));
+        HIPCHK(hipMemsetAsync(off_out, 0, 4 * (size_t)spp * nparts, st));
+        HIPCHK(hipStreamSynchronize(st));
+        for (int p = 0; p < nparts; ++p) part_n[p] = 0;
+        return KH_OK;
     }
     SkmStage s(c);
     KHCHK(skm_prepare(c, nseq, seqs, lens, on_device, tag_of, ntags, k, /*by_group=*/true, nslots, loc ? (u32)nseq : 0u, &s));
@@ -2601,7 +2611,6 @@ static int skm_pack_impl(kh_ctx* c, int nseq, const uint8_t* const* seqs, const 
         for (int i = 0; i < nseq; ++i) loc->inst[s.L.perm[i]] = hi[i];
     }
     for (Tmp* t : {&s.d_seq, &s.d_reg1, &s.d_spill}) { buf_unref(t->b); t->b = nullptr; }   // from here on: the records by slot
-    const u32 spp = (s.g.nslots + (u32)nparts - 1) / (u32)nparts;
     Tmp d_ctl;
     u32 nsub = loc ? 64u : 1u;   // (the one-GPU use: 64 cursors into its one part, which does not travel)
     // The caller wants every part without gaps (it travels): packed through 64 cursors into a buffer of our own and

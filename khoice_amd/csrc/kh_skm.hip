@@ -1184,14 +1184,17 @@ __global__ __launch_bounds__(NT) void k_skm_pack(const KhSkmPackJob jb) {
 // before it and rewrites the offsets of its slots.
 __global__ __launch_bounds__(256) void k_skm_pack_compact(const KhSkmCompactJob jb) {
     const u32 sub = blockIdx.x, part = blockIdx.y, tid = threadIdx.x;
+    const u64 subcap = jb.part_cap / jb.nsub;
+    // (a cursor that ran past its sub-range has counted a slot k_skm_pack refused — the host reports the overflow; the
+    // clamp keeps the copy inside the part)
+    auto used = [&](u32 q) { const u32 v = jb.cursors[part * jb.nsub + q]; return (u64)v < subcap ? v : (u32)subcap; };
     u32 before = 0, total = 0;
     for (u32 q = 0; q < jb.nsub; ++q) {   // uniform
-        const u32 v = jb.cursors[part * jb.nsub + q];
+        const u32 v = used(q);
         before += q < sub ? v : 0u;
         total += v;
     }
-    const u32 n = jb.cursors[part * jb.nsub + sub];
-    const u64 subcap = jb.part_cap / jb.nsub;
+    const u32 n = used(sub);
     const u64 src = (u64)part * jb.part_cap + (u64)sub * subcap, dst = (u64)part * jb.part_cap + before;
     for (u32 i = tid + 256u * blockIdx.z; i < n; i += 256u * gridDim.z) {   // (z: slices of the copy)
         jb.out_rec[dst + i] = jb.tmp_rec[src + i];

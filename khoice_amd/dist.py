@@ -408,6 +408,24 @@ def across_records_exchange(ops, eng, seqs, group_of: Sequence[int], k: int, cs:
     return out if overlap is None else (out, local)
 
 
+RECORDS_MAX_GROUPS = 32   # a record's mask has one bit per local group
+
+
+def exchange_form(k: int, group_of: Sequence[int], group=None, device=None) -> str:
+    """"records" or "sets": the form of steps 7-8 for 17 <= k <= 32, the SAME on every rank.  The records form needs
+    at most 32 groups on every rank; one all_reduce(MAX) of [local groups, not applicable here] decides, so a rank
+    holding 33 groups sends all of them to the set exchange.  A rank without sequences counts 0 groups.
+    Collective: every rank must call it."""
+    import os
+    from .engine import Engine
+    lo, hi = Engine.SKM_EXCHANGE_K
+    ngroups = max(group_of) + 1 if len(group_of) else 0
+    off = not (lo <= k <= hi) or bool(os.environ.get("KHOICE_DIST_SET_EXCHANGE"))
+    t = torch.tensor([ngroups, int(off)], dtype=torch.int64, device=device)
+    dist.all_reduce(t, op=dist.ReduceOp.MAX, group=group)
+    return "records" if int(t[0]) <= RECORDS_MAX_GROUPS and not int(t[1]) else "sets"
+
+
 def exp1_step(eng, seqs, group_of: Sequence[int], k: int, cs: int = 5000, hist_len: int = 5001,
               group=None):
     """One benchmark step on N GPUs: steps 1-6 locally, steps 7-8 through the exchange.
@@ -420,13 +438,16 @@ def exp1_step(eng, seqs, group_of: Sequence[int], k: int, cs: int = 5000, hist_l
         res["across_hist"] = across_groups_auto(ops, gsets, k, cs, hist_len, group)
         del res["group_sets"]
         return res
-    import os
-    lo, hi = eng.SKM_EXCHANGE_K
-    if lo <= k <= hi and max(group_of) < 32 and not os.environ.get("KHOICE_DIST_SET_EXCHANGE"):
+    if exchange_form(k, group_of, group, ops.comm_device) == "records":
         # the super-k-mer form on every rank: steps 1-6 locally (no set is built), steps 7-8 by exchange of records
-        # (the local run is handed to the exchange: it runs while the packed records travel)
-        across, res = across_records_exchange(ops, eng, seqs, group_of, k, cs, hist_len, group,
-                                              overlap=lambda: eng.exp1_run(seqs, group_of, k, cs=cs, hist_len=hist_len, across=False))
+        # (the local run is handed to the exchange: it runs while the packed records travel; a rank without sequences
+        # has nothing to run locally)
+        def local():
+            if not len(seqs):
+                return {"within_hist": np.zeros((0, hist_len), dtype=np.uint64), "across_hist": None,
+                        "distinct_per_seq": np.zeros(0, dtype=np.uint64)}
+            return eng.exp1_run(seqs, group_of, k, cs=cs, hist_len=hist_len, across=False)
+        across, res = across_records_exchange(ops, eng, seqs, group_of, k, cs, hist_len, group, overlap=local)
         res["across_hist"] = across
         res["exchange"] = "records"
         return res

@@ -326,8 +326,6 @@ def records_worker(rank, world, port, groups_per_rank, q):
             for j in range(2):
                 seqs.append(synth.clean_text(synth.genome_records(first + g, j, 3000, anc)))
                 group_of.append(g)
-        if not seqs:                       # a rank without groups still takes part in every collective
-            seqs, group_of = [b"ACGT"], [0]
         ops = OracleOps(K, rank, world)
         hist = kdist.across_records_exchange(ops, RecordStandIn(rank, world), seqs, group_of, K, 5000, 64)
         q.put((rank, hist.tolist()))
@@ -353,3 +351,35 @@ def test_records_exchange_matches_single_process(layout):
     for _, h in got:
         assert h == want
     assert sum(want[2:]) > 0
+
+
+def form_worker(rank, world, port, groups_per_rank, q):
+    from khoice_amd import dist as kdist
+    dist.init_process_group("gloo", init_method=f"tcp://127.0.0.1:{port}", rank=rank, world_size=world)
+    try:
+        group_of = [g for g in range(groups_per_rank[rank]) for _ in range(2)]
+        q.put((rank, kdist.exchange_form(K, group_of), kdist.exchange_form(41, group_of)))
+    finally:
+        dist.destroy_process_group()
+
+
+@pytest.mark.parametrize("layout,want", [([33, 3], "sets"), ([0, 3], "records"), ([3, 3], "records")])
+def test_exchange_form_is_collective(layout, want):
+    """exp1_step's choice between the records and the set exchange is agreed by all ranks: a rank with 33 groups sends
+    every rank to the set exchange (their collectives differ: ranks that chose apart would deadlock), a rank without
+    sequences counts no groups and does not raise, and k outside the records form's range gives sets everywhere."""
+    world = len(layout)
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = free_port()
+    procs = [ctx.Process(target=form_worker, args=(r, world, port, layout, q)) for r in range(world)]
+    for p in procs:
+        p.start()
+    got = [q.get(timeout=90) for _ in range(world)]
+    for p in procs:
+        p.join(timeout=60)
+        assert p.exitcode == 0
+    assert sorted(r for r, _, _ in got) == list(range(world))
+    for _, form, form41 in got:
+        assert form == want
+        assert form41 == "sets"
