@@ -101,8 +101,8 @@ def test_skm_two_word_keys_edges_and_shapes(eng):
     seqs.append(body[:8192 + 62].encode())
     seqs.append(body[:63].encode())
     group_of = [i % 4 for i in range(len(seqs))]
-    for k in (33, 41, 63):
-        check(eng, seqs, group_of, k, cs=5000, hist_len=64, expect_skm=False)
+    for k in (33, 41, 63):   # every one of these inputs runs in the two-word form (none declines)
+        check(eng, seqs, group_of, k, cs=5000, hist_len=64)
     # 64 operands, repeats inside genomes
     sizes = [1, 2, 30, 7, 24]
     seqs, group_of = [], []
