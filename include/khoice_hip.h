@@ -16,6 +16,9 @@
  *   - k-mers are 2k-bit integers, first base most significant, A=0 C=1 G=2 T=3;
  *     host-side key arrays use W = ceil(2k/64) little-endian 64-bit words per key
  *   - there is NO CPU fallback: without a usable HIP device every call fails
+ *   - counters and cs are 32-bit: every set operation combines the whole counters of its
+ *     operands (sums and differences in 64-bit arithmetic) and saturates the result at cs, so
+ *     any counter and any cs in [1, 2^32 - 1] is exact; a counter of 0 never occurs in a set
  */
 #ifndef KHOICE_HIP_H
 #define KHOICE_HIP_H
@@ -174,7 +177,8 @@ int kh_set_info(const kh_set *set, uint64_t *n, int *k, int *words_per_key, int 
 int kh_set_counter_max(const kh_set *set, uint32_t *counter_max);
 /* copy to host in storage order (NOT sorted by key): keys un-mixed, n*W words; counts n */
 int kh_set_download(kh_ctx *ctx, const kh_set *set, uint64_t *keys, uint32_t *counts);
-/* build a set from host arrays of DISTINCT keys in any order (counts may be NULL => 1) */
+/* build a set from host arrays of DISTINCT keys in any order (counts may be NULL => 1); a key of
+ * 4^k or more, or a counter of 0, fails with KH_E_ARG */
 int kh_set_upload(kh_ctx *ctx, int k, uint64_t n, const uint64_t *keys, const uint32_t *counts,
                   kh_set **out);
 /* raw device views for zero-copy exchange (multi-GPU): mixed keys sorted ascending,

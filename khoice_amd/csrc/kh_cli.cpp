@@ -346,7 +346,9 @@ struct Parser {
     }
 };
 
-const uint32_t kNoSat = 0x7fffffffu;   // intermediate results never saturate
+// intermediate results saturate only at the counter width: exact as long as no intermediate
+// counter of the expression passes 2^32 - 1
+const uint32_t kNoSat = 0xffffffffu;
 
 Set eval(const Expr& e, std::map<std::string, Set>& inputs, uint32_t cs, bool top) {
     if (!e.op) {

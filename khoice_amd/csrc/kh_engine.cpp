@@ -1067,14 +1067,15 @@ extern "C" int kh_union_sum(kh_ctx* c, const kh_set* const* sets, int nsets, uin
         std::vector<const kh_set*> in(sets, sets + nsets);
         return run_setop(c, in, KH_OP_UNION, KH_OC_SUM, cs, out, hist, hist_len);
     }
-    // fan-in above one launch's limit: sum groups of 64 without saturation, then sum the sums
+    // fan-in above one launch's limit: sum groups of up to KH_MAX_INPUT_SETS, then sum the sums.
+    // The partial sums saturate at cs already: exact, since counters are never negative.
     std::vector<kh_set*> partial;
     auto cleanup = [&]() { for (auto* p : partial) kh_set_free(p); };
     for (int i = 0; i < nsets; i += KH_MAX_INPUT_SETS) {
         const int m = std::min(KH_MAX_INPUT_SETS, nsets - i);
         std::vector<const kh_set*> in(sets + i, sets + i + m);
         kh_set* p = nullptr;
-        int r = run_setop(c, in, KH_OP_UNION, KH_OC_SUM, 0x7fffffffu, &p, nullptr, 0);
+        int r = run_setop(c, in, KH_OP_UNION, KH_OC_SUM, cs, &p, nullptr, 0);
         if (r != KH_OK) { cleanup(); return r; }
         partial.push_back(p);
     }
@@ -1350,6 +1351,15 @@ extern "C" int kh_set_upload(kh_ctx* c, int k, uint64_t n, const uint64_t* keys,
     KHCHK(check_k(k));
     HIPCHK(hipSetDevice(c->dev));
     const int W = k <= 32 ? 1 : 2;
+    // a key of 4^k or more would mix into a wrong slot and come back as another key; a zero
+    // counter would be carried into unions, which never hold one
+    const u64 top_mask = W == 1 ? ~kh_mask(2 * k) : ~kh_mask(2 * k - 64);
+    for (u64 i = 0; i < n; ++i) {
+        if (keys[i * W + W - 1] & top_mask)
+            return kh_fail(KH_E_ARG, "kh_set_upload: key %llu is not below 4^%d", (unsigned long long)i, k);
+        if (counts && counts[i] == 0)
+            return kh_fail(KH_E_ARG, "kh_set_upload: counter %llu is 0", (unsigned long long)i);
+    }
     // order by mixed key on the host (upload is a test / interchange path, not the hot path)
     std::vector<u64> mixed((size_t)n * W);
     for (u64 i = 0; i < n; ++i) kh_mix_host(k, keys + i * W, mixed.data() + i * W);

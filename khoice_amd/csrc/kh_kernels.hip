@@ -1499,7 +1499,10 @@ __device__ __forceinline__ long long combine_counters(int mode, long long a, lon
 
 // PAY=false: n-ary union of sets whose counters are all 1, counters summed: the counter of a
 // key is simply the length of its run, no payload array needed (the step_3 / step_7 case,
-// exp_type_1.smk:182,250).  PAY=true: payload = counter | (operand index > 0) << 31.
+// exp_type_1.smk:182,250).  PAY=true: payload = the whole 32-bit counter for an n-ary union (it
+// only ever sums); for a binary operation (nsets == 2) it is the element's gather position instead,
+// which tells the operand apart (position >= the slice start of operand 1) and from which `eval`
+// reads the counter back, so that no counter bit has to carry the operand.
 template <int W, bool PAY>
 __global__ __launch_bounds__(KH_SORT_THREADS, KH_SORT_WAVES_PER_SIMD) void k_setop(
     const KhSetopBatch batch, u32 njobs, u32 cap, int k, int op, int mode, u32 cs, u32 hist_len,
@@ -1564,6 +1567,11 @@ __global__ __launch_bounds__(KH_SORT_THREADS, KH_SORT_WAVES_PER_SIMD) void k_set
     KmerKey<W> kreg[E];
     u32 preg[E];
     u32 n = 0;
+    // binary operations: the slices of both operands, for `eval` to read counters back by gather
+    // position (a binary operation always takes the wave-local form)
+    const bool binary = PAY && nsets == 2;
+    u32 b_soff1 = 0, b_uni0 = 0, b_uni1 = 0;
+    u64 b_beg0 = 0, b_beg1 = 0, b_cnt0 = 0, b_cnt1 = 0;
     if (wave_local) {
         const bool have = lane < nsets;
         if (!early && have) {
@@ -1606,6 +1614,15 @@ __global__ __launch_bounds__(KH_SORT_THREADS, KH_SORT_WAVES_PER_SIMD) void k_set
             const u32 hi = (u32)__builtin_amdgcn_readlane((int)(u32)(v >> 32), (int)src);
             return ((u64)hi << 32) | lo;
         };
+        if (binary) {
+            b_soff1 = (u32)__builtin_amdgcn_readlane((int)soff, 1);
+            b_beg0 = lane64(sbeg, 0);
+            b_beg1 = lane64(sbeg, 1);
+            b_cnt0 = lane64(scnt, 0);
+            b_cnt1 = lane64(scnt, 1);
+            b_uni0 = (u32)__builtin_amdgcn_readlane((int)suni, 0);
+            b_uni1 = (u32)__builtin_amdgcn_readlane((int)suni, 1);
+        }
 #pragma unroll
         for (int e = 0; e < E; ++e) {
             kreg[e] = key_zero<W>();
@@ -1636,10 +1653,7 @@ __global__ __launch_bounds__(KH_SORT_THREADS, KH_SORT_WAVES_PER_SIMD) void k_set
                 kreg[e] = reinterpret_cast<const KmerKey<W>*>(my_skey)[idx];
                 if (PAY) {
                     const u32* cp = reinterpret_cast<const u32*>(my_scnt);
-                    u32 c = cp ? cp[idx] : my_suni;
-                    if (c > 0x7fffffffu) c = 0x7fffffffu;
-                    // binary operations tag the second operand; n-ary unions only ever sum
-                    preg[e] = c | ((nsets == 2 && ga == 1) ? 0x80000000u : 0u);
+                    preg[e] = binary ? i : (cp ? cp[idx] : my_suni);
                 }
             }
         }
@@ -1734,10 +1748,7 @@ __global__ __launch_bounds__(KH_SORT_THREADS, KH_SORT_WAVES_PER_SIMD) void k_set
             kreg[e] = reinterpret_cast<const KmerKey<W>*>(skey[ga])[idx];
             if (PAY) {
                 const u32* cp = reinterpret_cast<const u32*>(scnt[ga]);
-                u32 c = cp ? cp[idx] : suni[ga];
-                if (c > 0x7fffffffu) c = 0x7fffffffu;
-                // binary operations tag the second operand; n-ary unions only ever sum
-                preg[e] = c | ((nsets == 2 && ga == 1) ? 0x80000000u : 0u);
+                preg[e] = cp ? cp[idx] : suni[ga];   // more than 64 operands: an n-ary union
             }
         }
     }
@@ -1761,7 +1772,12 @@ __global__ __launch_bounds__(KH_SORT_THREADS, KH_SORT_WAVES_PER_SIMD) void k_set
             bool ha = false, hb = false;
             for (u32 t = h0; t < h1; ++t) {
                 const u32 p = pay[t];
-                if (p >> 31) { cb += p & 0x7fffffffu; hb = true; } else { ca += p; ha = true; }
+                if (!binary) { ca += p; ha = true; continue; }
+                const bool second = p >= b_soff1;
+                const u32* cp = reinterpret_cast<const u32*>(second ? b_cnt1 : b_cnt0);
+                const u64 idx = second ? b_beg1 + (p - b_soff1) : b_beg0 + p;
+                const u32 v = cp ? cp[idx] : (second ? b_uni1 : b_uni0);
+                if (second) { cb += v; hb = true; } else { ca += v; ha = true; }
             }
             switch (op) {
                 case KH_OP_UNION:

@@ -123,3 +123,23 @@ def test_read_fasta_host_gives_the_oracles_records(lib, tmp_path):
             got = E.Engine.read_fasta(eng, str(p)).decode("latin-1")
             want = [r for r in O.fasta_records(data) if r]
             assert [r for r in got.split("\n") if r] == want, name
+
+
+@pytest.mark.parametrize("k", list(range(1, 65)))
+def test_numpy_mix_restatement_matches_host_mix(lib, k):
+    # tests/util.py's vectorised mix (used to place keys in chosen slots) against kh_mix_host / kh_unmix_host
+    from tests.util import mix_np, top32_np, unmix_np
+    rng = np.random.default_rng(1000 + k)
+    w = 1 if k <= 32 else 2
+    nbits = 2 * k
+    vals = [0, 1, (1 << nbits) - 1, (1 << nbits) - 2] + [
+        int.from_bytes(rng.bytes(16), "little") & ((1 << nbits) - 1) for _ in range(200)]
+    keys = np.array([[v & (2**64 - 1), v >> 64][:w] for v in vals], dtype=np.uint64)
+    mixed = mix_np(k, keys)
+    for i in range(keys.shape[0]):
+        assert (mixed[i] == E.mix_host(k, keys[i])).all(), (k, vals[i])
+        assert (unmix_np(k, mixed[i:i + 1])[0] == E.unmix_host(k, mixed[i])).all(), (k, vals[i])
+        mv = int(mixed[i, 0]) | (int(mixed[i, 1]) << 64 if w == 2 else 0)
+        top = mv >> (nbits - 32) if nbits >= 32 else (mv << (32 - nbits))
+        assert int(top32_np(k, mixed[i:i + 1])[0]) == top
+    assert (unmix_np(k, mixed) == keys).all()
