@@ -785,7 +785,11 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs) 
                                     S = (u32)(((u64)H * T) >> 32) + (u32)KH_TUNE_SKM_FULL_ROUNDS;
                                     S = S & (T - 1u);
                                 } else if (level == 2 && probes >= T) {
-                                    atomicOr(jb.ctl, KH_ERR_CAPACITY);   // cannot happen: a round holds at most T keys
+                                    // The main table is full.  With R > 1 the key subsets are picked by hash bits, not by
+                                    // count: a skewed slot (up to SKM_PASSES x NT chunks) can put more than T + T2
+                                    // distinct keys into one subset.  The key is dropped here; the host sees the error,
+                                    // counts a retry and hands the whole call to the key-array form.
+                                    atomicOr(jb.ctl, KH_ERR_CAPACITY);
                                     mine = false;
                                 } else {
                                     S = level == 1 ? ((S + 1u) & (T2 - 1u)) : ((S + 1u) & (T - 1u));
