@@ -20,6 +20,7 @@
 #include "../../include/khoice_hip.h"
 #include "kh_engine.h"
 #include "kh_launch.h"
+#include "kh_skm_rec.h"
 
 // ------------------------------------------------------------------------------ errors
 static thread_local std::string g_last_error;
@@ -2875,7 +2876,7 @@ static int exp1_big_group_skm(kh_ctx* c, int n, const uint8_t* const* seqs, cons
                     for (u32 j = lo; j < hi; ++j) {
                         const uint4 r = hrec[order[i + j]];
                         prec.push_back(r);
-                        pmask.push_back(1u << ((r.w >> 21) & 31u));
+                        pmask.push_back(1u << (SkmRec1::tag(r.w) & 31u));   // (tags of the exchange form are below 32)
                     }
                     i += len;
                 }

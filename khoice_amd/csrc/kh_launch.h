@@ -119,8 +119,8 @@ struct KhTagJob {
 
 // ---- super-k-mer form of the fused path (kh_skm.hip): records of n consecutive k-mers that share their
 // minimizer slot, partitioned in two levels (coarse bucket, then slot = coarse * S + fine), then one LDS
-// hash set per slot.  A record is 16 bytes: bits [0, 2(n+k-1)) the bases (base j at bits 2j, A0 C1 G2 T3),
-// bits 108..116 the fine index of its slot, 117..122 the genome (operand) number, 123..127 n.
+// hash set per slot.  A record is 16 bytes (32 with two-word keys): the bases, the fine index of its slot, the genome
+// (operand) number and n; kh_skm_rec.h is the one definition of both formats.
 #ifndef KH_TUNE_SKM_STAGE
 #define KH_TUNE_SKM_STAGE 2048   // (1024 / 1536 / 2048 / 2304 / 2560: scatter 0.82 / 0.68 / 0.645 / 0.69 / 0.735 ms; above 2048 only two workgroups fit a CU)
 #endif
@@ -162,7 +162,6 @@ struct KhSkmJob {
 };
 bool kh_skm_supports_w(u32 w);   // m-mers per k-mer the scatter kernel is instantiated for
 size_t kh_skm_scatter_lds_bytes(u32 nb1);
-size_t kh_skm_regroup_lds_bytes(u32 S);
 size_t kh_skm_union_lds_bytes();
 u32 kh_skm_union_max_cap2();   // records of a slot the union takes
 void kh_launch_skm_scatter(const KhSkmJob& job, u32 ntiles, hipStream_t st);
@@ -217,7 +216,6 @@ struct KhSkmPhasedJob {
     int k;
 };
 constexpr u32 KH_SKM_PHASED_MAX_DUP_PIECES = 32;   // pieces whose repeats can be counted (LDS counters)
-size_t kh_skm_pack_lds_bytes();
 size_t kh_skm_phased_lds_bytes();
 void kh_launch_skm_pack(const KhSkmPackJob& job, hipStream_t st);
 void kh_launch_skm_phased(const KhSkmPhasedJob& job, u32 grid, hipStream_t st);
@@ -231,7 +229,6 @@ u32 kh_skm2_table();
 u32 kh_skm2_union_per_cu();   // workgroups of the two-word union that fit a CU
 void kh_launch_skm2_big(const KhSkmJob& job, u32 cs, u32 nbig, hipStream_t st);
 size_t kh_skm2_scatter_lds_bytes(u32 nb1);
-size_t kh_skm2_regroup_lds_bytes(u32 S);
 size_t kh_skm2_union_lds_bytes(u32 nbins);
 void kh_launch_skm2_scatter(const KhSkmJob& job, u32 ntiles, hipStream_t st);
 void kh_launch_skm2_regroup(const KhSkmJob& job, hipStream_t st);

@@ -50,9 +50,6 @@ void kh_debug_set_stamps_skm(u64* p) { (void)hipMemcpyToSymbol(HIP_SYMBOL(g_skm_
 #else
 #define SKM_MARK(name) do {} while (0)
 #endif
-#ifndef KH_TUNE_SKM_FULL_ROUNDS
-#define KH_TUNE_SKM_FULL_ROUNDS 4   // probe rounds made by all keys of a thread together; the rest one key per lane (1 / 2 / 3 / 4 / 5 / 8 rounds: union 16.3 / 3.33 / 1.59 / 1.51 / 1.52 / 1.55 ms)
-#endif
 #ifndef KH_TUNE_SKM_SCATTER_PREFETCH
 #define KH_TUNE_SKM_SCATTER_PREFETCH 0   // 1: the next sub-tile's bases wait in registers while this one is processed (0.656 ms against 0.624: three workgroups per CU hide the load as well, with fewer registers)
 #endif
@@ -67,7 +64,6 @@ size_t kh_skm_scatter_lds_bytes(u32 nb1) {
     return flush_lds_bytes<SKM_CAP>(nbk) + (size_t)SKM_CW * 4 + (((size_t)SKM_CW * 2 + 15) & ~(size_t)15) + 64 * 4 + 4 * 32 * 4 +
            (size_t)SKM_NT * 8 + 64;
 }
-size_t kh_skm_regroup_lds_bytes(u32 S) { return flush_lds_bytes<SKM_RG_CAP>((S + 3) & ~3u) + (size_t)((S + 3) & ~3u) * 4 + 64; }
 
 // ------------------------------------------------------------------------------------------
 // S1: bases -> records, partitioned by coarse bucket.  WW = m-mers per k-mer (k - m + 1), compile time:
@@ -300,7 +296,7 @@ __global__ __launch_bounds__(SKM_NT, KH_TUNE_SKM_SCATTER_WAVES) void k_skm_scatt
                     const u32 x0 = __builtin_amdgcn_alignbit(c1, c0, sh);
                     const u32 x1 = keep(__builtin_amdgcn_alignbit(c2, c1, sh), bits - 32);
                     const u32 x2 = keep(__builtin_amdgcn_alignbit(c3, c2, sh), bits - 64);
-                    const u32 x3 = keep(__builtin_amdgcn_alignbit(c4, c3, sh), bits - 96) | (fine << 12) | (rtag << 21) | (n << 27);
+                    const u32 x3 = keep(__builtin_amdgcn_alignbit(c4, c3, sh), bits - 96) | SkmRec1::header(fine, rtag, n);
                     L.stage[at] = make_uint4(x0, x1, x2, x3);
                     L.sid[at] = (u16)coarse;
                     atomicAdd(&L.bcnt[coarse], 1u);
@@ -336,59 +332,6 @@ __global__ __launch_bounds__(SKM_NT, KH_TUNE_SKM_SCATTER_WAVES) void k_skm_scatt
 }
 
 // ------------------------------------------------------------------------------------------
-// S2a: one workgroup per coarse bucket walks its records 8192 at a time and regroups them by fine slot.
-// The workgroup owns every slot of its bucket: the slot cursors live in LDS, no global atomic is needed.
-// ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(SKM_RG_NT, 4) void k_skm_regroup(const KhSkmJob jb) {
-    extern __shared__ __attribute__((aligned(16))) u8 lds_raw[];
-    constexpr int RPT = (int)(SKM_RG_CAP / SKM_RG_NT);
-    const u32 nbk = (jb.S + 3) & ~3u;
-    const FlushLds L = flush_lds<SKM_RG_CAP>(lds_raw, nbk);
-    u32* lcur = reinterpret_cast<u32*>(lds_raw + flush_lds_bytes<SKM_RG_CAP>(nbk));   // [nbk] records written per slot
-    const u32 tid = threadIdx.x;
-    const u32 b = blockIdx.x;
-    const u32 have = jb.cur1[(size_t)b * KH_SKM_CUR1_STRIDE];
-    const u32 cnt = have < jb.cap1 ? have : jb.cap1;
-    const u32 first_slot = b * jb.S;
-    const u32 nfine = jb.nslots - first_slot < jb.S ? jb.nslots - first_slot : jb.S;
-    for (u32 i = tid; i < nbk; i += SKM_RG_NT) { L.bcnt[i] = 0; lcur[i] = 0; }
-    const uint4* __restrict__ src = jb.reg1 + (u64)b * jb.cap1;
-    uint4* __restrict__ dst = jb.reg2 + (u64)first_slot * jb.cap2;
-    uint4 nx[RPT];
-#pragma unroll
-    for (int r = 0; r < RPT; ++r) {
-        const u32 i = tid + (u32)r * SKM_RG_NT;
-        nx[r] = i < cnt ? src[i] : make_uint4(0, 0, 0, 0);
-    }
-    __syncthreads();
-    for (u32 start = 0; start < cnt; start += SKM_RG_CAP) {
-        const u32 n = cnt - start < SKM_RG_CAP ? cnt - start : SKM_RG_CAP;
-#pragma unroll
-        for (int r = 0; r < RPT; ++r) {
-            const u32 i = tid + (u32)r * SKM_RG_NT;
-            if (i < n) {
-                u32 fine = (nx[r].w >> 12) & 511u;
-                if (fine >= nfine) { fine = 0; atomicOr(jb.ctl, KH_ERR_ORDER); }   // a corrupt record never leaves its bucket
-                L.stage[i] = nx[r];
-                L.sid[i] = (u16)fine;
-                atomicAdd(&L.bcnt[fine], 1u);
-            }
-        }
-        // the next round's records: in flight during the flush
-#pragma unroll
-        for (int r = 0; r < RPT; ++r) {
-            const u32 i = start + SKM_RG_CAP + tid + (u32)r * SKM_RG_NT;
-            nx[r] = i < cnt ? src[i] : make_uint4(0, 0, 0, 0);
-        }
-        __syncthreads();
-        SkmSpill sp;
-        sp.rec = jb.spill_rec; sp.slot = jb.spill_slot; sp.n = jb.ctl + 5; sp.cap = jb.spill_cap; sp.first_slot = first_slot;
-        skm_flush<SKM_RG_NT, SKM_RG_CAP, true>(L, n, nfine, lcur, dst, jb.cap2, jb.ctl, sp);
-    }
-    for (u32 i = tid; i < nfine; i += SKM_RG_NT) jb.cur2[first_slot + i] = lcur[i];
-}
-
-// ------------------------------------------------------------------------------------------
 // S2b: one slot per workgroup -> LDS hash set {canonical k-mer, genome mask} -> histogram bins.
 //
 // 1. Identical records are expanded ONCE.  A record is a content-defined piece of sequence (a run of k-mers with
@@ -419,7 +362,6 @@ __global__ __launch_bounds__(SKM_RG_NT, 4) void k_skm_regroup(const KhSkmJob jb)
 constexpr u32 SKM_UE = KH_TUNE_SKM_UE;                // k-mers per chunk (2 or 4)
 constexpr u32 SKM_OB = SKM_UE == 2 ? 4 : 3;           // bits of a chunk's number inside its record (n <= 31)
 constexpr u32 SKM_PASSES = SKM_UE == 2 ? 3 : 2;       // chunks of a slot: at most SKM_PASSES per thread
-constexpr u32 SKM_HSTRIPE_WORDS = 288;                // histogram copies in LDS: 4 / 2 / 1 per bin for <= 72 / 144 / 255 bins
 template <u32 NT, u32 T> struct SkmUnionGeo {
     static constexpr u32 T2 = 128;                    // second table
     static constexpr u32 MAXREC = NT;                 // records of a slot (cap2 <= this): one per thread
@@ -436,6 +378,56 @@ u32 kh_skm_union_per_cu() { return 2u; }
 size_t kh_skm_union_lds_bytes() { return SkmUnion::LDS; }
 
 __device__ __forceinline__ u32 key_hash2(u32 lo, u32 hi) { return (lo ^ hi) * 0x9E3779B1u; }
+
+// ------------------------------------------------------------------------------------------
+// Record -> canonical k-mers, one chunk of E consecutive k-mers (k_skm_big, k_skm_phased; k_skm_union keeps a twin of
+// this in its own body, see there).  The first k-mer by a funnel shift + reversal of the 2-bit groups, the others by
+// ROLLING both strands (32-bit halves: a funnel shift and a shift-or each).  f(e, cl, ch) gets the canonical key of
+// every e < E as two halves, also of those behind the record's last k-mer: the caller knows how many it wants.
+// ------------------------------------------------------------------------------------------
+struct Skm1Consts {   // per launch: the 2k-bit mask and where the last base of a k-mer sits, as 32-bit halves (15 <= k <= 32)
+    u32 kml, kmh;
+    u32 fsh;          // right-aligns a reversed window
+    u32 tsh;          // 2k - 2: 28 .. 62
+    u32 tsh_sub;      // the same inside its word
+    bool tsh_high;    // (uniform) the last base of a k-mer sits in the high word
+    __device__ __forceinline__ explicit Skm1Consts(const int k)
+        : kml((u32)kh_mask(2 * k)), kmh((u32)(kh_mask(2 * k) >> 32)), fsh(64u - 2u * (u32)k), tsh(2u * (u32)k - 2u),
+          tsh_sub(tsh >= 32u ? tsh - 32u : tsh), tsh_high(tsh >= 32u) {}
+};
+template <int E, class F>
+__device__ __forceinline__ void skm1_expand(const uint4 r0, const u32 first, const Skm1Consts& kc, F&& f) {
+    const u64 clo = ((u64)r0.y << 32) | r0.x, chi = ((u64)r0.w << 32) | r0.z;
+    const u32 sh = 2u * first;   // 0, 2E, .. <= 60
+    const u64 lo = sh ? (clo >> sh) | (chi << (64u - sh)) : clo, hi = chi >> sh;
+    const u32 xl = (u32)lo & kc.kml, xh = (u32)(lo >> 32) & kc.kmh;   // the first k-mer, base j at bits 2j
+    const u64 fw = kh_revpairs64(((u64)xh << 32) | xl) >> kc.fsh;
+    u32 fl = (u32)fw, fh = (u32)(fw >> 32), rl = ~xl & kc.kml, rh = ~xh & kc.kmh;
+    const u32 t = (u32)((lo >> kc.tsh) | (hi << (64u - kc.tsh)));   // bits 2e: the last base of the chunk's k-mer e
+    const u32 tc = ~t;
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        if (e) {   // roll both strands by one base
+            fh = __builtin_amdgcn_alignbit(fh, fl, 30) & kc.kmh;
+            fl = ((fl << 2) | ((t >> (2 * e)) & 3u)) & kc.kml;
+            rl = __builtin_amdgcn_alignbit(rh, rl, 2);
+            rh >>= 2;
+            if (kc.tsh_high) rh |= ((tc >> (2 * e)) & 3u) << kc.tsh_sub; else rl |= ((tc >> (2 * e)) & 3u) << kc.tsh_sub;
+        }
+        const bool fwd = fh < rh || (fh == rh && fl < rl);
+        f((u32)e, fwd ? fl : rl, fwd ? fh : rh);
+    }
+}
+// the claim of the probe walk for a one-word key: one 64-bit compare-and-swap
+struct SkmClaim1 {
+    unsigned long long* tkey;   // key plane of the main table
+    u32 okey_off;               // the second table's, in entries behind it (one base pointer, an integer choice)
+    unsigned long long empty, K;
+    __device__ __forceinline__ u32 operator()(const bool second, const u32 S) const {
+        const unsigned long long o2 = atomicCAS(tkey + (second ? okey_off : 0u) + S, empty, K);
+        return o2 == empty ? SKM_FRESH : (o2 == K ? SKM_SAME_KEY : SKM_OTHER_KEY);
+    }
+};
 
 #ifdef KH_STAMPS
 #define SKM_USTAMP(idx)                                                                    \
@@ -507,6 +499,9 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs) 
         return n <= fit ? n : 0u;
     };
     SKM_MARK("init");
+    // The read-out below is the twin of SkmReadout (kh_skm_device.h), kept in place: with the shared struct this kernel
+    // had the same registers and 32 instructions fewer, and ran 1 % slower (1.431 -> 1.446 ms, three alternated runs
+    // each, the parent's spread 0.003).  A change of the bin rule has to be made in both.
     if (tid < (u32)KH_TAG_MAX_OPS) {
         const u32 g = jb.ginfo[tid], g0 = g & 0xffu, gn = (g >> 8) & 0xffu;
         const u64 gm = gn ? (gn >= 64u ? ~0ull : ((1ull << gn) - 1ull)) << g0 : 0ull;
@@ -563,7 +558,7 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs) 
         }
         // ---- stage this slot's records, one per thread
         u32 nj = 0;   // k-mers of this thread's record while it is alive
-        const u32 tg = (rr.w >> 21) & 63u;
+        const u32 tg = SkmRec1::tag(rr.w);
         const u32 rx = rr.x, ry = rr.y, rz = rr.z, rw = rr.w;   // (this slot's record; `rr` is loaded again below)
         {
             u32 z = 0;   // (opaque: a zero kept in four registers across the loop was spilled)
@@ -571,7 +566,7 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs) 
             for (u32 i = tid; i < T / 4; i += NT) reinterpret_cast<uint4*>(dd)[i] = make_uint4(z, z, z, z);
         }
         if (tid < nrec) {
-            nj = rr.w >> 27;
+            nj = SkmRec1::n(rr.w);
             stage[tid] = rr;
             rmask[tid] = 1u << (tg & 31u);
         }
@@ -583,7 +578,7 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs) 
         // record that stays takes its chunks from a counter (chunks in the low half, k-mers in the high half) and
         // enters them into the chunk table at once: no block scan, no phase of its own.
         if (__builtin_amdgcn_ballot_w64(nj != 0)) {   // (waves without records go straight to the barrier)
-            u32 h = rx * 0x9E3779B1u ^ ry * 0x85EBCA77u ^ rz * 0xC2B2AE3Du ^ (rw & ~(63u << 21)) * 0x27D4EB2Fu;
+            u32 h = rx * 0x9E3779B1u ^ ry * 0x85EBCA77u ^ rz * 0xC2B2AE3Du ^ SkmRec1::content_hash_word(rw) * 0x27D4EB2Fu;
             h ^= h >> 15;
             h *= 0x2C1B3C6Du;
             u32 hp = (u32)(((u64)h * T) >> 32);
@@ -598,7 +593,7 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs) 
                     } else {
                         const uint4 o = stage[old - 1u];
                         // the same bases, the same number of k-mers, a genome of the same half of the mask
-                        if (o.x == rx && o.y == ry && o.z == rz && ((o.w ^ rw) & ~(31u << 21)) == 0u) {
+                        if (o.x == rx && o.y == ry && o.z == rz && SkmRec1::same_content(o.w, rw)) {
                             const u32 bit = 1u << (tg & 31u);
                             const u32 was = atomicOr(&rmask[old - 1u], bit);
                             if (was & bit) {   // a second copy inside one genome: nj repeats
@@ -635,7 +630,7 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs) 
         if ((sc0 & 0xffffu) > G::MAXCH) {   // uniform, rare: the slot is handed to k_skm_big below; what the merge has counted is taken back
             if (tid < nrec && rmask[tid] == 0u) {
                 const u32 w = stage[tid].w;
-                atomicSub(&dupc[(w >> 21) & 63u], w >> 27);
+                atomicSub(&dupc[SkmRec1::tag(w)], SkmRec1::n(w));
             }
             __syncthreads();
         }
@@ -691,9 +686,13 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs) 
                     const u32 o = owner[c], ri = o >> SKM_OB, first = (o & ((1u << SKM_OB) - 1u)) * (u32)E;
                     const uint4 r0 = reg[ri];   // an L2 hit: the records were read a moment ago
                     bits = rmask[ri];
-                    half = (r0.w >> 26) & 1u;
-                    const u32 left = (r0.w >> 27) - first;
+                    half = SkmRec1::half(r0.w);
+                    const u32 left = SkmRec1::n(r0.w) - first;
                     const u32 cnt = left < (u32)E ? left : (u32)E;
+                    // The twin of skm1_expand<E> above, kept in place: through the shared expander (hash, kreg, slot_ and act
+                    // in a callback) registers, scratch and occupancy stay as they are, but the probe rounds behind it are
+                    // structured with 7 % more instructions (s_and_saveexec / s_or / s_cbranch_execz / v_mov).  A change
+                    // of the expansion has to be made in both.
                     const u64 clo = ((u64)r0.y << 32) | r0.x, chi = ((u64)r0.w << 32) | r0.z;
                     const u32 sh = 2u * first;   // 0, 2E, .. <= 60
                     const u64 lo = sh ? (clo >> sh) | (chi << (64u - sh)) : clo, hi = chi >> sh;
@@ -876,213 +875,23 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs) 
 }
 
 // ------------------------------------------------------------------------------------------
-// Overfull slots (one-word keys).  A minimizer that far more k-mers share than a hash predicts — poly-A, a tandem repeat's
-// unit, an insertion sequence in 50 copies — fills its slot's region; the regroup puts what does not fit on a side
-// list and the union leaves such slots alone.  Here one workgroup takes one of them whatever its size: the records
-// in the region, then its records on the side list (found by a scan of the list: it is short), every k-mer into the
-// table in rounds of key subsets; no merge of identical records, read-out by a scan of the table.  A handful of
-// slots per run: nothing here is tuned, it only has to be right and to keep the run in the fast form.
+// Overfull slots: k_skm_big (kh_skm_device.h) with one-word keys
 // ------------------------------------------------------------------------------------------
-constexpr u32 SKM_BIG_NT = 1024, SKM_BIG_T = 4096, SKM_BIG_T2 = 128, SKM_BIG_IDX = 4096;
-constexpr u32 SKM_BIG_BATCH = 256, SKM_BIG_MAXCH = SKM_BIG_BATCH << SKM_OB;   // records numbered at a time; their chunks at most
-size_t kh_skm_big_lds_bytes() {
-    return (size_t)SKM_BIG_T * 16 + (size_t)SKM_BIG_T2 * 16 + 1024 + 128 + 256 + (size_t)SKM_HSTRIPE_WORDS * 4 +
-           (size_t)SKM_BIG_MAXCH * 2 + (size_t)SKM_BIG_IDX * 4;
-}
-__global__ __launch_bounds__(SKM_BIG_NT) void k_skm_big(const KhSkmJob jb, u32 cs) {
-    extern __shared__ __attribute__((aligned(16))) u8 lds_raw[];
-    constexpr u32 NT = SKM_BIG_NT, T = SKM_BIG_T, T2 = SKM_BIG_T2, HBITS = 12;
-    constexpr int E = (int)SKM_UE;
-    constexpr u64 EMPTY = ~0ull;
-    u8* p = lds_raw;
-    unsigned long long* tkey = reinterpret_cast<unsigned long long*>(p);   p += (size_t)T * 8;
-    u32* tmlo = reinterpret_cast<u32*>(p);                                 p += (size_t)T * 4;
-    u32* tmhi = reinterpret_cast<u32*>(p);                                 p += (size_t)T * 4;
-    unsigned long long* okey = reinterpret_cast<unsigned long long*>(p);   p += (size_t)T2 * 8;
-    u32* omlo = reinterpret_cast<u32*>(p);                                 p += (size_t)T2 * 4;
-    u32* omhi = reinterpret_cast<u32*>(p);                                 p += (size_t)T2 * 4;
-    uint4* gtab = reinterpret_cast<uint4*>(p);                             p += 1024;
-    u32* scratch = reinterpret_cast<u32*>(p);                              p += 128;   // [0] chunks, [2] k-mers, [3] side-list records
-    u32* dupc = reinterpret_cast<u32*>(p);                                 p += 256;
-    u32* hstripe = reinterpret_cast<u32*>(p);                              p += (size_t)SKM_HSTRIPE_WORDS * 4;
-    u16* owner = reinterpret_cast<u16*>(p);                                p += (size_t)SKM_BIG_MAXCH * 2;
-    u32* sidx = reinterpret_cast<u32*>(p);                                 // [SKM_BIG_IDX] this slot's records on the side list
-    const u32 tid = threadIdx.x, lane = lane_id();
-    const u32 nbins = jb.nbins, cap2 = jb.cap2;
-    const int k = jb.k;
-    const u32 slot = jb.big_list[blockIdx.x];
-    const u32 sshift = nbins <= 72u ? 2u : (nbins <= 144u ? 1u : 0u), smask = (1u << sshift) - 1u;
-    const u32 kml = (u32)kh_mask(2 * k), kmh = (u32)(kh_mask(2 * k) >> 32), fsh = 64u - 2u * (u32)k, tsh = 2u * (u32)k - 2u;
-    const bool tsh_high = tsh >= 32u;
-    const u32 tsh_sub = tsh_high ? tsh - 32u : tsh;
-    if (tid < (u32)KH_TAG_MAX_OPS) {
-        const u32 g = jb.ginfo[tid], g0 = g & 0xffu, gn = (g >> 8) & 0xffu;
-        const u64 gm = gn ? (gn >= 64u ? ~0ull : ((1ull << gn) - 1ull)) << g0 : 0ull;
-        gtab[tid] = make_uint4((u32)gm, (u32)(gm >> 32), (g >> 16) << sshift, 0u);
-        dupc[tid] = 0;
+constexpr u32 SKM_BIG_T = 4096, SKM_BIG_T2 = 128;
+struct SkmBig1 {
+    using Rec = SkmRec1;
+    using Consts = Skm1Consts;
+    using Key = unsigned long long;
+    static constexpr u32 T = SKM_BIG_T, T2 = SKM_BIG_T2, KEY_BYTES = 8, BATCH = 256, OB = SKM_OB;
+    static constexpr int E = (int)SKM_UE;
+    template <class F> static __device__ __forceinline__ void expand(const SkmRecord<1>& r, const u32 first, const Consts& kc, F&& f) {
+        skm1_expand<E>(r.v[0], first, kc, [&](const u32 e, const u32 cl, const u32 ch) __attribute__((always_inline)) { f(e, ((u64)ch << 32) | cl); });
     }
-    if (tid < SKM_HSTRIPE_WORDS) hstripe[tid] = 0;
-    if (tid < 8) scratch[tid] = 0;
-    __syncthreads();
-    // ---- this slot's records on the side list
-    u32 nspill_all = jb.ctl[5];
-    nspill_all = nspill_all < jb.spill_cap ? nspill_all : jb.spill_cap;
-    for (u32 i = tid; i < nspill_all; i += NT) {
-        if (jb.spill_slot[i] == slot) {
-            const u32 at = atomicAdd(&scratch[3], 1u);
-            if (at < SKM_BIG_IDX) sidx[at] = i;
-        }
+    static __device__ __forceinline__ u32 hash(const Key K) { return key_hash2((u32)K, (u32)(K >> 32)); }
+    static __device__ __forceinline__ SkmClaim1 claim(u8* kmain, const u32 okey_off, const Key K) {
+        return SkmClaim1{reinterpret_cast<unsigned long long*>(kmain), okey_off, ~0ull, K};
     }
-    __syncthreads();
-    u32 nside = scratch[3];
-    if (nside > SKM_BIG_IDX) {   // (more than this kernel indexes: the host falls back)
-        if (tid == 0) atomicOr(jb.ctl, KH_ERR_CAPACITY);
-        nside = SKM_BIG_IDX;
-    }
-    const u32 nreg = jb.cur2[slot] < cap2 ? jb.cur2[slot] : cap2;   // (full for an overfull slot; a slot listed for its chunks may hold fewer)
-    const uint4* __restrict__ reg = jb.reg2 + (u64)slot * cap2;
-    const u32 nall = nreg + nside;
-    auto record = [&](u32 i) -> uint4 { return i < nreg ? reg[i] : jb.spill_rec[sidx[i - nreg]]; };
-    // ---- k-mer instances of the slot -> rounds
-    {
-        u32 mine = 0;
-        for (u32 i = tid; i < nall; i += NT) mine += record(i).w >> 27;
-        const u32 tot = wave_scan_add(mine);
-        if (lane == KH_WAVE - 1 && tot) atomicAdd(&scratch[2], tot);
-    }
-    __syncthreads();
-    const u32 N = scratch[2];
-    const u32 R = (N + 3071u) / 3072u;
-    if (tid == 0 && N > T) atomicMax(jb.ctl + 1, N);
-    auto eval_mask = [&](u32 mlo, u32 mhi) -> bool {
-        const u32 lsel = lane & smask;
-        u32 ng = 0;
-        do {
-            const u32 first = mlo ? (u32)__builtin_ctz(mlo) : 32u + (u32)__builtin_ctz(mhi);
-            const uint4 g = gtab[first];
-            u32 c = (u32)__popc(mlo & g.x) + (u32)__popc(mhi & g.y);
-            c = c < cs ? c : cs;
-            atomicAdd(&hstripe[g.z + (c << sshift) + lsel], 1u);
-            const u32 keep_hi = mlo ? ~0u : mhi - 1u;
-            mlo &= ~g.x & (mlo - 1u);
-            mhi &= ~g.y & keep_hi;
-            ++ng;
-        } while (mlo | mhi);
-        if (ng == 1u) return true;
-        atomicAdd(&hstripe[((jb.abase + (ng < cs ? ng : cs)) << sshift) + lsel], 1u);
-        return false;
-    };
-    for (u32 q = blockIdx.y; q < R; q += gridDim.y) {   // (the rounds are independent: workgroups (slot, y) share them out)
-        {
-            uint4* k4 = reinterpret_cast<uint4*>(tkey);
-#pragma unroll
-            for (u32 e = 0; e < T / 2 / NT; ++e) k4[e * NT + tid] = make_uint4(0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu);
-            reinterpret_cast<uint4*>(tmlo)[tid] = make_uint4(0u, 0u, 0u, 0u);
-            reinterpret_cast<uint4*>(tmhi)[tid] = make_uint4(0u, 0u, 0u, 0u);
-            if (tid < T2) { okey[tid] = EMPTY; omlo[tid] = 0u; omhi[tid] = 0u; }
-        }
-        __syncthreads();
-        for (u32 b0 = 0; b0 < nall; b0 += SKM_BIG_BATCH) {   // batches of records, one per thread of the first waves
-            const u32 mine_i = b0 + tid;
-            const u32 nj = tid < SKM_BIG_BATCH && mine_i < nall ? record(mine_i).w >> 27 : 0u;
-            const u32 nch = (nj + (u32)E - 1u) / (u32)E;
-            {
-                const u32 incl = wave_scan_add(nch);
-                u32 wbase = 0;
-                if (lane == KH_WAVE - 1 && incl) wbase = atomicAdd(&scratch[0], incl);
-                wbase = (u32)__builtin_amdgcn_readlane((int)wbase, KH_WAVE - 1);
-                const u32 cstart = wbase + incl - nch;
-                if (cstart + nch <= SKM_BIG_MAXCH) {
-#pragma unroll
-                    for (u32 cc = 0; cc < (1u << SKM_OB); ++cc)
-                        if (cc < nch) owner[cstart + cc] = (u16)((tid << SKM_OB) | cc);
-                }
-            }
-            __syncthreads();
-            u32 C = scratch[0];
-            if (C > SKM_BIG_MAXCH) {   // (cannot happen: a record has at most 1 << SKM_OB chunks)
-                if (tid == 0) atomicOr(jb.ctl, KH_ERR_CAPACITY);
-                C = 0;
-            }
-            for (u32 c = tid; c < C; c += NT) {
-                const u32 o = owner[c], ri = b0 + (o >> SKM_OB), first = (o & ((1u << SKM_OB) - 1u)) * (u32)E;
-                const uint4 r0 = record(ri);
-                const u32 tg = (r0.w >> 21) & 63u, bit = 1u << (tg & 31u), half = tg >> 5;
-                const u32 left = (r0.w >> 27) - first;
-                const u32 cnt = left < (u32)E ? left : (u32)E;
-                const u64 clo = ((u64)r0.y << 32) | r0.x, chi = ((u64)r0.w << 32) | r0.z;
-                const u32 sh = 2u * first;
-                const u64 lo = sh ? (clo >> sh) | (chi << (64u - sh)) : clo, hi = chi >> sh;
-                const u32 xl = (u32)lo & kml, xh = (u32)(lo >> 32) & kmh;
-                const u64 fw = kh_revpairs64(((u64)xh << 32) | xl) >> fsh;
-                u32 fl = (u32)fw, fh = (u32)(fw >> 32), rl = ~xl & kml, rh = ~xh & kmh;
-                const u32 t = (u32)((lo >> tsh) | (hi << (64u - tsh)));
-                const u32 tc = ~t;
-#pragma unroll
-                for (int e = 0; e < E; ++e) {
-                    if (e) {
-                        fh = __builtin_amdgcn_alignbit(fh, fl, 30) & kmh;
-                        fl = ((fl << 2) | ((t >> (2 * e)) & 3u)) & kml;
-                        rl = __builtin_amdgcn_alignbit(rh, rl, 2);
-                        rh >>= 2;
-                        if (tsh_high) rh |= ((tc >> (2 * e)) & 3u) << tsh_sub; else rl |= ((tc >> (2 * e)) & 3u) << tsh_sub;
-                    }
-                    if ((u32)e >= cnt) break;
-                    const bool fwd = fh < rh || (fh == rh && fl < rl);
-                    const u32 cl = fwd ? fl : rl, ch = fwd ? fh : rh;
-                    const unsigned long long K = ((u64)ch << 32) | cl;
-                    const u32 H = key_hash2(cl, ch);
-                    if (R != 1 && (((H >> 4) & 0xffffu) * R) >> 16 != q) continue;
-                    u32 S = H >> (32 - HBITS), probes = 0, level = 0;
-                    while (true) {
-                        unsigned long long* kp = level == 1 ? okey : tkey;
-                        const unsigned long long o2 = atomicCAS(&kp[S], EMPTY, K);
-                        if (o2 == EMPTY || o2 == K) {
-                            u32* mp = level == 1 ? (half ? omhi : omlo) : (half ? tmhi : tmlo);
-                            if (atomicOr(mp + S, bit) & bit) atomicAdd(&dupc[tg], 1u);   // this genome had the k-mer already
-                            break;
-                        }
-                        ++probes;
-                        if (level == 0 && probes >= (u32)KH_TUNE_SKM_FULL_ROUNDS) {
-                            level = 1; probes = 0;
-                            S = ((H ^ (H >> 15)) * 0x85EBCA77u) >> (32 - HBITS + 5);
-                        } else if (level == 1 && probes >= 8u) {
-                            level = 2; probes = 0;
-                            S = ((H >> (32 - HBITS)) + (u32)KH_TUNE_SKM_FULL_ROUNDS) & (T - 1u);
-                        } else if (level == 2 && probes >= T) {
-                            atomicOr(jb.ctl, KH_ERR_CAPACITY);
-                            break;
-                        } else {
-                            S = (S + 1u) & (level == 1 ? T2 - 1u : T - 1u);
-                        }
-                    }
-                }
-            }
-            __syncthreads();
-            if (tid == 0) scratch[0] = 0;
-            __syncthreads();
-        }
-        // ---- read-out: every occupied entry
-        u32 ones = 0;
-#pragma unroll
-        for (u32 e = 0; e < T / NT; ++e) {
-            const u32 i = e * NT + tid;
-            if (tkey[i] != EMPTY && eval_mask(tmlo[i], tmhi[i])) ++ones;
-        }
-        if (tid < T2 && okey[tid] != EMPTY && eval_mask(omlo[tid], omhi[tid])) ++ones;
-        ones = wave_scan_add(ones);
-        if (lane == KH_WAVE - 1 && ones) atomicAdd(&hstripe[(jb.abase + 1u) << sshift], ones);
-        __syncthreads();
-    }
-    unsigned long long* __restrict__ rep = jb.hist + (u64)(blockIdx.x % jb.reps) * nbins;
-    for (u32 i = tid; i < nbins; i += NT) {
-        u32 v = 0;
-        for (u32 j = 0; j <= smask; ++j) v += hstripe[(i << sshift) + j];
-        if (v) atomicAdd(&rep[i], (unsigned long long)v);
-    }
-    if (tid < (u32)KH_TAG_MAX_OPS && dupc[tid]) atomicAdd(&jb.dup[tid], (unsigned long long)dupc[tid]);
-    if (tid == 0 && blockIdx.y == 0) atomicAdd(jb.ctl + 3, N);
-}
+};
 
 // ------------------------------------------------------------------------------------------
 // The exchange form (multi-GPU step 7-8): slots are a GLOBAL function of the minimizer, so ranks
@@ -1101,7 +910,6 @@ __global__ __launch_bounds__(SKM_BIG_NT) void k_skm_big(const KhSkmJob jb, u32 c
 // (NT threads = the most records a slot may hold: the host picks 256 / 512 / 1024 from the regions' capacity — a
 // workgroup per slot costs ~5 us whatever it holds, and four or eight of the small ones fit a CU instead of two)
 static size_t skm_pack_lds_bytes(u32 nt) { return (size_t)nt * 16 + (size_t)nt * 4 * 4 + (size_t)nt * 4 + 64; }
-size_t kh_skm_pack_lds_bytes() { return skm_pack_lds_bytes(1024); }
 
 template <u32 NT>
 __global__ __launch_bounds__(NT) void k_skm_pack(const KhSkmPackJob jb) {
@@ -1123,10 +931,10 @@ __global__ __launch_bounds__(NT) void k_skm_pack(const KhSkmPackJob jb) {
     const uint4 rr = tid < nrec ? (jb.reg2 + (u64)slot * jb.cap2)[tid] : make_uint4(0, 0, 0, 0);
     reinterpret_cast<uint4*>(dd)[tid] = make_uint4(0u, 0u, 0u, 0u);
     if (tid == 0) { scratch[0] = 0; scratch[1] = 0; }
-    const u32 tg = (rr.w >> 21) & 63u;
+    const u32 tg = SkmRec1::tag(rr.w);
     u32 nj = 0;
     if (tid < nrec) {
-        nj = rr.w >> 27;
+        nj = SkmRec1::n(rr.w);
         stage[tid] = rr;
         rmask[tid] = 1u << (tg & 31u);
         if (tg >= 32u) atomicOr(jb.ctl, KH_ERR_ORDER);   // tags of the exchange form are below 32
@@ -1134,7 +942,7 @@ __global__ __launch_bounds__(NT) void k_skm_pack(const KhSkmPackJob jb) {
     __syncthreads();
     bool won = false;
     if (__builtin_amdgcn_ballot_w64(nj != 0)) {
-        u32 h = rr.x * 0x9E3779B1u ^ rr.y * 0x85EBCA77u ^ rr.z * 0xC2B2AE3Du ^ (rr.w & ~(63u << 21)) * 0x27D4EB2Fu;
+        u32 h = rr.x * 0x9E3779B1u ^ rr.y * 0x85EBCA77u ^ rr.z * 0xC2B2AE3Du ^ SkmRec1::content_hash_word(rr.w) * 0x27D4EB2Fu;
         h ^= h >> 15;
         h *= 0x2C1B3C6Du;
         u32 hp = h >> TSH;
@@ -1145,7 +953,7 @@ __global__ __launch_bounds__(NT) void k_skm_pack(const KhSkmPackJob jb) {
                 if (old == 0u) { won = true; pend = false; }
                 else {
                     const uint4 o = stage[old - 1u];
-                    if (o.x == rr.x && o.y == rr.y && o.z == rr.z && ((o.w ^ rr.w) & ~(31u << 21)) == 0u) {
+                    if (o.x == rr.x && o.y == rr.y && o.z == rr.z && SkmRec1::same_content(o.w, rr.w)) {
                         const u32 bit = 1u << (tg & 31u);
                         const u32 was = atomicOr(&rmask[old - 1u], bit);
                         if ((was & bit) && jb.dup) atomicAdd(&jb.dup[tg & 31u], (unsigned long long)nj);   // a second copy under one tag
@@ -1230,7 +1038,7 @@ size_t kh_skm_phased_lds_bytes() {
 // 3072 chunks over all pieces (or more than 32 pieces) is numbered a phase at a time instead.
 __global__ __launch_bounds__(SKM_PH_NT, 8) void k_skm_phased(const KhSkmPhasedJob jb) {
     extern __shared__ __attribute__((aligned(16))) u8 lds_raw[];
-    constexpr u32 NT = SKM_PH_NT, T = SKM_PH_T, T2 = SKM_PH_T2, HBITS = 12, NP = SKM_PH_STAGED;
+    constexpr u32 NT = SKM_PH_NT, T = SKM_PH_T, T2 = SKM_PH_T2, NP = SKM_PH_STAGED;
     constexpr int E = (int)SKM_PH_E;
     constexpr u64 EMPTY = ~0ull;
     u8* p = lds_raw;
@@ -1240,6 +1048,7 @@ __global__ __launch_bounds__(SKM_PH_NT, 8) void k_skm_phased(const KhSkmPhasedJo
     unsigned long long* okey = reinterpret_cast<unsigned long long*>(p);   p += (size_t)T2 * 8;
     u32* omlo = reinterpret_cast<u32*>(p);                                 p += (size_t)T2 * 4;
     u32* ocnt = reinterpret_cast<u32*>(p);                                 p += (size_t)T2 * 4;
+    constexpr u32 OKEY_OFF = 2 * T, OMLO_OFF = 2 * T + 2 * T2;             // okey - tkey, omlo - tmlo (the probe walk addresses both tables from one base)
     u32* scratch = reinterpret_cast<u32*>(p);                              p += 128;   // [0] chunks of the phase, [1] entries made, [2] k-mers of the slot, [3] staged?, [8..23] wave totals
     u32* lhist = reinterpret_cast<u32*>(p);                                p += (size_t)SKM_PH_HBINS * 4;
     u16* owner = reinterpret_cast<u16*>(p);                                p += (size_t)SKM_PH_MAXCH * 2;
@@ -1253,10 +1062,7 @@ __global__ __launch_bounds__(SKM_PH_NT, 8) void k_skm_phased(const KhSkmPhasedJo
     u32* pflag = reinterpret_cast<u32*>(p);                                // dup_row << 1 | join_next
     const u32 tid0 = threadIdx.x;
     u32 tid = tid0, lane = lane_id();
-    const int k = jb.k;
-    const u32 kml = (u32)kh_mask(2 * k), kmh = (u32)(kh_mask(2 * k) >> 32), fsh = 64u - 2u * (u32)k, tsh = 2u * (u32)k - 2u;
-    const bool tsh_high = tsh >= 32u;
-    const u32 tsh_sub = tsh_high ? tsh - 32u : tsh;
+    const Skm1Consts kc(jb.k);
     const u32 hbins = jb.hist_len < SKM_PH_HBINS ? jb.hist_len : SKM_PH_HBINS;   // counts below this: LDS; above: global atomics
     const bool want_dup = jb.dup != nullptr;
     const bool staged = jb.npieces <= NP;
@@ -1279,60 +1085,22 @@ __global__ __launch_bounds__(SKM_PH_NT, 8) void k_skm_phased(const KhSkmPhasedJo
     __syncthreads();
     unsigned long long emptyv = EMPTY;
     // ---- one chunk: E k-mers of record r0 from its k-mer `first` on, with the genomes / groups `bits`, enter the table
-    auto insert_chunk = [&](const uint4 r0, const u32 bits, const u32 first, const u32 ph, const u32 R, const u32 q, u32& fresh_n) {
-        const u32 left = (r0.w >> 27) - first;
-        const u32 cnt = left < (u32)E ? left : (u32)E;
-        const u64 clo = ((u64)r0.y << 32) | r0.x, chi = ((u64)r0.w << 32) | r0.z;
-        const u32 sh = 2u * first;
-        const u64 lo = sh ? (clo >> sh) | (chi << (64u - sh)) : clo, hi = chi >> sh;
-        const u32 xl = (u32)lo & kml, xh = (u32)(lo >> 32) & kmh;
-        const u64 fw = kh_revpairs64(((u64)xh << 32) | xl) >> fsh;
-        u32 fl = (u32)fw, fh = (u32)(fw >> 32), rl = ~xl & kml, rh = ~xh & kmh;
-        const u32 t = (u32)((lo >> tsh) | (hi << (64u - tsh)));
-        const u32 tc = ~t;
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-            if (e) {
-                fh = __builtin_amdgcn_alignbit(fh, fl, 30) & kmh;
-                fl = ((fl << 2) | ((t >> (2 * e)) & 3u)) & kml;
-                rl = __builtin_amdgcn_alignbit(rh, rl, 2);
-                rh >>= 2;
-                if (tsh_high) rh |= ((tc >> (2 * e)) & 3u) << tsh_sub; else rl |= ((tc >> (2 * e)) & 3u) << tsh_sub;
-            }
-            if ((u32)e >= cnt) break;
-            const bool fwd = fh < rh || (fh == rh && fl < rl);
-            const u32 cl = fwd ? fl : rl, ch = fwd ? fh : rh;
+    auto insert_chunk = [&](const uint4 r0, const u32 bits, const u32 first, const u32 ph, const u32 R, const u32 q, u32& fresh_n) __attribute__((always_inline)) {
+        const u32 cnt = SkmRec1::n(r0.w) - first;   // k-mers of the record from `first` on: the chunk holds min(cnt, E)
+        skm1_expand<E>(r0, first, kc, [&](const u32 e, const u32 cl, const u32 ch) __attribute__((always_inline)) {
+            if (e >= cnt) return;
             const unsigned long long K = ((u64)ch << 32) | cl;
             const u32 H = key_hash2(cl, ch);
-            if (R != 1 && (((H >> 4) & 0xffffu) * R) >> 16 != q) continue;   // another round's key
-            // main table: KH_TUNE_SKM_FULL_ROUNDS probes, then the second table (8), then the main one to the end
-            u32 S = H >> (32 - HBITS), probes = 0, level = 0;
-            while (true) {
-                unsigned long long* kp = level == 1 ? okey : tkey;
-                const unsigned long long o2 = atomicCAS(&kp[S], emptyv, K);
-                if (o2 == emptyv || o2 == K) {
-                    if (want_dup) {   // uniform: bits set already = a second instance under that tag (rare: global counters)
-                        u32 d = atomicOr((level == 1 ? omlo : tmlo) + S, bits) & bits;
-                        while (d) { atomicAdd(&jb.dup[ph * 32u + (u32)__builtin_ctz(d)], 1ull); d &= d - 1u; }
-                    } else atomicOr((level == 1 ? omlo : tmlo) + S, bits);
-                    if (o2 == emptyv) ++fresh_n;
-                    break;
-                }
-                ++probes;
-                if (level == 0 && probes >= (u32)KH_TUNE_SKM_FULL_ROUNDS) {
-                    level = 1; probes = 0;
-                    S = ((H ^ (H >> 15)) * 0x85EBCA77u) >> (32 - HBITS + 5);
-                } else if (level == 1 && probes >= 8u) {
-                    level = 2; probes = 0;
-                    S = ((H >> (32 - HBITS)) + (u32)KH_TUNE_SKM_FULL_ROUNDS) & (T - 1u);
-                } else if (level == 2 && probes >= T) {
-                    atomicOr(jb.ctl, KH_ERR_CAPACITY);   // the table is full
-                    break;
-                } else {
-                    S = (S + 1u) & (level == 1 ? T2 - 1u : T - 1u);
-                }
-            }
-        }
+            if (R != 1 && (((H >> 4) & 0xffffu) * R) >> 16 != q) return;   // another round's key
+            skm_probe_walk<T, T2>(H, jb.ctl, SkmClaim1{tkey, OKEY_OFF, emptyv, K}, [&](const bool second, const u32 S, const bool fresh) __attribute__((always_inline)) {
+                u32* const mp = tmlo + (second ? OMLO_OFF : 0u) + S;
+                if (want_dup) {   // uniform: bits set already = a second instance under that tag (rare: global counters)
+                    u32 d = atomicOr(mp, bits) & bits;
+                    while (d) { atomicAdd(&jb.dup[ph * 32u + (u32)__builtin_ctz(d)], 1ull); d &= d - 1u; }
+                } else atomicOr(mp, bits);
+                if (fresh) ++fresh_n;
+            });
+        });
     };
     // ---- behind a phase's insertions: its tags are counted, the mask plane is free for the next phase
     auto count_fresh = [&](const u32 fresh_n) {
@@ -1392,7 +1160,7 @@ __global__ __launch_bounds__(SKM_PH_NT, 8) void k_skm_phased(const KhSkmPhasedJo
             } else {
                 if (myph < NP) {
                     const u64 at = (u64)poff[myph] + myidx;
-                    my_nj = prec[myph][at].w >> 27;
+                    my_nj = SkmRec1::n(prec[myph][at].w);
                     const u32 touch = pmsk[myph][at];   // (the mask's cache line sets out now)
                     asm volatile("" ::"v"(touch));
                     rloc[tid] = (u16)((myph << 10) | myidx);
@@ -1432,7 +1200,7 @@ __global__ __launch_bounds__(SKM_PH_NT, 8) void k_skm_phased(const KhSkmPhasedJo
                 const KhSkmPiece pc = jb.pieces[ph];
                 u32 nrec = ((ConstU32)(unsigned long long)pc.count)[slot];
                 nrec = nrec < NT ? nrec : NT;
-                if (tid < nrec) mine += (pc.rec + ((ConstU32)(unsigned long long)pc.off)[slot])[tid].w >> 27;
+                if (tid < nrec) mine += SkmRec1::n((pc.rec + ((ConstU32)(unsigned long long)pc.off)[slot])[tid].w);
             }
             if (__builtin_amdgcn_ballot_w64(mine != 0)) {
                 const u32 tot = wave_scan_add(mine);
@@ -1492,7 +1260,7 @@ __global__ __launch_bounds__(SKM_PH_NT, 8) void k_skm_phased(const KhSkmPhasedJo
                     const u32* __restrict__ msk = pc.mask + roff;
                     for (u32 b0 = 0; b0 < nrec; b0 += BATCH) {
                         // ---- number the chunks of the batch's records
-                        const u32 nj = tid < BATCH && b0 + tid < nrec ? rec[b0 + tid].w >> 27 : 0u;
+                        const u32 nj = tid < BATCH && b0 + tid < nrec ? SkmRec1::n(rec[b0 + tid].w) : 0u;
                         const u32 nch = (nj + (u32)E - 1u) / (u32)E;
                         if (__builtin_amdgcn_ballot_w64(nch != 0)) {
                             const u32 incl = wave_scan_add(nch);
@@ -1552,9 +1320,6 @@ __global__ __launch_bounds__(SKM_PH_NT, 8) void k_skm_phased(const KhSkmPhasedJo
 // ------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------
-template <class K> static void skm_allow_lds(K kern, size_t bytes) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
 template <int WW> static void launch_scatter_w(const KhSkmJob& job, u32 ntiles, size_t lds, hipStream_t st) {
     skm_allow_lds(k_skm_scatter<WW>, lds);
     hipLaunchKernelGGL(k_skm_scatter<WW>, dim3(ntiles), dim3(SKM_NT), lds, st, job);
@@ -1571,11 +1336,7 @@ void kh_launch_skm_scatter(const KhSkmJob& job, u32 ntiles, hipStream_t st) {
         default: break;   // the host asks kh_skm_supports_w first
     }
 }
-void kh_launch_skm_regroup(const KhSkmJob& job, hipStream_t st) {
-    const size_t lds = kh_skm_regroup_lds_bytes(job.S);
-    skm_allow_lds(k_skm_regroup, lds);
-    hipLaunchKernelGGL(k_skm_regroup, dim3(job.nb1), dim3(SKM_RG_NT), lds, st, job);
-}
+void kh_launch_skm_regroup(const KhSkmJob& job, hipStream_t st) { skm_launch_regroup<SkmRec1>(job, st); }
 void kh_launch_skm_union(const KhSkmJob& job, u32 cs, u32 grid, hipStream_t st) {
     const size_t lds = kh_skm_union_lds_bytes();
     skm_allow_lds(k_skm_union<1024, 4096>, lds);
@@ -1604,10 +1365,4 @@ void kh_launch_skm_phased(const KhSkmPhasedJob& job, u32 grid, hipStream_t st) {
     skm_allow_lds(k_skm_phased, lds);
     hipLaunchKernelGGL(k_skm_phased, dim3(grid), dim3(SKM_PH_NT), lds, st, job);
 }
-static u32 big_y() { const char* e = getenv("KHOICE_SKM_BIG_Y"); const int v = e ? atoi(e) : 4; return (u32)(v < 1 ? 1 : (v > 16 ? 16 : v)); }
-void kh_launch_skm_big(const KhSkmJob& job, u32 cs, u32 nbig, hipStream_t st) {
-    if (!nbig) return;
-    const size_t lds = kh_skm_big_lds_bytes();
-    skm_allow_lds(k_skm_big, lds);
-    hipLaunchKernelGGL(k_skm_big, dim3(nbig, nbig < 2048u ? big_y() : 1u), dim3(SKM_BIG_NT), lds, st, job, cs);   // y: the rounds of a slot side by side
-}
+void kh_launch_skm_big(const KhSkmJob& job, u32 cs, u32 nbig, hipStream_t st) { skm_launch_big<SkmBig1>(job, cs, nbig, st); }

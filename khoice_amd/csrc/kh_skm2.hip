@@ -2,8 +2,8 @@
 //
 // Same three steps as kh_skm.hip (which see: minimizer records, two LDS counting-sort levels, one LDS hash
 // set per slot), with what 2k > 64 bits changes:
-//   * a record is 32 bytes: bits [0, 2(n+k-1)) the bases, in the last word n (6 bits, 26..31), the genome
-//     number (20..25), the fine slot index (10 bits, 10..19); n <= min(63, 118 - k);
+//   * a record is 32 bytes (SkmRec2, kh_skm_rec.h): bits [0, 2(n+k-1)) the bases, in the last word n (6 bits), the
+//     genome number and the fine slot index (10 bits); n <= min(63, 118 - k);
 //   * a k-mer has up to 49 m-mers: the sliding minimum needs the hashes of the NEXT TWO threads (two DPP
 //     wave_shl steps) and 96 validity flags per thread;
 //   * the hash set cannot claim a 128-bit key with one compare-and-swap.  An entry is claimed on the LOW word
@@ -29,12 +29,7 @@ namespace {
 #define KH_TUNE_SKM2_STAGE 1536   // (768 / 1024 / 1536: scatter 0.99 / 0.90 / 0.85 ms at k = 41)
 #endif
 constexpr u32 SKM2_CAP = KH_TUNE_SKM2_STAGE;    // 32-byte records staged per flush of the scatter
-constexpr u32 SKM2_RG_CAP = 4096;               // records per round of the regroup
 constexpr u32 SKM2_CWN = 10;                    // code words a thread keeps: bases p .. p + 159
-
-__device__ __forceinline__ u32 rec2_n(u32 w7) { return w7 >> 26; }
-__device__ __forceinline__ u32 rec2_tag(u32 w7) { return (w7 >> 20) & 63u; }
-__device__ __forceinline__ u32 rec2_fine(u32 w7) { return (w7 >> 10) & 1023u; }
 
 }   // namespace
 
@@ -42,7 +37,6 @@ size_t kh_skm2_scatter_lds_bytes(u32 nb1) {
     const u32 nbk = (nb1 + 3) & ~3u;
     return flush_lds_bytes<SKM2_CAP, 8>(nbk) + (size_t)SKM_CW * 4 + (((size_t)SKM_CW * 2 + 15) & ~(size_t)15) + 64 * 4 + 4 * 64 * 4 + 64;
 }
-size_t kh_skm2_regroup_lds_bytes(u32 S) { return flush_lds_bytes<SKM2_RG_CAP, 8>((S + 3) & ~3u) + (size_t)((S + 3) & ~3u) * 4 + 64; }
 
 // ------------------------------------------------------------------------------------------
 // S1: bases -> 32-byte records, partitioned by coarse bucket.  WW = m-mers per k-mer, compile time.
@@ -218,7 +212,7 @@ __global__ __launch_bounds__(SKM_NT, 2) void k_skm2_scatter(const KhSkmJob jb) {
                             const u32 wv = __builtin_amdgcn_alignbit(src[i + 1], src[i], r5);
                             out[i] = bits >= 32u * (i + 1) ? wv : (bits > 32u * i ? wv & ((1u << (bits - 32u * i)) - 1u) : 0u);
                         }
-                        out[7] |= (fine << 10) | (rtag << 20) | (n << 26);
+                        out[7] |= SkmRec2::header(fine, rtag, n);
                         L.stage[2 * at] = make_uint4(out[0], out[1], out[2], out[3]);
                         L.stage[2 * at + 1] = make_uint4(out[4], out[5], out[6], out[7]);
                         L.sid[at] = (u16)coarse;
@@ -252,60 +246,6 @@ __global__ __launch_bounds__(SKM_NT, 2) void k_skm2_scatter(const KhSkmJob jb) {
 }
 
 // ------------------------------------------------------------------------------------------
-// S2a: one workgroup per coarse bucket, 4096 records per round, regrouped by fine slot (cursors in LDS)
-// ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(SKM_RG_NT, 4) void k_skm2_regroup(const KhSkmJob jb) {
-    extern __shared__ __attribute__((aligned(16))) u8 lds_raw[];
-    constexpr int RPT = (int)(SKM2_RG_CAP / SKM_RG_NT);
-    const u32 nbk = (jb.S + 3) & ~3u;
-    const FlushLds L = flush_lds<SKM2_RG_CAP, 8>(lds_raw, nbk);
-    u32* lcur = reinterpret_cast<u32*>(lds_raw + flush_lds_bytes<SKM2_RG_CAP, 8>(nbk));   // [nbk] records written per slot
-    const u32 tid = threadIdx.x;
-    const u32 b = blockIdx.x;
-    const u32 have = jb.cur1[(size_t)b * KH_SKM_CUR1_STRIDE];
-    const u32 cnt = have < jb.cap1 ? have : jb.cap1;
-    const u32 first_slot = b * jb.S;
-    const u32 nfine = jb.nslots - first_slot < jb.S ? jb.nslots - first_slot : jb.S;
-    for (u32 i = tid; i < nbk; i += SKM_RG_NT) { L.bcnt[i] = 0; lcur[i] = 0; }
-    const uint4* __restrict__ src = jb.reg1 + (u64)b * jb.cap1 * 2;
-    uint4* __restrict__ dst = jb.reg2 + (u64)first_slot * jb.cap2 * 2;
-    uint4 nx[RPT][2];
-#pragma unroll
-    for (int r = 0; r < RPT; ++r) {
-        const u32 i = tid + (u32)r * SKM_RG_NT;
-        nx[r][0] = i < cnt ? src[2 * i] : make_uint4(0, 0, 0, 0);
-        nx[r][1] = i < cnt ? src[2 * i + 1] : make_uint4(0, 0, 0, 0);
-    }
-    __syncthreads();
-    for (u32 start = 0; start < cnt; start += SKM2_RG_CAP) {
-        const u32 n = cnt - start < SKM2_RG_CAP ? cnt - start : SKM2_RG_CAP;
-#pragma unroll
-        for (int r = 0; r < RPT; ++r) {
-            const u32 i = tid + (u32)r * SKM_RG_NT;
-            if (i < n) {
-                u32 fine = rec2_fine(nx[r][1].w);
-                if (fine >= nfine) { fine = 0; atomicOr(jb.ctl, KH_ERR_ORDER); }   // a corrupt record never leaves its bucket
-                L.stage[2 * i] = nx[r][0];
-                L.stage[2 * i + 1] = nx[r][1];
-                L.sid[i] = (u16)fine;
-                atomicAdd(&L.bcnt[fine], 1u);
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < RPT; ++r) {   // the next round's records: in flight during the flush
-            const u32 i = start + SKM2_RG_CAP + tid + (u32)r * SKM_RG_NT;
-            nx[r][0] = i < cnt ? src[2 * i] : make_uint4(0, 0, 0, 0);
-            nx[r][1] = i < cnt ? src[2 * i + 1] : make_uint4(0, 0, 0, 0);
-        }
-        __syncthreads();
-        SkmSpill sp;
-        sp.rec = jb.spill_rec; sp.slot = jb.spill_slot; sp.n = jb.ctl + 5; sp.cap = jb.spill_cap; sp.first_slot = first_slot;
-        skm_flush<SKM_RG_NT, SKM2_RG_CAP, true, 8>(L, n, nfine, lcur, dst, jb.cap2, jb.ctl, sp);
-    }
-    for (u32 i = tid; i < nfine; i += SKM_RG_NT) jb.cur2[first_slot + i] = lcur[i];
-}
-
-// ------------------------------------------------------------------------------------------
 // S2b: LDS hash set {128-bit canonical k-mer, genome mask} per slot -> histogram bins.  The same plan as the one-word
 // union of kh_skm.hip (which see): PERSISTENT workgroups with the next slot's record on its way while this one is
 // worked on; identical records (the same piece of sequence in several genomes of a group) merged before anything is
@@ -330,9 +270,8 @@ constexpr u32 SKM2_MAXREC = SKM2_STAGE < SKM2_UNT ? SKM2_STAGE : SKM2_UNT;   // 
 constexpr u32 SKM2_DD = SKM2_UT * 2;               // entries of the set of record contents (the high key plane)
 constexpr u32 SKM2_PASSES = 4;
 constexpr u32 SKM2_MAXCH = SKM2_PASSES * SKM2_UNT; // chunks of a slot after the merge
-constexpr u32 SKM2_HSTRIPE_WORDS = 288;
 size_t kh_skm2_union_lds_bytes(u32) {
-    return (size_t)SKM2_UT * 24 + (size_t)SKM2_UT2 * 24 + 1024 + 128 + 256 + (size_t)SKM2_HSTRIPE_WORDS * 4 + (size_t)SKM2_MAXCH * 2 +
+    return (size_t)SKM2_UT * 24 + (size_t)SKM2_UT2 * 24 + 1024 + 128 + 256 + (size_t)SKM_HSTRIPE_WORDS * 4 + (size_t)SKM2_MAXCH * 2 +
            (size_t)SKM2_MAXREC * 4;
 }
 u32 kh_skm2_max_cap2() { return SKM2_MAXREC; }
@@ -340,6 +279,92 @@ u32 kh_skm2_table() { return SKM2_UT; }
 u32 kh_skm2_union_per_cu() { return kh_skm2_union_lds_bytes(0) * 3 <= 160 * 1024 && SKM2_UNT * 3 <= 2048 ? 3u : 2u; }
 
 __device__ __forceinline__ u32 key2_hash(u64 lo, u64 hi) { return ((u32)lo ^ (u32)(lo >> 32) ^ (u32)hi ^ (u32)(hi >> 32)) * 0x9E3779B1u; }
+
+// ------------------------------------------------------------------------------------------
+// Record -> canonical two-word k-mers, one chunk of E <= 2 consecutive k-mers (k_skm2_union, k_skm_big).  128 bits of the record from base `first` on by a select of words and a funnel
+// shift; the forward key is that window with the order of its bases reversed, the reverse complement the
+// complemented window; the second k-mer by rolling both strands.  f(e, key) gets the canonical key of every e < E,
+// also of one behind the record's last k-mer: the caller knows how many it wants.
+// ------------------------------------------------------------------------------------------
+struct Skm2Key { unsigned long long lo, hi; };
+struct Skm2Consts {   // per launch: the 2k-bit mask, the shift that right-aligns a reversed 128-bit window, where the last base sits (33 <= k <= 63)
+    u32 kb;           // 2k: 66 .. 126
+    u32 km[4];
+    u64 kmhi;
+    u32 fs;           // 128 - 2k: 2 .. 62
+    u32 tsh;          // where the last base sits in the high word: 0 .. 60
+    __device__ __forceinline__ explicit Skm2Consts(const int k) : kb(2 * (u32)k), fs(128u - kb), tsh(kb - 2u - 64u) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) km[i] = kb >= 32u * (i + 1) ? 0xffffffffu : (kb > 32u * i ? (1u << (kb - 32u * i)) - 1u : 0u);
+        kmhi = ((u64)km[3] << 32) | km[2];
+    }
+};
+template <int E, class F>
+__device__ __forceinline__ void skm2_expand(const uint4 a, const uint4 b, const u32 first, const Skm2Consts& kc, F&& f) {
+    static_assert(E <= 2, "one base behind the first k-mer is kept");
+    // 128 bits of the record from base `first` on: words wq .. wq + 4, funnel-shifted
+    const u32 sh = 2 * first, wq = sh >> 5, r5 = sh & 31u;
+    const u32 R0 = a.x, R1 = a.y, R2 = a.z, R3 = a.w, R4 = b.x, R5 = b.y, R6 = b.z, R7 = SkmRec2::bases(b.w);
+    const bool q1 = wq & 1u, q2 = wq & 2u;
+    auto sel = [&](u32 v0, u32 v1, u32 v2, u32 v3) -> u32 {
+        const u32 lo2 = q1 ? v1 : v0, hi2 = q1 ? v3 : v2;
+        return q2 ? hi2 : lo2;
+    };
+    const u32 s0 = sel(R0, R1, R2, R3), s1 = sel(R1, R2, R3, R4), s2 = sel(R2, R3, R4, R5),
+              s3 = sel(R3, R4, R5, R6), s4 = sel(R4, R5, R6, R7);
+    u32 xw[4];
+    xw[0] = __builtin_amdgcn_alignbit(s1, s0, r5);
+    xw[1] = __builtin_amdgcn_alignbit(s2, s1, r5);
+    xw[2] = __builtin_amdgcn_alignbit(s3, s2, r5);
+    xw[3] = __builtin_amdgcn_alignbit(s4, s3, r5);
+    // the base behind the first k-mer (bits 2k .. 2k + 1 of the window): the second k-mer's last
+    const u32 nbw = kc.kb >= 96u ? xw[3] : xw[2];
+    const u32 nb = (nbw >> (kc.kb & 31u)) & 3u;
+    const u32 x0 = xw[0] & kc.km[0], x1 = xw[1] & kc.km[1], x2 = xw[2] & kc.km[2], x3 = xw[3] & kc.km[3];
+    // forward key: the window with the order of its bases reversed, right-aligned
+    const u32 y0 = revpairs32(x3), y1 = revpairs32(x2), y2 = revpairs32(x1), y3 = revpairs32(x0);
+    const u64 ylo = ((u64)y1 << 32) | y0, yhi = ((u64)y3 << 32) | y2;
+    u64 flo = (ylo >> kc.fs) | ((yhi << 1) << (63 - kc.fs)), fhi = yhi >> kc.fs;
+    // reverse complement key: the complemented window
+    u64 rlo = ((u64)(x1 ^ kc.km[1]) << 32) | (x0 ^ kc.km[0]), rhi = ((u64)(x3 ^ kc.km[3]) << 32) | (x2 ^ kc.km[2]);
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        if (e) {   // roll both strands by one base
+            fhi = ((fhi << 2) | (flo >> 62)) & kc.kmhi;
+            flo = (flo << 2) | nb;
+            rlo = (rlo >> 2) | (rhi << 62);
+            rhi = (rhi >> 2) | ((u64)(3u - nb) << kc.tsh);
+        }
+        const bool fwd = fhi < rhi || (fhi == rhi && flo < rlo);
+        f((u32)e, Skm2Key{fwd ? flo : rlo, fwd ? fhi : rhi});
+    }
+}
+// The claim of the probe walk for a two-word key (see the head of the file): claim the LOW word, the winner
+// publishes the high word; a key that meets its own low word waits for the high word and compares.
+struct SkmClaim2 {
+    unsigned long long* tklo;   // low key plane of the main table
+    u32 hi_off, okey_off;       // in entries behind it: the high plane of the same table; the second table's low plane
+    u32 ohi_off;                //   and, from there, the second table's high plane
+    Skm2Key K;
+    __device__ __forceinline__ u32 operator()(const bool second, const u32 S) const {
+        unsigned long long* const kl = tklo + (second ? okey_off : 0u) + S;
+        unsigned long long* const kh = kl + (second ? ohi_off : hi_off);
+        const unsigned long long o2 = atomicCAS(kl, ~0ull, K.lo);
+        bool hit = o2 == ~0ull;
+        const bool fresh = hit;
+        // the owners of this step publish their high words BEFORE any lane of the wave waits for one
+        // (one if / else would let the waiting lanes run first and spin on a masked-off owner for ever)
+        if (hit) __hip_atomic_store(kh, K.hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        __builtin_amdgcn_wave_barrier();
+        if (!hit && o2 == K.lo) {
+            unsigned long long h2;
+            do h2 = __hip_atomic_load(kh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            while (h2 == ~0ull);
+            hit = h2 == K.hi;
+        }
+        return fresh ? SKM_FRESH : (hit ? SKM_SAME_KEY : SKM_OTHER_KEY);
+    }
+};
 
 __global__ __launch_bounds__(SKM2_UNT, SKM2_UNT == 1024 ? 8 : 6) void k_skm2_union(const KhSkmJob jb, u32 cs) {
     extern __shared__ __attribute__((aligned(16))) u8 lds_raw[];
@@ -356,10 +381,11 @@ __global__ __launch_bounds__(SKM2_UNT, SKM2_UNT == 1024 ? 8 : 6) void k_skm2_uni
     unsigned long long* okhi = reinterpret_cast<unsigned long long*>(p);   p += (size_t)T2 * 8;
     u32* omlo = reinterpret_cast<u32*>(p);                                 p += (size_t)T2 * 4;
     u32* omhi = reinterpret_cast<u32*>(p);                                 p += (size_t)T2 * 4;
-    uint4* gtab = reinterpret_cast<uint4*>(p);                             p += 1024;
+    SkmReadout ro;   // (kh_skm_device.h: genome masks -> histogram bins)
+    ro.gtab = reinterpret_cast<uint4*>(p);                                 p += 1024;
     u32* scratch = reinterpret_cast<u32*>(p);                              p += 128;
-    u32* dupc = reinterpret_cast<u32*>(p);                                 p += 256;
-    u32* hstripe = reinterpret_cast<u32*>(p);                              p += (size_t)SKM2_HSTRIPE_WORDS * 4;
+    u32* dupc = ro.dupc = reinterpret_cast<u32*>(p);                       p += 256;
+    ro.hstripe = reinterpret_cast<u32*>(p);                                p += (size_t)SKM_HSTRIPE_WORDS * 4;
     u16* owner = reinterpret_cast<u16*>(p);                                p += (size_t)SKM2_MAXCH * 2;
     u32* rmask = reinterpret_cast<u32*>(p);
     // the records are staged in the low key plane (32 bytes each), the set of their contents is the high key plane
@@ -370,15 +396,8 @@ __global__ __launch_bounds__(SKM2_UNT, SKM2_UNT == 1024 ? 8 : 6) void k_skm2_uni
     u32 tid = tid0, lane = lane_id();
     const u32 nbins = jb.nbins, cap2 = jb.cap2, nslots = jb.nslots, stride = gridDim.x;
     const int k = jb.k;
-    const u32 sshift = nbins <= 72u ? 2u : (nbins <= 144u ? 1u : 0u), smask = (1u << sshift) - 1u;
     // the 2k-bit mask, the shift that right-aligns a reversed 128-bit window, where the last base sits (33 <= k <= 63)
-    const u32 kb = 2 * (u32)k;          // 66 .. 126
-    u32 km[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) km[i] = kb >= 32u * (i + 1) ? 0xffffffffu : (kb > 32u * i ? (1u << (kb - 32u * i)) - 1u : 0u);
-    const u64 kmhi = ((u64)km[3] << 32) | km[2];
-    const u32 fs = 128u - kb;           // 2 .. 62
-    const u32 tsh = kb - 2u - 64u;      // where the last base sits in the high word: 0 .. 60
+    const Skm2Consts kc(k);
     auto clear_keys = [&]() {   // key words all ones (low: empty, high: not yet published): T * 16 bytes
         uint4* k4 = reinterpret_cast<uint4*>(tklo);
         for (u32 i = tid; i < T; i += NT) k4[i] = make_uint4(0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu);
@@ -392,36 +411,12 @@ __global__ __launch_bounds__(SKM2_UNT, SKM2_UNT == 1024 ? 8 : 6) void k_skm2_uni
     typedef const u32 __attribute__((address_space(4))) * ConstU32;
     const ConstU32 counts = (ConstU32)(unsigned long long)jb.cur2;
     const u32 fit = cap2 < SKM2_MAXREC ? cap2 : SKM2_MAXREC;
-    auto count_of = [&](u32 sl) -> u32 {   // (an overfull slot is k_skm2_big's: empty here)
+    auto count_of = [&](u32 sl) -> u32 {   // (an overfull slot is k_skm_big's: empty here)
         const u32 n = sl < nslots ? counts[sl] : 0u;
         return n <= fit ? n : 0u;
     };
-    if (tid < (u32)KH_TAG_MAX_OPS) {
-        const u32 g = jb.ginfo[tid], g0 = g & 0xffu, gn = (g >> 8) & 0xffu;
-        const u64 gm = gn ? (gn >= 64u ? ~0ull : ((1ull << gn) - 1ull)) << g0 : 0ull;
-        gtab[tid] = make_uint4((u32)gm, (u32)(gm >> 32), (g >> 16) << sshift, 0u);
-        dupc[tid] = 0;
-    }
-    if (tid < SKM2_HSTRIPE_WORDS) hstripe[tid] = 0;
+    ro.init(jb.ginfo, nbins, jb.abase, tid);
     if (tid == 0) scratch[0] = 0;
-    auto eval_mask = [&](u32 mlo, u32 mhi) -> bool {
-        const u32 lsel = lane & smask;
-        u32 ng = 0;
-        do {
-            const u32 first = mlo ? (u32)__builtin_ctz(mlo) : 32u + (u32)__builtin_ctz(mhi);
-            const uint4 g = gtab[first];
-            u32 c = (u32)__popc(mlo & g.x) + (u32)__popc(mhi & g.y);
-            c = c < cs ? c : cs;
-            atomicAdd(&hstripe[g.z + (c << sshift) + lsel], 1u);
-            const u32 keep_hi = mlo ? ~0u : mhi - 1u;
-            mlo &= ~g.x & (mlo - 1u);
-            mhi &= ~g.y & keep_hi;
-            ++ng;
-        } while (mlo | mhi);
-        if (ng == 1u) return true;
-        atomicAdd(&hstripe[((jb.abase + (ng < cs ? ng : cs)) << sshift) + lsel], 1u);
-        return false;
-    };
     u32 st_full = 0, st_exp = 0;
     u32 slot = blockIdx.x;
     u32 nrec = count_of(slot);
@@ -434,13 +429,13 @@ __global__ __launch_bounds__(SKM2_UNT, SKM2_UNT == 1024 ? 8 : 6) void k_skm2_uni
         lane = tid & (KH_WAVE - 1u);
         const uint4* __restrict__ reg = jb.reg2 + (u64)slot * cap2 * 2;
         const u32 nrec_after = count_of(slot + 2u * stride);
-        if (counts[slot] > fit && tid0 == 0) {   // an overfull slot: listed for k_skm2_big
+        if (counts[slot] > fit && tid0 == 0) {   // an overfull slot: listed for k_skm_big
             const u32 at = atomicAdd(jb.ctl + 6, 1u);
             if (at < jb.big_cap) jb.big_list[at] = slot;
         }
         // ---- stage this slot's records, one per thread
         u32 nj = 0;
-        const u32 tg = rec2_tag(rb.w);
+        const u32 tg = SkmRec2::tag(rb.w);
         const u32 a0 = ra.x, a1 = ra.y, a2 = ra.z, a3 = ra.w, b0 = rb.x, b1 = rb.y, b2 = rb.z, b3 = rb.w;
         {
             u32 z = 0;
@@ -448,7 +443,7 @@ __global__ __launch_bounds__(SKM2_UNT, SKM2_UNT == 1024 ? 8 : 6) void k_skm2_uni
             for (u32 i = tid; i < DD / 4; i += NT) reinterpret_cast<uint4*>(dd)[i] = make_uint4(z, z, z, z);
         }
         if (tid < nrec) {
-            nj = rec2_n(b3);
+            nj = SkmRec2::n(b3);
             stage[2 * tid] = ra;
             stage[2 * tid + 1] = rb;
             rmask[tid] = 1u << (tg & 31u);
@@ -457,7 +452,7 @@ __global__ __launch_bounds__(SKM2_UNT, SKM2_UNT == 1024 ? 8 : 6) void k_skm2_uni
         // ---- identical records meet
         if (__builtin_amdgcn_ballot_w64(nj != 0)) {
             u32 h = a0 * 0x9E3779B1u ^ a1 * 0x85EBCA77u ^ a2 * 0xC2B2AE3Du ^ a3 * 0x27D4EB2Fu ^ b0 * 0x165667B1u ^ b1 * 0xD3A2646Cu ^
-                    b2 * 0xFD7046C5u ^ (b3 & ~(63u << 20)) * 0xB55A4F09u;
+                    b2 * 0xFD7046C5u ^ SkmRec2::content_hash_word(b3) * 0xB55A4F09u;
             h ^= h >> 15;
             h *= 0x2C1B3C6Du;
             u32 hp = (u32)(((u64)h * DD) >> 32);
@@ -470,12 +465,12 @@ __global__ __launch_bounds__(SKM2_UNT, SKM2_UNT == 1024 ? 8 : 6) void k_skm2_uni
                     else {
                         const uint4 oa = stage[2 * (old - 1u)], ob = stage[2 * (old - 1u) + 1];
                         if (oa.x == a0 && oa.y == a1 && oa.z == a2 && oa.w == a3 && ob.x == b0 && ob.y == b1 && ob.z == b2 &&
-                            ((ob.w ^ b3) & ~(31u << 20)) == 0u) {   // the same bases and number of k-mers, a genome of the same half
+                            SkmRec2::same_content(ob.w, b3)) {   // the same bases and number of k-mers, a genome of the same half
                             const u32 bit = 1u << (tg & 31u);
                             const u32 was = atomicOr(&rmask[old - 1u], bit);
                             if (was & bit) {
                                 atomicAdd(&dupc[tg], nj);
-                                rmask[tid] = 0u;   // "has counted repeats" (taken back if the slot is handed to k_skm2_big)
+                                rmask[tid] = 0u;   // "has counted repeats" (taken back if the slot is handed to k_skm_big)
                             }
                             pend = false;
                         } else hp = hp + 1u == DD ? 0u : hp + 1u;
@@ -496,10 +491,10 @@ __global__ __launch_bounds__(SKM2_UNT, SKM2_UNT == 1024 ? 8 : 6) void k_skm2_uni
         }
         __syncthreads();
         const u32 sc0 = scratch[0];
-        if ((sc0 & 0xffffu) > SKM2_MAXCH) {   // uniform, rare: the slot goes to k_skm2_big below; what the merge has counted is taken back
+        if ((sc0 & 0xffffu) > SKM2_MAXCH) {   // uniform, rare: the slot goes to k_skm_big below; what the merge has counted is taken back
             if (tid < nrec && rmask[tid] == 0u) {
                 const u32 w = stage[2 * tid + 1].w;
-                atomicSub(&dupc[rec2_tag(w)], rec2_n(w));
+                atomicSub(&dupc[SkmRec2::tag(w)], SkmRec2::n(w));
             }
             __syncthreads();
         }
@@ -511,7 +506,7 @@ __global__ __launch_bounds__(SKM2_UNT, SKM2_UNT == 1024 ? 8 : 6) void k_skm2_uni
         u32 C = sc0 & 0xffffu, N = sc0 >> 16;
         st_full = N > st_full ? N : st_full;
         st_exp += N;
-        if (C > SKM2_MAXCH) {   // uniform: more chunks than are numbered here: k_skm2_big takes the slot
+        if (C > SKM2_MAXCH) {   // uniform: more chunks than are numbered here: k_skm_big takes the slot
             if (tid == 0) {
                 if (jb.big_list) {
                     const u32 at = atomicAdd(jb.ctl + 6, 1u);
@@ -543,49 +538,16 @@ __global__ __launch_bounds__(SKM2_UNT, SKM2_UNT == 1024 ? 8 : 6) void k_skm2_uni
                     const u32 o = owner[c], ri = o >> SKM2_OB, first = (o & ((1u << SKM2_OB) - 1u)) * (u32)E;
                     const uint4 a = reg[2 * ri], b = reg[2 * ri + 1];
                     bits = rmask[ri];
-                    half = (b.w >> 25) & 1u;
-                    const u32 left = rec2_n(b.w) - first;
+                    half = SkmRec2::half(b.w);
+                    const u32 left = SkmRec2::n(b.w) - first;
                     const u32 cnt = left < (u32)E ? left : (u32)E;
-                    // 128 bits of the record from base `first` on: words wq .. wq + 4, funnel-shifted
-                    const u32 sh = 2 * first, wq = sh >> 5, r5 = sh & 31u;
-                    const u32 R0 = a.x, R1 = a.y, R2 = a.z, R3 = a.w, R4 = b.x, R5 = b.y, R6 = b.z, R7 = b.w & 0x3ffu;
-                    const bool q1 = wq & 1u, q2 = wq & 2u;
-                    auto sel = [&](u32 v0, u32 v1, u32 v2, u32 v3) -> u32 {
-                        const u32 lo2 = q1 ? v1 : v0, hi2 = q1 ? v3 : v2;
-                        return q2 ? hi2 : lo2;
-                    };
-                    const u32 s0 = sel(R0, R1, R2, R3), s1 = sel(R1, R2, R3, R4), s2 = sel(R2, R3, R4, R5),
-                              s3 = sel(R3, R4, R5, R6), s4 = sel(R4, R5, R6, R7);
-                    u32 xw[4];
-                    xw[0] = __builtin_amdgcn_alignbit(s1, s0, r5);
-                    xw[1] = __builtin_amdgcn_alignbit(s2, s1, r5);
-                    xw[2] = __builtin_amdgcn_alignbit(s3, s2, r5);
-                    xw[3] = __builtin_amdgcn_alignbit(s4, s3, r5);
-                    // the base behind the first k-mer (bits 2k .. 2k + 1 of the window): the second k-mer's last
-                    const u32 nbw = kb >= 96u ? xw[3] : xw[2];
-                    const u32 nb = (nbw >> (kb & 31u)) & 3u;
-                    const u32 x0 = xw[0] & km[0], x1 = xw[1] & km[1], x2 = xw[2] & km[2], x3 = xw[3] & km[3];
-                    // forward key: the window with the order of its bases reversed, right-aligned
-                    const u32 y0 = revpairs32(x3), y1 = revpairs32(x2), y2 = revpairs32(x1), y3 = revpairs32(x0);
-                    const u64 ylo = ((u64)y1 << 32) | y0, yhi = ((u64)y3 << 32) | y2;
-                    u64 flo = (ylo >> fs) | ((yhi << 1) << (63 - fs)), fhi = yhi >> fs;
-                    // reverse complement key: the complemented window
-                    u64 rlo = ((u64)(x1 ^ km[1]) << 32) | (x0 ^ km[0]), rhi = ((u64)(x3 ^ km[3]) << 32) | (x2 ^ km[2]);
-#pragma unroll
-                    for (int e = 0; e < E; ++e) {
-                        if (e) {   // roll both strands by one base
-                            fhi = ((fhi << 2) | (flo >> 62)) & kmhi;
-                            flo = (flo << 2) | nb;
-                            rlo = (rlo >> 2) | (rhi << 62);
-                            rhi = (rhi >> 2) | ((u64)(3u - nb) << tsh);
-                        }
-                        const bool fwd = fhi < rhi || (fhi == rhi && flo < rlo);
-                        klo[e] = fwd ? flo : rlo;
-                        khi[e] = fwd ? fhi : rhi;
+                    skm2_expand<E>(a, b, first, kc, [&](const u32 e, const Skm2Key K) __attribute__((always_inline)) {
+                        klo[e] = K.lo;
+                        khi[e] = K.hi;
                         const u32 h = key2_hash(klo[e], khi[e]);
                         slot_[e] = (u32)(((u64)h * T) >> 32);
-                        if ((u32)e < cnt && (R == 1 || (((h >> 4) & 0xffffu) * R) >> 16 == q)) act |= 1u << e;
-                    }
+                        if (e < cnt && (R == 1 || (((h >> 4) & 0xffffu) * R) >> 16 == q)) act |= 1u << e;
+                    });
                 }
                 if (!__builtin_amdgcn_ballot_w64(act != 0)) continue;
                 u32* const mp = half ? tmhi : tmlo;
@@ -622,7 +584,7 @@ __global__ __launch_bounds__(SKM2_UNT, SKM2_UNT == 1024 ? 8 : 6) void k_skm2_uni
             }                                                                                                          \
         }                                                                                                              \
     }
-                for (u32 round = 0; round < 4u && __builtin_amdgcn_ballot_w64(act != 0); ++round) SKM2_ROUND(tklo, tkhi, mp, T, 0u)
+                for (u32 round = 0; round < (u32)KH_TUNE_SKM_FULL_ROUNDS && __builtin_amdgcn_ballot_w64(act != 0); ++round) SKM2_ROUND(tklo, tkhi, mp, T, 0u)
                 if (__builtin_amdgcn_ballot_w64(act != 0)) {
                     u32* const mp2 = half ? omhi : omlo;
 #pragma unroll
@@ -630,7 +592,7 @@ __global__ __launch_bounds__(SKM2_UNT, SKM2_UNT == 1024 ? 8 : 6) void k_skm2_uni
                     for (u32 round = 0; round < 8u && __builtin_amdgcn_ballot_w64(act != 0); ++round) SKM2_ROUND(oklo, okhi, mp2, T2, 0x4000u)
                     if (__builtin_amdgcn_ballot_w64(act != 0)) {   // a crowded second table: on in the main one
 #pragma unroll
-                        for (int e = 0; e < E; ++e) { const u32 x = (u32)(((u64)key2_hash(klo[e], khi[e]) * T) >> 32) + 4u; slot_[e] = x >= T ? x - T : x; }
+                        for (int e = 0; e < E; ++e) { const u32 x = (u32)(((u64)key2_hash(klo[e], khi[e]) * T) >> 32) + (u32)KH_TUNE_SKM_FULL_ROUNDS; slot_[e] = x >= T ? x - T : x; }
                         for (u32 round = 0; round < T && __builtin_amdgcn_ballot_w64(act != 0); ++round) SKM2_ROUND(tklo, tkhi, mp, T, 0u)
                         if (__builtin_amdgcn_ballot_w64(act != 0) && lane == 0) atomicOr(jb.ctl, KH_ERR_CAPACITY);
                     }
@@ -659,13 +621,13 @@ __global__ __launch_bounds__(SKM2_UNT, SKM2_UNT == 1024 ? 8 : 6) void k_skm2_uni
                     if (f & 0x8000u) {
                         const u32 at = f & 0x3fffu;
                         const bool second = f & 0x4000u;
-                        if (eval_mask((second ? omlo : tmlo)[at], (second ? omhi : tmhi)[at])) ++ones;
+                        if (ro.eval_mask(lane, (second ? omlo : tmlo)[at], (second ? omhi : tmhi)[at], cs)) ++ones;
                     }
                 }
             }
             if (__builtin_amdgcn_ballot_w64(ones != 0)) {
                 ones = wave_scan_add(ones);
-                if (lane == KH_WAVE - 1) atomicAdd(&hstripe[(jb.abase + 1u) << sshift], ones);
+                if (lane == KH_WAVE - 1) ro.add_single_group(ones);
             }
             if (q + 1 < R) __syncthreads();
         }
@@ -674,13 +636,7 @@ __global__ __launch_bounds__(SKM2_UNT, SKM2_UNT == 1024 ? 8 : 6) void k_skm2_uni
     }
     __syncthreads();
     tid = tid0;
-    unsigned long long* __restrict__ rep = jb.hist + (u64)(blockIdx.x % jb.reps) * nbins;
-    for (u32 i = tid; i < nbins; i += NT) {
-        u32 v = 0;
-        for (u32 j = 0; j <= smask; ++j) v += hstripe[(i << sshift) + j];
-        if (v) atomicAdd(&rep[i], (unsigned long long)v);
-    }
-    if (tid < (u32)KH_TAG_MAX_OPS && dupc[tid]) atomicAdd(&jb.dup[tid], (unsigned long long)dupc[tid]);
+    ro.flush(jb.hist + (u64)(blockIdx.x % jb.reps) * nbins, nbins, jb.dup, tid, NT);
     if (tid == 0) {
         if (st_full > T) atomicMax(jb.ctl + 1, st_full);
         atomicAdd(jb.ctl + 3, st_exp);
@@ -688,234 +644,28 @@ __global__ __launch_bounds__(SKM2_UNT, SKM2_UNT == 1024 ? 8 : 6) void k_skm2_uni
 }
 
 // ------------------------------------------------------------------------------------------
-// Overfull slots with two-word keys (as k_skm_big in kh_skm.hip): one workgroup per listed slot takes the records in
-// its region and its records on the side list, every k-mer into a 2048-entry table in rounds of key subsets, read-out by
-// a scan of the table.  Nothing here is tuned: a handful of slots per run.
+// Overfull slots: k_skm_big (kh_skm_device.h) with two-word keys, a table of 2048 entries
 // ------------------------------------------------------------------------------------------
-constexpr u32 SKM2_BIG_NT = 1024, SKM2_BIG_T = 2048, SKM2_BIG_T2 = 64, SKM2_BIG_IDX = 4096;
-constexpr u32 SKM2_BIG_BATCH = 128, SKM2_BIG_MAXCH = SKM2_BIG_BATCH << SKM2_OB;
-size_t kh_skm2_big_lds_bytes() {
-    return (size_t)SKM2_BIG_T * 24 + (size_t)SKM2_BIG_T2 * 24 + 1024 + 128 + 256 + (size_t)SKM2_HSTRIPE_WORDS * 4 +
-           (size_t)SKM2_BIG_MAXCH * 2 + (size_t)SKM2_BIG_IDX * 4;
-}
-__global__ __launch_bounds__(SKM2_BIG_NT) void k_skm2_big(const KhSkmJob jb, u32 cs) {
-    extern __shared__ __attribute__((aligned(16))) u8 lds_raw[];
-    constexpr u32 NT = SKM2_BIG_NT, T = SKM2_BIG_T, T2 = SKM2_BIG_T2, HBITS = 11;
-    constexpr int E = (int)SKM2_UE;
-    constexpr u64 EMPTY = ~0ull;
-    u8* p = lds_raw;
-    unsigned long long* tklo = reinterpret_cast<unsigned long long*>(p);   p += (size_t)T * 8;
-    unsigned long long* tkhi = reinterpret_cast<unsigned long long*>(p);   p += (size_t)T * 8;
-    u32* tmlo = reinterpret_cast<u32*>(p);                                 p += (size_t)T * 4;
-    u32* tmhi = reinterpret_cast<u32*>(p);                                 p += (size_t)T * 4;
-    unsigned long long* oklo = reinterpret_cast<unsigned long long*>(p);   p += (size_t)T2 * 8;
-    unsigned long long* okhi = reinterpret_cast<unsigned long long*>(p);   p += (size_t)T2 * 8;
-    u32* omlo = reinterpret_cast<u32*>(p);                                 p += (size_t)T2 * 4;
-    u32* omhi = reinterpret_cast<u32*>(p);                                 p += (size_t)T2 * 4;
-    uint4* gtab = reinterpret_cast<uint4*>(p);                             p += 1024;
-    u32* scratch = reinterpret_cast<u32*>(p);                              p += 128;
-    u32* dupc = reinterpret_cast<u32*>(p);                                 p += 256;
-    u32* hstripe = reinterpret_cast<u32*>(p);                              p += (size_t)SKM2_HSTRIPE_WORDS * 4;
-    u16* owner = reinterpret_cast<u16*>(p);                                p += (size_t)SKM2_BIG_MAXCH * 2;
-    u32* sidx = reinterpret_cast<u32*>(p);
-    const u32 tid = threadIdx.x, lane = lane_id();
-    const u32 nbins = jb.nbins, cap2 = jb.cap2;
-    const int k = jb.k;
-    const u32 slot = jb.big_list[blockIdx.x];
-    const u32 sshift = nbins <= 72u ? 2u : (nbins <= 144u ? 1u : 0u), smask = (1u << sshift) - 1u;
-    const u32 kb = 2 * (u32)k;
-    u32 km[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) km[i] = kb >= 32u * (i + 1) ? 0xffffffffu : (kb > 32u * i ? (1u << (kb - 32u * i)) - 1u : 0u);
-    const u64 kmhi = ((u64)km[3] << 32) | km[2];
-    const u32 fs = 128u - kb, tsh = kb - 2u - 64u;
-    if (tid < (u32)KH_TAG_MAX_OPS) {
-        const u32 g = jb.ginfo[tid], g0 = g & 0xffu, gn = (g >> 8) & 0xffu;
-        const u64 gm = gn ? (gn >= 64u ? ~0ull : ((1ull << gn) - 1ull)) << g0 : 0ull;
-        gtab[tid] = make_uint4((u32)gm, (u32)(gm >> 32), (g >> 16) << sshift, 0u);
-        dupc[tid] = 0;
+struct SkmBig2 {
+    using Rec = SkmRec2;
+    using Consts = Skm2Consts;
+    using Key = Skm2Key;
+    static constexpr u32 T = 2048, T2 = 64, KEY_BYTES = 16, BATCH = 128, OB = SKM2_OB;
+    static constexpr int E = (int)SKM2_UE;
+    template <class F> static __device__ __forceinline__ void expand(const SkmRecord<2>& r, const u32 first, const Consts& kc, F&& f) {
+        skm2_expand<E>(r.v[0], r.v[1], first, kc, f);
     }
-    if (tid < SKM2_HSTRIPE_WORDS) hstripe[tid] = 0;
-    if (tid < 8) scratch[tid] = 0;
-    __syncthreads();
-    u32 nspill_all = jb.ctl[5];
-    nspill_all = nspill_all < jb.spill_cap ? nspill_all : jb.spill_cap;
-    for (u32 i = tid; i < nspill_all; i += NT) {
-        if (jb.spill_slot[i] == slot) {
-            const u32 at = atomicAdd(&scratch[3], 1u);
-            if (at < SKM2_BIG_IDX) sidx[at] = i;
-        }
+    static __device__ __forceinline__ u32 hash(const Key& K) { return key2_hash(K.lo, K.hi); }
+    static __device__ __forceinline__ SkmClaim2 claim(u8* kmain, const u32 okey_off, const Key& K) {
+        return SkmClaim2{reinterpret_cast<unsigned long long*>(kmain), T, okey_off, T2, K};
     }
-    __syncthreads();
-    u32 nside = scratch[3];
-    if (nside > SKM2_BIG_IDX) {
-        if (tid == 0) atomicOr(jb.ctl, KH_ERR_CAPACITY);
-        nside = SKM2_BIG_IDX;
-    }
-    const u32 nreg = jb.cur2[slot] < cap2 ? jb.cur2[slot] : cap2;
-    const uint4* __restrict__ reg = jb.reg2 + (u64)slot * cap2 * 2;
-    const u32 nall = nreg + nside;
-    auto rec_a = [&](u32 i) -> uint4 { return i < nreg ? reg[2 * i] : jb.spill_rec[2 * (u64)sidx[i - nreg]]; };
-    auto rec_b = [&](u32 i) -> uint4 { return i < nreg ? reg[2 * i + 1] : jb.spill_rec[2 * (u64)sidx[i - nreg] + 1]; };
-    {
-        u32 mine = 0;
-        for (u32 i = tid; i < nall; i += NT) mine += rec2_n(rec_b(i).w);
-        const u32 tot = wave_scan_add(mine);
-        if (lane == KH_WAVE - 1 && tot) atomicAdd(&scratch[2], tot);
-    }
-    __syncthreads();
-    const u32 N = scratch[2];
-    const u32 R = (N + 1535u) / 1536u;
-    if (tid == 0 && N > T) atomicMax(jb.ctl + 1, N);
-    auto eval_mask = [&](u32 mlo, u32 mhi) -> bool {
-        const u32 lsel = lane & smask;
-        u32 ng = 0;
-        do {
-            const u32 first = mlo ? (u32)__builtin_ctz(mlo) : 32u + (u32)__builtin_ctz(mhi);
-            const uint4 g = gtab[first];
-            u32 c = (u32)__popc(mlo & g.x) + (u32)__popc(mhi & g.y);
-            c = c < cs ? c : cs;
-            atomicAdd(&hstripe[g.z + (c << sshift) + lsel], 1u);
-            const u32 keep_hi = mlo ? ~0u : mhi - 1u;
-            mlo &= ~g.x & (mlo - 1u);
-            mhi &= ~g.y & keep_hi;
-            ++ng;
-        } while (mlo | mhi);
-        if (ng == 1u) return true;
-        atomicAdd(&hstripe[((jb.abase + (ng < cs ? ng : cs)) << sshift) + lsel], 1u);
-        return false;
-    };
-    for (u32 q = blockIdx.y; q < R; q += gridDim.y) {   // (the rounds are independent: workgroups (slot, y) share them out)
-        for (u32 i = tid; i < T; i += NT) reinterpret_cast<uint4*>(tklo)[i] = make_uint4(0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu);
-        for (u32 i = tid; i < T / 2; i += NT) reinterpret_cast<uint4*>(tmlo)[i] = make_uint4(0u, 0u, 0u, 0u);
-        if (tid < T2) { oklo[tid] = EMPTY; okhi[tid] = EMPTY; omlo[tid] = 0u; omhi[tid] = 0u; }
-        __syncthreads();
-        for (u32 b0 = 0; b0 < nall; b0 += SKM2_BIG_BATCH) {
-            const u32 mine_i = b0 + tid;
-            const u32 nj = tid < SKM2_BIG_BATCH && mine_i < nall ? rec2_n(rec_b(mine_i).w) : 0u;
-            const u32 nch = (nj + (u32)E - 1u) / (u32)E;
-            {
-                const u32 incl = wave_scan_add(nch);
-                u32 wbase = 0;
-                if (lane == KH_WAVE - 1 && incl) wbase = atomicAdd(&scratch[0], incl);
-                wbase = (u32)__builtin_amdgcn_readlane((int)wbase, KH_WAVE - 1);
-                const u32 cstart = wbase + incl - nch;
-                if (cstart + nch <= SKM2_BIG_MAXCH)
-                    for (u32 cc = 0; cc < nch; ++cc) owner[cstart + cc] = (u16)((tid << SKM2_OB) | cc);
-            }
-            __syncthreads();
-            u32 C = scratch[0];
-            if (C > SKM2_BIG_MAXCH) {
-                if (tid == 0) atomicOr(jb.ctl, KH_ERR_CAPACITY);
-                C = 0;
-            }
-            for (u32 c = tid; c < C; c += NT) {
-                const u32 o = owner[c], ri = b0 + (o >> SKM2_OB), first = (o & ((1u << SKM2_OB) - 1u)) * (u32)E;
-                const uint4 a = rec_a(ri), b = rec_b(ri);
-                const u32 tg = rec2_tag(b.w), bit = 1u << (tg & 31u), half = tg >> 5;
-                const u32 left = rec2_n(b.w) - first;
-                const u32 cnt = left < (u32)E ? left : (u32)E;
-                const u32 sh = 2 * first, wq = sh >> 5, r5 = sh & 31u;
-                const u32 R0 = a.x, R1 = a.y, R2 = a.z, R3 = a.w, R4 = b.x, R5 = b.y, R6 = b.z, R7 = b.w & 0x3ffu;
-                const bool q1 = wq & 1u, q2 = wq & 2u;
-                auto sel = [&](u32 v0, u32 v1, u32 v2, u32 v3) -> u32 {
-                    const u32 lo2 = q1 ? v1 : v0, hi2 = q1 ? v3 : v2;
-                    return q2 ? hi2 : lo2;
-                };
-                const u32 s0 = sel(R0, R1, R2, R3), s1 = sel(R1, R2, R3, R4), s2 = sel(R2, R3, R4, R5),
-                          s3 = sel(R3, R4, R5, R6), s4 = sel(R4, R5, R6, R7);
-                u32 xw[4];
-                xw[0] = __builtin_amdgcn_alignbit(s1, s0, r5);
-                xw[1] = __builtin_amdgcn_alignbit(s2, s1, r5);
-                xw[2] = __builtin_amdgcn_alignbit(s3, s2, r5);
-                xw[3] = __builtin_amdgcn_alignbit(s4, s3, r5);
-                const u32 nbw = kb >= 96u ? xw[3] : xw[2];
-                const u32 nb = (nbw >> (kb & 31u)) & 3u;
-                const u32 x0 = xw[0] & km[0], x1 = xw[1] & km[1], x2 = xw[2] & km[2], x3 = xw[3] & km[3];
-                const u32 y0 = revpairs32(x3), y1 = revpairs32(x2), y2 = revpairs32(x1), y3 = revpairs32(x0);
-                const u64 ylo = ((u64)y1 << 32) | y0, yhi = ((u64)y3 << 32) | y2;
-                u64 flo = (ylo >> fs) | ((yhi << 1) << (63 - fs)), fhi = yhi >> fs;
-                u64 rlo = ((u64)(x1 ^ km[1]) << 32) | (x0 ^ km[0]), rhi = ((u64)(x3 ^ km[3]) << 32) | (x2 ^ km[2]);
-#pragma unroll
-                for (int e = 0; e < E; ++e) {
-                    if (e) {
-                        fhi = ((fhi << 2) | (flo >> 62)) & kmhi;
-                        flo = (flo << 2) | nb;
-                        rlo = (rlo >> 2) | (rhi << 62);
-                        rhi = (rhi >> 2) | ((u64)(3u - nb) << tsh);
-                    }
-                    if ((u32)e >= cnt) break;
-                    const bool fwd = fhi < rhi || (fhi == rhi && flo < rlo);
-                    const unsigned long long KL = fwd ? flo : rlo, KH = fwd ? fhi : rhi;
-                    const u32 H = key2_hash(KL, KH);
-                    if (R != 1 && (((H >> 4) & 0xffffu) * R) >> 16 != q) continue;
-                    u32 S = H >> (32 - HBITS), probes = 0, level = 0;
-                    while (true) {
-                        unsigned long long* kl = level == 1 ? oklo : tklo;
-                        unsigned long long* kh = level == 1 ? okhi : tkhi;
-                        const unsigned long long o2 = atomicCAS(&kl[S], EMPTY, KL);
-                        bool hit = o2 == EMPTY;
-                        // the owners of this step publish their high words BEFORE any lane of the wave waits for one
-                        // (one if / else would let the waiting lanes run first and spin on a masked-off owner for ever)
-                        if (hit) __hip_atomic_store(&kh[S], KH, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                        __builtin_amdgcn_wave_barrier();
-                        if (!hit && o2 == KL) {
-                            unsigned long long h2;
-                            do h2 = __hip_atomic_load(&kh[S], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                            while (h2 == EMPTY);
-                            hit = h2 == KH;
-                        }
-                        if (hit) {
-                            u32* mp = level == 1 ? (half ? omhi : omlo) : (half ? tmhi : tmlo);
-                            if (atomicOr(mp + S, bit) & bit) atomicAdd(&dupc[tg], 1u);
-                            break;
-                        }
-                        ++probes;
-                        if (level == 0 && probes >= 4u) {
-                            level = 1; probes = 0;
-                            S = ((H ^ (H >> 15)) * 0x85EBCA77u) >> 26;
-                        } else if (level == 1 && probes >= 8u) {
-                            level = 2; probes = 0;
-                            S = ((H >> (32 - HBITS)) + 4u) & (T - 1u);
-                        } else if (level == 2 && probes >= T) {
-                            atomicOr(jb.ctl, KH_ERR_CAPACITY);
-                            break;
-                        } else {
-                            S = (S + 1u) & (level == 1 ? T2 - 1u : T - 1u);
-                        }
-                    }
-                }
-            }
-            __syncthreads();
-            if (tid == 0) scratch[0] = 0;
-            __syncthreads();
-        }
-        u32 ones = 0;
-        for (u32 i = tid; i < T; i += NT)
-            if (tklo[i] != EMPTY && eval_mask(tmlo[i], tmhi[i])) ++ones;
-        if (tid < T2 && oklo[tid] != EMPTY && eval_mask(omlo[tid], omhi[tid])) ++ones;
-        ones = wave_scan_add(ones);
-        if (lane == KH_WAVE - 1 && ones) atomicAdd(&hstripe[(jb.abase + 1u) << sshift], ones);
-        __syncthreads();
-    }
-    unsigned long long* __restrict__ rep = jb.hist + (u64)(blockIdx.x % jb.reps) * nbins;
-    for (u32 i = tid; i < nbins; i += NT) {
-        u32 v = 0;
-        for (u32 j = 0; j <= smask; ++j) v += hstripe[(i << sshift) + j];
-        if (v) atomicAdd(&rep[i], (unsigned long long)v);
-    }
-    if (tid < (u32)KH_TAG_MAX_OPS && dupc[tid]) atomicAdd(&jb.dup[tid], (unsigned long long)dupc[tid]);
-    if (tid == 0 && blockIdx.y == 0) atomicAdd(jb.ctl + 3, N);
-}
+};
 
 // ------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------
-template <class K> static void skm2_allow_lds(K kern, size_t bytes) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
 template <int WW> static void launch_scatter2_w(const KhSkmJob& job, u32 ntiles, size_t lds, hipStream_t st) {
-    skm2_allow_lds(k_skm2_scatter<WW>, lds);
+    skm_allow_lds(k_skm2_scatter<WW>, lds);
     hipLaunchKernelGGL(k_skm2_scatter<WW>, dim3(ntiles), dim3(SKM_NT), lds, st, job);
 }
 // m-mers per k-mer the two-word scatter is instantiated for: every third value, so that one of the minimizer
@@ -931,20 +681,10 @@ void kh_launch_skm2_scatter(const KhSkmJob& job, u32 ntiles, hipStream_t st) {
         default: break;   // the host asks kh_skm2_supports_w first
     }
 }
-void kh_launch_skm2_regroup(const KhSkmJob& job, hipStream_t st) {
-    const size_t lds = kh_skm2_regroup_lds_bytes(job.S);
-    skm2_allow_lds(k_skm2_regroup, lds);
-    hipLaunchKernelGGL(k_skm2_regroup, dim3(job.nb1), dim3(SKM_RG_NT), lds, st, job);
-}
+void kh_launch_skm2_regroup(const KhSkmJob& job, hipStream_t st) { skm_launch_regroup<SkmRec2>(job, st); }
 void kh_launch_skm2_union(const KhSkmJob& job, u32 cs, u32 grid, hipStream_t st) {
     const size_t lds = kh_skm2_union_lds_bytes(job.nbins);
-    skm2_allow_lds(k_skm2_union, lds);
+    skm_allow_lds(k_skm2_union, lds);
     hipLaunchKernelGGL(k_skm2_union, dim3(grid), dim3(SKM2_UNT), lds, st, job, cs);
 }
-static u32 big_y() { const char* e = getenv("KHOICE_SKM_BIG_Y"); const int v = e ? atoi(e) : 4; return (u32)(v < 1 ? 1 : (v > 16 ? 16 : v)); }
-void kh_launch_skm2_big(const KhSkmJob& job, u32 cs, u32 nbig, hipStream_t st) {
-    if (!nbig) return;
-    const size_t lds = kh_skm2_big_lds_bytes();
-    skm2_allow_lds(k_skm2_big, lds);
-    hipLaunchKernelGGL(k_skm2_big, dim3(nbig, nbig < 2048u ? big_y() : 1u), dim3(SKM2_BIG_NT), lds, st, job, cs);   // y: the rounds of a slot side by side
-}
+void kh_launch_skm2_big(const KhSkmJob& job, u32 cs, u32 nbig, hipStream_t st) { skm_launch_big<SkmBig2>(job, cs, nbig, st); }

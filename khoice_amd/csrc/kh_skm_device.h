@@ -1,10 +1,19 @@
 // khoice_amd — device helpers shared by the two super-k-mer kernel files (kh_skm.hip: one-word keys,
-// kh_skm2.hip: two-word keys): minimizer hashing, sliding minimum, the LDS counting-sort flush, code-word prefetch.
+// kh_skm2.hip: two-word keys): minimizer hashing, sliding minimum, the LDS counting-sort flush, code-word prefetch,
+// and the pieces both key widths are built from: the record formats (kh_skm_rec.h), the one-key probe walk, the
+// read-out of genome masks into histogram bins, the regroup kernel and the kernel of the overfull slots.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstdlib>
+
 #include "kh_device.h"
 #include "kh_launch.h"
+#include "kh_skm_rec.h"
+
+#ifndef KH_TUNE_SKM_FULL_ROUNDS
+#define KH_TUNE_SKM_FULL_ROUNDS 4   // probe rounds made by all keys of a thread together; the rest one key per lane (1 / 2 / 3 / 4 / 5 / 8 rounds: union 16.3 / 3.33 / 1.59 / 1.51 / 1.52 / 1.55 ms)
+#endif
 
 namespace {
 
@@ -15,7 +24,7 @@ constexpr u32 SKM_CW = (SKM_SUB + KH_HALO) / 16;
 constexpr u32 SKM_CAP = KH_SKM_STAGE;          // records staged in LDS per flush of the scatter
 constexpr int SKM_WMIN = 5, SKM_WMAX = 18;     // m-mers per k-mer the scatter is instantiated for
 constexpr u32 SKM_RG_NT = 1024;                // regroup: one workgroup per coarse bucket
-constexpr u32 SKM_RG_CAP = 8192;               // records per round of the regroup
+static_assert(KH_SKM_MAX_FINE == 1u << SkmRec1::FINE_BITS && KH_SKM2_MAX_FINE == 1u << SkmRec2::FINE_BITS, "a fine slot index fills its field");
 
 __device__ __forceinline__ u32 revpairs32(u32 x) {
     x = __builtin_bitreverse32(x);
@@ -236,4 +245,330 @@ __device__ __forceinline__ void skm_store(const SkmFetch& f, u32* code, u16* bad
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// The probe walk of ONE key by one lane (k_skm_big, k_skm_phased; the unions' vectorised rounds make the same
+// decisions for all keys of a thread at once and fall back to a loop of their own): KH_TUNE_SKM_FULL_ROUNDS probes
+// in the main table of T entries, eight in the second table of T2 with an independent hash, then the main table
+// to its end; a full main table is KH_ERR_CAPACITY.  Occupied entries stay occupied, so every copy of a key takes
+// the same decisions as the first.  claim(second, S) tries entry S of the main or the second table for the key and
+// says what it found; hit(second, S, fresh) is called once, for the entry the key ends in.
+// ------------------------------------------------------------------------------------------
+enum SkmClaimed : u32 { SKM_OTHER_KEY = 0, SKM_SAME_KEY = 1, SKM_FRESH = 2 };
+constexpr u32 skm_log2(u32 x) { return x <= 1u ? 0u : 1u + skm_log2(x >> 1); }
+template <u32 T, u32 T2, class Claim, class Hit>
+__device__ __forceinline__ void skm_probe_walk(const u32 H, u32* __restrict__ ctl, Claim&& claim, Hit&& hit) {
+    static_assert((T & (T - 1u)) == 0u && (T2 & (T2 - 1u)) == 0u, "table indices are hash bits and wrap by a mask");
+    constexpr u32 HBITS = skm_log2(T), H2BITS = skm_log2(T2);
+    u32 S = H >> (32 - HBITS), probes = 0, level = 0;   // level 0: main table, 1: second table, 2: main table, unbounded
+    while (true) {
+        const u32 c = claim(level == 1, S);
+        if (c != SKM_OTHER_KEY) {
+            hit(level == 1, S, c == SKM_FRESH);
+            break;
+        }
+        ++probes;
+        if (level == 0 && probes >= (u32)KH_TUNE_SKM_FULL_ROUNDS) {
+            level = 1; probes = 0;
+            S = ((H ^ (H >> 15)) * 0x85EBCA77u) >> (32 - H2BITS);
+        } else if (level == 1 && probes >= 8u) {   // a crowded second table: on in the main one
+            level = 2; probes = 0;
+            S = ((H >> (32 - HBITS)) + (u32)KH_TUNE_SKM_FULL_ROUNDS) & (T - 1u);
+        } else if (level == 2 && probes >= T) {
+            atomicOr(ctl, KH_ERR_CAPACITY);   // the main table is full: the key is dropped, the host falls back
+            break;
+        } else {
+            S = (S + 1u) & (level == 1 ? T2 - 1u : T - 1u);
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// Read-out: the genome mask of one distinct k-mer -> histogram bins, kept in LDS until the workgroup ends.
+// Per group that holds the k-mer: popcount of the mask inside the group -> the group's bin; number of groups -> the
+// across-group bin.  hstripe holds 4 / 2 / 1 copies of every bin for <= 72 / 144 / 255 bins (sshift = 2 / 1 / 0; a
+// lane adds to the copy of its number: fewer LDS atomics on one address), so 288 words take any of the three.
+// Pointers and two uniform values only: `lane` and `tid` are arguments because the unions re-derive them per slot
+// from an opaque copy of threadIdx.x (LDS addresses formed from them are then not kept live across the slot loop).
+// ------------------------------------------------------------------------------------------
+constexpr u32 SKM_HSTRIPE_WORDS = 288;
+struct SkmReadout {
+    uint4* gtab;    // [KH_TAG_MAX_OPS] per operand: its group's mask (two halves), first bin << sshift
+    u32* hstripe;   // [SKM_HSTRIPE_WORDS]
+    u32* dupc;      // [KH_TAG_MAX_OPS] per genome: instances whose (k-mer, genome) pair was seen before
+    u32 sshift, abase;
+    // (by threads 0 .. 287 at least; a barrier follows before the first eval_mask)
+    __device__ __forceinline__ void init(const u32* __restrict__ ginfo, const u32 nbins, const u32 abase_, const u32 tid) {
+        sshift = nbins <= 72u ? 2u : (nbins <= 144u ? 1u : 0u);
+        abase = abase_;
+        if (tid < (u32)KH_TAG_MAX_OPS) {
+            const u32 g = ginfo[tid], g0 = g & 0xffu, gn = (g >> 8) & 0xffu;
+            const u64 gm = gn ? (gn >= 64u ? ~0ull : ((1ull << gn) - 1ull)) << g0 : 0ull;
+            gtab[tid] = make_uint4((u32)gm, (u32)(gm >> 32), (g >> 16) << sshift, 0u);
+            dupc[tid] = 0;
+        }
+        if (tid < SKM_HSTRIPE_WORDS) hstripe[tid] = 0;
+    }
+    // one distinct k-mer; true when it sits in exactly one group — nearly all do: the callers count those per wave
+    // and hand the wave's total to add_single_group
+    __device__ __forceinline__ bool eval_mask(const u32 lane, u32 mlo, u32 mhi, const u32 cs) const {
+        const u32 lsel = lane & ((1u << sshift) - 1u);
+        u32 ng = 0;
+        do {
+            const u32 first = mlo ? (u32)__builtin_ctz(mlo) : 32u + (u32)__builtin_ctz(mhi);
+            const uint4 g = gtab[first];
+            u32 c = (u32)__popc(mlo & g.x) + (u32)__popc(mhi & g.y);
+            c = c < cs ? c : cs;
+            atomicAdd(&hstripe[g.z + (c << sshift) + lsel], 1u);
+            const u32 keep_hi = mlo ? ~0u : mhi - 1u;   // (the lowest bit goes in any case: a tag outside every group cannot hang the loop)
+            mlo &= ~g.x & (mlo - 1u);
+            mhi &= ~g.y & keep_hi;
+            ++ng;
+        } while (mlo | mhi);
+        if (ng == 1u) return true;
+        atomicAdd(&hstripe[((abase + (ng < cs ? ng : cs)) << sshift) + lsel], 1u);
+        return false;
+    }
+    __device__ __forceinline__ void add_single_group(const u32 n) const { atomicAdd(&hstripe[(abase + 1u) << sshift], n); }
+    // behind a barrier: the workgroup's bins into one replica of the histogram, its repeats into the genomes' counters
+    __device__ __forceinline__ void flush(unsigned long long* __restrict__ rep, const u32 nbins, unsigned long long* __restrict__ dup,
+                                          const u32 tid, const u32 nt) const {
+        for (u32 i = tid; i < nbins; i += nt) {
+            u32 v = 0;
+            for (u32 j = 0; j < (1u << sshift); ++j) v += hstripe[(i << sshift) + j];
+            if (v) atomicAdd(&rep[i], (unsigned long long)v);
+        }
+        if (tid < (u32)KH_TAG_MAX_OPS && dupc[tid]) atomicAdd(&dup[tid], (unsigned long long)dupc[tid]);
+    }
+};
+
+template <u32 Q> struct SkmRecord { uint4 v[Q]; };   // a record in registers; its header: the last word of v[Q - 1]
+
+template <class K> void skm_allow_lds(K kern, size_t bytes) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+}
+
 }   // namespace
+
+// ------------------------------------------------------------------------------------------
+// S2a: one workgroup per coarse bucket walks its records a round at a time and regroups them by fine slot.
+// The workgroup owns every slot of its bucket: the slot cursors live in LDS, no global atomic is needed.
+// A round is SKM_RG_U4 uint4 of records whatever their size: 8192 one-word records, 4096 two-word ones.
+// ------------------------------------------------------------------------------------------
+constexpr u32 SKM_RG_U4 = 8192;
+template <class Rec> constexpr size_t skm_regroup_lds_bytes(u32 S) {
+    return flush_lds_bytes<SKM_RG_U4 / Rec::Q, 4 * Rec::Q>((S + 3) & ~3u) + (size_t)((S + 3) & ~3u) * 4 + 64;
+}
+template <class Rec>
+__global__ __launch_bounds__(SKM_RG_NT, 4) void k_skm_regroup(const KhSkmJob jb) {
+    extern __shared__ __attribute__((aligned(16))) u8 lds_raw[];
+    constexpr u32 Q = Rec::Q, CAP = SKM_RG_U4 / Q, RW = 4 * Q;
+    constexpr int RPT = (int)(CAP / SKM_RG_NT);
+    const u32 nbk = (jb.S + 3) & ~3u;
+    const FlushLds L = flush_lds<CAP, RW>(lds_raw, nbk);
+    u32* lcur = reinterpret_cast<u32*>(lds_raw + flush_lds_bytes<CAP, RW>(nbk));   // [nbk] records written per slot
+    const u32 tid = threadIdx.x;
+    const u32 b = blockIdx.x;
+    const u32 have = jb.cur1[(size_t)b * KH_SKM_CUR1_STRIDE];
+    const u32 cnt = have < jb.cap1 ? have : jb.cap1;
+    const u32 first_slot = b * jb.S;
+    const u32 nfine = jb.nslots - first_slot < jb.S ? jb.nslots - first_slot : jb.S;
+    for (u32 i = tid; i < nbk; i += SKM_RG_NT) { L.bcnt[i] = 0; lcur[i] = 0; }
+    const uint4* __restrict__ src = jb.reg1 + (u64)b * jb.cap1 * Q;
+    uint4* __restrict__ dst = jb.reg2 + (u64)first_slot * jb.cap2 * Q;
+    uint4 nx[RPT][Q];
+#pragma unroll
+    for (int r = 0; r < RPT; ++r) {
+        const u32 i = tid + (u32)r * SKM_RG_NT;
+#pragma unroll
+        for (u32 q = 0; q < Q; ++q) nx[r][q] = i < cnt ? src[Q * i + q] : make_uint4(0, 0, 0, 0);
+    }
+    __syncthreads();
+    for (u32 start = 0; start < cnt; start += CAP) {
+        const u32 n = cnt - start < CAP ? cnt - start : CAP;
+#pragma unroll
+        for (int r = 0; r < RPT; ++r) {
+            const u32 i = tid + (u32)r * SKM_RG_NT;
+            if (i < n) {
+                u32 fine = Rec::fine(nx[r][Q - 1].w);
+                if (fine >= nfine) { fine = 0; atomicOr(jb.ctl, KH_ERR_ORDER); }   // a corrupt record never leaves its bucket
+#pragma unroll
+                for (u32 q = 0; q < Q; ++q) L.stage[Q * i + q] = nx[r][q];
+                L.sid[i] = (u16)fine;
+                atomicAdd(&L.bcnt[fine], 1u);
+            }
+        }
+        // the next round's records: in flight during the flush
+#pragma unroll
+        for (int r = 0; r < RPT; ++r) {
+            const u32 i = start + CAP + tid + (u32)r * SKM_RG_NT;
+#pragma unroll
+            for (u32 q = 0; q < Q; ++q) nx[r][q] = i < cnt ? src[Q * i + q] : make_uint4(0, 0, 0, 0);
+        }
+        __syncthreads();
+        SkmSpill sp;
+        sp.rec = jb.spill_rec; sp.slot = jb.spill_slot; sp.n = jb.ctl + 5; sp.cap = jb.spill_cap; sp.first_slot = first_slot;
+        skm_flush<SKM_RG_NT, CAP, true, RW>(L, n, nfine, lcur, dst, jb.cap2, jb.ctl, sp);
+    }
+    for (u32 i = tid; i < nfine; i += SKM_RG_NT) jb.cur2[first_slot + i] = lcur[i];
+}
+template <class Rec> void skm_launch_regroup(const KhSkmJob& job, hipStream_t st) {
+    const size_t lds = skm_regroup_lds_bytes<Rec>(job.S);
+    skm_allow_lds(k_skm_regroup<Rec>, lds);
+    hipLaunchKernelGGL(k_skm_regroup<Rec>, dim3(job.nb1), dim3(SKM_RG_NT), lds, st, job);
+}
+
+// ------------------------------------------------------------------------------------------
+// Overfull slots.  A minimizer that far more k-mers share than a hash predicts — poly-A, a tandem repeat's unit, an
+// insertion sequence in 50 copies — fills its slot's region; the regroup puts what does not fit on a side list and
+// the union leaves such slots alone (as it does slots with more chunks than it numbers).  Here one workgroup takes
+// one of them whatever its size: the records in the region, then its records on the side list (found by a scan of
+// the list: it is short), every k-mer into the table by the probe walk above, in rounds of key subsets shared out
+// over blockIdx.y; no merge of identical records, read-out by a scan of the table.  A handful of slots per run:
+// nothing here is tuned, it only has to be right and to keep the run in the fast form.
+//
+// One kernel for both key widths.  Tr (SkmBig1 in kh_skm.hip, SkmBig2 in kh_skm2.hip) supplies:
+//   Rec, Consts, Key         the record format, the per-launch constants of the expander, a canonical key
+//   T, T2, KEY_BYTES         main and second table; per entry KEY_BYTES of key planes (u64 planes, the first of
+//                            which is all ones in an empty entry), then two u32 planes: the halves of the genome mask
+//   BATCH, OB, E             records numbered at a time; bits of a chunk's number inside its record; k-mers per chunk
+//   expand(r, first, kc, f)  the chunk expander: f(e, key) for the E k-mers from k-mer `first` of record r on
+//   hash(key), claim(main, off, key)      the table hash; the claim functor of the probe walk (key planes of the main
+//                            table, the second table's `off` u64 behind them)
+// ------------------------------------------------------------------------------------------
+constexpr u32 SKM_BIG_NT = 1024, SKM_BIG_IDX = 4096;   // threads; records of one slot on the side list that are indexed
+template <class Tr> constexpr size_t skm_big_lds_bytes() {
+    return (size_t)(Tr::T + Tr::T2) * (Tr::KEY_BYTES + 8) + 1024 + 128 + 256 + (size_t)SKM_HSTRIPE_WORDS * 4 +
+           (size_t)(Tr::BATCH << Tr::OB) * 2 + (size_t)SKM_BIG_IDX * 4;
+}
+template <class Tr>
+__global__ __launch_bounds__(SKM_BIG_NT) void k_skm_big(const KhSkmJob jb, u32 cs) {
+    extern __shared__ __attribute__((aligned(16))) u8 lds_raw[];
+    using Rec = typename Tr::Rec;
+    constexpr u32 NT = SKM_BIG_NT, T = Tr::T, T2 = Tr::T2, Q = Rec::Q, MAXCH = Tr::BATCH << Tr::OB;
+    constexpr u32 ROUND = T - T / 4;   // k-mer instances a round takes
+    constexpr u32 E = (u32)Tr::E;
+    constexpr u64 EMPTY = ~0ull;
+    u8* p = lds_raw;
+    u8* kmain = p;                                                         p += (size_t)T * Tr::KEY_BYTES;
+    u32* tmlo = reinterpret_cast<u32*>(p);                                 p += (size_t)T * 4;
+    u32* tmhi = reinterpret_cast<u32*>(p);                                 p += (size_t)T * 4;
+    u8* ksecond = p;                                                       p += (size_t)T2 * Tr::KEY_BYTES;
+    u32* omlo = reinterpret_cast<u32*>(p);                                 p += (size_t)T2 * 4;
+    u32* omhi = reinterpret_cast<u32*>(p);                                 p += (size_t)T2 * 4;
+    constexpr u32 omask_off = (T * 8 + T2 * Tr::KEY_BYTES) / 4;            // omlo - tmlo
+    constexpr u32 okey_off = T * (Tr::KEY_BYTES + 8) / 8;                  // the second table's key planes behind the main one's, in u64
+    SkmReadout ro;
+    ro.gtab = reinterpret_cast<uint4*>(p);                                 p += 1024;
+    u32* scratch = reinterpret_cast<u32*>(p);                              p += 128;   // [0] chunks, [2] k-mers, [3] side-list records
+    ro.dupc = reinterpret_cast<u32*>(p);                                   p += 256;
+    ro.hstripe = reinterpret_cast<u32*>(p);                                p += (size_t)SKM_HSTRIPE_WORDS * 4;
+    u16* owner = reinterpret_cast<u16*>(p);                                p += (size_t)MAXCH * 2;
+    u32* sidx = reinterpret_cast<u32*>(p);                                 // [SKM_BIG_IDX] this slot's records on the side list
+    const u32 tid = threadIdx.x, lane = lane_id();
+    const u32 cap2 = jb.cap2;
+    const u32 slot = jb.big_list[blockIdx.x];
+    const typename Tr::Consts kc(jb.k);
+    ro.init(jb.ginfo, jb.nbins, jb.abase, tid);
+    if (tid < 8) scratch[tid] = 0;
+    __syncthreads();
+    // ---- this slot's records on the side list
+    u32 nspill_all = jb.ctl[5];
+    nspill_all = nspill_all < jb.spill_cap ? nspill_all : jb.spill_cap;
+    for (u32 i = tid; i < nspill_all; i += NT) {
+        if (jb.spill_slot[i] == slot) {
+            const u32 at = atomicAdd(&scratch[3], 1u);
+            if (at < SKM_BIG_IDX) sidx[at] = i;
+        }
+    }
+    __syncthreads();
+    u32 nside = scratch[3];
+    if (nside > SKM_BIG_IDX) {   // (more than this kernel indexes: the host falls back)
+        if (tid == 0) atomicOr(jb.ctl, KH_ERR_CAPACITY);
+        nside = SKM_BIG_IDX;
+    }
+    const u32 nreg = jb.cur2[slot] < cap2 ? jb.cur2[slot] : cap2;   // (full for an overfull slot; a slot listed for its chunks may hold fewer)
+    const uint4* __restrict__ reg = jb.reg2 + (u64)slot * cap2 * Q;
+    const u32 nall = nreg + nside;
+    // uint4 q of record i; the header sits in the last word of uint4 Q - 1
+    auto rec_q = [&](u32 i, u32 q) __attribute__((always_inline)) -> uint4 { return i < nreg ? reg[(u64)Q * i + q] : jb.spill_rec[(u64)Q * sidx[i - nreg] + q]; };
+    // ---- k-mer instances of the slot -> rounds
+    {
+        u32 mine = 0;
+        for (u32 i = tid; i < nall; i += NT) mine += Rec::n(rec_q(i, Q - 1).w);
+        const u32 tot = wave_scan_add(mine);
+        if (lane == KH_WAVE - 1 && tot) atomicAdd(&scratch[2], tot);
+    }
+    __syncthreads();
+    const u32 N = scratch[2];
+    const u32 R = (N + ROUND - 1u) / ROUND;
+    if (tid == 0 && N > T) atomicMax(jb.ctl + 1, N);
+    for (u32 q = blockIdx.y; q < R; q += gridDim.y) {   // (the rounds are independent: workgroups (slot, y) share them out)
+        // a fresh table: key planes all ones, both mask planes zero
+        for (u32 i = tid; i < T * Tr::KEY_BYTES / 16; i += NT) reinterpret_cast<uint4*>(kmain)[i] = make_uint4(0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu);
+        for (u32 i = tid; i < T2 * Tr::KEY_BYTES / 16; i += NT) reinterpret_cast<uint4*>(ksecond)[i] = make_uint4(0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu);
+        for (u32 i = tid; i < T / 2; i += NT) reinterpret_cast<uint4*>(tmlo)[i] = make_uint4(0u, 0u, 0u, 0u);
+        if (tid < T2) { omlo[tid] = 0u; omhi[tid] = 0u; }
+        __syncthreads();
+        for (u32 b0 = 0; b0 < nall; b0 += Tr::BATCH) {   // batches of records, one per thread of the first waves
+            const u32 mine_i = b0 + tid;
+            const u32 nj = tid < Tr::BATCH && mine_i < nall ? Rec::n(rec_q(mine_i, Q - 1).w) : 0u;
+            const u32 nch = (nj + E - 1u) / E;
+            {
+                const u32 incl = wave_scan_add(nch);
+                u32 wbase = 0;
+                if (lane == KH_WAVE - 1 && incl) wbase = atomicAdd(&scratch[0], incl);
+                wbase = (u32)__builtin_amdgcn_readlane((int)wbase, KH_WAVE - 1);
+                const u32 cstart = wbase + incl - nch;
+                if (cstart + nch <= MAXCH)
+                    for (u32 cc = 0; cc < nch; ++cc) owner[cstart + cc] = (u16)((tid << Tr::OB) | cc);
+            }
+            __syncthreads();
+            u32 C = scratch[0];
+            if (C > MAXCH) {   // (cannot happen: a record has at most 1 << OB chunks)
+                if (tid == 0) atomicOr(jb.ctl, KH_ERR_CAPACITY);
+                C = 0;
+            }
+            for (u32 c = tid; c < C; c += NT) {
+                const u32 o = owner[c], ri = b0 + (o >> Tr::OB), first = (o & ((1u << Tr::OB) - 1u)) * E;
+                SkmRecord<Q> r0;
+#pragma unroll
+                for (u32 qq = 0; qq < Q; ++qq) r0.v[qq] = rec_q(ri, qq);
+                const u32 hw = r0.v[Q - 1].w;
+                const u32 tg = Rec::tag(hw), bit = 1u << (tg & 31u), half = Rec::half(hw);
+                const u32 cnt = Rec::n(hw) - first;   // k-mers of the record from `first` on: the chunk holds min(cnt, E)
+                Tr::expand(r0, first, kc, [&](const u32 e, const typename Tr::Key& K) __attribute__((always_inline)) {
+                    if (e >= cnt) return;
+                    const u32 H = Tr::hash(K);
+                    if (R != 1 && (((H >> 4) & 0xffffu) * R) >> 16 != q) return;   // another round's key
+                    skm_probe_walk<T, T2>(H, jb.ctl, Tr::claim(kmain, okey_off, K), [&](const bool second, const u32 S, bool) __attribute__((always_inline)) {
+                        // (the planes of the two mask halves follow each other; one base pointer and integer offsets:
+                        // a choice between two pointers held by reference is a choice between their homes in memory)
+                        u32* const mp = tmlo + (second ? omask_off + half * T2 : half * T) + S;
+                        if (atomicOr(mp, bit) & bit) atomicAdd(&ro.dupc[tg], 1u);   // this genome had the k-mer already
+                    });
+                });
+            }
+            __syncthreads();
+            if (tid == 0) scratch[0] = 0;
+            __syncthreads();
+        }
+        // ---- read-out: every occupied entry
+        u32 ones = 0;
+        for (u32 i = tid; i < T; i += NT)
+            if (reinterpret_cast<const u64*>(kmain)[i] != EMPTY && ro.eval_mask(lane, tmlo[i], tmhi[i], cs)) ++ones;
+        if (tid < T2 && reinterpret_cast<const u64*>(ksecond)[tid] != EMPTY && ro.eval_mask(lane, omlo[tid], omhi[tid], cs)) ++ones;
+        ones = wave_scan_add(ones);
+        if (lane == KH_WAVE - 1 && ones) ro.add_single_group(ones);
+        __syncthreads();
+    }
+    ro.flush(jb.hist + (u64)(blockIdx.x % jb.reps) * jb.nbins, jb.nbins, jb.dup, tid, NT);
+    if (tid == 0 && blockIdx.y == 0) atomicAdd(jb.ctl + 3, N);
+}
+template <class Tr> void skm_launch_big(const KhSkmJob& job, u32 cs, u32 nbig, hipStream_t st) {
+    if (!nbig) return;
+    const char* e = getenv("KHOICE_SKM_BIG_Y");   // the rounds of a slot side by side (1 .. 16 workgroups per slot)
+    const int y = e ? atoi(e) : 4;
+    const size_t lds = skm_big_lds_bytes<Tr>();
+    skm_allow_lds(k_skm_big<Tr>, lds);
+    hipLaunchKernelGGL(k_skm_big<Tr>, dim3(nbig, nbig < 2048u ? (u32)(y < 1 ? 1 : (y > 16 ? 16 : y)) : 1u), dim3(SKM_BIG_NT), lds, st, job, cs);
+}
