@@ -1038,6 +1038,9 @@ static int setop_finish(SetopJob& j, kh_set** out) {
         // to spare (never by less than 1/8, by 4 when the record is missing)
         const u64 fullest = (u32)j.tail[2];
         u64 next = fullest > j.cap ? j.target * j.cap * 9 / (fullest * 10) : j.target / 4;
+        // that rule assumes keys spread evenly over the ranges; operands that crowd more keys than a slot holds into
+        // a sliver of the key space barely shrink under it, so from the third re-plan on the fill is quartered
+        if (attempt >= 2) next = std::min<u64>(next, j.target / 4);
         j.target = std::max<u64>(16, std::min<u64>(next, j.target * 7 / 8));
         KHCHK(setop_launch(j));
         HIPCHK(hipStreamSynchronize(c->st));

@@ -170,3 +170,113 @@ def view_keys(v, k):
     out = np.empty((v.shape[0], 2), dtype=np.uint64)
     out[:, 0], out[:, 1] = v["lo"], v["hi"]
     return out
+
+
+# ---------------------------------------------------------------- planted keys: choose bucket and fine bin
+# A numpy restatement of kh_slot (kh_common.h) and fine_bin (kh_kernels.hip), and texts whose k-mers are chosen by
+# them, so that a test decides how many keys a bucket of the batched build holds and how they fall into the fine
+# bins of its distribution sort.  tests/test_gpu_build_edges.py proves every construction on the C oracle's keys.
+M32 = (1 << 32) - 1
+
+
+def slot_np(k, mixed, nslots):
+    """kh_slot: slot of each mixed key among nslots equal-width, order-preserving slots."""
+    return (top32_np(k, mixed) * np.uint64(nslots)) >> np.uint64(32)
+
+
+def fine_bin_np(k, mixed, nslots, fine_bits):
+    """fine_bin: the fine bin (of 2^fine_bits) of each mixed key inside its slot."""
+    return ((top32_np(k, mixed) * np.uint64(nslots)) & np.uint64(M32)) >> np.uint64(32 - fine_bits)
+
+
+def _rev_pairs64(x):
+    """The 32 two-bit groups of each uint64 in reverse order."""
+    x = ((x >> np.uint64(2)) & np.uint64(0x3333333333333333)) | ((x & np.uint64(0x3333333333333333)) << np.uint64(2))
+    x = ((x >> np.uint64(4)) & np.uint64(0x0F0F0F0F0F0F0F0F)) | ((x & np.uint64(0x0F0F0F0F0F0F0F0F)) << np.uint64(4))
+    return x.byteswap()
+
+
+def revcomp_np(k, keys):
+    """keys[n, W] uint64 (k-mer codes) -> codes of their reverse complements."""
+    keys = np.ascontiguousarray(keys, dtype=np.uint64).reshape(-1, words(k))
+    out = np.empty_like(keys)
+    if k <= 32:
+        out[:, 0] = _rev_pairs64(~keys[:, 0]) >> np.uint64(64 - 2 * k)
+        return out
+    s = 128 - 2 * k
+    rlo, rhi = _rev_pairs64(~keys[:, 0]), _rev_pairs64(~keys[:, 1])      # the 128-bit reversal is (rlo, rhi)
+    if s == 0:
+        out[:, 0], out[:, 1] = rhi, rlo
+    else:
+        out[:, 0] = (rhi >> np.uint64(s)) | (rlo << np.uint64(64 - s))
+        out[:, 1] = rlo >> np.uint64(s)
+    return out
+
+
+def planted_codes(k, nb, b, f, n, rng, fine_bits):
+    """n distinct canonical k-mer codes[n, W] whose mixed key lies in slot b of nb slots and, unless f is None, in fine
+    bin f of that slot.  The 32-bit product (top32 * nb) is chosen first: p = b << 32 | f << (32 - fine_bits) | r;
+    top = ceil(p / nb) is kept when top * nb still has slot b and fine bin f."""
+    assert 2 * k >= 40 and 0 <= b < nb
+    sh = 32 - fine_bits
+    lo = (b << 32) | ((f << sh) if f is not None else 0)
+    span = (1 << sh) if f is not None else (1 << 32)
+    tops_all = None
+    if span <= (1 << 20):
+        p = np.uint64(lo) + np.arange(span, dtype=np.uint64)
+        tops_all = np.unique((p + np.uint64(nb - 1)) // np.uint64(nb))
+    got = np.zeros((0, words(k)), dtype=np.uint64)
+    for _ in range(200):
+        m = 4 * (n - got.shape[0]) + 64
+        if tops_all is not None:
+            top = tops_all[rng.integers(0, tops_all.shape[0], size=m)]
+        else:
+            p = np.uint64(lo) + rng.integers(0, span, size=m, dtype=np.uint64)
+            top = (p + np.uint64(nb - 1)) // np.uint64(nb)
+        top = top[top <= np.uint64(M32)]
+        prod = top * np.uint64(nb)
+        ok = (prod >> np.uint64(32)) == np.uint64(b)
+        if f is not None:
+            ok &= ((prod & np.uint64(M32)) >> np.uint64(sh)) == np.uint64(f)
+        codes = unmix_np(k, mixed_from_top32(k, top[ok], rng))
+        rc = revcomp_np(k, codes)
+        if words(k) == 1:
+            canon = codes[:, 0] <= rc[:, 0]
+        else:
+            canon = (codes[:, 1] < rc[:, 1]) | ((codes[:, 1] == rc[:, 1]) & (codes[:, 0] <= rc[:, 0]))
+        codes = codes[canon]
+        both = np.concatenate([got, codes])
+        _, first = np.unique(key_view(both), return_index=True)
+        got = both[np.sort(first)]
+        if got.shape[0] >= n:
+            return got[:n]
+    raise AssertionError(f"no {n} canonical keys in slot {b}/{nb}, fine bin {f}")
+
+
+def codes_text(k, keys):
+    """keys[n, W] uint64 -> the n k-mers as ASCII rows uint8[n, k]."""
+    keys = np.ascontiguousarray(keys, dtype=np.uint64).reshape(-1, words(k))
+    out = np.empty((keys.shape[0], k), dtype=np.uint8)
+    alpha = np.frombuffer(b"ACGT", dtype=np.uint8)
+    for j in range(k):
+        bit = 2 * (k - 1 - j)
+        out[:, j] = alpha[((keys[:, bit >> 6] >> np.uint64(bit & 63)) & np.uint64(3)).astype(np.intp)]
+    return out
+
+
+def planted_text(k, keys, mult, npos, rng, head=b""):
+    """A text of exactly npos k-mer start positions: `head`, then keys[i] written mult[i] times, every copy closed by
+    one N, in shuffled order, then N to the end.  N adds positions but no keys."""
+    rows = codes_text(k, keys)
+    order = rng.permutation(np.repeat(np.arange(rows.shape[0]), np.asarray(mult, dtype=np.int64)))
+    body = np.full((order.shape[0], k + 1), ord("N"), dtype=np.uint8)
+    body[:, :k] = rows[order]
+    text = bytes(head) + body.tobytes()
+    pad = npos + k - 1 - len(text)
+    assert pad >= 0, (npos, len(text))
+    return text + b"N" * pad
+
+
+def random_dna_np(rng, n, alphabet=b"ACGT"):
+    """n random bases as bytes (numpy generator: millions of bases in milliseconds)."""
+    return np.frombuffer(alphabet, dtype=np.uint8)[rng.integers(0, len(alphabet), size=n)].tobytes()
