@@ -223,6 +223,16 @@ int kh_load(kh_ctx *ctx, const char *prefix, kh_set **out);
  *   across_set     optional: the step_7 union (caller frees)
  * When across_hist and across_set are both NULL steps 7-8 are skipped (multi-GPU callers run
  * them after the exchange of the group sets).
+ *
+ * Forms.  With group_sets the call builds per-genome sets and unions them (the general path).  Without, one of
+ * three fused forms answers, the same numbers in each:
+ *   k <= 12, no across_set      presence bitmaps (kh_bmp.hip): one bit per genome and k-mer code in directly
+ *                               addressed bitmaps built in LDS, counted with bit-sliced counters; no 64-genome
+ *                               mask: up to 1023 genomes per group, 1023 groups, 4096 histogram bins in one pass
+ *   17 <= k <= 63, no across_set  super-k-mer records (kh_skm.hip, kh_skm2.hip)
+ *   otherwise                   key arrays (k = 13..16, k = 64, across_set, and whatever the other two decline)
+ * Switches (environment): KHOICE_NO_BMP, KHOICE_NO_SKM (also keeps the bitmaps off: "the key arrays, please"),
+ * KHOICE_BMP_MAX_K (up to 13), KHOICE_BMP_MAX_BYTES (memory the partial bitmaps may take), KHOICE_NO_FUSED.
  */
 int kh_exp1_run(kh_ctx *ctx, int nseq, const uint8_t *const *seqs, const uint64_t *lens,
                 int on_device, const int *group_of, int ngroups, int k, uint32_t cs,

@@ -1,0 +1,315 @@
+// khoice_amd — presence-bitmap form of the fused experiment-type-1 step for small k (gfx950).
+//
+// A k-mer of k <= 13 is a number below 2^26: "which genomes hold it" is one bit per genome in a directly addressed
+// bitmap of 4^k bits, and every histogram of the step is a count over those bits.  Two kernels:
+//   k_bmp_build    text -> presence bitmaps.  A workgroup owns one (genome, split, code range): it keeps the bitmap of
+//                  its range in LDS, walks its split tile by tile (the staging of load_codes, canonical code of every valid position,
+//                  one LDS OR where the code falls in the range) and then stores every word of the range, zeros
+//                  included, with plain vector stores: every word of the partial bitmaps [split][4^k bits] is written
+//                  by exactly one workgroup, so nothing is cleared beforehand and nothing in device memory is atomic.
+//   k_bmp_readout  bit-sliced counting.  A lane owns one 64-bit word (64 consecutive codes): per group it ORs the
+//                  splits of every genome, adds the genome's word into a bit-sliced counter (ripple carry over the
+//                  slices), and reads the counter out as one equality mask per count value, whose popcount goes to the
+//                  LDS bin of (group, count).  The groups' "present" words feed a second bit-sliced counter over
+//                  groups: the across-group bins.  The popcount of a genome's own word is its distinct k-mers.
+// There is no genome mask: any number of genomes and groups (up to 1023 per counter) is answered in one pass.
+#include "kh_device.h"
+#include "kh_launch.h"
+
+namespace {
+
+constexpr u32 BMP_NT = 1024;          // threads of a build workgroup: with the 128 KiB bitmap one workgroup fills a CU
+constexpr u32 BMP_CHUNK = 16;         // positions per thread and round: one staged word (+ the next for the k - 1 halo)
+constexpr u32 BMP_FETCH = (KH_BMP_TILE / BMP_CHUNK + 1 + BMP_NT - 1) / BMP_NT;   // staged words a thread fetches per tile
+constexpr u32 BMP_PREFILTER_RANGES = 16;   // from this many ranges on, candidates are picked by their leading bases first
+constexpr u32 BMP_MAX_LEAD = 5;       // leading bases of a range at most (k = 13 with ranges of 2^16 codes)
+
+// ------------------------------------------------------------------------------------------
+// k_bmp_build
+// LDS: [bitmap: rw u64][code: tile_pos / 16 + 1 u32][bad16: tile_pos / 16 + 1 u16][count: 1 u32]
+// ------------------------------------------------------------------------------------------
+template <int K>
+__global__ __launch_bounds__(BMP_NT) void k_bmp_build(const KhBmpJob jb) {
+    extern __shared__ __attribute__((aligned(16))) u8 lds_raw[];
+    const u32 tid = threadIdx.x;
+    const u32 rw = 1u << (jb.range_bits - 6);                    // 64-bit words of this workgroup's range
+    const u32 nranges = jb.nranges;
+    const u32 range = blockIdx.x % nranges, si = blockIdx.x / nranges;
+    const KhBmpSplit sp = jb.splits[si];
+    const u32 twords = jb.tile_pos / BMP_CHUNK;                  // chunks of a tile; one more word is staged for the halo
+    u32* bm = reinterpret_cast<u32*>(lds_raw);
+    u32* code = reinterpret_cast<u32*>(lds_raw + 8 * (size_t)rw);
+    u16* bad16 = reinterpret_cast<u16*>(code + twords + 1);
+    u32* total = reinterpret_cast<u32*>(lds_raw + 8 * (size_t)rw + (((size_t)(twords + 1) * 6 + 15) & ~(size_t)15));
+
+    if (rw >= 2) {
+        uint4* b4 = reinterpret_cast<uint4*>(bm);
+        for (u32 i = tid; i < rw / 2; i += BMP_NT) b4[i] = make_uint4(0, 0, 0, 0);
+    } else if (tid < 2) {
+        bm[tid] = 0;
+    }
+    if (tid == 0) *total = 0;
+
+    constexpr u32 KMASK = (1u << (2 * K)) - 1u;                  // K <= 13: 26 bits
+    constexpr u64 PAIRS = 0x5555555555555555ull;
+    const u32 rlo = range << jb.range_bits;                      // first code of the range
+    const u32 rmask = (1u << jb.range_bits) - 1u;                // (range_bits <= 2K: codes of other ranges differ above it)
+    // Many ranges (k = 12: sixteen passes over the text): the range is the leading `nlead` bases of the canonical
+    // code, i.e. the first bases of the k-mer or the complements of its last ones.  Both are compared for all
+    // positions of a chunk at once on the staged 2-bit codes, and only the candidates (2 in `nranges` positions) get
+    // their codes worked out.  lead_fw[d] / lead_rc[d]: base d of the range / its complement in every pair of bits.
+    const u32 lead_bits = 2 * K - jb.range_bits;
+    const u32 nlead = (lead_bits & 1u) || nranges < BMP_PREFILTER_RANGES ? 0u : lead_bits / 2;
+    u64 lead_fw[BMP_MAX_LEAD], lead_rc[BMP_MAX_LEAD];
+#pragma unroll
+    for (u32 d = 0; d < BMP_MAX_LEAD; ++d) {
+        const u32 v = d < nlead ? (range >> (2 * (nlead - 1 - d))) & 3u : 0u;
+        lead_fw[d] = PAIRS * v;
+        lead_rc[d] = PAIRS * (3u - v);
+    }
+    // the raw bytes of the next tile are fetched while the current one is worked on
+    const u32 swords = twords + 1;
+    kh_u32x4 pre[BMP_FETCH];
+    auto fetch = [&](const u64 t0) {
+#pragma unroll
+        for (u32 i = 0; i < BMP_FETCH; ++i) {
+            const u32 w = tid + i * BMP_NT;
+            pre[i] = codes_fetch(sp.seq, sp.len, t0 + 16ull * w, w < swords, jb.splits);
+        }
+    };
+    u32 nvalid = 0;
+    if (sp.p0 < sp.p1) fetch(sp.p0);
+    for (u64 t0 = sp.p0; t0 < sp.p1; t0 += jb.tile_pos) {
+        __syncthreads();                                         // the bitmap is cleared; the last tile has been read
+#pragma unroll
+        for (u32 i = 0; i < BMP_FETCH; ++i) {
+            const u32 w = tid + i * BMP_NT;
+            u32 codes, bad;
+            codes_decode(pre[i], sp.seq, sp.len, t0 + 16ull * w, codes, bad);
+            if (w < swords) {
+                code[w] = codes;
+                bad16[w] = (u16)bad;
+            }
+        }
+        __syncthreads();
+        if (t0 + jb.tile_pos < sp.p1) fetch(t0 + jb.tile_pos);
+        const u64 tend = t0 + jb.tile_pos < sp.p1 ? t0 + jb.tile_pos : sp.p1;
+        const u32 nch = (u32)((tend - t0 + BMP_CHUNK - 1) / BMP_CHUNK);
+        for (u32 c = tid; c < nch; c += BMP_NT) {
+            // bases 16c .. 16c + 31 of the tile: base j at bits 2j; a position breaks where any of its k bases does.
+            // (A split ends at a multiple of 16 or at the genome's last position, behind which every base is flagged.)
+            const u64 cw = (u64)code[c] | ((u64)code[c + 1] << 32);
+            u32 inv = (u32)bad16[c] | ((u32)bad16[c + 1] << 16);
+            {
+                u32 w = 1;
+#pragma unroll
+                for (int s = 0; s < 3; ++s)
+                    if (2 * w <= (u32)K) { inv |= inv >> w; w *= 2; }
+                inv |= inv >> ((u32)K - w);
+            }
+            const u32 valid = ~inv & 0xffffu;
+            nvalid += __builtin_popcount(valid);
+            if (!valid) continue;
+            const u64 fwd = kh_revpairs64(cw);                   // base j at bits 62 - 2j: first base most significant
+            const u64 rcw = ~cw;                                 // the complement of base j + m at bits 2(j + m): the reverse complement's digit m
+            if (nlead) {
+                u64 cf = PAIRS, cr = PAIRS;                      // bit 2j: position j may have its canonical code in the range
+#pragma unroll
+                for (u32 d = 0; d < BMP_MAX_LEAD; ++d) {
+                    if (d < nlead) {
+                        const u64 tf = cw ^ lead_fw[d], tr = cw ^ lead_rc[d];
+                        cf &= ~(tf | (tf >> 1)) >> (2 * d);
+                        cr &= ~(tr | (tr >> 1)) >> (2 * ((u32)K - 1 - d));
+                    }
+                }
+                // candidates that are valid positions: bit 2j of m.  The code of position j is cut out of a 64-bit
+                // word by a shift below 32 and a truncation: one v_alignbit each for the two strands.
+                u32 vp = valid;                                  // bit j -> bit 2j
+                vp = (vp | (vp << 8)) & 0x00ff00ffu;
+                vp = (vp | (vp << 4)) & 0x0f0f0f0fu;
+                vp = (vp | (vp << 2)) & 0x33333333u;
+                vp = (vp | (vp << 1)) & 0x55555555u;
+                u32 m = (u32)(cf | cr) & vp;
+                const u64 fwk = fwd >> (64 - 2 * (15 + K));      // the forward code of position j at bits 2(15 - j)
+                const u32 fl = (u32)fwk, fh = (u32)(fwk >> 32), rl = (u32)rcw, rh = (u32)(rcw >> 32);
+                while (m) {
+                    const u32 t = (u32)__builtin_ctz(m);         // 2j
+                    m &= m - 1;
+                    const u32 fw = __builtin_amdgcn_alignbit(fh, fl, 30u - t) & KMASK;
+                    const u32 rc = __builtin_amdgcn_alignbit(rh, rl, t) & KMASK;
+                    const u32 canon = fw < rc ? fw : rc;
+                    if ((canon >> jb.range_bits) == range) {
+                        const u32 b = canon & rmask;
+                        atomicOr(&bm[b >> 5], 1u << (b & 31u));
+                    }
+                }
+                continue;
+            }
+#pragma unroll
+            for (u32 j = 0; j < BMP_CHUNK; ++j) {
+                const u32 fw = (u32)(fwd >> (64 - 2 * (j + K))) & KMASK;
+                const u32 rc = (u32)(rcw >> (2 * j)) & KMASK;
+                const u32 canon = fw < rc ? fw : rc;
+                if (((valid >> j) & 1u) && (canon & ~rmask) == rlo) {
+                    const u32 b = canon & rmask;
+                    atomicOr(&bm[b >> 5], 1u << (b & 31u));
+                }
+            }
+        }
+    }
+    // valid positions of the genome (the `kmers` statistic): counted once, by the workgroups of range 0
+    if (range == 0) {
+        const u32 wsum = wave_scan_add(nvalid);
+        if (lane_id() == KH_WAVE - 1 && wsum) atomicAdd(total, wsum);
+    }
+    __syncthreads();
+    if (range == 0 && tid == 0 && *total) atomicAdd(&jb.inst[sp.op], (unsigned long long)*total);
+    // every word of the range, zeros included
+    u64* out = jb.partial + (size_t)si * jb.nwords + (size_t)range * rw;
+    if (rw >= 2) {
+        const uint4* b4 = reinterpret_cast<const uint4*>(bm);
+        uint4* o4 = reinterpret_cast<uint4*>(out);
+        for (u32 i = tid; i < rw / 2; i += BMP_NT) o4[i] = b4[i];
+    } else if (tid == 0) {
+        out[0] = (u64)bm[0] | ((u64)bm[1] << 32);
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// k_bmp_readout
+// LDS: [bins: nbins + nops u32][gx: 2 x waves x 64 u64]  (bins of the groups, the across-group bins, then one counter
+// per genome; the genome words the waves hand to wave 0)
+// ------------------------------------------------------------------------------------------
+constexpr int BMP_SLICES = 10;        // counts up to 1023: genomes of a group, groups
+
+// x (one bit per code) is added to the bit-sliced counter c: ripple carry over the first `ns` slices
+__device__ __forceinline__ void slices_add(u64 (&c)[BMP_SLICES], u64 x, const u32 ns) {
+#pragma unroll
+    for (int s = 0; s < BMP_SLICES; ++s) {
+        if ((u32)s < ns) {   // wave-uniform: the slices stay in registers
+            const u64 t = c[s] & x;
+            c[s] ^= x;
+            x = t;
+        }
+    }
+}
+// codes whose counter equals v
+__device__ __forceinline__ u64 slices_equal(const u64 (&c)[BMP_SLICES], const u32 v, const u32 ns) {
+    u64 eq = ~0ull;
+#pragma unroll
+    for (int s = 0; s < BMP_SLICES; ++s)
+        if ((u32)s < ns) eq &= ((v >> s) & 1u) ? c[s] : ~c[s];
+    return eq;
+}
+__device__ __forceinline__ u32 bit_length(u32 n) { return 32u - (u32)__builtin_clz(n | 1u); }
+
+// the sum of v over the wave is added to *bin by one lane (all lanes of the wave must be here)
+__device__ __forceinline__ void wave_add_to_bin(u32* bin, const u32 v) {
+    const u32 sum = wave_scan_add(v);
+    if (lane_id() == KH_WAVE - 1 && sum) atomicAdd(bin, sum);
+}
+
+// blockDim = (64, wy): the 64 lanes of a wave own 64 consecutive words.  The genomes are taken wy at a time: wave y ORs
+// the splits of genome i0 + y (so the loads of wy genomes are in flight together, not one genome's after the other's)
+// and leaves the word in LDS; wave 0 then counts the wy words in order.  One barrier per round, two buffers in turn:
+// round n + 2 writes the buffer of round n only behind barrier n + 1, which wave 0 reaches when it has counted round n.
+__global__ __launch_bounds__(1024) void k_bmp_readout(const KhBmpJob jb) {
+    extern __shared__ __attribute__((aligned(16))) u8 lds_raw[];
+    u32* bins = reinterpret_cast<u32*>(lds_raw);
+    const u32 nb = jb.nbins + jb.nops;
+    u64* gx = reinterpret_cast<u64*>(lds_raw + ((4 * (size_t)nb + 15) & ~(size_t)15));   // [2][wy][64]
+    const u32 lane = threadIdx.x, y = threadIdx.y, wy = blockDim.y;
+    const u32 tid = y * KH_WAVE + lane, nt = wy * KH_WAVE;
+    for (u32 i = tid; i < nb; i += nt) bins[i] = 0;
+    __syncthreads();
+    const u32 asl = bit_length(jb.ngroups);
+    u32 round = 0;
+    for (u64 wb = blockIdx.x; wb * KH_WAVE < jb.nwords; wb += gridDim.x) {
+        const u64 w = wb * KH_WAVE + lane;
+        const bool active = w < jb.nwords;
+        // wave 0: the group being counted, its bit-sliced counter c, and the counter a over groups
+        u32 g = 0;
+        KhBmpGroup gr = jb.groups[0];
+        u32 ns = bit_length(gr.size);
+        u64 a[BMP_SLICES], c[BMP_SLICES], any = 0;
+#pragma unroll
+        for (int s = 0; s < BMP_SLICES; ++s) a[s] = c[s] = 0;
+        for (u32 i0 = 0; i0 < jb.nops; i0 += wy, ++round) {
+            u64 x = 0;
+            if (i0 + y < jb.nops && active) {
+                const KhBmpOp op = jb.ops[i0 + y];
+                const u64* p = jb.partial + (size_t)op.split0 * jb.nwords + w;
+#pragma unroll 8
+                for (u32 s = 0; s < op.nsplits; ++s) x |= p[(size_t)s * jb.nwords];
+            }
+            u64* buf = gx + (size_t)(round & 1u) * wy * KH_WAVE;
+            buf[y * KH_WAVE + lane] = x;
+            __syncthreads();
+            if (y != 0) continue;
+            const u32 n = jb.nops - i0 < wy ? jb.nops - i0 : wy;
+            for (u32 j = 0; j < n; ++j) {
+                const u32 i = i0 + j;
+                const u64 xx = buf[j * KH_WAVE + lane];
+                wave_add_to_bin(&bins[jb.nbins + i], (u32)__builtin_popcountll(xx));   // the genome's distinct k-mers
+                any |= xx;
+                slices_add(c, xx, ns);
+                if (i + 1 == gr.first + gr.size) {   // the group is complete: one bin per count, and its presence counted
+                    for (u32 v = 1; v <= gr.size; ++v)
+                        wave_add_to_bin(&bins[gr.bin0 + v], (u32)__builtin_popcountll(slices_equal(c, v, ns)));
+                    slices_add(a, any, asl);
+                    any = 0;
+#pragma unroll
+                    for (int s = 0; s < BMP_SLICES; ++s) c[s] = 0;
+                    if (++g < jb.ngroups) {
+                        gr = jb.groups[g];
+                        ns = bit_length(gr.size);
+                    }
+                }
+            }
+        }
+        if (y == 0)
+            for (u32 v = 1; v <= jb.ngroups; ++v)
+                wave_add_to_bin(&bins[jb.abase + v], (u32)__builtin_popcountll(slices_equal(a, v, asl)));
+    }
+    __syncthreads();
+    unsigned long long* rep = jb.hist + (size_t)(blockIdx.x % jb.reps) * nb;
+    for (u32 i = tid; i < nb; i += nt)
+        if (bins[i]) atomicAdd(&rep[i], (unsigned long long)bins[i]);
+}
+
+template <class K> void bmp_allow_lds(K kern, size_t bytes) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+}
+template <int K> void launch_build(const KhBmpJob& job, u32 nsplits, size_t lds, hipStream_t st) {
+    bmp_allow_lds(k_bmp_build<K>, lds);
+    hipLaunchKernelGGL(k_bmp_build<K>, dim3(nsplits * job.nranges), dim3(BMP_NT), lds, st, job);
+}
+
+}   // namespace
+
+// ------------------------------------------------------------------------------------------
+// launchers
+// ------------------------------------------------------------------------------------------
+size_t kh_bmp_build_lds_bytes(u32 range_bits, u32 tile_pos) {
+    const size_t stage = ((size_t)(tile_pos / BMP_CHUNK + 1) * 6 + 15) & ~(size_t)15;
+    return ((size_t)1 << (range_bits - 3)) + stage + 16;
+}
+size_t kh_bmp_readout_lds_bytes(u32 nbins, u32 nops, u32 waves) {
+    return ((4 * ((size_t)nbins + nops) + 15) & ~(size_t)15) + 2 * (size_t)waves * KH_WAVE * 8;
+}
+void kh_launch_bmp_build(const KhBmpJob& job, u32 nsplits, hipStream_t st) {
+    if (!nsplits) return;
+    const size_t lds = kh_bmp_build_lds_bytes(job.range_bits, job.tile_pos);
+    switch (job.k) {
+#define BMP_K(KK) case KK: launch_build<KK>(job, nsplits, lds, st); break;
+        BMP_K(1) BMP_K(2) BMP_K(3) BMP_K(4) BMP_K(5) BMP_K(6) BMP_K(7) BMP_K(8) BMP_K(9) BMP_K(10) BMP_K(11) BMP_K(12)
+        BMP_K(13)
+#undef BMP_K
+        default: break;   // the host asks for k <= KH_BMP_INST_MAX_K only
+    }
+}
+void kh_launch_bmp_readout(const KhBmpJob& job, u32 grid, u32 waves, hipStream_t st) {
+    const size_t lds = kh_bmp_readout_lds_bytes(job.nbins, job.nops, waves);
+    bmp_allow_lds(k_bmp_readout, lds);
+    hipLaunchKernelGGL(k_bmp_readout, dim3(grid), dim3(KH_WAVE, waves), lds, st, job);
+}

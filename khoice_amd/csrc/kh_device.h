@@ -91,6 +91,36 @@ __device__ __forceinline__ void load_codes(const u8* __restrict__ sbase, const u
     }
 }
 
+// load_codes word by word in two halves, for kernels that keep the global load of their next tile in flight while they
+// work on the current one.  codes_fetch issues ONE unconditional load: the 16 bytes at base b0 of a sequence when all
+// of them are bases of it, else 16 bytes at `safe` (any readable device address; the value is not used) — no branch
+// around the load and, in codes_decode, no path that leaves its result unread, so the compiler needs no wait for it
+// anywhere but at the decode.  The pointer is cast to the global address space: out of a table in memory it would be
+// a flat pointer, whose loads also count as LDS traffic and would make the tile being worked on wait for them.
+// codes_decode gives the word's 16 two-bit codes and break flags; the last, partial word of a sequence is read there,
+// byte by byte (never a byte past the end).
+typedef u32 kh_u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ kh_u32x4 codes_fetch(const u8* __restrict__ sbase, const u64 len, const u64 b0, const bool want,
+                                                const void* safe) {
+    typedef __attribute__((address_space(1))) const kh_u32x4 global_u32x4;
+    const u8* p = (want && b0 + 16 <= len) ? sbase + b0 : static_cast<const u8*>(safe);
+    return *(global_u32x4*)(uintptr_t)p;
+}
+__device__ __forceinline__ void codes_decode(const kh_u32x4 f, const u8* __restrict__ sbase, const u64 len, const u64 b0,
+                                             u32& codes, u32& bad) {
+    decode16(make_uint4(f.x, f.y, f.z, f.w), codes, bad);
+    if (b0 >= len) {
+        codes = 0;
+        bad = 0xffffu;
+    } else if (len - b0 < 16) {
+        const u32 left = (u32)(len - b0);
+        u32 w4[4] = {0, 0, 0, 0};
+        for (u32 i = 0; i < left; ++i) w4[i >> 2] |= (u32)sbase[b0 + i] << (8 * (i & 3));
+        decode16(make_uint4(w4[0], w4[1], w4[2], w4[3]), codes, bad);
+        bad |= (0xffffu << left) & 0xffffu;
+    }
+}
+
 // reverse the order of the 32 two-bit groups of x
 __device__ __forceinline__ u64 kh_revpairs64(u64 x) {
     x = ((u64)__builtin_bitreverse32((u32)x) << 32) | (u64)__builtin_bitreverse32((u32)(x >> 32));

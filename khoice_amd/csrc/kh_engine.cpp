@@ -203,7 +203,8 @@ void kh_ctx::prof_collect() {
 static const char* kClsNames[KC_COUNT] = {"extract_hist", "bucket_plan", "extract_scatter",
                                           "bucket_sort_rle", "range_bounds", "setop", "histogram",
                                           "remix", "copy_in", "union_tagged", "skm_scatter",
-                                          "skm_regroup", "skm_union", "skm_big", "skm_pack", "skm_phased"};
+                                          "skm_regroup", "skm_union", "skm_big", "skm_pack", "skm_phased", "bmp_build",
+                                          "bmp_readout"};
 
 // ------------------------------------------------------------------------------ ctx API
 extern "C" int kh_device_count(void) {
@@ -1988,6 +1989,204 @@ static int exp1_skm(kh_ctx* c, const Exp1In& in, uint64_t* within_hist, uint64_t
     *done = true;
     return KH_OK;
 }
+// The presence-bitmap form of the fused path (kh_bmp.hip) for k <= KH_BMP_MAX_K, histograms and distinct counts only: a
+// k-mer is a number below 4^k, so "which genomes hold it" is one bit per genome in a directly addressed bitmap.
+// k_bmp_build turns every split of a genome into a partial bitmap, k_bmp_readout counts over them with bit-sliced
+// counters.  There is no genome mask: groups of up to 1023 genomes and up to 1023 groups are one pass.  *done == false:
+// the form does not apply (nothing was launched, no retry is counted) — the caller goes on to the other forms.
+static int exp1_bmp(kh_ctx* c, const Exp1In& in, uint64_t* within_hist, uint64_t* across_hist, uint64_t* distinct_per_seq,
+                    bool* done) {
+    *done = false;
+    const int k = in.k, nseq = in.nseq, ngroups = in.ngroups;
+    int max_k = KH_BMP_MAX_K;
+    if (const char* e = getenv("KHOICE_BMP_MAX_K")) max_k = std::min(KH_BMP_INST_MAX_K, atoi(e));
+    // (KHOICE_NO_SKM: "the key arrays, please"; KHOICE_SKM_MIN_K lowered to this k: the super-k-mer form keeps it)
+    if (k > max_k || getenv("KHOICE_NO_BMP") || getenv("KHOICE_NO_SKM") || skm_form_k(k)) return KH_OK;
+    if ((u32)ngroups > KH_BMP_MAX_COUNT) return KH_OK;
+    {
+        std::vector<u32> gsize(ngroups, 0);
+        u64 nbins = (u64)ngroups + 1;
+        for (int i = 0; i < nseq; ++i) gsize[in.group_of[i]]++;
+        for (int g = 0; g < ngroups; ++g) {
+            if (!gsize[g] || gsize[g] > KH_BMP_MAX_COUNT) return KH_OK;   // (a group without genomes: the general path reports it)
+            nbins += gsize[g] + 1;
+        }
+        if (nbins > KH_BMP_MAX_BINS) return KH_OK;
+    }
+    TagLayout L;
+    KHCHK(tag_layout(&L, nseq, in.group_of, ngroups, false));
+
+    // ---- geometry: ranges of the code space, tiles, splits
+    const u64 nwords = k >= 3 ? 1ull << (2 * k - 6) : 1;
+    u32 range_bits = KH_BMP_RANGE_BITS;
+    if (const char* e = getenv("KHOICE_BMP_RANGE_BITS")) range_bits = (u32)std::min(20, std::max(16, atoi(e)));   // experiments
+    range_bits = std::min<u32>(range_bits, (u32)std::max(6, 2 * k));
+    const u32 nranges = (u32)((nwords * 64) >> range_bits);
+    u32 tile_pos = KH_BMP_TILE;
+    if (const char* e = getenv("KHOICE_BMP_TILE_POS"))
+        tile_pos = std::min<u32>(KH_BMP_TILE, std::max<u32>(16, (u32)strtoul(e, nullptr, 10) & ~15u));
+    u64 bases = 0, maxpos = 0;
+    const u64 positions = kmer_positions(nseq, in.lens, k, &bases);
+    for (int i = 0; i < nseq; ++i) maxpos = std::max<u64>(maxpos, in.lens[i] >= (u64)k ? in.lens[i] - k + 1 : 0);
+    // Splits: genomes x splits x ranges is a small multiple of the CU count, but a split is long enough to pay for the
+    // words of its range that its workgroup clears and stores (one bit per position would be the break-even)
+    const u64 want_wgs = 4ull * (u64)std::max(1, c->cus);
+    const u64 want_splits = std::max<u64>(1, want_wgs / nranges);
+    u64 split_pos = std::max<u64>((positions + want_splits - 1) / want_splits, std::max<u64>(tile_pos, (1ull << range_bits) / 16));
+    if (const char* e = getenv("KHOICE_BMP_SPLIT_POS")) split_pos = std::max<u64>(16, strtoull(e, nullptr, 10));
+    split_pos = (split_pos + 15) & ~15ull;
+    auto count_splits = [&](u64 sp) {
+        u64 n = 0;
+        for (int i = 0; i < nseq; ++i) {
+            const u64 npos = in.lens[i] >= (u64)k ? in.lens[i] - k + 1 : 0;
+            n += std::max<u64>(1, (npos + sp - 1) / sp);   // a genome without k-mers: one split, all zeros
+        }
+        return n;
+    };
+    HIPCHK(hipSetDevice(c->dev));
+    u64 budget = 1ull << 30;
+    {
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) budget = (free_b + c->pool.cached_bytes) / 4;
+    }
+    if (const char* e = getenv("KHOICE_BMP_MAX_BYTES")) budget = strtoull(e, nullptr, 10);
+    u64 nsplits = count_splits(split_pos);
+    while (nsplits * nwords * 8 > budget && split_pos < maxpos) {   // fewer, longer splits: fewer partial bitmaps
+        split_pos *= 2;
+        nsplits = count_splits(split_pos);
+    }
+    if (nsplits * nwords * 8 > budget || nsplits * nranges > 0x7fffffffull) return KH_OK;
+    const size_t lds_build = kh_bmp_build_lds_bytes(range_bits, tile_pos);
+    if (lds_build > 160u * 1024u) return KH_OK;
+    if (getenv("KHOICE_BMP_DEBUG"))
+        fprintf(stderr, "[bmp] k=%d range_bits=%u R=%u tile_pos=%u split_pos=%llu splits=%llu workgroups=%llu bitmap_bytes=%llu\n", k,
+                range_bits, nranges, tile_pos, (unsigned long long)split_pos, (unsigned long long)nsplits,
+                (unsigned long long)(nsplits * nranges), (unsigned long long)(nsplits * nwords * 8));
+
+    // ---- tables: splits, operands (group-major order), groups
+    hipStream_t st = c->st;
+    std::vector<KhBmpSplit> splits;
+    std::vector<KhBmpOp> ops(nseq);
+    std::vector<KhBmpGroup> groups(ngroups);
+    std::vector<u64> pack_off(nseq);
+    splits.reserve(nsplits);
+    u64 seq_bytes = 0;
+    bool need_pack = false;
+    for (int i = 0; i < nseq; ++i) {
+        const int src = L.perm[i];
+        const u64 len = in.lens[src], npos = len >= (u64)k ? len - k + 1 : 0;
+        pack_off[i] = seq_bytes;
+        seq_bytes += (len + 15) & ~15ull;
+        if (!(in.on_device && (reinterpret_cast<uintptr_t>(in.seqs[src]) & 15) == 0)) need_pack = true;
+        ops[i].split0 = (u32)splits.size();
+        u64 p0 = 0;
+        do {
+            const u64 p1 = std::min(npos, p0 + split_pos);
+            splits.push_back(KhBmpSplit{nullptr, len, p0, p1, (u32)i, 0});
+            p0 = p1;
+        } while (p0 < npos);
+        ops[i].nsplits = (u32)splits.size() - ops[i].split0;
+    }
+    seq_bytes += 256;
+    for (int g = 0; g < ngroups; ++g) groups[g] = KhBmpGroup{(u32)L.gstart[g], (u32)L.gsize[g], L.bin0[g], 0};
+    const u32 nb = L.nbins + (u32)nseq;   // the bins, then one distinct counter per operand
+    // the read-out: a wave per 64 words and genome; where the words alone leave most of the chip idle (k <= 10: at
+    // most 256 blocks of 64 words) sixteen genomes are in flight per block, else four
+    const u64 rblocks = (nwords + 63) / 64;
+    const u32 rwaves = rblocks <= 256 ? 16u : 4u;
+    const u32 rgrid = (u32)std::min<u64>(rblocks, 8ull * (u64)std::max(1, c->cus));
+    const u32 reps = std::min<u32>(rgrid, std::max<u32>(1, std::min<u32>(64, 65536u / nb)));
+    // workspace: [hist: reps x nb u64][inst: nseq u64] (zeroed, read back) [splits][ops][groups] (one upload)
+    const size_t off_inst = 8 * (size_t)reps * nb, off_splits = off_inst + 8 * (size_t)nseq,
+                 off_ops = off_splits + sizeof(KhBmpSplit) * splits.size(), off_groups = off_ops + sizeof(KhBmpOp) * (size_t)nseq,
+                 ws_bytes = off_groups + sizeof(KhBmpGroup) * (size_t)ngroups;
+    Tmp d_seq, d_ws, d_partial;
+    TMP_ALLOC(d_seq, c, need_pack ? seq_bytes : 256);
+    TMP_ALLOC(d_ws, c, ws_bytes);
+    TMP_ALLOC(d_partial, c, (size_t)(nsplits * nwords * 8));
+    const size_t up_bytes = ws_bytes - off_splits, down_bytes = off_splits;
+    Pinned pin{c};
+    PIN_ALLOC(pin, up_bytes + down_bytes + 64);
+    u8* h_up = static_cast<u8*>(pin.p);
+    u8* h_down = h_up + ((up_bytes + 63) & ~(size_t)63);
+    c->prof_begin(KC_COPY_IN);
+    for (int i = 0; i < nseq; ++i) {
+        const uint8_t* src = in.seqs[L.perm[i]];
+        const u8* dev = src;
+        if (!(in.on_device && (reinterpret_cast<uintptr_t>(src) & 15) == 0)) {
+            dev = d_seq.as<u8>() + pack_off[i];
+            if (in.lens[L.perm[i]])
+                HIPCHK(hipMemcpyAsync(d_seq.as<u8>() + pack_off[i], src, in.lens[L.perm[i]],
+                                      in.on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+        }
+        for (u32 s = 0; s < ops[i].nsplits; ++s) splits[ops[i].split0 + s].seq = dev;
+    }
+    memcpy(h_up, splits.data(), sizeof(KhBmpSplit) * splits.size());
+    memcpy(h_up + (off_ops - off_splits), ops.data(), sizeof(KhBmpOp) * (size_t)nseq);
+    memcpy(h_up + (off_groups - off_splits), groups.data(), sizeof(KhBmpGroup) * (size_t)ngroups);
+    u8* wsp = d_ws.as<u8>();
+    HIPCHK(hipMemsetAsync(wsp, 0, off_splits, st));
+    HIPCHK(hipMemcpyAsync(wsp + off_splits, h_up, up_bytes, hipMemcpyHostToDevice, st));
+    c->prof_end();
+
+    KhBmpJob job;
+    job.splits = reinterpret_cast<const KhBmpSplit*>(wsp + off_splits);
+    job.ops = reinterpret_cast<const KhBmpOp*>(wsp + off_ops);
+    job.groups = reinterpret_cast<const KhBmpGroup*>(wsp + off_groups);
+    job.partial = d_partial.as<u64>();
+    job.inst = reinterpret_cast<unsigned long long*>(wsp + off_inst);
+    job.hist = reinterpret_cast<unsigned long long*>(wsp);
+    job.nwords = nwords;
+    job.tile_pos = tile_pos;
+    job.range_bits = range_bits; job.nranges = nranges;
+    job.nops = (u32)nseq; job.ngroups = (u32)ngroups; job.nbins = L.nbins; job.abase = L.abase; job.reps = reps;
+    job.k = k;
+    c->prof_begin(KC_BMP_BUILD);
+    kh_launch_bmp_build(job, (u32)nsplits, st);
+    c->prof_end();
+    HIPCHK(hipGetLastError());
+    c->prof_begin(KC_BMP_READOUT);
+    kh_launch_bmp_readout(job, rgrid, rwaves, st);
+    c->prof_end();
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(h_down, wsp, down_bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+
+    // ---- the replicas summed; counts saturate at cs and at the last bin
+    const u64* h_hist = reinterpret_cast<const u64*>(h_down);
+    const u64* h_inst = reinterpret_cast<const u64*>(h_down + off_inst);
+    std::vector<u64> bins(nb, 0);
+    for (u32 r = 0; r < reps; ++r)
+        for (u32 b = 0; b < nb; ++b) bins[b] += h_hist[(size_t)r * nb + b];
+    auto bin_of = [&](int cnt) { return std::min<u32>(std::min<u32>((u32)cnt, in.cs), in.hist_len - 1); };
+    if (within_hist) {
+        memset(within_hist, 0, 8 * (size_t)ngroups * in.hist_len);
+        for (int g = 0; g < ngroups; ++g)
+            for (int cnt = 1; cnt <= L.gsize[g]; ++cnt) within_hist[(size_t)g * in.hist_len + bin_of(cnt)] += bins[L.bin0[g] + cnt];
+    }
+    u64 across_n = 0;
+    if (across_hist) memset(across_hist, 0, 8 * (size_t)in.hist_len);
+    for (int cnt = 1; cnt <= ngroups; ++cnt) {
+        across_n += bins[L.abase + cnt];
+        if (across_hist) across_hist[bin_of(cnt)] += bins[L.abase + cnt];
+    }
+    u64 inst = 0, dsum = 0;
+    for (int i = 0; i < nseq; ++i) {
+        const u64 d = bins[L.nbins + i];
+        inst += h_inst[i];
+        dsum += d;
+        if (distinct_per_seq) distinct_per_seq[L.perm[i]] = d;
+    }
+    c->stat.bases += bases;
+    c->stat.builds += nseq;
+    c->stat.kmers += inst;
+    c->stat.distinct += dsum;
+    c->stat.setop_in += dsum;
+    c->stat.setop_out += across_n;
+    c->stat.setops++;
+    *done = true;
+    return KH_OK;
+}
 // The fused form of steps 1-8 (no per-genome / per-group database is handed out): ONE batched build
 // in grid mode, ONE tagged union over all genomes, ONE host synchronisation.  *done == false on
 // return means "not applicable or a slot overflowed": the caller takes the general path.
@@ -2481,7 +2680,10 @@ extern "C" int kh_exp1_run(kh_ctx* c, int nseq, const uint8_t* const* seqs, cons
         const u64 budget = exp1_wave_bases(c, k);
         std::vector<Exp1Batch> batches;
         bool done = false;
-        if (exp1_batches(in, budget, &batches)) {
+        // small k, histograms and distinct counts only: the presence-bitmap form, which has no genome mask and so is
+        // tried before the input is cut into batches of 64 genomes
+        if (!across_set) KHCHK(exp1_bmp(c, in, within_hist, across_hist, distinct_per_seq, &done));
+        if (!done && exp1_batches(in, budget, &batches)) {
             if (batches.size() == 1 && !batches[0].big) {   // all groups in one batch
                 const StatCheckpoint cp{c};
                 if (!across_set) {   // histograms and distinct counts only: the super-k-mer form

@@ -234,6 +234,45 @@ void kh_launch_skm2_scatter(const KhSkmJob& job, u32 ntiles, hipStream_t st);
 void kh_launch_skm2_regroup(const KhSkmJob& job, hipStream_t st);
 void kh_launch_skm2_union(const KhSkmJob& job, u32 cs, u32 grid, hipStream_t st);   // persistent, as the one-word union
 
+// ---- presence-bitmap form of the fused path (kh_bmp.hip): k <= KH_BMP_MAX_K, histograms and distinct counts only.
+// k_bmp_build writes one partial bitmap of 4^k bits (at least one 64-bit word) per split of a genome, k_bmp_readout
+// counts over them with bit-sliced counters: no genome mask, any number of genomes and groups up to the limits below.
+#ifndef KH_TUNE_BMP_RANGE_BITS
+#define KH_TUNE_BMP_RANGE_BITS 20   // codes per build workgroup: 2^20 bits = 128 KiB of LDS, one workgroup per CU
+#endif
+constexpr int KH_BMP_RANGE_BITS = KH_TUNE_BMP_RANGE_BITS;
+constexpr int KH_BMP_MAX_K = 12;         // the form is taken up to this k (KHOICE_BMP_MAX_K: up to KH_BMP_INST_MAX_K)
+constexpr int KH_BMP_INST_MAX_K = 13;    // largest k the build kernel is instantiated for
+constexpr u32 KH_BMP_MAX_COUNT = 1023;   // genomes of a group, groups: ten counter slices
+constexpr u32 KH_BMP_MAX_BINS = 4096;
+constexpr u32 KH_BMP_TILE = 65520;       // positions staged per round of a build workgroup: 4095 words of 16 and the halo word
+struct KhBmpSplit {                 // a run of consecutive k-mer positions of one genome
+    const u8* seq;                  // the genome's base 0 (16-B aligned; bytes past len are never read)
+    u64 len;
+    u64 p0, p1;                     // positions [p0, p1); p0 a multiple of 16, p1 a multiple of 16 or the genome's last
+    u32 op;                         // the genome's operand number
+    u32 pad;
+};
+struct KhBmpOp { u32 split0, nsplits; };              // an operand's partial bitmaps: [split0, split0 + nsplits), at least one
+struct KhBmpGroup { u32 first, size, bin0, pad; };    // operands [first, first + size) (group-major order), first bin
+struct KhBmpJob {
+    const KhBmpSplit* splits;
+    const KhBmpOp* ops;             // [nops]
+    const KhBmpGroup* groups;       // [ngroups]
+    u64* partial;                   // [splits][nwords]
+    unsigned long long* inst;       // [nops] zeroed: valid k-mer positions per genome
+    unsigned long long* hist;       // [reps][nbins + nops] zeroed: the bins, then the distinct k-mers of every operand
+    u64 nwords;                     // 64-bit words of one bitmap: max(1, 4^k / 64)
+    u32 tile_pos;                   // positions staged per round: a multiple of 16
+    u32 range_bits, nranges;        // codes per build workgroup (log2, >= 6), ranges of the code space
+    u32 nops, ngroups, nbins, abase, reps;
+    int k;
+};
+size_t kh_bmp_build_lds_bytes(u32 range_bits, u32 tile_pos);
+size_t kh_bmp_readout_lds_bytes(u32 nbins, u32 nops, u32 waves);
+void kh_launch_bmp_build(const KhBmpJob& job, u32 nsplits, hipStream_t st);   // nsplits * nranges workgroups
+void kh_launch_bmp_readout(const KhBmpJob& job, u32 grid, u32 waves, hipStream_t st);   // grid workgroups of `waves` waves walk the words
+
 struct KhLookback {      // workspace of one ordered single-pass launch
     u64* desc;           // [nparts] tile descriptors, zeroed before launch
     u32* ticket;         // zeroed before launch
