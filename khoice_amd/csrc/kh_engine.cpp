@@ -1459,7 +1459,7 @@ extern "C" int kh_set_wrap_device(kh_ctx* c, int k, uint64_t n, const void* keys
 extern "C" int kh_set_partition_bounds(kh_ctx* c, const kh_set* s, uint32_t nparts, uint64_t* bounds) {
     if (!c || !s || !bounds || !nparts) return kh_fail(KH_E_ARG, "kh_set_partition_bounds: bad argument");
     HIPCHK(hipSetDevice(c->dev));
-    if (!s->n) { for (u32 i = 0; i <= nparts; ++i) bounds[i] = 0; return KH_OK; }
+    if (!s->n) { for (u64 i = 0; i <= nparts; ++i) bounds[i] = 0; return KH_OK; }   // u64: nparts may be 2^32 - 1
     KhSetView v{s->keys_ptr(), nullptr, s->n, 1, 0};
     Tmp d_view, d_bounds;
     TMP_ALLOC(d_view, c, sizeof v);
@@ -1474,11 +1474,13 @@ extern "C" int kh_set_partition_bounds(kh_ctx* c, const kh_set* s, uint32_t npar
 extern "C" int kh_sets_partition_bounds(kh_ctx* c, const kh_set* const* sets, int nsets, uint32_t nparts,
                                         uint64_t* bounds) {
     if (!c || !sets || !bounds || !nparts || nsets <= 0) return kh_fail(KH_E_ARG, "kh_sets_partition_bounds: bad argument");
+    for (int i = 0; i < nsets; ++i)
+        if (!sets[i]) return kh_fail(KH_E_ARG, "kh_sets_partition_bounds: set %d is NULL", i);
     HIPCHK(hipSetDevice(c->dev));
     const int k = sets[0]->k, W = sets[0]->W;
     std::vector<KhSetView> v(nsets);
     for (int i = 0; i < nsets; ++i) {
-        if (!sets[i] || sets[i]->k != k) return kh_fail(KH_E_KMISMATCH, "sets built with different k");
+        if (sets[i]->k != k) return kh_fail(KH_E_KMISMATCH, "sets built with different k");
         v[i] = KhSetView{sets[i]->n ? sets[i]->keys_ptr() : nullptr, nullptr, sets[i]->n, 1, 0};
     }
     Tmp d_view, d_bounds;

@@ -10,7 +10,8 @@ import os
 import numpy as np
 import pytest
 
-from tests.util import key_view, mixed_from_top32, unmix_np, view_keys, words
+from tests.util import (Operand, boundary_mixed, clustered_mixed, counter_mix, distinct_raw, edge_mixed, key_view,
+                        mixed_from_top32, ref_hist, uniform_mixed, unmix_np, view_keys, words)
 
 pytestmark = pytest.mark.gpu
 
@@ -65,78 +66,6 @@ def planner_slots(total, nsets, W):
     return max(1, -(-total // target))
 
 
-def edge_mixed(k):
-    """Mixed keys 0, 1, max - 1, max: the first and the last slot."""
-    m = (1 << (2 * k)) - 1
-    vals = sorted({0, 1, m - 1, m})
-    return np.array([[v & (2**64 - 1), v >> 64][:words(k)] for v in vals], dtype=np.uint64)
-
-
-def boundary_mixed(k, rng, slots, per=3):
-    """Runs of keys whose top 32 bits are ceil(r * 2^32 / n) or one below, for every n in `slots`."""
-    tops = []
-    for n in slots:
-        for r in range(1, n):
-            t = -(-(r << 32) // n)
-            tops += [t] * per + [t - 1] * per
-    if not tops:
-        return np.zeros((0, words(k)), dtype=np.uint64)
-    return mixed_from_top32(k, np.array(tops, dtype=np.uint64), rng)
-
-
-def uniform_mixed(k, n, rng):
-    return mixed_from_top32(k, rng.integers(0, 1 << 32, size=n, dtype=np.uint64), rng)
-
-
-def clustered_mixed(k, n, rng, frac, start=0):
-    """n mixed keys whose top 32 bits lie in [start, start + 2^32 * frac)."""
-    width = max(1, int((1 << 32) * frac))
-    return mixed_from_top32(k, np.uint64(start) + rng.integers(0, width, size=n, dtype=np.uint64), rng)
-
-
-def distinct_raw(k, mixed):
-    """Distinct mixed keys -> their k-mer codes (what kh_set_upload takes), in random order."""
-    v = np.unique(key_view(mixed))
-    return unmix_np(k, view_keys(v, k))
-
-
-def counter_mix(rng, n, extra=()):
-    """Counters over [1, 2^32 - 1] with mass at the histogram tiers, near 2^31, near 2^32 and near
-    every value of `extra` (the cs values of a test)."""
-    centres = [2**31 - 1, 2**31, U32 - 2] + list(extra)
-    kind = rng.integers(0, 6, size=n)
-    c = np.empty(n, dtype=np.int64)
-    c[kind == 0] = rng.integers(1, 16, size=int((kind == 0).sum()))
-    c[kind == 1] = rng.integers(16, 520, size=int((kind == 1).sum()))
-    c[kind == 2] = rng.integers(500, 6000, size=int((kind == 2).sum()))
-    c[kind == 3] = rng.integers(1, U32 + 1, size=int((kind == 3).sum()), dtype=np.int64)
-    near = rng.choice(np.array(centres, dtype=np.int64), size=int((kind >= 4).sum()))
-    c[kind >= 4] = near + rng.integers(-2, 3, size=near.shape[0])
-    return np.clip(c, 1, U32)
-
-
-class Operand:
-    """Host copy (keys[n, W] k-mer codes, int64 counters) of a set uploaded to the engine."""
-
-    def __init__(self, eng, k, keys, counts=None, uniform=None):
-        self.k, self.keys = k, keys
-        n = keys.shape[0]
-        if counts is not None:
-            self.counts = np.asarray(counts, dtype=np.int64)
-            self.set = eng.upload(k, keys, self.counts.astype(np.uint32))
-        else:
-            base = eng.upload(k, keys)
-            self.counts = np.full(n, 1 if uniform is None else uniform, dtype=np.int64)
-            self.set = base if uniform is None else base.set_counts(uniform)
-
-    def with_uniform(self, eng, v):
-        o = Operand.__new__(Operand)
-        o.k, o.keys = self.k, self.keys
-        o.counts = np.full(self.keys.shape[0], v, dtype=np.int64)
-        o.set = self.set.set_counts(v)
-        return o
-
-
 # ---------------------------------------------------------------- reference
 class Pair:
     """Key alignment of two operands (independent of their counters)."""
@@ -185,11 +114,6 @@ def ref_union(k, operands, cs=None):
     tot = np.zeros(u.shape[0], dtype=np.int64)
     np.add.at(tot, inv.reshape(-1), c)
     return view_keys(u, k), (tot if cs is None else np.minimum(tot, cs))
-
-
-def ref_hist(counts, hist_len):
-    return np.bincount(np.minimum(np.asarray(counts, dtype=np.int64), hist_len - 1),
-                       minlength=hist_len).astype(np.uint64)
 
 
 def assert_set(got, keys, counts, what):
