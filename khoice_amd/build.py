@@ -48,25 +48,29 @@ def _run(cmd):
     subprocess.check_call(cmd)
 
 
-def build_library(force: bool = False) -> str:
-    os.makedirs(LIBDIR, exist_ok=True)
-    objdir = os.path.join(LIBDIR, "obj")
+def build_library(force: bool = False, lib: str = LIB, flags=()) -> str:
+    """The shipped library, or with `lib` / `flags` a variant of it (another path, extra compiler flags such as
+    -DKH_STAMPS; tools/build_variant.sh, tools/build_diag.sh): the same sources, the same link line."""
+    libdir = os.path.dirname(lib)
+    objdir = os.path.join(libdir, "obj" if lib == LIB else os.path.basename(lib).rsplit(".", 1)[0] + ".obj")
     os.makedirs(objdir, exist_ok=True)
     hipcc = _hipcc()
     hdrs = [h if os.path.isabs(h) else os.path.join(CSRC, h) for h in HEADERS]
+    srcs = [os.path.join(CSRC, src) for src in HIP_SOURCES]
+    if not force and not _newer(lib, srcs + hdrs):
+        return lib      # built from these sources already (its objects need not have travelled with it)
     objs = []
-    for src in HIP_SOURCES:
-        path = os.path.join(CSRC, src)
-        obj = os.path.join(objdir, src.rsplit(".", 1)[0] + ".o")
+    for path in srcs:
+        obj = os.path.join(objdir, os.path.basename(path).rsplit(".", 1)[0] + ".o")
         objs.append(obj)
         if force or _newer(obj, [path] + hdrs):
-            _run([hipcc, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-x", "hip",
+            _run([hipcc, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-x", "hip", *flags,
                   "-I", os.path.join(ROOT, "include"), "-c", path, "-o", obj])
-    if force or _newer(LIB, objs):
+    if force or _newer(lib, objs):
         # --no-undefined: a launcher declared in kh_launch.h but not defined must fail the build,
         # not the first dlopen on the GPU box
-        _run([hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-Wl,--no-undefined", "-o", LIB] + objs + ["-lz", "-ldl"])
-    return LIB
+        _run([hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-Wl,--no-undefined", "-o", lib] + objs + ["-lz", "-ldl"])
+    return lib
 
 
 def build_clis(force: bool = False):

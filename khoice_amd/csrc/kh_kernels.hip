@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
+#include <type_traits>
 
 #include "kh_launch.h"
 #include "kh_device.h"
@@ -614,19 +615,19 @@ __device__ u32 find_runs(const KmerKey<W>* s, u32 n, u16* hstart, u32* wave_tot)
     return base;
 }
 
-// LDS carve shared by k_bucket_sort_rle and k_setop (everything lives in dynamic LDS so that
-// its base stays 16-B aligned):  keys[cap] | pay[cap] (optional) | aux | lhist[KH_LHIST_BINS] |
-// tab[128 + KH_FINE_BINS/32 + KH_WORKLIST] (ballot table, dirty-bin bitmap, repair work list) |
-// scratch[32] u32 | bcast[4] u64, where aux holds the fine-bin table
-// bins[KH_FINE_BINS+1] u32 while sorting and hstart[cap+2] u16 afterwards.
+// LDS carve shared by the sort kernels (everything lives in dynamic LDS so that its base stays
+// 16-B aligned):  keys[cap] | pay[cap] (optional) | aux | lhist[KH_LHIST_BINS] |
+// tab: ballots[128] dirty[KH_FINE_BINS/32] worklist[KH_WORKLIST] (ballot table, dirty-bin bitmap,
+// repair work list) | scratch[32] u32 | bcast[4] u64, where aux holds the fine-bin table
+// bins[KH_FINE_BINS/2+1] u32 while sorting and hstart[cap+2] u16 afterwards.
 struct SortLds {
     u8* base;
     u32 cap;
     int W;
-    bool pay;
-    __host__ __device__ size_t keys_off() const { return 0; }
+    bool has_pay;
+    static constexpr size_t BALLOTS = 128;
     __host__ __device__ size_t pay_off() const { return (size_t)cap * 8 * W; }
-    __host__ __device__ size_t hstart_off() const { return pay_off() + (pay ? (size_t)cap * 4 : 0); }
+    __host__ __device__ size_t hstart_off() const { return pay_off() + (has_pay ? (size_t)cap * 4 : 0); }
     __host__ __device__ size_t lhist_off() const {
         size_t aux = ((size_t)cap + 2) * 2;
         if (aux < (size_t)(KH_FINE_BINS / 2 + 1) * 4) aux = (size_t)(KH_FINE_BINS / 2 + 1) * 4;
@@ -634,10 +635,21 @@ struct SortLds {
     }
     __host__ __device__ size_t tab_off() const { return lhist_off() + KH_LHIST_BINS * 4; }
     __host__ __device__ size_t scratch_off() const {
-        return tab_off() + (128 + KH_FINE_BINS / 32 + KH_WORKLIST) * 4;
+        return tab_off() + (BALLOTS + KH_FINE_BINS / 32 + KH_WORKLIST) * 4;
     }
     __host__ __device__ size_t bcast_off() const { return scratch_off() + 32 * 4; }
     __host__ __device__ size_t total() const { return bcast_off() + 4 * 8; }
+    template <class T> __device__ __forceinline__ T* at(size_t off) const { return reinterpret_cast<T*>(base + off); }
+    template <int WW> __device__ __forceinline__ KmerKey<WW>* keys() const { return at<KmerKey<WW>>(0); }
+    __device__ __forceinline__ u32* pay() const { return at<u32>(pay_off()); }
+    __device__ __forceinline__ u32* bins() const { return at<u32>(hstart_off()); }      // while sorting
+    __device__ __forceinline__ u16* hstart() const { return at<u16>(hstart_off()); }    // afterwards
+    __device__ __forceinline__ u32* lhist() const { return at<u32>(lhist_off()); }
+    __device__ __forceinline__ u32* ballots() const { return at<u32>(tab_off()); }
+    __device__ __forceinline__ u32* dirty() const { return ballots() + BALLOTS; }
+    __device__ __forceinline__ u32* worklist() const { return dirty() + KH_FINE_BINS / 32; }
+    __device__ __forceinline__ u32* scratch() const { return at<u32>(scratch_off()); }
+    __device__ __forceinline__ u64* bcast() const { return at<u64>(bcast_off()); }
 };
 size_t kh_sort_lds_bytes(int W, u32 cap, bool pay) {
     SortLds L{nullptr, cap, W, pay};
@@ -1217,6 +1229,61 @@ __device__ void grid_emit(const KmerKey<W>* s, const u32 n, u32* tab, KmerKey<W>
 }
 
 // ------------------------------------------------------------------------------------------
+// Fold of a bucket with more keys than fit LDS (duplicate-heavy input), chunk by chunk:
+// [distinct keys so far | next raw chunk] -> sort -> one entry per run, until part[lo, lo + n64)
+// is consumed.  PAY: a counter plane is carried (pay[r] = saturating copies of key r so far);
+// without it only the first key of every run is kept.  Returns the number of distinct keys, now
+// sorted in s[0..) — or KH_FOLD_FAIL when they exceed capp, the only bucket that cannot be handled.
+// All threads of the block must call it.
+// ------------------------------------------------------------------------------------------
+constexpr u32 KH_FOLD_FAIL = 0xffffffffu;
+template <int W, bool PAY>
+__device__ u32 fold_oversize(const KmerKey<W>* __restrict__ part, const u64 lo, const u64 n64, KmerKey<W>* s,
+                             u32* pay, const u32 capp, u16* hstart, u32* scratch) {
+    const u32 tid = threadIdx.x, nt = blockDim.x;
+    u32 acc = 0;
+    u64 consumed = 0;
+    bool fail = false;
+    while (consumed < n64) {
+        if (acc >= capp) { fail = true; break; }
+        const u64 left = n64 - consumed;
+        const u32 take = left < (u64)(capp - acc) ? (u32)left : (capp - acc);
+        const u32 m = acc + take;
+        for (u32 i = acc + tid; i < m; i += nt) {
+            s[i] = part[lo + consumed + (i - acc)];
+            if (PAY) pay[i] = 1u;
+        }
+        __syncthreads();
+        bitonic_sort_lds<W, PAY>(s, pay, m);
+        const u32 dd = find_runs<W>(s, m, hstart, scratch);
+        // fold runs in place: slot r <- (first key of run r, saturating sum of its payloads)
+        for (u32 r0 = 0; r0 < dd; r0 += nt) {
+            const u32 r = r0 + tid;
+            KmerKey<W> kv = key_zero<W>();
+            u64 sum = 0;
+            if (r < dd) {
+                const u32 h0 = hstart[r];
+                kv = s[h0];
+                if constexpr (PAY) {
+                    const u32 h1 = hstart[r + 1];
+                    for (u32 j = h0; j < h1; ++j) sum += pay[j];
+                    if (sum > 0xffffffffull) sum = 0xffffffffull;
+                }
+            }
+            __syncthreads();
+            if (r < dd) {
+                s[r] = kv;
+                if (PAY) pay[r] = (u32)sum;
+            }
+            __syncthreads();
+        }
+        acc = dd;
+        consumed += take;
+    }
+    return fail ? KH_FOLD_FAIL : acc;
+}
+
+// ------------------------------------------------------------------------------------------
 // pass C: per-bucket sort + run-length count + ordered output
 // ------------------------------------------------------------------------------------------
 // Normal buckets (n <= cap): keys-only distribution sort, counter = run length.
@@ -1232,23 +1299,23 @@ __global__ __launch_bounds__(KH_SORT_THREADS, KH_SORT_WAVES_PER_SIMD) void k_buc
     u32 cs) {
     extern __shared__ __attribute__((aligned(16))) u8 lds_raw[];
     const SortLds L{lds_raw, cap, W, false};
-    KmerKey<W>* s = reinterpret_cast<KmerKey<W>*>(lds_raw + L.keys_off());
-    u16* hstart = reinterpret_cast<u16*>(lds_raw + L.hstart_off());
-    u32* tab = reinterpret_cast<u32*>(lds_raw + L.tab_off());
-    u32* scratch = reinterpret_cast<u32*>(lds_raw + L.scratch_off());
+    KmerKey<W>* s = L.keys<W>();
+    u16* hstart = L.hstart();
+    u32* tab = L.ballots();
+    u32* scratch = L.scratch();
     // pair-mode carve (oversize path): keys[capp] | pay[capp] inside the key region
     const u32 capp = ((cap * 8u * W) / (8u * W + 4u)) & ~63u;
     u32* pay = reinterpret_cast<u32*>(lds_raw + (size_t)capp * 8 * W);
     constexpr int E = ((W == 1 ? KH_SORT_CAP_W1 : KH_SORT_CAP_W2) + KH_SORT_THREADS - 1) / KH_SORT_THREADS;
 
-    const u32 tid = threadIdx.x, nt = blockDim.x;
+    const u32 tid = threadIdx.x;
     // index order: the bucket is known at once and its bounds are fetched while the block clears
     // its bins (the barrier the sort needs after the clear then comes after the key loads have
     // been issued); ticket order: everything waits for the ticket
     const bool early = lb.dynamic == 0;
     KhBucketWork wk{0, 0, 0, 0, 0, 0};
     if (early) wk = work[blockIdx.x];
-    distribute_clear(reinterpret_cast<u32*>(hstart), tab + 128, scratch);
+    distribute_clear(L.bins(), L.dirty(), scratch);
     if (!early) {
         if (tid == 0) scratch[16] = atomicAdd(lb.ticket, 1u);
         __syncthreads();
@@ -1285,8 +1352,8 @@ __global__ __launch_bounds__(KH_SORT_THREADS, KH_SORT_WAVES_PER_SIMD) void k_buc
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #endif
         KH_STAMP(q, 1);
-        distribute_sort<W, false, E>(kreg, preg, n, s, nullptr, reinterpret_cast<u32*>(hstart),
-                                     tab + 128, tab + 128 + KH_FINE_BINS / 32, scratch, k, seg_nb, q);
+        distribute_sort<W, false, E>(kreg, preg, n, s, nullptr, L.bins(), L.dirty(), L.worklist(), scratch, k,
+                                     seg_nb, q);
         auto eval = [&](u32 h0, u32 h1) -> u32 {
             const u32 c = h1 - h0;
             return (c >= ci && c <= cx) ? c : 0u;
@@ -1297,40 +1364,8 @@ __global__ __launch_bounds__(KH_SORT_THREADS, KH_SORT_WAVES_PER_SIMD) void k_buc
     }
 
     // ---- oversize bucket: fold chunk by chunk into (key, counter) pairs
-    u32 acc = 0;
-    u64 consumed = 0;
-    bool fail = false;
-    while (consumed < n64) {
-        if (acc >= capp) { fail = true; break; }
-        const u64 left = n64 - consumed;
-        const u32 take = left < (u64)(capp - acc) ? (u32)left : (capp - acc);
-        const u32 m = acc + take;
-        for (u32 i = acc + tid; i < m; i += nt) {
-            s[i] = part[lo + consumed + (i - acc)];
-            pay[i] = 1u;
-        }
-        __syncthreads();
-        bitonic_sort_lds<W, true>(s, pay, m);
-        const u32 dd = find_runs<W>(s, m, hstart, scratch);
-        // fold runs in place: slot r <- (key, saturating sum of payloads)
-        for (u32 r0 = 0; r0 < dd; r0 += nt) {
-            const u32 r = r0 + tid;
-            KmerKey<W> kv = key_zero<W>();
-            u64 sum = 0;
-            if (r < dd) {
-                const u32 h0 = hstart[r], h1 = hstart[r + 1];
-                kv = s[h0];
-                for (u32 j = h0; j < h1; ++j) sum += pay[j];
-                if (sum > 0xffffffffull) sum = 0xffffffffull;
-            }
-            __syncthreads();
-            if (r < dd) { s[r] = kv; pay[r] = (u32)sum; }
-            __syncthreads();
-        }
-        acc = dd;
-        consumed += take;
-    }
-    if (fail) {
+    u32 acc = fold_oversize<W, true>(part, lo, n64, s, pay, capp, hstart, scratch);
+    if (acc == KH_FOLD_FAIL) {
         if (tid == 0) atomicOr(lb.err, KH_ERR_CAPACITY);
         acc = 0;
     }
@@ -1392,48 +1427,21 @@ __global__ __launch_bounds__(KH_SORT_THREADS, KH_SORT_WAVES_PER_SIMD) void k_gri
     int k, KmerKey<W>* __restrict__ out_keys, u32* __restrict__ err, const KhGrid grid) {
     extern __shared__ __attribute__((aligned(16))) u8 lds_raw[];
     const SortLds L{lds_raw, cap, W, false};
-    KmerKey<W>* s = reinterpret_cast<KmerKey<W>*>(lds_raw + L.keys_off());
-    u16* hstart = reinterpret_cast<u16*>(lds_raw + L.hstart_off());
-    u32* tab = reinterpret_cast<u32*>(lds_raw + L.tab_off());
-    u32* scratch = reinterpret_cast<u32*>(lds_raw + L.scratch_off());
-    const u32 capp = cap;      // plain sets: only the distinct keys are kept while folding
+    KmerKey<W>* s = L.keys<W>();
     constexpr int E = ((W == 1 ? KH_SORT_CAP_W1 : KH_SORT_CAP_W2) + KH_SORT_THREADS - 1) / KH_SORT_THREADS;
-    const u32 tid = threadIdx.x, nt = blockDim.x;
+    const u32 tid = threadIdx.x;
     const u32 count = over[0];
     for (u32 it = blockIdx.x; it < count; it += gridDim.x) {
         const KhBucketWork wk = work[over[1u + it]];
-        const u64 lo = wk.lo, n64 = wk.n;
-        u32 acc = 0;
-        u64 consumed = 0;
-        bool fail = false;
-        __syncthreads();   // the previous bucket's readers of s / pay / tab are done
-        while (consumed < n64) {
-            if (acc >= capp) { fail = true; break; }
-            const u64 left = n64 - consumed;
-            const u32 take = left < (u64)(capp - acc) ? (u32)left : (capp - acc);
-            const u32 m = acc + take;
-            for (u32 i = acc + tid; i < m; i += nt) {
-                s[i] = part[lo + consumed + (i - acc)];
-            }
-            __syncthreads();
-            bitonic_sort_lds<W, false>(s, nullptr, m);
-            const u32 dd = find_runs<W>(s, m, hstart, scratch);
-            for (u32 r0 = 0; r0 < dd; r0 += nt) {      // fold runs in place: slot r <- first key of run r
-                const u32 r = r0 + tid;
-                KmerKey<W> kv = key_zero<W>();
-                if (r < dd) kv = s[hstart[r]];
-                __syncthreads();
-                if (r < dd) s[r] = kv;
-                __syncthreads();
-            }
-            acc = dd;
-            consumed += take;
-        }
-        if (fail) {
+        const u64 lo = wk.lo;
+        __syncthreads();   // the previous bucket's readers of s / tab are done
+        // plain sets: only the distinct keys are kept while folding, so all of cap is theirs
+        u32 acc = fold_oversize<W, false>(part, lo, wk.n, s, nullptr, cap, L.hstart(), L.scratch());
+        if (acc == KH_FOLD_FAIL) {
             if (tid == 0) atomicOr(err, KH_ERR_CAPACITY);
             acc = 0;
         }
-        grid_emit<W, E>(s, acc, tab, out_keys + lo, grid.off + (u64)wk.gb * (grid.S + 1), grid.S, k, wk.nb,
+        grid_emit<W, E>(s, acc, L.ballots(), out_keys + lo, grid.off + (u64)wk.gb * (grid.S + 1), grid.S, k, wk.nb,
                         grid.distinct + wk.gb / grid.nb);
     }
 }
@@ -1465,7 +1473,11 @@ __global__ void k_range_bounds(const KhSetView* __restrict__ sets, u32 nsets, u3
 }
 
 // the same for several independent set operations in one launch (blockIdx.y = operation): the
-// group unions of one wave are planned together, and ten latency-bound little launches become one
+// group unions of one wave are planned together, and ten latency-bound little launches become one.
+// A TWIN of the body above, kept on purpose: with one shared __device__ body both kernels read the
+// block size a second time (+7 / +5 instructions of 249 / 258) and the seven launches of a 25-genome
+// union sequence at k = 41 took 0.1801 ms against 0.1747 (parent's spread 0.0026; profiles/README.md,
+// 2026-10-17).
 template <int W>
 __global__ void k_range_bounds_batch(const KhBoundsJob* __restrict__ jobs, int k) {
     const KhBoundsJob jb = jobs[blockIdx.y];
@@ -1495,6 +1507,98 @@ __device__ __forceinline__ long long combine_counters(int mode, long long a, lon
         case KH_OC_LEFT: return a;
         default: return b;
     }
+}
+
+// ------------------------------------------------------------------------------------------
+// Block-private histogram whose low bins (where nearly all counters of a k-mer database fall)
+// are kept once per lane, so that a wave does not serialise on one LDS address: almost every
+// counter of a union is tiny (1 for the across-group sum, 1..G within a group).  Counters below 16
+// go to 64 lane-private copies that flush() folds into the block's bins, one wave per counter.
+// ------------------------------------------------------------------------------------------
+struct BlockHist {
+    u32* lh;       // [KH_LHIST_BINS]
+    u32* stripe;   // [16][64]
+    u32 nt;        // threads of the block, read once (k_setop has no scalar register to spare for more)
+    __device__ __forceinline__ void clear_bins() {
+        for (u32 i = threadIdx.x; i < KH_LHIST_BINS; i += nt) lh[i] = 0;
+    }
+    __device__ __forceinline__ void clear_stripes() {
+        for (u32 i = threadIdx.x; i < 16 * 64; i += nt) stripe[i] = 0;
+    }
+    __device__ void clear() {
+        clear_bins();
+        clear_stripes();
+        __syncthreads();
+    }
+    __device__ __forceinline__ void add(u32 c, unsigned long long* hist, u32 hist_len) {
+        if (c < 16u) atomicAdd(&stripe[c * 64 + (threadIdx.x & 63)], 1u);
+        else if (c < KH_LHIST_BINS) atomicAdd(&lh[c], 1u);
+        else atomicAdd(&hist[c < hist_len ? c : hist_len - 1], 1ull);
+    }
+    __device__ void flush(unsigned long long* hist, u32 hist_len) {
+        __syncthreads();
+        for (u32 c = threadIdx.x >> 6; c < 16; c += nt >> 6) {
+            u32 v = stripe[c * 64 + (threadIdx.x & 63)];
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+            if ((threadIdx.x & 63) == 0 && v) atomicAdd(&lh[c], v);
+        }
+        __syncthreads();
+        for (u32 i = threadIdx.x; i < KH_LHIST_BINS; i += nt) {
+            const u32 v = lh[i];
+            if (v) atomicAdd(&hist[i < hist_len ? i : hist_len - 1], (unsigned long long)v);
+        }
+    }
+};
+
+// ------------------------------------------------------------------------------------------
+// Wave-local slice gather.  Lane g of EVERY wave describes operand g of the slot (at most 64
+// operands; redundant loads, served by the caches): no LDS descriptors, no "wave 0 scans, everyone
+// waits", no chain of dependent LDS reads in front of the key loads.  The slices are concatenated
+// in operand order, soff = exclusive scan of their lengths; element i belongs to the last operand
+// whose slice starts at or before i.
+// ------------------------------------------------------------------------------------------
+// value of lane `src` (wave-uniform), via scalar reads
+__device__ __forceinline__ u32 read_lane(u32 v, u32 src) {
+    return (u32)__builtin_amdgcn_readlane((int)v, (int)src);
+}
+__device__ __forceinline__ u64 read_lane(u64 v, u32 src) {
+    return ((u64)read_lane((u32)(v >> 32), src) << 32) | read_lane((u32)v, src);
+}
+// value of lane g: through the scalar path when g is wave-uniform, by shuffle when it is per lane
+__device__ __forceinline__ u32 lane_value(u32 v, u32 g, bool uniform) { return uniform ? read_lane(v, g) : (u32)__shfl(v, g); }
+__device__ __forceinline__ u64 lane_value(u64 v, u32 g, bool uniform) { return uniform ? read_lane(v, g) : (u64)__shfl(v, g); }
+struct WaveGather {
+    u32 soff;   // first gathered index of this lane's operand; operands that do not exist start "after everything"
+    u32 lane;
+    __device__ __forceinline__ WaveGather(bool have, u32 incl, u32 len, u32 lane_)
+        : soff(have ? incl - len : 0xffffffffu), lane(lane_) {}
+    // This wave's 64 elements of a pass are [B, B + 64): nearly always inside ONE operand.  Returns the
+    // operand of element B + lane and replaces every v — what this lane holds about ITS operand, a
+    // 32- or 64-bit value each — by the same about the element's operand.  What is fetched is the
+    // caller's business; one branch serves all of it.
+    template <class... V> __device__ __forceinline__ u32 fetch(const u32 B, V&... v) const {
+        const u32 g_lo = (u32)__builtin_amdgcn_readfirstlane((int)__popcll(__ballot(soff <= B))) - 1u;
+        const u32 g_hi = (u32)__builtin_amdgcn_readfirstlane((int)__popcll(__ballot(soff <= B + (KH_WAVE - 1)))) - 1u;
+        u32 ga = g_lo;
+        if (g_lo == g_hi) {
+            ((v = lane_value(v, g_lo, true)), ...);
+        } else {   // operand boundaries inside the 64 elements: per-lane choice
+            for (u32 gg = g_lo + 1; gg <= g_hi; ++gg) ga += (read_lane(soff, gg) <= B + lane) ? 1u : 0u;
+            ((v = lane_value(v, ga, false)), ...);
+        }
+        return ga;
+    }
+};
+// n64 keys in the slot against what the kernel can hold: the count, or 0 with KH_ERR_CAPACITY raised
+// and the fullest slot seen recorded behind the error word (the host re-plans with finer slots)
+__device__ __forceinline__ u32 slot_total(u64 n64, u32 limit, u32* err) {
+    if (n64 <= (u64)limit) return (u32)n64;
+    if (threadIdx.x == 0) {
+        atomicOr(err, KH_ERR_CAPACITY);
+        atomicMax(err + 1, n64 > 0xffffffffull ? 0xffffffffu : (u32)n64);
+    }
+    return 0;
 }
 
 // PAY=false: n-ary union of sets whose counters are all 1, counters summed: the counter of a
@@ -1529,25 +1633,22 @@ __global__ __launch_bounds__(KH_SORT_THREADS, KH_SORT_WAVES_PER_SIMD) void k_set
     const u32 slot0 = jb.slot0, nslots = jb.nslots;
     extern __shared__ __attribute__((aligned(16))) u8 lds_raw[];
     const SortLds L{lds_raw, cap, W, PAY};
-    KmerKey<W>* s = reinterpret_cast<KmerKey<W>*>(lds_raw + L.keys_off());
-    u32* pay = reinterpret_cast<u32*>(lds_raw + L.pay_off());
-    u16* hstart = reinterpret_cast<u16*>(lds_raw + L.hstart_off());
-    u32* lhist = reinterpret_cast<u32*>(lds_raw + L.lhist_off());
-    u32* tab = reinterpret_cast<u32*>(lds_raw + L.tab_off());
-    u32* scratch = reinterpret_cast<u32*>(lds_raw + L.scratch_off());
-    u64* bcast = reinterpret_cast<u64*>(lds_raw + L.bcast_off());
+    KmerKey<W>* s = L.keys<W>();
+    u32* pay = L.pay();
+    u16* hstart = L.hstart();
+    u32* tab = L.ballots();
+    u32* scratch = L.scratch();
+    u64* bcast = L.bcast();
     constexpr int CAPC = PAY ? (W == 1 ? KH_SORT_CAP_PAY_W1 : KH_SORT_CAP_PAY_W2)
                              : (W == 1 ? KH_SORT_CAP_W1 : KH_SORT_CAP_W2);
     constexpr int E = (CAPC + KH_SORT_THREADS - 1) / KH_SORT_THREADS;
-    const u32 tid = threadIdx.x, nt = blockDim.x, lane = lane_id();
+    const u32 tid = threadIdx.x, lane = lane_id();
     const u64 per = (u64)nslots + 1;
     // index order: the slot is known at once, so the first wave's descriptor loads are in
     // flight while the block clears its bins; ticket order: they wait for the ticket
     const bool early = lb.dynamic == 0;
     u32 q = slot_idx;             // part number inside this chain; the slot itself is slot0 + q
-    // With at most 64 operands every wave describes the slot for ITSELF, lane g holding operand g
-    // (redundant loads, served by the caches): no LDS descriptors, no "wave 0 scans, everyone
-    // waits", no chain of dependent LDS reads in front of the key loads.
+    // with at most 64 operands every wave describes the slot for ITSELF (WaveGather)
     const bool wave_local = nsets <= (u32)KH_WAVE;
     u64 pre_b0 = 0, pre_b1 = 0;
     KhSetView pre_sv{nullptr, nullptr, 0, 0, 0};
@@ -1556,7 +1657,7 @@ __global__ __launch_bounds__(KH_SORT_THREADS, KH_SORT_WAVES_PER_SIMD) void k_set
         pre_b1 = bounds[lane * per + slot0 + q + 1];
         pre_sv = sets[lane];
     }
-    distribute_clear(reinterpret_cast<u32*>(hstart), tab + 128, scratch);
+    distribute_clear(L.bins(), L.dirty(), scratch);
     if (!early) {
         if (tid == 0) scratch[16] = atomicAdd(lb.ticket, 1u);
         __syncthreads();
@@ -1597,57 +1698,29 @@ __global__ __launch_bounds__(KH_SORT_THREADS, KH_SORT_WAVES_PER_SIMD) void k_set
         }
         out_keys += chain_in;
         if (out_counts) out_counts += chain_in;
-        if (n64 > (u64)CAPC || n64 > (u64)cap) {
-            if (tid == 0) {
-                atomicOr(lb.err, KH_ERR_CAPACITY);
-                atomicMax(lb.err + 1, n64 > 0xffffffffull ? 0xffffffffu : (u32)n64);   // fullest slot seen
-            }
-        } else {
-            n = (u32)n64;
-        }
-        // operands that do not exist start "after everything"
-        const u32 soff = have ? incl - len : 0xffffffffu;
+        n = slot_total(n64, min((u32)CAPC, cap), lb.err);
+        const WaveGather wg(have, incl, len, lane);
         const u64 sbeg = pre_b0, skey = reinterpret_cast<u64>(pre_sv.keys), scnt = reinterpret_cast<u64>(pre_sv.counts);
         const u32 suni = pre_sv.uniform;
-        auto lane64 = [](u64 v, u32 src) -> u64 {   // value of lane `src` (uniform), via scalar reads
-            const u32 lo = (u32)__builtin_amdgcn_readlane((int)(u32)v, (int)src);
-            const u32 hi = (u32)__builtin_amdgcn_readlane((int)(u32)(v >> 32), (int)src);
-            return ((u64)hi << 32) | lo;
-        };
         if (binary) {
-            b_soff1 = (u32)__builtin_amdgcn_readlane((int)soff, 1);
-            b_beg0 = lane64(sbeg, 0);
-            b_beg1 = lane64(sbeg, 1);
-            b_cnt0 = lane64(scnt, 0);
-            b_cnt1 = lane64(scnt, 1);
-            b_uni0 = (u32)__builtin_amdgcn_readlane((int)suni, 0);
-            b_uni1 = (u32)__builtin_amdgcn_readlane((int)suni, 1);
+            b_soff1 = read_lane(wg.soff, 1);
+            b_beg0 = read_lane(sbeg, 0);
+            b_beg1 = read_lane(sbeg, 1);
+            b_cnt0 = read_lane(scnt, 0);
+            b_cnt1 = read_lane(scnt, 1);
+            b_uni0 = read_lane(suni, 0);
+            b_uni1 = read_lane(suni, 1);
         }
 #pragma unroll
         for (int e = 0; e < E; ++e) {
             kreg[e] = key_zero<W>();
             preg[e] = 0;
-            // this wave's 64 elements of pass e are [B, B + 64): nearly always inside ONE operand
             const u32 B = (u32)e * KH_SORT_THREADS + (tid & ~(u32)(KH_WAVE - 1));
             const u32 i = B + lane;
-            const u32 g_lo = (u32)__builtin_amdgcn_readfirstlane((int)__popcll(__ballot(soff <= B))) - 1u;
-            const u32 g_hi = (u32)__builtin_amdgcn_readfirstlane((int)__popcll(__ballot(soff <= B + (KH_WAVE - 1)))) - 1u;
-            u32 ga = g_lo, my_soff;
-            u64 my_sbeg, my_skey, my_scnt = 0;
-            u32 my_suni = 0;
-            if (g_lo == g_hi) {
-                my_soff = (u32)__builtin_amdgcn_readlane((int)soff, (int)g_lo);
-                my_sbeg = lane64(sbeg, g_lo);
-                my_skey = lane64(skey, g_lo);
-                if (PAY) { my_scnt = lane64(scnt, g_lo); my_suni = (u32)__builtin_amdgcn_readlane((int)suni, (int)g_lo); }
-            } else {   // an operand boundary inside the 64 elements: per-lane choice
-                for (u32 gg = g_lo + 1; gg <= g_hi; ++gg)
-                    ga += ((u32)__builtin_amdgcn_readlane((int)soff, (int)gg) <= i) ? 1u : 0u;
-                my_soff = __shfl(soff, ga);
-                my_sbeg = __shfl(sbeg, ga);
-                my_skey = __shfl(skey, ga);
-                if (PAY) { my_scnt = __shfl(scnt, ga); my_suni = __shfl(suni, ga); }
-            }
+            u32 my_soff = wg.soff, my_suni = suni;
+            u64 my_sbeg = sbeg, my_skey = skey, my_scnt = scnt;
+            if (PAY) wg.fetch(B, my_soff, my_sbeg, my_skey, my_scnt, my_suni);
+            else wg.fetch(B, my_soff, my_sbeg, my_skey);
             if (i < n) {
                 const u64 idx = my_sbeg + (i - my_soff);
                 kreg[e] = reinterpret_cast<const KmerKey<W>*>(my_skey)[idx];
@@ -1719,14 +1792,7 @@ __global__ __launch_bounds__(KH_SORT_THREADS, KH_SORT_WAVES_PER_SIMD) void k_set
     // earlier chain can reach that far (every output key is one of the inputs)
     out_keys += bcast[2];
     if (out_counts) out_counts += bcast[2];
-    if (n64 > (u64)CAPC || n64 > (u64)cap) {
-        if (tid == 0) {
-            atomicOr(lb.err, KH_ERR_CAPACITY);
-            atomicMax(lb.err + 1, n64 > 0xffffffffull ? 0xffffffffu : (u32)n64);   // fullest slot seen
-        }
-    } else {
-        n = (u32)n64;
-    }
+    n = slot_total(n64, min((u32)CAPC, cap), lb.err);
     // gather straight into registers: element i of the concatenated slices belongs to the last
     // operand whose slice starts at or before i; all loads of a thread are independent
     u32 ga = 0;   // operand of this thread's current element: found once, then only advanced
@@ -1754,13 +1820,16 @@ __global__ __launch_bounds__(KH_SORT_THREADS, KH_SORT_WAVES_PER_SIMD) void k_set
     }
     }
     __syncthreads();   // the slice descriptors are no longer needed
-    for (u32 i = tid; i < KH_LHIST_BINS; i += nt) lhist[i] = 0;
+    // fused counter histogram: the lane-private copies take the sort's work-list region, free by
+    // the time the sort is over
+    static_assert(KH_WORKLIST >= 16 * 64, "lane-private histogram needs the work-list region");
+    BlockHist bh{L.lhist(), L.worklist(), blockDim.x};
+    bh.clear_bins();
 #ifdef KH_STAMPS
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #endif
     KH_STAMP(q, 1);
-    distribute_sort<W, PAY, E>(kreg, preg, n, s, pay, reinterpret_cast<u32*>(hstart), tab + 128,
-                               tab + 128 + KH_FINE_BINS / 32, scratch, k, nslots, q);
+    distribute_sort<W, PAY, E>(kreg, preg, n, s, pay, L.bins(), L.dirty(), L.worklist(), scratch, k, nslots, q);
 
     // counter of run s[h0..h1) under the requested operation (0 = key dropped)
     auto eval = [&](u32 h0, u32 h1) -> u32 {
@@ -1797,44 +1866,121 @@ __global__ __launch_bounds__(KH_SORT_THREADS, KH_SORT_WAVES_PER_SIMD) void k_set
         if (c <= 0) return 0u;
         return c > (long long)cs ? cs : (u32)c;
     };
-    // Fused histogram: almost every counter of a union is tiny (1 for the across-group sum,
-    // 1..G within a group), so a plain LDS histogram would serialise a whole wave on one
-    // address.  Counters below 16 go to 64 lane-private copies (the sort's work-list region is
-    // free by now) that are folded into lhist afterwards.
-    u32* stripe = tab + 128 + KH_FINE_BINS / 32;            // [16][64]
-    static_assert(KH_WORKLIST >= 16 * 64, "lane-private histogram needs the work-list region");
     if (hist) {
         __syncthreads();                                    // the sort is done with its work list
-        for (u32 i = tid; i < 16 * 64; i += nt) stripe[i] = 0;
+        bh.clear_stripes();
     }
     auto sink = [&](u64 o, const KmerKey<W>& key, u32 c) {
         out_keys[o] = key;
         if (out_counts) out_counts[o] = c;
-        if (hist) {
-            if (c < 16u) atomicAdd(&stripe[c * 64 + lane], 1u);
-            else if (c < KH_LHIST_BINS) atomicAdd(&lhist[c], 1u);
-            else atomicAdd(&hist[c < hist_len ? c : hist_len - 1], 1ull);
-        }
+        if (hist) bh.add(c, hist, hist_len);
     };
     const u64 chain_out = rle_emit<W, E>(s, n, hstart, tab, eval, sink, lb, q, scratch,
                                          op == KH_OP_UNION && mode != KH_OC_DIFF);
     if (q == nranges - 1 && tid == 0)   // the chain is complete: its outputs join the operation's total
         atomicAdd(reinterpret_cast<unsigned long long*>(jb.ctl + 4), (unsigned long long)chain_out);
-    if (hist) {
-        __syncthreads();
-        for (u32 c = tid >> 6; c < 16; c += nt >> 6) {      // one wave folds two counters
-            u32 v = stripe[c * 64 + lane];
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-            if (lane == 0 && v) atomicAdd(&lhist[c], v);
+    if (hist) bh.flush(hist, hist_len);
+}
+
+// ---- pieces shared by the tagged unions (k_union_tagged, k_union_hash) ----------------------
+// Slice of operand `lane` in slot (bucket b, sub-range f) of the bucket grid: first key and length.
+// A corrupt index (running backwards) reads as "too full", never as a wrap, and raises KH_ERR_ORDER.
+struct TagSlice {
+    u64 sbeg;
+    u32 len;
+};
+__device__ __forceinline__ TagSlice tag_slice(const KhTagJob& jb, u32 lane, u32 b, u32 f) {
+    TagSlice sl{0, 0};
+    if (lane < jb.nops) {
+        const u32 gb = lane * jb.nb + b;
+        const u16* __restrict__ o = jb.off + (u64)gb * (jb.S + 1) + f;
+        const u32 o0 = o[0], o1 = o[1];
+        sl.sbeg = jb.bstart[gb] + o0;
+        sl.len = o1 >= o0 ? o1 - o0 : 0xffffffu;
+        if (o1 < o0) atomicOr(jb.ctl, KH_ERR_ORDER);
+    }
+    return sl;
+}
+// Fine bin of a key inside sub-range f of its bucket: the slot is fine bins [fb0, fb0 + width) of
+// the bucket (kh_first_bin), i.e. positions [fb0 << 19, ...) of the bucket's 32-bit position scale;
+// binmul stretches the widest slot over the KH_FINE_BINS bins.  A key from outside the slot
+// (corrupt index) lands in the last bin instead of outside the table.
+struct SlotBin {
+    u32 rel0, binmul, nbv;
+    int k;
+    __device__ __forceinline__ SlotBin(const KhTagJob& jb, u32 f, int k_)
+        : rel0(kh_first_bin(f, jb.S) << (32 - KH_FINE_BITS)), binmul(jb.binmul), nbv(jb.nbv), k(k_) {}
+    template <int W> __device__ __forceinline__ u32 operator()(const KmerKey<W>& key) const {
+        const u32 frac = (u32)((u64)kh_top32(key, k) * (u64)nbv);
+        const u32 fb = (u32)(((u64)(frac - rel0) * (u64)binmul) >> 32);
+        return fb < (u32)KH_FINE_BINS ? fb : (u32)KH_FINE_BINS - 1u;
+    }
+};
+// Read-out of genome masks into the compact LDS histogram hstripe[nbins][8] (8 copies per bin,
+// copy = lane & 7): the per-group bins of step_4 at ginfo's bin0, the across-group bins at abase.
+// ginfo[g] = first genome | genomes << 8 | bin0 << 16 of the group that genome g belongs to.
+// (The super-k-mer kernels have a read-out of their own, SkmReadout: DESIGN.md §3.)
+struct TagReadout {
+    u32* ginfo;     // [KH_TAG_MAX_OPS]
+    u32* hstripe;   // [nbins][8]
+    u32 abase, cs, lane;
+    u32 ones;       // this thread's keys that sit in exactly one group
+    __device__ __forceinline__ TagReadout(u32* ginfo_, u32* hstripe_, const KhTagJob& jb, u32 cs_)
+        : ginfo(ginfo_), hstripe(hstripe_), abase(jb.abase), cs(cs_), lane(lane_id()), ones(0) {}
+    __device__ __forceinline__ void init(const KhTagJob& jb, const u32 nt) {   // a barrier must follow
+        for (u32 i = threadIdx.x; i < (u32)KH_TAG_MAX_OPS; i += nt) ginfo[i] = jb.ginfo[i];
+        for (u32 i = threadIdx.x; i < jb.nbins * 8u; i += nt) hstripe[i] = 0;
+    }
+    __device__ __forceinline__ void bump(u32 bin) { atomicAdd(&hstripe[bin * 8u + (lane & 7u)], 1u); }
+    __device__ __forceinline__ u32 first_group(u64 mask) const { return ginfo[__ffsll((unsigned long long)mask) - 1]; }
+    // a genome mask -> per-group counts (step_4 bins) + number of groups (returned); g = first_group(mask)
+    __device__ __forceinline__ u32 eval_mask(u64 mask, u32 g) {
+        u32 ng = 0;
+        while (true) {
+            const u32 g0 = g & 0xffu, gn = (g >> 8) & 0xffu, bin0 = g >> 16;
+            const u64 gm = (gn >= 64u ? ~0ull : ((1ull << gn) - 1ull)) << g0;
+            u32 c = (u32)__popcll(mask & gm);
+            c = c < cs ? c : cs;
+            bump(bin0 + c);
+            mask &= ~gm;
+            ++ng;
+            if (!mask) break;
+            g = first_group(mask);
         }
-        __syncthreads();
-        for (u32 i = tid; i < KH_LHIST_BINS; i += nt) {
-            const u32 v = lhist[i];
-            if (v) atomicAdd(&hist[i < hist_len ? i : hist_len - 1], (unsigned long long)v);
+        return ng < cs ? ng : cs;
+    }
+    // one key seen in ng groups; the across-group bin "1" would otherwise take one LDS atomic per
+    // key: it is counted in a register and added once per wave (finish_ones)
+    __device__ __forceinline__ void add_across(u32 ng) {
+        if (ng == 1u) ++ones;
+        else bump(abase + ng);
+    }
+    template <int E> __device__ __forceinline__ void add_masks(const u64 (&mk)[E]) {   // 0 = no key
+        u32 gi[E];   // first group of every mask (nearly always the only one): table reads issued together
+#pragma unroll
+        for (int e = 0; e < E; ++e) gi[e] = ginfo[mk[e] ? __ffsll((unsigned long long)mk[e]) - 1 : 0];
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+            if (!mk[e]) continue;
+            add_across(eval_mask(mk[e], gi[e]));
         }
     }
-}
+    __device__ __forceinline__ void finish_ones() {   // every lane of the wave must call it
+        const u32 sum = wave_scan_add(ones);
+        if (lane == KH_WAVE - 1 && sum) atomicAdd(&hstripe[(abase + 1u) * 8u], sum);
+    }
+    // the block's histogram joins replica blockIdx.x % reps of the job's
+    __device__ __forceinline__ void flush(const KhTagJob& jb, const u32 nt) {
+        __syncthreads();
+        unsigned long long* __restrict__ rep = jb.hist + (u64)(blockIdx.x % jb.reps) * jb.nbins;
+        for (u32 i = threadIdx.x; i < jb.nbins; i += nt) {
+            u32 v = 0;
+#pragma unroll
+            for (u32 j = 0; j < 8; ++j) v += hstripe[i * 8u + j];
+            if (v) atomicAdd(&rep[i], (unsigned long long)v);
+        }
+    }
+};
 
 // ------------------------------------------------------------------------------------------
 // Tagged n-ary union over gridded genome sets (KhTagJob in kh_launch.h): steps 3+4 and 7+8 of
@@ -1849,20 +1995,19 @@ __global__ __launch_bounds__(KH_SORT_THREADS, KH_SORT_WAVES_PER_SIMD) void k_uni
     const KhTagJob jb, u32 cap, int k, u32 cs) {
     extern __shared__ __attribute__((aligned(16))) u8 lds_raw[];
     const SortLds L{lds_raw, cap, W, true};
-    KmerKey<W>* s = reinterpret_cast<KmerKey<W>*>(lds_raw + L.keys_off());
-    u32* pay = reinterpret_cast<u32*>(lds_raw + L.pay_off());
-    u16* hstart = reinterpret_cast<u16*>(lds_raw + L.hstart_off());
+    KmerKey<W>* s = L.keys<W>();
+    u32* pay = L.pay();
+    u16* hstart = L.hstart();
+    u32* tab = L.ballots();
+    u32* scratch = L.scratch();
     // Carve (kh_tag_lds_bytes): the sort's carve, ginfo[64] in its lhist region, then the compact
-    // histogram hstripe[nbins][8] (8 copies per bin, copy = lane & 7).
-    u32* ginfo = reinterpret_cast<u32*>(lds_raw + L.lhist_off());
-    u32* tab = reinterpret_cast<u32*>(lds_raw + L.tab_off());
-    u32* scratch = reinterpret_cast<u32*>(lds_raw + L.scratch_off());
-    u32* hstripe = reinterpret_cast<u32*>(lds_raw + L.total());   // [nbins][8]
+    // histogram hstripe[nbins][8] behind it.
+    TagReadout ro(L.lhist(), L.at<u32>(L.total()), jb, cs);
     constexpr int CAPC = W == 1 ? KH_SORT_CAP_PAY_W1 : KH_SORT_CAP_PAY_W2;
     constexpr int E = (CAPC + KH_SORT_THREADS - 1) / KH_SORT_THREADS;
     constexpr u32 NT = KH_SORT_THREADS;
     const u32 tid = threadIdx.x, lane = lane_id();
-    const u32 nb = jb.nb, S = jb.S, nops = jb.nops, nbins = jb.nbins;
+    const u32 nb = jb.nb, S = jb.S;
     const u32 nslots = nb * S;
     const KmerKey<W>* __restrict__ keys = reinterpret_cast<const KmerKey<W>*>(jb.keys);
     constexpr bool emit = EMIT;
@@ -1874,8 +2019,7 @@ __global__ __launch_bounds__(KH_SORT_THREADS, KH_SORT_WAVES_PER_SIMD) void k_uni
     lb.err = jb.ctl;
     lb.dynamic = 0;
 
-    for (u32 i = tid; i < (u32)KH_TAG_MAX_OPS; i += NT) ginfo[i] = jb.ginfo[i];
-    for (u32 i = tid; i < nbins * 8u; i += NT) hstripe[i] = 0;
+    ro.init(jb, NT);
 
     // One slot per workgroup.  (A workgroup looping over slots kept the histogram in LDS longer, but
     // the loop invariants hipcc hoisted out of it were spilled, and every scratch reload is an
@@ -1889,35 +2033,11 @@ __global__ __launch_bounds__(KH_SORT_THREADS, KH_SORT_WAVES_PER_SIMD) void k_uni
         const u32 b = r / S, f = r - b * S;
         KH_STAMP(r, 0);
         // ---- operand slices of this slot: lane g of every wave describes operand g
-        const bool have = lane < nops;
-        u64 sbeg = 0;
-        u32 len = 0;
-        if (have) {
-            const u32 gb = lane * nb + b;
-            const u16* __restrict__ o = jb.off + (u64)gb * (S + 1) + f;
-            const u32 o0 = o[0], o1 = o[1];
-            sbeg = jb.bstart[gb] + o0;
-            len = o1 >= o0 ? o1 - o0 : 0xffffffu;   // a corrupt index reads as "too full", never as a wrap
-            if (o1 < o0) atomicOr(jb.ctl, KH_ERR_ORDER);
-        }
-        distribute_clear(reinterpret_cast<u32*>(hstart), tab + 128, scratch);
-        const u32 incl = wave_scan_add(len);
-        const u32 n64 = (u32)__builtin_amdgcn_readlane((int)incl, KH_WAVE - 1);
-        u32 n = 0;
-        if (n64 > (u32)CAPC || n64 > cap) {
-            if (tid == 0) {
-                atomicOr(lb.err, KH_ERR_CAPACITY);
-                atomicMax(lb.err + 1, n64);
-            }
-        } else {
-            n = n64;
-        }
-        const u32 soff = have ? incl - len : 0xffffffffu;
-        auto lane64 = [](u64 v, u32 src) -> u64 {
-            const u32 lo = (u32)__builtin_amdgcn_readlane((int)(u32)v, (int)src);
-            const u32 hi = (u32)__builtin_amdgcn_readlane((int)(u32)(v >> 32), (int)src);
-            return ((u64)hi << 32) | lo;
-        };
+        const TagSlice sl = tag_slice(jb, lane, b, f);
+        distribute_clear(L.bins(), L.dirty(), scratch);
+        const u32 incl = wave_scan_add(sl.len);
+        const u32 n = slot_total(read_lane(incl, KH_WAVE - 1), min((u32)CAPC, cap), lb.err);
+        const WaveGather wg(lane < jb.nops, incl, sl.len, lane);
         KmerKey<W> kreg[E];
         u32 preg[E];
 #pragma unroll
@@ -1927,19 +2047,9 @@ __global__ __launch_bounds__(KH_SORT_THREADS, KH_SORT_WAVES_PER_SIMD) void k_uni
             const u32 B = (u32)e * NT + (tid & ~(u32)(KH_WAVE - 1));
             const u32 i = B + lane;
             if (B >= n) continue;   // wave-uniform
-            const u32 g_lo = (u32)__builtin_amdgcn_readfirstlane((int)__popcll(__ballot(soff <= B))) - 1u;
-            const u32 g_hi = (u32)__builtin_amdgcn_readfirstlane((int)__popcll(__ballot(soff <= B + (KH_WAVE - 1)))) - 1u;
-            u32 ga = g_lo, my_soff;
-            u64 my_sbeg;
-            if (g_lo == g_hi) {
-                my_soff = (u32)__builtin_amdgcn_readlane((int)soff, (int)g_lo);
-                my_sbeg = lane64(sbeg, g_lo);
-            } else {   // operand boundaries inside the 64 elements: per-lane choice
-                for (u32 gg = g_lo + 1; gg <= g_hi; ++gg)
-                    ga += ((u32)__builtin_amdgcn_readlane((int)soff, (int)gg) <= i) ? 1u : 0u;
-                my_soff = __shfl(soff, ga);
-                my_sbeg = __shfl(sbeg, ga);
-            }
+            u32 my_soff = wg.soff;
+            u64 my_sbeg = sl.sbeg;
+            const u32 ga = wg.fetch(B, my_soff, my_sbeg);
             if (i < n) {
                 kreg[e] = keys[my_sbeg + (i - my_soff)];
                 preg[e] = ga;
@@ -1950,33 +2060,7 @@ __global__ __launch_bounds__(KH_SORT_THREADS, KH_SORT_WAVES_PER_SIMD) void k_uni
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #endif
         KH_STAMP(r, 1);
-        // fine bin of a key inside this slot: the slot is fine bins [fb0, fb0 + width) of bucket b
-        // (kh_first_bin), i.e. positions [fb0 << 19, ...) of the bucket's 32-bit position scale;
-        // binmul stretches the widest slot over the KH_FINE_BINS bins.  A key from outside the slot
-        // (corrupt index) lands in the last bin instead of outside the table.
-        const u32 rel0 = kh_first_bin(f, S) << (32 - KH_FINE_BITS);
-        const u32 binmul = jb.binmul, nbv = jb.nbv;
-        auto binfn = [=](const KmerKey<W>& key) -> u32 {
-            const u32 frac = (u32)((u64)kh_top32(key, k) * (u64)nbv);
-            const u32 fb = (u32)(((u64)(frac - rel0) * (u64)binmul) >> 32);
-            return fb < (u32)KH_FINE_BINS ? fb : (u32)KH_FINE_BINS - 1u;
-        };
-        // a genome mask -> per-group counts (step_4 bins) + number of groups (returned)
-        auto eval_mask = [&](u64 mask, u32 g) -> u32 {
-            u32 ng = 0;
-            while (true) {
-                const u32 g0 = g & 0xffu, gn = (g >> 8) & 0xffu, bin0 = g >> 16;
-                const u64 gm = (gn >= 64u ? ~0ull : ((1ull << gn) - 1ull)) << g0;
-                u32 c = (u32)__popcll(mask & gm);
-                c = c < cs ? c : cs;
-                atomicAdd(&hstripe[(bin0 + c) * 8u + (lane & 7u)], 1u);
-                mask &= ~gm;
-                ++ng;
-                if (!mask) break;
-                g = ginfo[__ffsll((unsigned long long)mask) - 1];
-            }
-            return ng < cs ? ng : cs;
-        };
+        const SlotBin binfn(jb, f, k);
         if constexpr (!emit) {
             // (one-word keys normally take the hash-set form, k_union_hash below; this is the form for
             // two-word keys, which have no 128-bit compare-and-swap to meet in a table with)
@@ -1985,8 +2069,7 @@ __global__ __launch_bounds__(KH_SORT_THREADS, KH_SORT_WAVES_PER_SIMD) void k_uni
             // that copy's 64-bit mask.  The masks overlay the payload + bin-table carve (both free
             // once the keys are placed); tags stay in registers.
             u32 fr[E], at[E], vmask, bmax;
-            distribute_place<W, false, E>(kreg, preg, n, s, nullptr, reinterpret_cast<u32*>(hstart), scratch, binfn,
-                                          r, fr, at, vmask, bmax);
+            distribute_place<W, false, E>(kreg, preg, n, s, nullptr, L.bins(), scratch, binfn, r, fr, at, vmask, bmax);
             unsigned long long* rmask = reinterpret_cast<unsigned long long*>(pay);
             u32 lead[E];
             find_leaders<W, E>(kreg, s, fr, at, vmask, lead);
@@ -2005,49 +2088,29 @@ __global__ __launch_bounds__(KH_SORT_THREADS, KH_SORT_WAVES_PER_SIMD) void k_uni
             u64 mk[E];
 #pragma unroll
             for (int e = 0; e < E; ++e) mk[e] = ((vmask & (1u << e)) && lead[e] == at[e]) ? rmask[at[e]] : 0ull;
-            u32 gi[E];   // first group of every mask (nearly always the only one): table reads issued together
-#pragma unroll
-            for (int e = 0; e < E; ++e) gi[e] = ginfo[mk[e] ? __ffsll((unsigned long long)mk[e]) - 1 : 0];
-            u32 ones = 0;   // keys that sit in exactly one group
-#pragma unroll
-            for (int e = 0; e < E; ++e) {
-                if (!mk[e]) continue;
-                const u32 ng = eval_mask(mk[e], gi[e]);
-                if (ng == 1u) ++ones;
-                else atomicAdd(&hstripe[(jb.abase + ng) * 8u + (lane & 7u)], 1u);
-            }
-            // the across-group bin "1" would otherwise take one LDS atomic per key: per-wave sum
-            ones = wave_scan_add(ones);
-            if (lane == KH_WAVE - 1 && ones) atomicAdd(&hstripe[(jb.abase + 1u) * 8u], ones);
+            ro.add_masks(mk);
+            ro.finish_ones();
             __syncthreads();
             KH_STAMP(r, 8);
         } else {
             // the across-group set is written (multi-GPU exchange): full sort, ordered output
-            distribute_sort_bf<W, true, E>(kreg, preg, n, s, pay, reinterpret_cast<u32*>(hstart), tab + 128,
-                                           tab + 128 + KH_FINE_BINS / 32, scratch, binfn, r);
+            distribute_sort_bf<W, true, E>(kreg, preg, n, s, pay, L.bins(), L.dirty(), L.worklist(), scratch, binfn, r);
             auto eval = [&](u32 h0, u32 h1) -> u32 {
                 u64 mask = 0;
                 for (u32 t = h0; t < h1; ++t) mask |= 1ull << (pay[t] & 63u);
-                return eval_mask(mask, ginfo[__ffsll((unsigned long long)mask) - 1]);
+                return ro.eval_mask(mask, ro.first_group(mask));
             };
             auto sink = [&](u64 o, const KmerKey<W>& key, u32 c) {
                 out_keys[o] = key;
                 out_counts[o] = c;
-                atomicAdd(&hstripe[(jb.abase + c) * 8u + (lane & 7u)], 1u);
+                ro.bump(ro.abase + c);
             };
             const u64 chain_out = rle_emit<W, E>(s, n, hstart, tab, eval, sink, lb, r, scratch, true);
             if (r == nslots - 1 && tid == 0) *jb.out_n = chain_out;
             __syncthreads();
         }
     }
-    __syncthreads();
-    unsigned long long* __restrict__ rep = jb.hist + (u64)(blockIdx.x % jb.reps) * nbins;
-    for (u32 i = tid; i < nbins; i += NT) {
-        u32 v = 0;
-#pragma unroll
-        for (u32 j = 0; j < 8; ++j) v += hstripe[i * 8u + j];
-        if (v) atomicAdd(&rep[i], (unsigned long long)v);
-    }
+    ro.flush(jb, NT);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2086,28 +2149,17 @@ __global__ __launch_bounds__(NT, (T == 2048 ? 4 : 2) * (NT / 64) / 4) void k_uni
     u32* scratch = ginfo + 64;                                                               // [32]
     unsigned long long* special = reinterpret_cast<unsigned long long*>(scratch + 24);       // mask of the key ~0
     u32* hstripe = scratch + 32;                                                             // [nbins][8]
-    const u32 nbins = jb.nbins;
-    Ent* ovf = reinterpret_cast<Ent*>(hstripe + ((nbins * 8u + 3u) & ~3u));                  // [T2]
+    Ent* ovf = reinterpret_cast<Ent*>(hstripe + ((jb.nbins * 8u + 3u) & ~3u));               // [T2]
+    TagReadout ro(ginfo, hstripe, jb, cs);
     const u32 tid = threadIdx.x, lane = lane_id();
-    const u32 nb = jb.nb, S = jb.S, nops = jb.nops;
+    const u32 S = jb.S;
     const KmerKey<1>* __restrict__ keys = reinterpret_cast<const KmerKey<1>*>(jb.keys);
     const u32 r = blockIdx.x;
     const u32 b = r / S, f = r - b * S;
     // ---- operand slices of this slot: lane g of every wave describes operand g
-    const bool have = lane < nops;
-    u64 sbeg = 0;
-    u32 len = 0;
-    if (have) {
-        const u32 gb = lane * nb + b;
-        const u16* __restrict__ o = jb.off + (u64)gb * (S + 1) + f;
-        const u32 o0 = o[0], o1 = o[1];
-        sbeg = jb.bstart[gb] + o0;
-        len = o1 >= o0 ? o1 - o0 : 0xffffffu;   // a corrupt index reads as "too full", never as a wrap
-        if (o1 < o0) atomicOr(jb.ctl, KH_ERR_ORDER);
-    }
+    const TagSlice sl = tag_slice(jb, lane, b, f);
     // tables and tables' neighbours, written while the index loads are in flight
-    for (u32 i = tid; i < (u32)KH_TAG_MAX_OPS; i += NT) ginfo[i] = jb.ginfo[i];
-    for (u32 i = tid; i < nbins * 8u; i += NT) hstripe[i] = 0;
+    ro.init(jb, NT);
     {
         uint4* t4 = reinterpret_cast<uint4*>(lds_raw);
 #pragma unroll
@@ -2116,18 +2168,9 @@ __global__ __launch_bounds__(NT, (T == 2048 ? 4 : 2) * (NT / 64) / 4) void k_uni
         for (u32 i = tid; i < T2; i += NT) o4[i] = make_uint4(0xffffffffu, 0xffffffffu, 0u, 0u);
         if (tid == 0) *special = 0ull;
     }
-    const u32 incl = wave_scan_add(len);
-    const u32 n64 = (u32)__builtin_amdgcn_readlane((int)incl, KH_WAVE - 1);
-    u32 n = 0;
-    if (n64 > T) {
-        if (tid == 0) {
-            atomicOr(jb.ctl, KH_ERR_CAPACITY);
-            atomicMax(jb.ctl + 1, n64);
-        }
-    } else {
-        n = n64;
-    }
-    const u32 soff = have ? incl - len : 0xffffffffu;
+    const u32 incl = wave_scan_add(sl.len);
+    const u32 n = slot_total(read_lane(incl, KH_WAVE - 1), T, jb.ctl);
+    const WaveGather wg(lane < jb.nops, incl, sl.len, lane);
     u64 kreg[E];
     u32 tagp[(E + 3) / 4];
 #pragma unroll
@@ -2138,21 +2181,9 @@ __global__ __launch_bounds__(NT, (T == 2048 ? 4 : 2) * (NT / 64) / 4) void k_uni
         const u32 B = (u32)e * NT + (tid & ~(u32)(KH_WAVE - 1));
         const u32 i = B + lane;
         if (B >= n) continue;   // wave-uniform
-        const u32 g_lo = (u32)__builtin_amdgcn_readfirstlane((int)__popcll(__ballot(soff <= B))) - 1u;
-        const u32 g_hi = (u32)__builtin_amdgcn_readfirstlane((int)__popcll(__ballot(soff <= B + (KH_WAVE - 1)))) - 1u;
-        u32 ga = g_lo, my_soff;
-        u64 my_sbeg;
-        if (g_lo == g_hi) {
-            my_soff = (u32)__builtin_amdgcn_readlane((int)soff, (int)g_lo);
-            const u32 lo = (u32)__builtin_amdgcn_readlane((int)(u32)sbeg, (int)g_lo);
-            const u32 hi = (u32)__builtin_amdgcn_readlane((int)(u32)(sbeg >> 32), (int)g_lo);
-            my_sbeg = ((u64)hi << 32) | lo;
-        } else {   // operand boundaries inside the 64 elements: per-lane choice
-            for (u32 gg = g_lo + 1; gg <= g_hi; ++gg)
-                ga += ((u32)__builtin_amdgcn_readlane((int)soff, (int)gg) <= i) ? 1u : 0u;
-            my_soff = __shfl(soff, ga);
-            my_sbeg = __shfl(sbeg, ga);
-        }
+        u32 my_soff = wg.soff;
+        u64 my_sbeg = sl.sbeg;
+        const u32 ga = wg.fetch(B, my_soff, my_sbeg);
         if (i < n) {
             kreg[e] = keys[my_sbeg + (i - my_soff)].lo;
             tagp[e >> 2] |= ga << (8 * (e & 3));
@@ -2160,14 +2191,8 @@ __global__ __launch_bounds__(NT, (T == 2048 ? 4 : 2) * (NT / 64) / 4) void k_uni
     }
     __syncthreads();   // tables initialised
     auto tag = [&](int e) -> u32 { return (tagp[e >> 2] >> (8 * (e & 3))) & 63u; };
-    const u32 rel0 = kh_first_bin(f, S) << (32 - KH_FINE_BITS);
-    const u32 binmul = jb.binmul, nbv = jb.nbv;
-    auto home = [=](u64 key) -> u32 {
-        const u32 frac = (u32)((u64)kh_top32(KmerKey<1>{key}, k) * (u64)nbv);
-        u32 fb = (u32)(((u64)(frac - rel0) * (u64)binmul) >> 32);
-        fb = fb < (u32)KH_FINE_BINS ? fb : (u32)KH_FINE_BINS - 1u;
-        return fb >> (KH_FINE_BITS - HBITS);
-    };
+    const SlotBin binfn(jb, f, k);
+    auto home = [=](u64 key) -> u32 { return binfn(KmerKey<1>{key}) >> (KH_FINE_BITS - HBITS); };
     u32 slot[E], act = 0;
 #pragma unroll
     for (int e = 0; e < E; ++e) {
@@ -2208,103 +2233,34 @@ __global__ __launch_bounds__(NT, (T == 2048 ? 4 : 2) * (NT / 64) / 4) void k_uni
 #undef KH_PROBE_ROUNDS
     __syncthreads();
     // ---- every occupied entry is one distinct key of the slot: genome mask -> histogram bins
-    auto eval_mask = [&](u64 mask, u32 g) -> u32 {
-        u32 ng = 0;
-        while (true) {
-            const u32 g0 = g & 0xffu, gn = (g >> 8) & 0xffu, bin0 = g >> 16;
-            const u64 gm = (gn >= 64u ? ~0ull : ((1ull << gn) - 1ull)) << g0;
-            u32 c = (u32)__popcll(mask & gm);
-            c = c < cs ? c : cs;
-            atomicAdd(&hstripe[(bin0 + c) * 8u + (lane & 7u)], 1u);
-            mask &= ~gm;
-            ++ng;
-            if (!mask) break;
-            g = ginfo[__ffsll((unsigned long long)mask) - 1];
-        }
-        return ng < cs ? ng : cs;
-    };
     u64 mk[E];
 #pragma unroll
     for (int e = 0; e < E; ++e) {
         const Ent en = tbl[(u32)e * NT + tid];
         mk[e] = en.key != EMPTY ? en.mask : 0ull;
     }
-    u32 gi[E];
-#pragma unroll
-    for (int e = 0; e < E; ++e) gi[e] = ginfo[mk[e] ? __ffsll((unsigned long long)mk[e]) - 1 : 0];
-    u32 ones = 0;   // keys that sit in exactly one group
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-        if (!mk[e]) continue;
-        const u32 ng = eval_mask(mk[e], gi[e]);
-        if (ng == 1u) ++ones;
-        else atomicAdd(&hstripe[(jb.abase + ng) * 8u + (lane & 7u)], 1u);
-    }
+    ro.add_masks(mk);
     for (u32 i = tid; i < T2; i += NT) {   // keys that moved to the second table (a few per slot)
         const Ent en = ovf[i];
-        if (en.key != EMPTY) {
-            const u32 ng = eval_mask(en.mask, ginfo[__ffsll((unsigned long long)en.mask) - 1]);
-            if (ng == 1u) ++ones;
-            else atomicAdd(&hstripe[(jb.abase + ng) * 8u + (lane & 7u)], 1u);
-        }
+        if (en.key != EMPTY) ro.add_across(ro.eval_mask(en.mask, ro.first_group(en.mask)));
     }
     if (tid == 0 && *special) {   // the one key that cannot live in the tables (all bits set, k = 32 only)
         const u64 m = *special;
-        const u32 ng = eval_mask(m, ginfo[__ffsll((unsigned long long)m) - 1]);
-        if (ng == 1u) ++ones;
-        else atomicAdd(&hstripe[(jb.abase + ng) * 8u], 1u);
+        ro.add_across(ro.eval_mask(m, ro.first_group(m)));
     }
-    ones = wave_scan_add(ones);
-    if (lane == KH_WAVE - 1 && ones) atomicAdd(&hstripe[(jb.abase + 1u) * 8u], ones);
-    __syncthreads();
-    unsigned long long* __restrict__ rep = jb.hist + (u64)(blockIdx.x % jb.reps) * nbins;
-    for (u32 i = tid; i < nbins; i += NT) {
-        u32 v = 0;
-#pragma unroll
-        for (u32 j = 0; j < 8; ++j) v += hstripe[i * 8u + j];
-        if (v) atomicAdd(&rep[i], (unsigned long long)v);
-    }
+    ro.finish_ones();
+    ro.flush(jb, NT);
 }
 
 // ------------------------------------------------------------------------------------------
 // small utility kernels
 // ------------------------------------------------------------------------------------------
-// Block-private histogram whose low bins (where nearly all counters of a k-mer database fall)
-// are kept once per lane, so that a wave does not serialise on one LDS address.
-struct BlockHist {
-    u32* lh;       // [KH_LHIST_BINS]
-    u32* stripe;   // [16][64]
-    __device__ void clear() {
-        for (u32 i = threadIdx.x; i < KH_LHIST_BINS; i += blockDim.x) lh[i] = 0;
-        for (u32 i = threadIdx.x; i < 16 * 64; i += blockDim.x) stripe[i] = 0;
-        __syncthreads();
-    }
-    __device__ __forceinline__ void add(u32 c, unsigned long long* hist, u32 hist_len) {
-        if (c < 16u) atomicAdd(&stripe[c * 64 + (threadIdx.x & 63)], 1u);
-        else if (c < KH_LHIST_BINS) atomicAdd(&lh[c], 1u);
-        else atomicAdd(&hist[c < hist_len ? c : hist_len - 1], 1ull);
-    }
-    __device__ void flush(unsigned long long* hist, u32 hist_len) {
-        __syncthreads();
-        for (u32 i = threadIdx.x; i < 16; i += blockDim.x) {
-            u32 v = 0;
-            for (u32 l = 0; l < 64; ++l) v += stripe[i * 64 + ((l + i) & 63)];
-            lh[i] += v;
-        }
-        __syncthreads();
-        for (u32 i = threadIdx.x; i < KH_LHIST_BINS; i += blockDim.x) {
-            const u32 v = lh[i];
-            if (v) atomicAdd(&hist[i < hist_len ? i : hist_len - 1], (unsigned long long)v);
-        }
-    }
-};
-
 __global__ __launch_bounds__(256) void k_histogram(const u32* __restrict__ counts, u64 n,
                                                   unsigned long long* __restrict__ hist,
                                                   u32 hist_len) {
     __shared__ u32 lh[KH_LHIST_BINS];
     __shared__ u32 stripe[16 * 64];
-    BlockHist bh{lh, stripe};
+    BlockHist bh{lh, stripe, blockDim.x};
     bh.clear();
     const u64 stride = (u64)gridDim.x * blockDim.x;
     for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) bh.add(counts[i], hist, hist_len);
@@ -2347,7 +2303,7 @@ __global__ __launch_bounds__(256) void k_table_hist(const C* __restrict__ table,
                                                    unsigned long long* __restrict__ hist, u32 hist_len) {
     __shared__ u32 lh[KH_LHIST_BINS];
     __shared__ u32 stripe[16 * 64];
-    BlockHist bh{lh, stripe};
+    BlockHist bh{lh, stripe, blockDim.x};
     bh.clear();
     constexpr u32 PER = 16 / sizeof(C);
     const u64 nvec = (hi - lo) / PER;
@@ -2422,6 +2378,21 @@ static u32 grid_for(u64 n, u32 block, u32 cap_blocks = 2048) {
     return (u32)g;
 }
 
+// The run-time key width W (1 or 2 words) — and a run-time switch, where a kernel has one — as
+// compile-time constants: f(std::integral_constant<int, W>{}[, std::bool_constant<B>{}]).
+template <class F> static void with_w(int W, F f) {
+    if (W == 1) f(std::integral_constant<int, 1>{});
+    else f(std::integral_constant<int, 2>{});
+}
+template <class F> static void with_w(int W, bool b, F f) {
+    with_w(W, [&](auto w) {
+        if (b) f(w, std::true_type{});
+        else f(w, std::false_type{});
+    });
+}
+template <int W> static KmerKey<W>* keys_of(void* p) { return reinterpret_cast<KmerKey<W>*>(p); }
+template <int W> static const KmerKey<W>* keys_of(const void* p) { return reinterpret_cast<const KmerKey<W>*>(p); }
+
 template <class K> static void allow_lds(K kern, size_t bytes) {
     static thread_local size_t granted = 0;   // per kernel instantiation
     if (bytes > 48 * 1024 && bytes > granted) {
@@ -2438,28 +2409,19 @@ void kh_launch_extract(int W, bool scatter, const u8* seq, const KhSeg* segs, co
     if (scatter && nb_alloc <= 4 * KH_ST_THREADS && kh_extract_staged_lds_bytes(W, nb_alloc) <= 160 * 1024 &&
         !getenv("KHOICE_DIRECT_SCATTER")) {
         const size_t lds2 = kh_extract_staged_lds_bytes(W, nb_alloc);
-        if (W == 1) {
-            allow_lds(k_extract_staged<1>, lds2);
-            hipLaunchKernelGGL(k_extract_staged<1>, dim3(ntiles), dim3(KH_ST_THREADS), lds2, st, seq, segs, tiles,
-                               nb_alloc, k, thist, bstart, reinterpret_cast<KmerKey<1>*>(part), tile_pos);
-        } else {
-            allow_lds(k_extract_staged<2>, lds2);
-            hipLaunchKernelGGL(k_extract_staged<2>, dim3(ntiles), dim3(KH_ST_THREADS), lds2, st, seq, segs, tiles,
-                               nb_alloc, k, thist, bstart, reinterpret_cast<KmerKey<2>*>(part), tile_pos);
-        }
+        with_w(W, [&](auto w) {
+            allow_lds(k_extract_staged<w()>, lds2);
+            hipLaunchKernelGGL(k_extract_staged<w()>, dim3(ntiles), dim3(KH_ST_THREADS), lds2, st, seq, segs, tiles,
+                               nb_alloc, k, thist, bstart, keys_of<w()>(part), tile_pos);
+        });
         return;
     }
     const size_t lds = kh_extract_lds_bytes(nb_alloc);
-#define KH_EX(WW, SC)                                                                           \
-    do {                                                                                        \
-        allow_lds(k_extract<WW, SC>, lds);                                                      \
-        hipLaunchKernelGGL((k_extract<WW, SC>), dim3(ntiles), dim3(256), lds, st, seq, segs,    \
-                           tiles, nb_alloc, k, thist, bstart,                                   \
-                           reinterpret_cast<KmerKey<WW>*>(part), tile_pos);                     \
-    } while (0)
-    if (W == 1) { if (scatter) KH_EX(1, true); else KH_EX(1, false); }
-    else        { if (scatter) KH_EX(2, true); else KH_EX(2, false); }
-#undef KH_EX
+    with_w(W, scatter, [&](auto w, auto sc) {
+        allow_lds(k_extract<w(), sc()>, lds);
+        hipLaunchKernelGGL((k_extract<w(), sc()>), dim3(ntiles), dim3(256), lds, st, seq, segs, tiles, nb_alloc, k,
+                           thist, bstart, keys_of<w()>(part), tile_pos);
+    });
 }
 
 void kh_launch_col_totals(const KhSeg* segs, u32 nseg, u32 max_nb, const u32* thist, u64* tot,
@@ -2488,58 +2450,43 @@ void kh_launch_bucket_sort(int W, const void* part, const KhBucketWork* work,
     if (!nbuckets) return;
     const u32 cap = W == 1 ? KH_SORT_CAP_W1 : KH_SORT_CAP_W2;
     const size_t lds = kh_sort_lds_bytes(W, cap, false);
-    if (W == 1) {
-        allow_lds(k_bucket_sort_rle<1>, lds);
-        hipLaunchKernelGGL((k_bucket_sort_rle<1>), dim3(nbuckets), dim3(KH_SORT_THREADS), lds, st,
-                           reinterpret_cast<const KmerKey<1>*>(part), work, cap, k,
-                           reinterpret_cast<KmerKey<1>*>(out_keys), out_counts, lb, ci, cx, cs);
-    } else {
-        allow_lds(k_bucket_sort_rle<2>, lds);
-        hipLaunchKernelGGL((k_bucket_sort_rle<2>), dim3(nbuckets), dim3(KH_SORT_THREADS), lds, st,
-                           reinterpret_cast<const KmerKey<2>*>(part), work, cap, k,
-                           reinterpret_cast<KmerKey<2>*>(out_keys), out_counts, lb, ci, cx, cs);
-    }
+    with_w(W, [&](auto w) {
+        allow_lds(k_bucket_sort_rle<w()>, lds);
+        hipLaunchKernelGGL((k_bucket_sort_rle<w()>), dim3(nbuckets), dim3(KH_SORT_THREADS), lds, st,
+                           keys_of<w()>(part), work, cap, k, keys_of<w()>(out_keys), out_counts, lb, ci, cx, cs);
+    });
 }
 
-size_t kh_tag_lds_bytes(int W, u32 cap, u32 nbins, bool emit) {
-    (void)emit;
+size_t kh_tag_lds_bytes(int W, u32 cap, u32 nbins) {
     return kh_sort_lds_bytes(W, cap, true) + (((size_t)nbins * 32 + 15) & ~(size_t)15);
 }
 void kh_launch_union_tagged(int W, const KhTagJob& job, u32 grid, int k, u32 cs, hipStream_t st) {
     if (!grid) return;
     const u32 cap = W == 1 ? KH_SORT_CAP_PAY_W1 : KH_SORT_CAP_PAY_W2;
-    const size_t lds = kh_tag_lds_bytes(W, cap, job.nbins, job.desc != nullptr);
-#define KH_UT(WW, EE)                                                                                   \
-    do {                                                                                                \
-        allow_lds(k_union_tagged<WW, EE>, lds);                                                         \
-        hipLaunchKernelGGL((k_union_tagged<WW, EE>), dim3(grid), dim3(KH_SORT_THREADS), lds, st, job, cap, k, cs); \
-    } while (0)
-    const bool emit = job.desc != nullptr;
-    if (W == 1) { if (emit) KH_UT(1, true); else KH_UT(1, false); }
-    else        { if (emit) KH_UT(2, true); else KH_UT(2, false); }
-#undef KH_UT
+    const size_t lds = kh_tag_lds_bytes(W, cap, job.nbins);
+    with_w(W, job.desc != nullptr, [&](auto w, auto emit) {
+        allow_lds(k_union_tagged<w(), emit()>, lds);
+        hipLaunchKernelGGL((k_union_tagged<w(), emit()>), dim3(grid), dim3(KH_SORT_THREADS), lds, st, job, cap, k, cs);
+    });
 }
 
 void kh_launch_range_bounds(int W, const KhSetView* sets, u32 nsets, u32 nranges, int k,
                             u64* bounds, u64* zero, u64 zero_words, hipStream_t st) {
     const u64 total = ((u64)nranges + 1) * nsets;
     const u32 grid = (u32)((total + 255) / 256);
-    if (W == 1)
-        hipLaunchKernelGGL((k_range_bounds<1>), dim3(grid), dim3(256), 0, st, sets, nsets, nranges,
-                           k, bounds, zero, zero_words);
-    else
-        hipLaunchKernelGGL((k_range_bounds<2>), dim3(grid), dim3(256), 0, st, sets, nsets, nranges,
-                           k, bounds, zero, zero_words);
+    with_w(W, [&](auto w) {
+        hipLaunchKernelGGL((k_range_bounds<w()>), dim3(grid), dim3(256), 0, st, sets, nsets, nranges, k, bounds, zero,
+                           zero_words);
+    });
 }
 
 void kh_launch_range_bounds_batch(int W, const KhBoundsJob* jobs, u32 njobs, u64 max_threads, int k,
                                   hipStream_t st) {
     if (!njobs) return;
     const u32 grid = (u32)((max_threads + 255) / 256);
-    if (W == 1)
-        hipLaunchKernelGGL((k_range_bounds_batch<1>), dim3(grid, njobs), dim3(256), 0, st, jobs, k);
-    else
-        hipLaunchKernelGGL((k_range_bounds_batch<2>), dim3(grid, njobs), dim3(256), 0, st, jobs, k);
+    with_w(W, [&](auto w) {
+        hipLaunchKernelGGL((k_range_bounds_batch<w()>), dim3(grid, njobs), dim3(256), 0, st, jobs, k);
+    });
 }
 
 void kh_launch_setop(int W, bool pay, u32 cap, const KhSetopBatch& batch, u32 njobs, int k, int op, int mode,
@@ -2548,15 +2495,11 @@ void kh_launch_setop(int W, bool pay, u32 cap, const KhSetopBatch& batch, u32 nj
     for (u32 i = 0; i < njobs; ++i) width = std::max(width, batch.job[i].nranges);
     if (!njobs || !width) return;
     const size_t lds = kh_sort_lds_bytes(W, cap, pay);
-#define KH_SO(WW, PP)                                                                            \
-    do {                                                                                         \
-        allow_lds(k_setop<WW, PP>, lds);                                                         \
-        hipLaunchKernelGGL((k_setop<WW, PP>), dim3(width * njobs), dim3(KH_SORT_THREADS), lds, st, \
-                           batch, njobs, cap, k, op, mode, cs, hist_len, dynamic_order ? 1u : 0u); \
-    } while (0)
-    if (W == 1) { if (pay) KH_SO(1, true); else KH_SO(1, false); }
-    else        { if (pay) KH_SO(2, true); else KH_SO(2, false); }
-#undef KH_SO
+    with_w(W, pay, [&](auto w, auto p) {
+        allow_lds(k_setop<w(), p()>, lds);
+        hipLaunchKernelGGL((k_setop<w(), p()>), dim3(width * njobs), dim3(KH_SORT_THREADS), lds, st, batch, njobs, cap,
+                           k, op, mode, cs, hist_len, dynamic_order ? 1u : 0u);
+    });
 }
 
 void kh_launch_histogram(const u32* counts, u64 n, unsigned long long* hist, u32 hist_len,
@@ -2567,14 +2510,10 @@ void kh_launch_histogram(const u32* counts, u64 n, unsigned long long* hist, u32
 }
 void kh_launch_unmix(int W, const void* in, void* out, u64 n, int k, hipStream_t st) {
     if (!n) return;
-    if (W == 1)
-        hipLaunchKernelGGL((k_remix<1, true>), dim3(grid_for(n, 256)), dim3(256), 0, st,
-                           reinterpret_cast<const KmerKey<1>*>(in),
-                           reinterpret_cast<KmerKey<1>*>(out), n, k);
-    else
-        hipLaunchKernelGGL((k_remix<2, true>), dim3(grid_for(n, 256)), dim3(256), 0, st,
-                           reinterpret_cast<const KmerKey<2>*>(in),
-                           reinterpret_cast<KmerKey<2>*>(out), n, k);
+    with_w(W, [&](auto w) {
+        hipLaunchKernelGGL((k_remix<w(), true>), dim3(grid_for(n, 256)), dim3(256), 0, st, keys_of<w()>(in),
+                           keys_of<w()>(out), n, k);
+    });
 }
 void kh_launch_fill_u32(u32* p, u64 n, u32 v, hipStream_t st) {
     if (!n) return;
@@ -2607,12 +2546,10 @@ void kh_launch_membership(int W, const void* pivot, u64 n, const KhSetView* sets
                           u32 nwords, u64* masks, hipStream_t st) {
     if (!n) return;
     const u32 grid = (u32)((n + 255) / 256);
-    if (W == 1)
-        hipLaunchKernelGGL((k_membership<1>), dim3(grid), dim3(256), 0, st,
-                           reinterpret_cast<const KmerKey<1>*>(pivot), n, sets, nsets, k, nwords, masks);
-    else
-        hipLaunchKernelGGL((k_membership<2>), dim3(grid), dim3(256), 0, st,
-                           reinterpret_cast<const KmerKey<2>*>(pivot), n, sets, nsets, k, nwords, masks);
+    with_w(W, [&](auto w) {
+        hipLaunchKernelGGL((k_membership<w()>), dim3(grid), dim3(256), 0, st, keys_of<w()>(pivot), n, sets, nsets, k,
+                           nwords, masks);
+    });
 }
 
 u32 kh_union_hash_capacity() { return 4096u; }
@@ -2628,29 +2565,15 @@ void kh_launch_grid_bucket(int W, const void* part, const KhBucketWork* work, u3
                            const u32* over, u32* err, const KhGrid& grid, hipStream_t st) {
     if (!nbuckets) return;
     const u32 cap = kh_grid_bucket_capacity(W);
-    {   // the listed oversize buckets (usually none: the walkers find an empty list and leave)
-        const size_t lds2 = kh_sort_lds_bytes(W, cap, false);
-        const u32 walkers = std::min<u32>(nbuckets, 128);
-        if (W == 1) {
-            allow_lds(k_grid_oversize<1>, lds2);
-            hipLaunchKernelGGL((k_grid_oversize<1>), dim3(walkers), dim3(KH_SORT_THREADS), lds2, st,
-                               reinterpret_cast<const KmerKey<1>*>(part), work, over, cap, k,
-                               reinterpret_cast<KmerKey<1>*>(out_keys), err, grid);
-        } else {
-            allow_lds(k_grid_oversize<2>, lds2);
-            hipLaunchKernelGGL((k_grid_oversize<2>), dim3(walkers), dim3(KH_SORT_THREADS), lds2, st,
-                               reinterpret_cast<const KmerKey<2>*>(part), work, over, cap, k,
-                               reinterpret_cast<KmerKey<2>*>(out_keys), err, grid);
-        }
-    }
-    const size_t lds = kh_grid_bucket_lds_bytes(W, cap);
-    if (W == 1) {
-        allow_lds(k_grid_bucket<1>, lds);
-        hipLaunchKernelGGL((k_grid_bucket<1>), dim3(nbuckets), dim3(KH_SORT_THREADS), lds, st,
-                           reinterpret_cast<const KmerKey<1>*>(part), work, cap, k, reinterpret_cast<KmerKey<1>*>(out_keys), grid);
-    } else {
-        allow_lds(k_grid_bucket<2>, lds);
-        hipLaunchKernelGGL((k_grid_bucket<2>), dim3(nbuckets), dim3(KH_SORT_THREADS), lds, st,
-                           reinterpret_cast<const KmerKey<2>*>(part), work, cap, k, reinterpret_cast<KmerKey<2>*>(out_keys), grid);
-    }
+    const size_t lds = kh_grid_bucket_lds_bytes(W, cap), lds2 = kh_sort_lds_bytes(W, cap, false);
+    const u32 walkers = std::min<u32>(nbuckets, 128);
+    with_w(W, [&](auto w) {
+        // the listed oversize buckets (usually none: the walkers find an empty list and leave)
+        allow_lds(k_grid_oversize<w()>, lds2);
+        hipLaunchKernelGGL((k_grid_oversize<w()>), dim3(walkers), dim3(KH_SORT_THREADS), lds2, st, keys_of<w()>(part),
+                           work, over, cap, k, keys_of<w()>(out_keys), err, grid);
+        allow_lds(k_grid_bucket<w()>, lds);
+        hipLaunchKernelGGL((k_grid_bucket<w()>), dim3(nbuckets), dim3(KH_SORT_THREADS), lds, st, keys_of<w()>(part),
+                           work, cap, k, keys_of<w()>(out_keys), grid);
+    });
 }

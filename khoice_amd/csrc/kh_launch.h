@@ -309,7 +309,7 @@ void kh_launch_bucket_sort(int W, const void* part, const KhBucketWork* work,
 u32 kh_grid_bucket_capacity(int W);
 void kh_launch_grid_bucket(int W, const void* part, const KhBucketWork* work, u32 nbuckets, int k, void* out_keys,
                            const u32* over, u32* err, const KhGrid& grid, hipStream_t st);
-size_t kh_tag_lds_bytes(int W, u32 cap, u32 nbins, bool emit);
+size_t kh_tag_lds_bytes(int W, u32 cap, u32 nbins);
 // one-word keys, nothing emitted: the hash-set form (k_union_hash), one workgroup per slot
 u32 kh_union_hash_capacity();
 void kh_launch_union_hash(const KhTagJob& job, u32 grid, int k, u32 cs, hipStream_t st);

@@ -103,6 +103,49 @@ def test_fused_many_genomes_and_groups(eng):
     check(eng, seqs + [seqs[0]], group_of + [group_of[0]], 31, expect_fused=False)
 
 
+def many_operand_case(k):
+    """64 genomes of at most 61 k-mers each: lengths 0, k-1, k, k+1, then k + (7 g mod 61) bases.  Every fourth
+    genome shares its start with its predecessor (the shorter of the two is a prefix of the longer), so keys are
+    shared.  Five groups of 1, 2, 30, 7 and 24 genomes, passed shuffled."""
+    rng = random.Random(64)
+    lengths = [0, k - 1, k, k + 1] + [k + (7 * g) % 61 for g in range(4, 64)]
+    seqs = []
+    for g, n in enumerate(lengths):
+        if g % 4 == 3:
+            t = seqs[-1][:n] + random_dna(rng, max(0, n - len(seqs[-1])))
+        else:
+            t = random_dna(rng, n)
+        assert len(t) == n
+        seqs.append(t)
+    assert len(set(lengths)) == 62 and max(lengths) == k + 60              # 7 g mod 61 takes 60 values over g = 4 .. 63
+    group_of = [g for g, sz in enumerate([1, 2, 30, 7, 24]) for _ in range(sz)]
+    order = list(range(64))
+    rng.shuffle(order)
+    return [seqs[i].encode() for i in order], [group_of[i] for i in order]
+
+
+def test_fused_gather_across_many_operands(eng, monkeypatch):
+    """The wave-local gather where the 64 elements of a wave span MANY operands with empty ones in between (the
+    64-genome case above puts some 50 keys of every operand into a slot: one boundary per wave, two at most).  Here
+    an operand holds 0 .. 61 keys in all, so a wave's elements come from a dozen operands: in the hash form, the
+    fine-bin form of one-word and of two-word keys, and the emitting form of both."""
+    for k in (15, 33):
+        seqs, group_of = many_operand_case(k)
+        check(eng, seqs, group_of, k)
+        if k == 15:
+            monkeypatch.setenv("KHOICE_NO_UNION_HASH", "1")
+            check(eng, seqs, group_of, k)
+            monkeypatch.delenv("KHOICE_NO_UNION_HASH")
+        fused = eng.exp1_run(seqs, group_of, k, cs=5000, hist_len=64, want_across_set=True)
+        gen = eng.exp1_run(seqs, group_of, k, cs=5000, hist_len=64, want_sets=True)
+        assert (fused["within_hist"] == gen["within_hist"]).all()
+        assert (fused["across_hist"] == gen["across_hist"]).all()
+        assert (fused["distinct_per_seq"] == gen["distinct_per_seq"]).all()
+        fk, fc = fused["across_set"].download_sorted()
+        gk, gc = gen["across_set"].download_sorted()
+        assert (fk == gk).all() and (fc == gc).all()
+
+
 def test_fused_equals_general_path_and_across_set(eng):
     items = synth.species_set(4, 3, 150_000)
     seqs = [t for _, _, t in items]
