@@ -1042,7 +1042,8 @@ static int setop_finish(SetopJob& j, kh_set** out) {
         // that rule assumes keys spread evenly over the ranges; operands that crowd more keys than a slot holds into
         // a sliver of the key space barely shrink under it, so from the third re-plan on the fill is quartered
         if (attempt >= 2) next = std::min<u64>(next, j.target / 4);
-        j.target = std::max<u64>(16, std::min<u64>(next, j.target * 7 / 8));
+        // (no floor of 16 here: a few thousand keys in a thousandth of the key space need more ranges than total / 16)
+        j.target = std::max<u64>(1, std::min<u64>(next, j.target * 7 / 8));
         KHCHK(setop_launch(j));
         HIPCHK(hipStreamSynchronize(c->st));
     }
@@ -2449,7 +2450,9 @@ static int exp1_big_group(kh_ctx* c, const Exp1In& in, int g, u64 budget, uint64
         for (size_t j = i0; j < i0 + m; ++j) b.add(in, all.idx[j], b.ngroups++);
         kh_set* aset = nullptr;
         bool d = false;
-        KHCHK(exp1_fused_rescaled(c, in, b, 0x7fffffffu, nullptr, nullptr, &aset, exp1_waves(b.bases, budget), (u32)m, nullptr, &d));
+        // (a first attempt that overflows in a later wave has counted its earlier waves: rolled back like a single batch's)
+        const StatCheckpoint cp{c};
+        KHCHK(exp1_fused_rescaled(c, in, b, 0x7fffffffu, nullptr, nullptr, &aset, exp1_waves(b.bases, budget), (u32)m, &cp, &d));
         if (!d) return KH_OK;
         subs.push_back(aset);
         b.scatter(dist_out);

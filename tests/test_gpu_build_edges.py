@@ -29,16 +29,14 @@ import numpy as np
 import pytest
 
 from oracle import c_oracle as CO
-from tests.util import (codes_text, fine_bin_np, key_view, mix_np, planted_codes, planted_text, random_dna_np, slot_np,
-                        words)
+from tests.util import (CAP, FINE_BITS, MEAN, Planted, codes_text, fine_bin_np, grid_sub_ranges, key_view, mix_np,
+                        planted_text, random_dna_np, slot_np, words)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "khoice_amd", "csrc")
 
 # ---- the plan and sort-tier constants (test_constants_match_sources reads them out of the sources)
-MEAN = {1: 3700, 2: 1750}        # KH_TUNE_MEAN_W1, KH_BUCKET_MEAN_W2: k-mer positions per bucket
-CAP = {1: 4096, 2: 2048}         # KH_SORT_CAP_W1 / _W2: keys a bucket sorts in LDS
-FINE_BITS = 13                   # KH_TUNE_FINE_BITS
+# (MEAN, CAP and FINE_BITS live in tests/util.py beside Planted, which needs them)
 FINE_LIMIT = 64                  # fullest fine bin the in-bin repair accepts
 WORKLIST = 1024                  # keys of out-of-order bins the repair lists
 SUBTILE, SUBTILES_PER_TILE, HALO = 8192, 8, 96
@@ -107,34 +105,6 @@ def staged(w, nb):
 
 
 # =========================================================================== planted cases
-class Planted:
-    """Families of planted keys for one text of `nb` buckets."""
-
-    def __init__(self, k, nb, seed):
-        self.k, self.w, self.nb = k, words(k), nb
-        self.rng = np.random.default_rng(seed)
-        self.keys = np.zeros((0, self.w), dtype=np.uint64)
-        self.mult = np.zeros(0, dtype=np.int64)
-
-    def add(self, b, f, n, mult=1, avoid=()):
-        """n distinct keys in bucket b (fine bin f, or spread over the bucket when f is None, outside the fine bins
-        `avoid`), each written mult times (an int or one per key).  Returns the keys."""
-        got = planted_codes(self.k, self.nb, b, f, n + 8 * len(avoid), self.rng, FINE_BITS)
-        if avoid:
-            fine = fine_bin_np(self.k, mix_np(self.k, got), self.nb, FINE_BITS)
-            got = got[~np.isin(fine, np.array(avoid, dtype=np.uint64))]
-        got = got[:n]
-        assert got.shape[0] == n
-        if self.keys.shape[0]:
-            assert not np.isin(key_view(got), key_view(self.keys)).any()
-        self.keys = np.concatenate([self.keys, got])
-        self.mult = np.concatenate([self.mult, np.broadcast_to(np.asarray(mult, dtype=np.int64), (n,))])
-        return got
-
-    def text(self, head=b""):
-        return planted_text(self.k, self.keys, self.mult, self.nb * MEAN[self.w], self.rng, head)
-
-
 def nbuckets(k, text):
     return max(1, -(-(len(text) - k + 1) // MEAN[words(k)])) if len(text) >= k else 1
 
@@ -723,18 +693,6 @@ def test_segments_at_the_staging_limit(eng, monkeypatch):
 # --------------------------------------------------------------------------- 4. grid mode (key-array form of exp1)
 GRID_NB = 100
 GRID_GENOMES, GRID_GROUP_OF = 6, [0, 0, 0, 1, 1, 1]
-
-
-def grid_sub_ranges(k, ngenomes, fan, hash_form):
-    """S of build_once's grid mode for genomes of GRID_NB * mean positions each (kh_engine.cpp: 'sub-ranges per
-    bucket')."""
-    w = words(k)
-    cap = 4096 if (w == 1 and hash_form) else CAP[w]
-    zg = 5.0 * np.sqrt(fan)
-    x = 0.5 * (-zg + np.sqrt(zg * zg + 4.0 * cap))
-    target = max(16, min(cap * 92 // 100, int(x * x)))
-    per_bucket = ngenomes * MEAN[w]
-    return -(-per_bucket // target)
 
 
 @functools.lru_cache(maxsize=None)

@@ -432,20 +432,20 @@ def test_more_than_cap_keys_on_one_top32_fail_cleanly(eng, E, k):
 
 @pytest.mark.parametrize("k", [31, 47])
 def test_cluster_below_the_planner_floor(eng, E, k):
-    """The slot target has a floor of 16 keys: a set confined to 1/1024 of the space cannot be cut
-    fine enough and must fail with KH_E_CAPACITY; 1/256 sits at the floor: exact or that error."""
+    """The slot target used to stop at 16 keys, and a set confined to 1/1024 of the space failed with KH_E_CAPACITY.
+    The re-plan now goes down to one key per range: such a set, alone and united with itself, and one confined to
+    1/256 of the space are answered exactly."""
     rng = np.random.default_rng(k + 5)
     tight = Operand(eng, k, distinct_raw(k, clustered_mixed(k, 120_000, rng, 1.0 / 1024, 12345)))
-    with pytest.raises(E.KhoiceError) as ei:
-        eng.union_sum([tight.set], 255)
-    assert ei.value.code == E_CAPACITY
+    r0 = eng.stats()["retries"]
+    for ops in ([tight], [tight, tight]):
+        u = eng.union_sum([o.set for o in ops], 255)
+        keys, counts = ref_union(k, ops, 255)
+        assert_set(u, keys, counts, "1/1024 cluster")
+    assert eng.stats()["retries"] > r0                          # the first plan cannot hold it: it was re-planned
     _engine_still_works(eng)
     loose = Operand(eng, k, distinct_raw(k, clustered_mixed(k, 120_000, rng, 1.0 / 256, 1 << 31)))
-    try:
-        u = eng.union_sum([loose.set, loose.set], 255)
-    except E.KhoiceError as e:
-        assert e.code == E_CAPACITY
-    else:
-        keys, counts = ref_union(k, [loose, loose], 255)
-        assert_set(u, keys, counts, "1/256 cluster")
+    u = eng.union_sum([loose.set, loose.set], 255)
+    keys, counts = ref_union(k, [loose, loose], 255)
+    assert_set(u, keys, counts, "1/256 cluster")
     _engine_still_works(eng)

@@ -282,6 +282,52 @@ def random_dna_np(rng, n, alphabet=b"ACGT"):
     return np.frombuffer(alphabet, dtype=np.uint8)[rng.integers(0, len(alphabet), size=n)].tobytes()
 
 
+# ---- the plan constants the planted cases lean on (the test modules read them out of the sources)
+MEAN = {1: 3700, 2: 1750}        # KH_TUNE_MEAN_W1, KH_BUCKET_MEAN_W2: k-mer positions per bucket
+CAP = {1: 4096, 2: 2048}         # KH_SORT_CAP_W1 / _W2: keys a bucket sorts in LDS
+FINE_BITS = 13                   # KH_TUNE_FINE_BITS
+
+
+class Planted:
+    """Families of planted keys for one text of `nb` buckets."""
+
+    def __init__(self, k, nb, seed):
+        self.k, self.w, self.nb = k, words(k), nb
+        self.rng = np.random.default_rng(seed)
+        self.keys = np.zeros((0, self.w), dtype=np.uint64)
+        self.mult = np.zeros(0, dtype=np.int64)
+
+    def add(self, b, f, n, mult=1, avoid=()):
+        """n distinct keys in bucket b (fine bin f, or spread over the bucket when f is None, outside the fine bins
+        `avoid`), each written mult times (an int or one per key).  Returns the keys."""
+        got = planted_codes(self.k, self.nb, b, f, n + 8 * len(avoid), self.rng, FINE_BITS)
+        if avoid:
+            fine = fine_bin_np(self.k, mix_np(self.k, got), self.nb, FINE_BITS)
+            got = got[~np.isin(fine, np.array(avoid, dtype=np.uint64))]
+        got = got[:n]
+        assert got.shape[0] == n
+        if self.keys.shape[0]:
+            assert not np.isin(key_view(got), key_view(self.keys)).any()
+        self.keys = np.concatenate([self.keys, got])
+        self.mult = np.concatenate([self.mult, np.broadcast_to(np.asarray(mult, dtype=np.int64), (n,))])
+        return got
+
+    def text(self, head=b""):
+        return planted_text(self.k, self.keys, self.mult, self.nb * MEAN[self.w], self.rng, head)
+
+
+def grid_sub_ranges(k, ngenomes, fan, hash_form):
+    """S of build_once's grid mode for `ngenomes` genomes that all have a whole number of buckets of k-mer positions,
+    the same number each (kh_engine.cpp: 'sub-ranges per bucket'); fan: genomes of the largest group."""
+    w = words(k)
+    cap = 4096 if (w == 1 and hash_form) else CAP[w]
+    zg = 5.0 * np.sqrt(fan)
+    x = 0.5 * (-zg + np.sqrt(zg * zg + 4.0 * cap))
+    target = max(16, min(cap * 92 // 100, int(x * x)))
+    per_bucket = ngenomes * MEAN[w]
+    return -(-per_bucket // target)
+
+
 # ---------------------------------------------------------------- constructed sets
 # Keys chosen in MIXED space (so a test decides their slots and how they cluster), counters over the whole u32 range,
 # and the host copy of an uploaded set: shared by the modules that test set operations, views and tables.
