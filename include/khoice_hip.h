@@ -239,6 +239,38 @@ int kh_exp1_run(kh_ctx *ctx, int nseq, const uint8_t *const *seqs, const uint64_
                 uint64_t *within_hist, uint64_t *across_hist, uint32_t hist_len,
                 uint64_t *distinct_per_seq, kh_set **group_sets, kh_set **across_set);
 
+/* ---------------------------------------------------------------- fused experiment type 2
+ * The device side of exp_type_2.smk:289-507 for one k on resident sequences: a pivot genome was held out of every
+ * dataset (group); in how many genomes of its own group, and in how many of the OTHER groups, does each of its k-mers
+ * occur?  Replaces per k: `kmc` + `set_counts 1` per genome and pivot (:297,306,318,330), the -cs{cs} `complex` union
+ * per group (:342), `simple PIVOT UNION intersect -ocsum` + `transform histogram` (:363-365) and
+ * `simple PIVOT UNION kmers_subtract` + histogram (:377-379), `set_counts 1` of the group unions (:391), the
+ * `complex` union of the other groups per pivot (:465), and the same intersect / kmers_subtract pair against it
+ * (:479-481, :493-495).
+ *   seqs, lens, group_of, ngroups   the rest_of_set genomes, as for kh_exp1_run; every group needs a genome
+ *   pivot_seqs, pivot_lens          npivots pivot texts (host or device like seqs); pivot_group[p] = the group pivot p
+ *                                   was held out of; any number of pivots per group, none included
+ * With occ_w[v] = distinct canonical k-mers of pivot p in exactly v genomes of its group (the pivot is not one of
+ * them) and occ_a[v] = in exactly v groups other than its own (a group holds what any of its genomes holds):
+ *   within_hist  [npivots * hist_len]  bin min(1 + min(v, cs), cs, hist_len - 1) += occ_w[v], v >= 1: the histogram of
+ *                                      the intersect -ocsum result (the pivot's counter 1 + the union's, saturating)
+ *   within_only  [npivots]             occ_w[0]: bin 1 of the kmers_subtract result
+ *   across_hist, across_only           the same over occ_a; one group: no k-mer is met, all are in across_only
+ *   distinct_per_seq [nseq], distinct_per_pivot [npivots]   distinct canonical k-mers of every text
+ * Any output may be NULL.
+ *
+ * Forms, the same numbers in each: k <= 12 presence bitmaps (kh_bmp.hip: the pivots are further genomes of the
+ * bitmap build, one read-out kernel counts every pivot against its group's and the groups' bit-sliced counters);
+ * otherwise, and whenever the bitmaps do not fit (1023 genomes per group, 1023 groups, 4096 bins and counters, the
+ * memory budget), the calls above on sets in device memory.  Switches as for kh_exp1_run: KHOICE_NO_BMP,
+ * KHOICE_NO_SKM, KHOICE_BMP_MAX_K, KHOICE_BMP_MAX_BYTES. */
+int kh_exp2_run(kh_ctx *ctx, int nseq, const uint8_t *const *seqs, const uint64_t *lens, int on_device,
+                const int *group_of, int ngroups, int npivots, const uint8_t *const *pivot_seqs,
+                const uint64_t *pivot_lens, const int *pivot_group, int k, uint32_t cs,
+                uint64_t *within_hist, uint64_t *across_hist, uint32_t hist_len,
+                uint64_t *within_only, uint64_t *across_only,
+                uint64_t *distinct_per_seq, uint64_t *distinct_per_pivot);
+
 /* ---------------------------------------------------------------- multi-GPU exchange (RCCL over xGMI)
  * Steps 7-8 of exp_type_1.smk:243-259 when the groups are sharded over several GPUs, one process
  * per GPU: every rank runs kh_exp1_run on its own groups asking for `across_set` (counter = number

@@ -1,7 +1,7 @@
-// khoice_amd — presence-bitmap form of the fused experiment-type-1 step for small k (gfx950).
+// khoice_amd — presence-bitmap form of the fused experiment-type-1 and type-2 steps for small k (gfx950).
 //
 // A k-mer of k <= 13 is a number below 2^26: "which genomes hold it" is one bit per genome in a directly addressed
-// bitmap of 4^k bits, and every histogram of the step is a count over those bits.  Two kernels:
+// bitmap of 4^k bits, and every histogram of the step is a count over those bits.  Three kernels:
 //   k_bmp_build    text -> presence bitmaps.  A workgroup owns one (genome, split, code range): it keeps the bitmap of
 //                  its range in LDS, walks its split tile by tile (the staging of load_codes, canonical code of every valid position,
 //                  one LDS OR where the code falls in the range) and then stores every word of the range, zeros
@@ -13,6 +13,8 @@
 //                  LDS bin of (group, count).  The groups' "present" words feed a second bit-sliced counter over
 //                  groups: the across-group bins.  The popcount of a genome's own word is its distinct k-mers.
 // There is no genome mask: any number of genomes and groups (up to 1023 per counter) is answered in one pass.
+//   k_bmp_pivot    experiment type 2 with the walk of k_bmp_readout: pivot genomes are further operands of the build;
+//                  a pivot's word masks the counter of its group and the counter over groups (see at the kernel).
 #include "kh_device.h"
 #include "kh_launch.h"
 
@@ -277,6 +279,110 @@ __global__ __launch_bounds__(1024) void k_bmp_readout(const KhBmpJob jb) {
         if (bins[i]) atomicAdd(&rep[i], (unsigned long long)bins[i]);
 }
 
+// ------------------------------------------------------------------------------------------
+// k_bmp_pivot
+// LDS: as k_bmp_readout, [bins: nbins + nops u32][gx: 2 x waves x 64 u64]
+// ------------------------------------------------------------------------------------------
+// Experiment type 2 with the walk of k_bmp_readout.  The operands of a group are its genomes, then the pivots held
+// out of it.  First phase: a genome's word goes into the group's counter c and into `any`; behind the last genome `any`
+// is kept in present[group] (groups with pivots only) and added to the counter a over groups; a pivot's word P is
+// counted against c, which still stands: bin(pivot, v) += popcount(P & (c == v)), v = 0 .. size.  Second phase, a
+// complete: the pivots alone are handed over again, and with G = present[group], read back by the lane that stored it,
+// the other groups holding a code are a - 1 where G is set, else a.
+__global__ __launch_bounds__(1024) void k_bmp_pivot(const KhBmpPivotJob jb) {
+    extern __shared__ __attribute__((aligned(16))) u8 lds_raw[];
+    u32* bins = reinterpret_cast<u32*>(lds_raw);
+    const u32 nb = jb.nbins + jb.nops;
+    u64* gx = reinterpret_cast<u64*>(lds_raw + ((4 * (size_t)nb + 15) & ~(size_t)15));   // [2][wy][64]
+    const u32 lane = threadIdx.x, y = threadIdx.y, wy = blockDim.y;
+    const u32 tid = y * KH_WAVE + lane, nt = wy * KH_WAVE;
+    for (u32 i = tid; i < nb; i += nt) bins[i] = 0;
+    __syncthreads();
+    const u32 asl = bit_length(jb.ngroups);
+    u32 round = 0;
+    // wave y: the word of operand `i` (none: zero) into this round's buffer
+    auto hand_over = [&](const bool have, const u32 i, const u64 w) {
+        u64 x = 0;
+        if (have) {
+            const KhBmpOp op = jb.ops[i];
+            const u64* p = jb.partial + (size_t)op.split0 * jb.nwords + w;
+#pragma unroll 8
+            for (u32 s = 0; s < op.nsplits; ++s) x |= p[(size_t)s * jb.nwords];
+        }
+        u64* buf = gx + (size_t)(round & 1u) * wy * KH_WAVE;
+        buf[y * KH_WAVE + lane] = x;
+        __syncthreads();
+        return buf;
+    };
+    for (u64 wb = blockIdx.x; wb * KH_WAVE < jb.nwords; wb += gridDim.x) {
+        const u64 w = wb * KH_WAVE + lane;
+        const bool active = w < jb.nwords;
+        u32 g = 0;
+        KhBmpPivotGroup gr = jb.groups[0];
+        u32 ns = bit_length(gr.size);
+        u64 a[BMP_SLICES], c[BMP_SLICES], any = 0;
+#pragma unroll
+        for (int s = 0; s < BMP_SLICES; ++s) a[s] = c[s] = 0;
+        for (u32 i0 = 0; i0 < jb.nops; i0 += wy, ++round) {
+            const u64* buf = hand_over(i0 + y < jb.nops && active, i0 + y, w);
+            if (y != 0) continue;
+            const u32 n = jb.nops - i0 < wy ? jb.nops - i0 : wy;
+            for (u32 j = 0; j < n; ++j) {
+                const u32 i = i0 + j, gend = gr.first + gr.size;
+                const u64 xx = buf[j * KH_WAVE + lane];
+                wave_add_to_bin(&bins[jb.nbins + i], (u32)__builtin_popcountll(xx));   // the operand's distinct k-mers
+                if (i < gend) {
+                    any |= xx;
+                    slices_add(c, xx, ns);
+                    if (i + 1 == gend) {   // the genomes of the group are counted
+                        if (gr.npiv && active) jb.present[(size_t)gr.prow * jb.nwords + w] = any;
+                        slices_add(a, any, asl);
+                    }
+                } else {
+                    const u32 b0 = jb.pivots[gr.q0 + (i - gend)].bin0;
+                    for (u32 v = 0; v <= gr.size; ++v)
+                        wave_add_to_bin(&bins[b0 + v], (u32)__builtin_popcountll(xx & slices_equal(c, v, ns)));
+                }
+                if (i + 1 == gend + gr.npiv) {   // and its pivots
+                    any = 0;
+#pragma unroll
+                    for (int s = 0; s < BMP_SLICES; ++s) c[s] = 0;
+                    if (++g < jb.ngroups) {
+                        gr = jb.groups[g];
+                        ns = bit_length(gr.size);
+                    }
+                }
+            }
+        }
+        u32 gcur = ~0u;
+        u64 G = 0;
+        for (u32 q0 = 0; q0 < jb.npivots; q0 += wy, ++round) {
+            const bool have = q0 + y < jb.npivots && active;
+            const u64* buf = hand_over(have, have ? jb.pivots[q0 + y].op : 0u, w);
+            if (y != 0) continue;
+            const u32 n = jb.npivots - q0 < wy ? jb.npivots - q0 : wy;
+            for (u32 j = 0; j < n; ++j) {
+                const KhBmpPivot pv = jb.pivots[q0 + j];
+                const u64 xx = buf[j * KH_WAVE + lane];
+                if (pv.group != gcur) {
+                    gcur = pv.group;
+                    G = active ? jb.present[(size_t)jb.groups[gcur].prow * jb.nwords + w] : 0;
+                }
+                u64 e0 = slices_equal(a, 0, asl);
+                for (u32 v = 0; v < jb.ngroups; ++v) {
+                    const u64 e1 = slices_equal(a, v + 1, asl);
+                    wave_add_to_bin(&bins[pv.abin0 + v], (u32)__builtin_popcountll(xx & ((G & e1) | (~G & e0))));
+                    e0 = e1;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    unsigned long long* rep = jb.hist + (size_t)(blockIdx.x % jb.reps) * nb;
+    for (u32 i = tid; i < nb; i += nt)
+        if (bins[i]) atomicAdd(&rep[i], (unsigned long long)bins[i]);
+}
+
 template <class K> void bmp_allow_lds(K kern, size_t bytes) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
@@ -312,4 +418,9 @@ void kh_launch_bmp_readout(const KhBmpJob& job, u32 grid, u32 waves, hipStream_t
     const size_t lds = kh_bmp_readout_lds_bytes(job.nbins, job.nops, waves);
     bmp_allow_lds(k_bmp_readout, lds);
     hipLaunchKernelGGL(k_bmp_readout, dim3(grid), dim3(KH_WAVE, waves), lds, st, job);
+}
+void kh_launch_bmp_pivot(const KhBmpPivotJob& job, u32 grid, u32 waves, hipStream_t st) {
+    const size_t lds = kh_bmp_readout_lds_bytes(job.nbins, job.nops, waves);
+    bmp_allow_lds(k_bmp_pivot, lds);
+    hipLaunchKernelGGL(k_bmp_pivot, dim3(grid), dim3(KH_WAVE, waves), lds, st, job);
 }

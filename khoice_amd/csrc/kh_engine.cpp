@@ -204,7 +204,7 @@ static const char* kClsNames[KC_COUNT] = {"extract_hist", "bucket_plan", "extrac
                                           "bucket_sort_rle", "range_bounds", "setop", "histogram",
                                           "remix", "copy_in", "union_tagged", "skm_scatter",
                                           "skm_regroup", "skm_union", "skm_big", "skm_pack", "skm_phased", "bmp_build",
-                                          "bmp_readout"};
+                                          "bmp_readout", "bmp_pivot"};
 
 // ------------------------------------------------------------------------------ ctx API
 extern "C" int kh_device_count(void) {
@@ -1992,6 +1992,131 @@ static int exp1_skm(kh_ctx* c, const Exp1In& in, uint64_t* within_hist, uint64_t
     *done = true;
     return KH_OK;
 }
+// What the presence-bitmap forms (exp1_bmp, exp2_bmp) share: the switches, the geometry of the build, the tables of
+// splits and operands, and the copy-in of the texts.
+static bool bmp_form_k(int k) {
+    int max_k = KH_BMP_MAX_K;
+    if (const char* e = getenv("KHOICE_BMP_MAX_K")) max_k = std::min(KH_BMP_INST_MAX_K, atoi(e));
+    // (KHOICE_NO_SKM: "the key arrays, please"; KHOICE_SKM_MIN_K lowered to this k: the super-k-mer form keeps it)
+    return !(k > max_k || getenv("KHOICE_NO_BMP") || getenv("KHOICE_NO_SKM") || skm_form_k(k));
+}
+struct BmpStage {
+    u64 nwords = 0, nsplits = 0, bases = 0;
+    u32 range_bits = 0, nranges = 0, tile_pos = 0;
+    u32 rwaves = 0, rgrid = 0;            // launch shape of the read-out
+    std::vector<KhBmpSplit> splits;       // (seq: filled in by bmp_copy_in)
+    std::vector<KhBmpOp> ops;
+    std::vector<u64> pack_off;            // where an operand's text goes in the packed copy
+    u64 seq_bytes = 0;
+    bool need_pack = false;
+};
+// nops operands (seqs / lens in operand order).  extra_rows: further bitmaps of nwords words the caller keeps beside
+// the partial ones, under the same budget.  *fits == false: the form declines.
+static int bmp_plan(kh_ctx* c, int k, int nops, const uint8_t* const* seqs, const uint64_t* lens, int on_device,
+                    u64 extra_rows, BmpStage* s, bool* fits) {
+    *fits = false;
+    // ---- geometry: ranges of the code space, tiles, splits
+    const u64 nwords = k >= 3 ? 1ull << (2 * k - 6) : 1;
+    u32 range_bits = KH_BMP_RANGE_BITS;
+    if (const char* e = getenv("KHOICE_BMP_RANGE_BITS")) range_bits = (u32)std::min(20, std::max(16, atoi(e)));   // experiments
+    range_bits = std::min<u32>(range_bits, (u32)std::max(6, 2 * k));
+    const u32 nranges = (u32)((nwords * 64) >> range_bits);
+    u32 tile_pos = KH_BMP_TILE;
+    if (const char* e = getenv("KHOICE_BMP_TILE_POS"))
+        tile_pos = std::min<u32>(KH_BMP_TILE, std::max<u32>(16, (u32)strtoul(e, nullptr, 10) & ~15u));
+    u64 bases = 0, maxpos = 0;
+    const u64 positions = kmer_positions(nops, lens, k, &bases);
+    for (int i = 0; i < nops; ++i) maxpos = std::max<u64>(maxpos, lens[i] >= (u64)k ? lens[i] - k + 1 : 0);
+    // Splits: genomes x splits x ranges is a small multiple of the CU count, but a split is long enough to pay for the
+    // words of its range that its workgroup clears and stores (one bit per position would be the break-even)
+    const u64 want_wgs = 4ull * (u64)std::max(1, c->cus);
+    const u64 want_splits = std::max<u64>(1, want_wgs / nranges);
+    u64 split_pos = std::max<u64>((positions + want_splits - 1) / want_splits, std::max<u64>(tile_pos, (1ull << range_bits) / 16));
+    if (const char* e = getenv("KHOICE_BMP_SPLIT_POS")) split_pos = std::max<u64>(16, strtoull(e, nullptr, 10));
+    split_pos = (split_pos + 15) & ~15ull;
+    auto count_splits = [&](u64 sp) {
+        u64 n = 0;
+        for (int i = 0; i < nops; ++i) {
+            const u64 npos = lens[i] >= (u64)k ? lens[i] - k + 1 : 0;
+            n += std::max<u64>(1, (npos + sp - 1) / sp);   // a genome without k-mers: one split, all zeros
+        }
+        return n;
+    };
+    HIPCHK(hipSetDevice(c->dev));
+    u64 budget = 1ull << 30;
+    {
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) budget = (free_b + c->pool.cached_bytes) / 4;
+    }
+    if (const char* e = getenv("KHOICE_BMP_MAX_BYTES")) budget = strtoull(e, nullptr, 10);
+    u64 nsplits = count_splits(split_pos);
+    while ((nsplits + extra_rows) * nwords * 8 > budget && split_pos < maxpos) {   // fewer, longer splits: fewer partial bitmaps
+        split_pos *= 2;
+        nsplits = count_splits(split_pos);
+    }
+    if ((nsplits + extra_rows) * nwords * 8 > budget || nsplits * nranges > 0x7fffffffull) return KH_OK;
+    const size_t lds_build = kh_bmp_build_lds_bytes(range_bits, tile_pos);
+    if (lds_build > 160u * 1024u) return KH_OK;
+    if (getenv("KHOICE_BMP_DEBUG"))
+        fprintf(stderr, "[bmp] k=%d range_bits=%u R=%u tile_pos=%u split_pos=%llu splits=%llu workgroups=%llu bitmap_bytes=%llu\n", k,
+                range_bits, nranges, tile_pos, (unsigned long long)split_pos, (unsigned long long)nsplits,
+                (unsigned long long)(nsplits * nranges), (unsigned long long)((nsplits + extra_rows) * nwords * 8));
+
+    // ---- tables: splits and operands
+    s->nwords = nwords; s->nsplits = nsplits; s->bases = bases;
+    s->range_bits = range_bits; s->nranges = nranges; s->tile_pos = tile_pos;
+    s->ops.resize(nops);
+    s->pack_off.resize(nops);
+    s->splits.reserve(nsplits);
+    for (int i = 0; i < nops; ++i) {
+        const u64 len = lens[i], npos = len >= (u64)k ? len - k + 1 : 0;
+        s->pack_off[i] = s->seq_bytes;
+        s->seq_bytes += (len + 15) & ~15ull;
+        if (!(on_device && (reinterpret_cast<uintptr_t>(seqs[i]) & 15) == 0)) s->need_pack = true;
+        s->ops[i].split0 = (u32)s->splits.size();
+        u64 p0 = 0;
+        do {
+            const u64 p1 = std::min(npos, p0 + split_pos);
+            s->splits.push_back(KhBmpSplit{nullptr, len, p0, p1, (u32)i, 0});
+            p0 = p1;
+        } while (p0 < npos);
+        s->ops[i].nsplits = (u32)s->splits.size() - s->ops[i].split0;
+    }
+    s->seq_bytes += 256;
+    // the read-out: a wave per 64 words and genome; where the words alone leave most of the chip idle (k <= 10: at
+    // most 256 blocks of 64 words) sixteen genomes are in flight per block, else four
+    const u64 rblocks = (nwords + 63) / 64;
+    s->rwaves = rblocks <= 256 ? 16u : 4u;
+    s->rgrid = (u32)std::min<u64>(rblocks, 8ull * (u64)std::max(1, c->cus));
+    *fits = true;
+    return KH_OK;
+}
+// the texts that are not resident and aligned go into d_seq (s->seq_bytes, where s->need_pack); every split learns its text
+static int bmp_copy_in(kh_ctx* c, BmpStage* s, const uint8_t* const* seqs, const uint64_t* lens, int on_device, u8* d_seq) {
+    for (size_t i = 0; i < s->ops.size(); ++i) {
+        const uint8_t* src = seqs[i];
+        const u8* dev = src;
+        if (!(on_device && (reinterpret_cast<uintptr_t>(src) & 15) == 0)) {
+            dev = d_seq + s->pack_off[i];
+            if (lens[i])
+                HIPCHK(hipMemcpyAsync(d_seq + s->pack_off[i], src, lens[i], on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->st));
+        }
+        for (u32 j = 0; j < s->ops[i].nsplits; ++j) s->splits[s->ops[i].split0 + j].seq = dev;
+    }
+    return KH_OK;
+}
+static KhBmpJob bmp_build_job(const BmpStage& s, int k, const KhBmpSplit* d_splits, u64* d_partial, unsigned long long* d_inst) {
+    KhBmpJob job{};
+    job.splits = d_splits;
+    job.partial = d_partial;
+    job.inst = d_inst;
+    job.nwords = s.nwords;
+    job.tile_pos = s.tile_pos;
+    job.range_bits = s.range_bits; job.nranges = s.nranges;
+    job.nops = (u32)s.ops.size();
+    job.k = k;
+    return job;
+}
 // The presence-bitmap form of the fused path (kh_bmp.hip) for k <= KH_BMP_MAX_K, histograms and distinct counts only: a
 // k-mer is a number below 4^k, so "which genomes hold it" is one bit per genome in a directly addressed bitmap.
 // k_bmp_build turns every split of a genome into a partial bitmap, k_bmp_readout counts over them with bit-sliced
@@ -2001,10 +2126,7 @@ static int exp1_bmp(kh_ctx* c, const Exp1In& in, uint64_t* within_hist, uint64_t
                     bool* done) {
     *done = false;
     const int k = in.k, nseq = in.nseq, ngroups = in.ngroups;
-    int max_k = KH_BMP_MAX_K;
-    if (const char* e = getenv("KHOICE_BMP_MAX_K")) max_k = std::min(KH_BMP_INST_MAX_K, atoi(e));
-    // (KHOICE_NO_SKM: "the key arrays, please"; KHOICE_SKM_MIN_K lowered to this k: the super-k-mer form keeps it)
-    if (k > max_k || getenv("KHOICE_NO_BMP") || getenv("KHOICE_NO_SKM") || skm_form_k(k)) return KH_OK;
+    if (!bmp_form_k(k)) return KH_OK;
     if ((u32)ngroups > KH_BMP_MAX_COUNT) return KH_OK;
     {
         std::vector<u32> gsize(ngroups, 0);
@@ -2018,138 +2140,54 @@ static int exp1_bmp(kh_ctx* c, const Exp1In& in, uint64_t* within_hist, uint64_t
     }
     TagLayout L;
     KHCHK(tag_layout(&L, nseq, in.group_of, ngroups, false));
+    std::vector<const uint8_t*> oseq(nseq);   // the operands: group-major order
+    std::vector<uint64_t> olen(nseq);
+    for (int i = 0; i < nseq; ++i) { oseq[i] = in.seqs[L.perm[i]]; olen[i] = in.lens[L.perm[i]]; }
+    BmpStage s;
+    bool fits = false;
+    KHCHK(bmp_plan(c, k, nseq, oseq.data(), olen.data(), in.on_device, 0, &s, &fits));
+    if (!fits) return KH_OK;
 
-    // ---- geometry: ranges of the code space, tiles, splits
-    const u64 nwords = k >= 3 ? 1ull << (2 * k - 6) : 1;
-    u32 range_bits = KH_BMP_RANGE_BITS;
-    if (const char* e = getenv("KHOICE_BMP_RANGE_BITS")) range_bits = (u32)std::min(20, std::max(16, atoi(e)));   // experiments
-    range_bits = std::min<u32>(range_bits, (u32)std::max(6, 2 * k));
-    const u32 nranges = (u32)((nwords * 64) >> range_bits);
-    u32 tile_pos = KH_BMP_TILE;
-    if (const char* e = getenv("KHOICE_BMP_TILE_POS"))
-        tile_pos = std::min<u32>(KH_BMP_TILE, std::max<u32>(16, (u32)strtoul(e, nullptr, 10) & ~15u));
-    u64 bases = 0, maxpos = 0;
-    const u64 positions = kmer_positions(nseq, in.lens, k, &bases);
-    for (int i = 0; i < nseq; ++i) maxpos = std::max<u64>(maxpos, in.lens[i] >= (u64)k ? in.lens[i] - k + 1 : 0);
-    // Splits: genomes x splits x ranges is a small multiple of the CU count, but a split is long enough to pay for the
-    // words of its range that its workgroup clears and stores (one bit per position would be the break-even)
-    const u64 want_wgs = 4ull * (u64)std::max(1, c->cus);
-    const u64 want_splits = std::max<u64>(1, want_wgs / nranges);
-    u64 split_pos = std::max<u64>((positions + want_splits - 1) / want_splits, std::max<u64>(tile_pos, (1ull << range_bits) / 16));
-    if (const char* e = getenv("KHOICE_BMP_SPLIT_POS")) split_pos = std::max<u64>(16, strtoull(e, nullptr, 10));
-    split_pos = (split_pos + 15) & ~15ull;
-    auto count_splits = [&](u64 sp) {
-        u64 n = 0;
-        for (int i = 0; i < nseq; ++i) {
-            const u64 npos = in.lens[i] >= (u64)k ? in.lens[i] - k + 1 : 0;
-            n += std::max<u64>(1, (npos + sp - 1) / sp);   // a genome without k-mers: one split, all zeros
-        }
-        return n;
-    };
-    HIPCHK(hipSetDevice(c->dev));
-    u64 budget = 1ull << 30;
-    {
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) budget = (free_b + c->pool.cached_bytes) / 4;
-    }
-    if (const char* e = getenv("KHOICE_BMP_MAX_BYTES")) budget = strtoull(e, nullptr, 10);
-    u64 nsplits = count_splits(split_pos);
-    while (nsplits * nwords * 8 > budget && split_pos < maxpos) {   // fewer, longer splits: fewer partial bitmaps
-        split_pos *= 2;
-        nsplits = count_splits(split_pos);
-    }
-    if (nsplits * nwords * 8 > budget || nsplits * nranges > 0x7fffffffull) return KH_OK;
-    const size_t lds_build = kh_bmp_build_lds_bytes(range_bits, tile_pos);
-    if (lds_build > 160u * 1024u) return KH_OK;
-    if (getenv("KHOICE_BMP_DEBUG"))
-        fprintf(stderr, "[bmp] k=%d range_bits=%u R=%u tile_pos=%u split_pos=%llu splits=%llu workgroups=%llu bitmap_bytes=%llu\n", k,
-                range_bits, nranges, tile_pos, (unsigned long long)split_pos, (unsigned long long)nsplits,
-                (unsigned long long)(nsplits * nranges), (unsigned long long)(nsplits * nwords * 8));
-
-    // ---- tables: splits, operands (group-major order), groups
     hipStream_t st = c->st;
-    std::vector<KhBmpSplit> splits;
-    std::vector<KhBmpOp> ops(nseq);
     std::vector<KhBmpGroup> groups(ngroups);
-    std::vector<u64> pack_off(nseq);
-    splits.reserve(nsplits);
-    u64 seq_bytes = 0;
-    bool need_pack = false;
-    for (int i = 0; i < nseq; ++i) {
-        const int src = L.perm[i];
-        const u64 len = in.lens[src], npos = len >= (u64)k ? len - k + 1 : 0;
-        pack_off[i] = seq_bytes;
-        seq_bytes += (len + 15) & ~15ull;
-        if (!(in.on_device && (reinterpret_cast<uintptr_t>(in.seqs[src]) & 15) == 0)) need_pack = true;
-        ops[i].split0 = (u32)splits.size();
-        u64 p0 = 0;
-        do {
-            const u64 p1 = std::min(npos, p0 + split_pos);
-            splits.push_back(KhBmpSplit{nullptr, len, p0, p1, (u32)i, 0});
-            p0 = p1;
-        } while (p0 < npos);
-        ops[i].nsplits = (u32)splits.size() - ops[i].split0;
-    }
-    seq_bytes += 256;
     for (int g = 0; g < ngroups; ++g) groups[g] = KhBmpGroup{(u32)L.gstart[g], (u32)L.gsize[g], L.bin0[g], 0};
     const u32 nb = L.nbins + (u32)nseq;   // the bins, then one distinct counter per operand
-    // the read-out: a wave per 64 words and genome; where the words alone leave most of the chip idle (k <= 10: at
-    // most 256 blocks of 64 words) sixteen genomes are in flight per block, else four
-    const u64 rblocks = (nwords + 63) / 64;
-    const u32 rwaves = rblocks <= 256 ? 16u : 4u;
-    const u32 rgrid = (u32)std::min<u64>(rblocks, 8ull * (u64)std::max(1, c->cus));
-    const u32 reps = std::min<u32>(rgrid, std::max<u32>(1, std::min<u32>(64, 65536u / nb)));
+    const u32 reps = std::min<u32>(s.rgrid, std::max<u32>(1, std::min<u32>(64, 65536u / nb)));
     // workspace: [hist: reps x nb u64][inst: nseq u64] (zeroed, read back) [splits][ops][groups] (one upload)
     const size_t off_inst = 8 * (size_t)reps * nb, off_splits = off_inst + 8 * (size_t)nseq,
-                 off_ops = off_splits + sizeof(KhBmpSplit) * splits.size(), off_groups = off_ops + sizeof(KhBmpOp) * (size_t)nseq,
+                 off_ops = off_splits + sizeof(KhBmpSplit) * s.splits.size(), off_groups = off_ops + sizeof(KhBmpOp) * (size_t)nseq,
                  ws_bytes = off_groups + sizeof(KhBmpGroup) * (size_t)ngroups;
     Tmp d_seq, d_ws, d_partial;
-    TMP_ALLOC(d_seq, c, need_pack ? seq_bytes : 256);
+    TMP_ALLOC(d_seq, c, s.need_pack ? s.seq_bytes : 256);
     TMP_ALLOC(d_ws, c, ws_bytes);
-    TMP_ALLOC(d_partial, c, (size_t)(nsplits * nwords * 8));
+    TMP_ALLOC(d_partial, c, (size_t)(s.nsplits * s.nwords * 8));
     const size_t up_bytes = ws_bytes - off_splits, down_bytes = off_splits;
     Pinned pin{c};
     PIN_ALLOC(pin, up_bytes + down_bytes + 64);
     u8* h_up = static_cast<u8*>(pin.p);
     u8* h_down = h_up + ((up_bytes + 63) & ~(size_t)63);
     c->prof_begin(KC_COPY_IN);
-    for (int i = 0; i < nseq; ++i) {
-        const uint8_t* src = in.seqs[L.perm[i]];
-        const u8* dev = src;
-        if (!(in.on_device && (reinterpret_cast<uintptr_t>(src) & 15) == 0)) {
-            dev = d_seq.as<u8>() + pack_off[i];
-            if (in.lens[L.perm[i]])
-                HIPCHK(hipMemcpyAsync(d_seq.as<u8>() + pack_off[i], src, in.lens[L.perm[i]],
-                                      in.on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
-        }
-        for (u32 s = 0; s < ops[i].nsplits; ++s) splits[ops[i].split0 + s].seq = dev;
-    }
-    memcpy(h_up, splits.data(), sizeof(KhBmpSplit) * splits.size());
-    memcpy(h_up + (off_ops - off_splits), ops.data(), sizeof(KhBmpOp) * (size_t)nseq);
+    KHCHK(bmp_copy_in(c, &s, oseq.data(), olen.data(), in.on_device, d_seq.as<u8>()));
+    memcpy(h_up, s.splits.data(), sizeof(KhBmpSplit) * s.splits.size());
+    memcpy(h_up + (off_ops - off_splits), s.ops.data(), sizeof(KhBmpOp) * (size_t)nseq);
     memcpy(h_up + (off_groups - off_splits), groups.data(), sizeof(KhBmpGroup) * (size_t)ngroups);
     u8* wsp = d_ws.as<u8>();
     HIPCHK(hipMemsetAsync(wsp, 0, off_splits, st));
     HIPCHK(hipMemcpyAsync(wsp + off_splits, h_up, up_bytes, hipMemcpyHostToDevice, st));
     c->prof_end();
 
-    KhBmpJob job;
-    job.splits = reinterpret_cast<const KhBmpSplit*>(wsp + off_splits);
+    KhBmpJob job = bmp_build_job(s, k, reinterpret_cast<const KhBmpSplit*>(wsp + off_splits), d_partial.as<u64>(),
+                                 reinterpret_cast<unsigned long long*>(wsp + off_inst));
     job.ops = reinterpret_cast<const KhBmpOp*>(wsp + off_ops);
     job.groups = reinterpret_cast<const KhBmpGroup*>(wsp + off_groups);
-    job.partial = d_partial.as<u64>();
-    job.inst = reinterpret_cast<unsigned long long*>(wsp + off_inst);
     job.hist = reinterpret_cast<unsigned long long*>(wsp);
-    job.nwords = nwords;
-    job.tile_pos = tile_pos;
-    job.range_bits = range_bits; job.nranges = nranges;
-    job.nops = (u32)nseq; job.ngroups = (u32)ngroups; job.nbins = L.nbins; job.abase = L.abase; job.reps = reps;
-    job.k = k;
+    job.ngroups = (u32)ngroups; job.nbins = L.nbins; job.abase = L.abase; job.reps = reps;
     c->prof_begin(KC_BMP_BUILD);
-    kh_launch_bmp_build(job, (u32)nsplits, st);
+    kh_launch_bmp_build(job, (u32)s.nsplits, st);
     c->prof_end();
     HIPCHK(hipGetLastError());
     c->prof_begin(KC_BMP_READOUT);
-    kh_launch_bmp_readout(job, rgrid, rwaves, st);
+    kh_launch_bmp_readout(job, s.rgrid, s.rwaves, st);
     c->prof_end();
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(h_down, wsp, down_bytes, hipMemcpyDeviceToHost, st));
@@ -2180,7 +2218,7 @@ static int exp1_bmp(kh_ctx* c, const Exp1In& in, uint64_t* within_hist, uint64_t
         dsum += d;
         if (distinct_per_seq) distinct_per_seq[L.perm[i]] = d;
     }
-    c->stat.bases += bases;
+    c->stat.bases += s.bases;
     c->stat.builds += nseq;
     c->stat.kmers += inst;
     c->stat.distinct += dsum;
@@ -2709,6 +2747,270 @@ extern "C" int kh_exp1_run(kh_ctx* c, int nseq, const uint8_t* const* seqs, cons
         if (done) return KH_OK;
     }
     return exp1_general(c, in, within_hist, across_hist, distinct_per_seq, group_sets, across_set);
+}
+
+// ------------------------------------------------------------------------------ fused experiment type 2
+struct Exp2In {   // the arguments of kh_exp2_run that both forms read
+    int nseq; const uint8_t* const* seqs; const uint64_t* lens; int on_device;
+    const int* group_of; int ngroups;
+    int npivots; const uint8_t* const* pivot_seqs; const uint64_t* pivot_lens; const int* pivot_group;
+    int k; u32 cs, hist_len;
+};
+struct Exp2Out {   // any of them may be NULL
+    uint64_t *within_hist, *across_hist, *within_only, *across_only, *distinct_per_seq, *distinct_per_pivot;
+    // occ[v] k-mers of pivot p occur in v genomes of its group (across == false) / in v other groups: what
+    // `intersect -ocsum` with the -cs{cs} union, then `transform histogram`, and `kmers_subtract` make of them
+    void add(const Exp2In& in, int p, bool across, u32 v, u64 occ) const {
+        uint64_t* hist = across ? across_hist : within_hist;
+        uint64_t* only = across ? across_only : within_only;
+        if (v == 0) {
+            if (only) only[p] += occ;
+        } else if (hist) {
+            hist[(size_t)p * in.hist_len + std::min(std::min(1 + std::min(v, in.cs), in.cs), in.hist_len - 1)] += occ;
+        }
+    }
+    void clear(const Exp2In& in) const {
+        for (uint64_t* h : {within_hist, across_hist})
+            if (h) memset(h, 0, 8 * (size_t)in.npivots * in.hist_len);
+        for (uint64_t* o : {within_only, across_only, distinct_per_pivot})
+            if (o) memset(o, 0, 8 * (size_t)in.npivots);
+        if (distinct_per_seq) memset(distinct_per_seq, 0, 8 * (size_t)in.nseq);
+    }
+};
+// The presence-bitmap form (kh_bmp.hip): the pivots are further operands of the unchanged k_bmp_build, k_bmp_pivot
+// counts every pivot's word against the bit-sliced counter of its group and against the counter over groups.  *done ==
+// false: the form does not apply (nothing was launched, no retry is counted).
+static int exp2_bmp(kh_ctx* c, const Exp2In& in, const Exp2Out& out, bool* done) {
+    *done = false;
+    const int k = in.k, nseq = in.nseq, ngroups = in.ngroups, npiv = in.npivots, nops = nseq + npiv;
+    if (!bmp_form_k(k) || (u32)ngroups > KH_BMP_MAX_COUNT) return KH_OK;
+    // ---- operands in group-major order: the genomes of a group, then its pivots
+    std::vector<KhBmpPivotGroup> groups(ngroups, KhBmpPivotGroup{0, 0, 0, 0, 0, 0});
+    for (int i = 0; i < nseq; ++i) groups[in.group_of[i]].size++;
+    for (int p = 0; p < npiv; ++p) groups[in.pivot_group[p]].npiv++;
+    u32 prows = 0;
+    u64 nbins = 0;
+    {
+        u32 first = 0, q0 = 0;
+        for (KhBmpPivotGroup& g : groups) {
+            if (g.size > KH_BMP_MAX_COUNT) return KH_OK;
+            g.first = first;
+            g.q0 = q0;
+            if (g.npiv) g.prow = prows++;
+            first += g.size + g.npiv;
+            q0 += g.npiv;
+            nbins += (u64)g.npiv * (g.size + 1 + (u32)ngroups);
+        }
+    }
+    if (nbins + (u64)nops > KH_BMP_MAX_BINS) return KH_OK;
+    std::vector<const uint8_t*> oseq(nops);
+    std::vector<uint64_t> olen(nops);
+    std::vector<int> op_of_seq(nseq), q_of_pivot(npiv);
+    std::vector<KhBmpPivot> pivots(npiv);
+    {
+        std::vector<u32> at(ngroups), qat(ngroups);
+        for (int g = 0; g < ngroups; ++g) { at[g] = groups[g].first; qat[g] = groups[g].q0; }
+        for (int i = 0; i < nseq; ++i) {
+            const u32 o = at[in.group_of[i]]++;
+            op_of_seq[i] = (int)o; oseq[o] = in.seqs[i]; olen[o] = in.lens[i];
+        }
+        for (int p = 0; p < npiv; ++p) {
+            const int g = in.pivot_group[p];
+            const u32 o = at[g]++, q = qat[g]++;
+            q_of_pivot[p] = (int)q; oseq[o] = in.pivot_seqs[p]; olen[o] = in.pivot_lens[p];
+            pivots[q] = KhBmpPivot{o, (u32)g, 0, 0};
+        }
+        u32 b = 0;
+        for (KhBmpPivot& pv : pivots) {
+            pv.bin0 = b;
+            pv.abin0 = b + groups[pv.group].size + 1;
+            b = pv.abin0 + (u32)ngroups;
+        }
+    }
+    BmpStage s;
+    bool fits = false;
+    KHCHK(bmp_plan(c, k, nops, oseq.data(), olen.data(), in.on_device, prows, &s, &fits));
+    if (!fits) return KH_OK;
+
+    hipStream_t st = c->st;
+    const u32 nb = (u32)nbins + (u32)nops;
+    const u32 reps = std::min<u32>(s.rgrid, std::max<u32>(1, std::min<u32>(64, 65536u / nb)));
+    // workspace: [hist: reps x nb u64][inst: nops u64] (zeroed, read back) [splits][ops][groups][pivots] (one upload)
+    const size_t off_inst = 8 * (size_t)reps * nb, off_splits = off_inst + 8 * (size_t)nops,
+                 off_ops = off_splits + sizeof(KhBmpSplit) * s.splits.size(), off_groups = off_ops + sizeof(KhBmpOp) * (size_t)nops,
+                 off_pivots = off_groups + sizeof(KhBmpPivotGroup) * (size_t)ngroups,
+                 ws_bytes = off_pivots + sizeof(KhBmpPivot) * (size_t)npiv;
+    Tmp d_seq, d_ws, d_partial, d_present;
+    TMP_ALLOC(d_seq, c, s.need_pack ? s.seq_bytes : 256);
+    TMP_ALLOC(d_ws, c, ws_bytes);
+    TMP_ALLOC(d_partial, c, (size_t)(s.nsplits * s.nwords * 8));
+    TMP_ALLOC(d_present, c, (size_t)(std::max<u64>(1, prows) * s.nwords * 8));
+    const size_t up_bytes = ws_bytes - off_splits, down_bytes = off_splits;
+    Pinned pin{c};
+    PIN_ALLOC(pin, up_bytes + down_bytes + 64);
+    u8* h_up = static_cast<u8*>(pin.p);
+    u8* h_down = h_up + ((up_bytes + 63) & ~(size_t)63);
+    c->prof_begin(KC_COPY_IN);
+    KHCHK(bmp_copy_in(c, &s, oseq.data(), olen.data(), in.on_device, d_seq.as<u8>()));
+    memcpy(h_up, s.splits.data(), sizeof(KhBmpSplit) * s.splits.size());
+    memcpy(h_up + (off_ops - off_splits), s.ops.data(), sizeof(KhBmpOp) * (size_t)nops);
+    memcpy(h_up + (off_groups - off_splits), groups.data(), sizeof(KhBmpPivotGroup) * (size_t)ngroups);
+    if (npiv) memcpy(h_up + (off_pivots - off_splits), pivots.data(), sizeof(KhBmpPivot) * (size_t)npiv);
+    u8* wsp = d_ws.as<u8>();
+    HIPCHK(hipMemsetAsync(wsp, 0, off_splits, st));
+    HIPCHK(hipMemcpyAsync(wsp + off_splits, h_up, up_bytes, hipMemcpyHostToDevice, st));
+    c->prof_end();
+
+    const KhBmpJob build = bmp_build_job(s, k, reinterpret_cast<const KhBmpSplit*>(wsp + off_splits), d_partial.as<u64>(),
+                                         reinterpret_cast<unsigned long long*>(wsp + off_inst));
+    KhBmpPivotJob job;
+    job.ops = reinterpret_cast<const KhBmpOp*>(wsp + off_ops);
+    job.groups = reinterpret_cast<const KhBmpPivotGroup*>(wsp + off_groups);
+    job.pivots = reinterpret_cast<const KhBmpPivot*>(wsp + off_pivots);
+    job.partial = d_partial.as<u64>();
+    job.present = d_present.as<u64>();
+    job.hist = reinterpret_cast<unsigned long long*>(wsp);
+    job.nwords = s.nwords;
+    job.nops = (u32)nops; job.ngroups = (u32)ngroups; job.npivots = (u32)npiv; job.nbins = (u32)nbins; job.reps = reps;
+    c->prof_begin(KC_BMP_BUILD);
+    kh_launch_bmp_build(build, (u32)s.nsplits, st);
+    c->prof_end();
+    HIPCHK(hipGetLastError());
+    c->prof_begin(KC_BMP_PIVOT);
+    kh_launch_bmp_pivot(job, s.rgrid, s.rwaves, st);
+    c->prof_end();
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(h_down, wsp, down_bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+
+    // ---- the replicas summed, the bins folded
+    const u64* h_hist = reinterpret_cast<const u64*>(h_down);
+    const u64* h_inst = reinterpret_cast<const u64*>(h_down + off_inst);
+    std::vector<u64> bins(nb, 0);
+    for (u32 r = 0; r < reps; ++r)
+        for (u32 b = 0; b < nb; ++b) bins[b] += h_hist[(size_t)r * nb + b];
+    out.clear(in);
+    u64 inst = 0, dsum = 0, held = 0;
+    for (int o = 0; o < nops; ++o) { inst += h_inst[o]; dsum += bins[nbins + o]; }
+    for (int i = 0; i < nseq; ++i)
+        if (out.distinct_per_seq) out.distinct_per_seq[i] = bins[nbins + op_of_seq[i]];
+    for (int p = 0; p < npiv; ++p) {
+        const KhBmpPivot& pv = pivots[q_of_pivot[p]];
+        if (out.distinct_per_pivot) out.distinct_per_pivot[p] = bins[nbins + pv.op];
+        for (u32 v = 0; v <= groups[pv.group].size; ++v) out.add(in, p, false, v, bins[pv.bin0 + v]);
+        for (u32 v = 0; v < (u32)ngroups; ++v) out.add(in, p, true, v, bins[pv.abin0 + v]);
+        held += bins[nbins + pv.op] - bins[pv.bin0];
+    }
+    c->stat.bases += s.bases;
+    c->stat.builds += nops;
+    c->stat.kmers += inst;
+    c->stat.distinct += dsum;
+    c->stat.setop_in += dsum;
+    c->stat.setop_out += held;   // pivot k-mers their own group holds
+    c->stat.setops++;
+    *done = true;
+    return KH_OK;
+}
+// The set form: the calls of exp_type_2.smk:289-507 on sets that stay in device memory — one batched plain build of
+// genomes and pivots, the -cs{cs} union of every group, set_counts 1, per pivot group the union of the other groups,
+// and intersect -ocsum / kmers_subtract of every pivot with both.
+static int exp2_sets(kh_ctx* c, const Exp2In& in, const Exp2Out& out) {
+    struct Bag {   // every intermediate set, freed on every way out
+        std::vector<kh_set*> v;
+        ~Bag() { for (kh_set* s : v) kh_set_free(s); }
+        kh_set** slot() { v.push_back(nullptr); return &v.back(); }
+    } bag;
+    const int nseq = in.nseq, ngroups = in.ngroups, npiv = in.npivots, n = nseq + npiv;
+    std::vector<const uint8_t*> seqs(in.seqs, in.seqs + nseq);
+    std::vector<uint64_t> lens(in.lens, in.lens + nseq);
+    seqs.insert(seqs.end(), in.pivot_seqs, in.pivot_seqs + npiv);
+    lens.insert(lens.end(), in.pivot_lens, in.pivot_lens + npiv);
+    bag.v.assign(n, nullptr);
+    KHCHK(kh_build_batch(c, n, seqs.data(), lens.data(), in.on_device, in.k, 1, KH_NO_MAX, KH_KMC_DEFAULT_CS, 0, bag.v.data()));
+    auto plain = [&](int i) { return bag.v[i]; };   // genomes, then pivots
+    out.clear(in);
+    for (int i = 0; i < nseq; ++i)
+        if (out.distinct_per_seq) out.distinct_per_seq[i] = plain(i)->n;
+    std::vector<int> has_pivot(ngroups, 0);
+    for (int p = 0; p < npiv; ++p) has_pivot[in.pivot_group[p]] = 1;
+    std::vector<kh_set*> unions(ngroups, nullptr), gsets(ngroups, nullptr), others(ngroups, nullptr);
+    for (int g = 0; g < ngroups; ++g) {
+        std::vector<const kh_set*> members;
+        for (int i = 0; i < nseq; ++i)
+            if (in.group_of[i] == g) members.push_back(plain(i));
+        kh_set** u = bag.slot();
+        KHCHK(kh_union_sum(c, members.data(), (int)members.size(), in.cs, u, nullptr, 0));
+        unions[g] = *u;
+        kh_set** gs = bag.slot();
+        KHCHK(kh_set_counts(c, unions[g], 1, gs));
+        gsets[g] = *gs;
+    }
+    for (int g = 0; g < ngroups && ngroups > 1; ++g) {
+        if (!has_pivot[g]) continue;
+        std::vector<const kh_set*> rest;
+        for (int h = 0; h < ngroups; ++h)
+            if (h != g) rest.push_back(gsets[h]);
+        kh_set** o = bag.slot();
+        KHCHK(kh_union_sum(c, rest.data(), (int)rest.size(), in.cs, o, nullptr, 0));
+        others[g] = *o;
+    }
+    std::vector<uint64_t> hist(in.hist_len);
+    for (int p = 0; p < npiv; ++p) {
+        const kh_set* pivot = plain(nseq + p);
+        const int g = in.pivot_group[p];
+        if (out.distinct_per_pivot) out.distinct_per_pivot[p] = pivot->n;
+        for (int across = 0; across < 2; ++across) {
+            const kh_set* other = across ? others[g] : unions[g];
+            uint64_t* h = across ? out.across_hist : out.within_hist;
+            uint64_t* only = across ? out.across_only : out.within_only;
+            if (!other) {   // one group: nothing to meet, the pivot's k-mers are all its own
+                if (only) only[p] = pivot->n;
+                continue;
+            }
+            if (h) {
+                Bag r;
+                KHCHK(kh_simple(c, pivot, other, KH_INTERSECT, KH_MODE_SUM, in.cs, r.slot()));
+                KHCHK(kh_histogram(c, r.v[0], hist.data(), in.hist_len));
+                memcpy(h + (size_t)p * in.hist_len, hist.data(), 8 * (size_t)in.hist_len);
+            }
+            if (only) {
+                Bag r;
+                KHCHK(kh_simple(c, pivot, other, KH_KMERS_SUBTRACT, KH_MODE_LEFT, in.cs, r.slot()));
+                only[p] = r.v[0]->n;
+            }
+        }
+    }
+    return KH_OK;
+}
+extern "C" int kh_exp2_run(kh_ctx* c, int nseq, const uint8_t* const* seqs, const uint64_t* lens, int on_device,
+                           const int* group_of, int ngroups, int npivots, const uint8_t* const* pivot_seqs,
+                           const uint64_t* pivot_lens, const int* pivot_group, int k, uint32_t cs, uint64_t* within_hist,
+                           uint64_t* across_hist, uint32_t hist_len, uint64_t* within_only, uint64_t* across_only,
+                           uint64_t* distinct_per_seq, uint64_t* distinct_per_pivot) {
+    if (!c || !seqs || !lens || !group_of || nseq <= 0 || ngroups <= 0 || npivots < 0 ||
+        (npivots && (!pivot_seqs || !pivot_lens || !pivot_group)))
+        return kh_fail(KH_E_ARG, "kh_exp2_run: bad argument");
+    if (hist_len < 2) return kh_fail(KH_E_ARG, "hist_len must be >= 2");
+    KHCHK(check_k(k));
+    if (cs < 1) return kh_fail(KH_E_ARG, "cs must be >= 1");
+    std::vector<int> gsize(ngroups, 0);
+    for (int i = 0; i < nseq; ++i) {
+        if (group_of[i] < 0 || group_of[i] >= ngroups)
+            return kh_fail(KH_E_ARG, "group_of[%d]=%d outside [0,%d)", i, group_of[i], ngroups);
+        gsize[group_of[i]]++;
+    }
+    for (int g = 0; g < ngroups; ++g)
+        if (!gsize[g]) return kh_fail(KH_E_ARG, "group %d has no sequences", g);
+    for (int p = 0; p < npivots; ++p)
+        if (pivot_group[p] < 0 || pivot_group[p] >= ngroups)
+            return kh_fail(KH_E_ARG, "pivot_group[%d]=%d outside [0,%d)", p, pivot_group[p], ngroups);
+    const Exp2In in{nseq, seqs, lens, on_device, group_of, ngroups, npivots, pivot_seqs, pivot_lens, pivot_group, k, cs, hist_len};
+    const Exp2Out out{within_hist, across_hist, within_only, across_only, distinct_per_seq, distinct_per_pivot};
+    HIPCHK(hipSetDevice(c->dev));
+    bool done = false;
+    KHCHK(exp2_bmp(c, in, out, &done));
+    if (done) return KH_OK;
+    return exp2_sets(c, in, out);
 }
 
 // ------------------------------------------------------------------------------ exchange form of steps 7-8

@@ -273,6 +273,29 @@ size_t kh_bmp_readout_lds_bytes(u32 nbins, u32 nops, u32 waves);
 void kh_launch_bmp_build(const KhBmpJob& job, u32 nsplits, hipStream_t st);   // nsplits * nranges workgroups
 void kh_launch_bmp_readout(const KhBmpJob& job, u32 grid, u32 waves, hipStream_t st);   // grid workgroups of `waves` waves walk the words
 
+// ---- experiment type 2 from the same bitmaps (k_bmp_pivot): the pivots are further operands of k_bmp_build, placed
+// behind the genomes of the group they were held out of.  Bins: per pivot (group-major order) size + 1 within-group
+// bins (count 0 .. size of its group) and ngroups across-group bins (count 0 .. ngroups - 1 of the OTHER groups), then
+// one distinct counter per operand.
+struct KhBmpPivotGroup {            // operands [first, first + size): genomes; [first + size, first + size + npiv): pivots
+    u32 first, size, npiv;
+    u32 q0;                         // the group's first pivot (group-major pivot number)
+    u32 prow;                       // its row of `present` (npiv != 0 only)
+    u32 pad;
+};
+struct KhBmpPivot { u32 op, group, bin0, abin0; };    // operand number, group, first within-group bin, first across-group bin
+struct KhBmpPivotJob {
+    const KhBmpOp* ops;             // [nops]
+    const KhBmpPivotGroup* groups;  // [ngroups]
+    const KhBmpPivot* pivots;       // [npivots]
+    const u64* partial;             // [splits][nwords], written by k_bmp_build
+    u64* present;                   // [groups with pivots][nwords] scratch: a word is stored and read back by one lane
+    unsigned long long* hist;       // [reps][nbins + nops] zeroed
+    u64 nwords;
+    u32 nops, ngroups, npivots, nbins, reps;
+};
+void kh_launch_bmp_pivot(const KhBmpPivotJob& job, u32 grid, u32 waves, hipStream_t st);   // launch shape and LDS of the read-out
+
 struct KhLookback {      // workspace of one ordered single-pass launch
     u64* desc;           // [nparts] tile descriptors, zeroed before launch
     u32* ticket;         // zeroed before launch

@@ -5,6 +5,7 @@ and offers the batched form on one resident engine.
 
     run(work_root, k_values, num_datasets)        rule-per-process through kmc / kmc_tools on PATH
     run_batched(...)                              same histogram files and CSVs, no process launches
+    run_fused(...)                                the same again from one kh_exp2_run per k: no set is kept
 
 Inputs: input_type_2/{rest_of_set/dataset_N/*.fna.gz, pivot/dataset_N/pivot_N.fna.gz}
 (staged out of DATABASE_ROOT at exp_type_2.smk:31-48 — data management, not k-mer work).
@@ -191,6 +192,42 @@ def run_batched(work_root: str, k_values: Sequence, num_datasets: int, device: i
                         d = os.path.join(work_root, f"{scope}_dataset_results_type_2/k_{k}/dataset_{num + 1}/{op}")
                         os.makedirs(d, exist_ok=True)
                         res.histogram_file(_hist_lines(res.counter_max()), os.path.join(d, f"dataset_{num + 1}_pivot_{op}_group.hist.txt"))
+    out = _csv_stage(work_root, k_values, num_datasets)
+    out["processes"] = 0
+    return out
+
+
+def run_fused(work_root: str, k_values: Sequence, num_datasets: int, device: int = 0):
+    """The files and CSVs of run_batched from one Engine.exp2_run per k (kh_exp2_run: presence bitmaps for k <= 12,
+    the set operations inside the library above): the texts are read once, the intersect histogram is the call's
+    within_hist / across_hist, the kmers_subtract histogram its within_only / across_only in line 1."""
+    from concurrent.futures import ThreadPoolExecutor
+    import numpy as np
+    from .. import engine as E
+    k_values = [str(k) for k in k_values]
+    prepare(work_root, k_values, num_datasets)
+    cs, lines = 5000, _hist_lines(5000)       # the -cs5000 unions give `simple` its counter range, as in run_batched
+    with E.Engine(device) as eng:
+        paths, owner = [], []
+        for num in range(1, num_datasets + 1):
+            for g in rest_of_set(work_root, num):
+                paths.append(os.path.join(work_root, f"input_type_2/rest_of_set/dataset_{num}/{g}.fna.gz"))
+                owner.append(num - 1)
+        pivot_paths = [os.path.join(work_root, f"input_type_2/pivot/dataset_{num}/pivot_{num}.fna.gz")
+                       for num in range(1, num_datasets + 1)]
+        with ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 1)) as pool:
+            texts = list(pool.map(eng.read_fasta, paths + pivot_paths))
+        for k in k_values:
+            res = eng.exp2_run(texts[:len(paths)], owner, texts[len(paths):], list(range(num_datasets)), int(k),
+                               cs=cs, hist_len=cs + 1)
+            for num in range(num_datasets):
+                for scope in ("within", "across") if num_datasets > 1 else ("within",):
+                    only = np.zeros(2, dtype=np.uint64)
+                    only[1] = res[f"{scope}_only"][num]
+                    for op, hist in (("intersect", res[f"{scope}_hist"][num]), ("subtract", only)):
+                        d = os.path.join(work_root, f"{scope}_dataset_results_type_2/k_{k}/dataset_{num + 1}/{op}")
+                        os.makedirs(d, exist_ok=True)
+                        eng.write_histogram_text(os.path.join(d, f"dataset_{num + 1}_pivot_{op}_group.hist.txt"), hist, lines)
     out = _csv_stage(work_root, k_values, num_datasets)
     out["processes"] = 0
     return out
