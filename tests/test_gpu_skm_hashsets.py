@@ -24,7 +24,9 @@ import numpy as np
 import pytest
 
 from oracle import c_oracle as CO
-from tests.util import mix_np, mixed_from_top32, random_dna, top32_np, unmix_np
+from tests import util
+from tests.util import (PAIRS, instances, mix_np, mixed_from_top32, random_dna, records_of, revcomp, skm_line, top32_np,
+                        unmix_np)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "khoice_amd", "csrc")
@@ -39,8 +41,6 @@ HASH_ROUNDS = 3            # KH_TUNE_HASH_ROUNDS: main-table probes of k_union_h
 UH_T2 = 512                # k_union_hash<512, 4096>: second table (T / 8)
 
 M32 = 0xFFFFFFFF
-COMP = {"A": "T", "C": "G", "G": "C", "T": "A"}
-PAIRS = [(5000, 80), (2, 5)]          # (cs, hist_len): nothing clamps / both clamp
 
 
 def minimizer_len(k):
@@ -73,10 +73,6 @@ def code_of(s):
     for ch in s:
         c = (c << 2) | "ACGT".index(ch)
     return c
-
-
-def revcomp(s):
-    return "".join(COMP[ch] for ch in reversed(s))
 
 
 def canon_of(s):
@@ -198,45 +194,18 @@ def filler_records(k, n, seed):
     return [random_dna(rng, k - m, "CGT") + "A" * m + random_dna(rng, k - m, "CGT") for _ in range(n)]
 
 
-# ---- genomes: halves, repeats, identical records
+# ---- genomes: halves, repeats, identical records (tests/util.py: shared with the two-word module)
 def two_kmer(s):
-    """A record of two k-mers, s and a neighbour, both holding A^m: s + C, or C + s when A^m starts s."""
-    return s + "C" if s.find("A" * minimizer_len(len(s))) > 0 else "C" + s
+    return util.two_kmer(s, minimizer_len(len(s)))
 
 
 def layout(keys, ngen, group_size, extra_records=()):
-    """Lone records of `keys` in ngen genomes (groups of group_size): key i in genome i % ngen; every third also in
-    genome (i + ngen // 2) % ngen (with 40 genomes: identical records in both halves of the 64-bit mask, which must
-    not merge); every even one again in its genome as its reverse complement (another record, the same key: a
-    repeat); every i % 4 == 1 again inside a two-k-mer record (two_kmer)."""
-    recs = [[] for _ in range(ngen)]
-    for i, s in enumerate(keys):
-        g = i % ngen
-        recs[g].append(s)
-        if i % 3 == 0:
-            recs[(g + ngen // 2) % ngen].append(s)
-        if i % 2 == 0:
-            recs[g].append(revcomp(s))
-        elif i % 4 == 1:
-            recs[g].append(two_kmer(s))
-    for j, r in enumerate(extra_records):
-        recs[(7 * j) % ngen].append(r)
-    return ["N".join(r).encode() for r in recs], [g // group_size for g in range(ngen)]
+    return util.skm_layout(keys, ngen, group_size, minimizer_len(len(keys[0])), extra_records)
 
 
 # ---- the inputs of each case (memoised: the CPU and the GPU tests use the same ones)
 _CACHE = {}
-
-
-def memo(fn):
-    def f(*a):
-        key = (fn.__name__,) + a
-        if key not in _CACHE:
-            _CACHE[key] = fn(*a)
-        return _CACHE[key]
-    f.__name__ = fn.__name__
-    f.__doc__ = fn.__doc__
-    return f
+memo = util.memo_in(_CACHE)
 
 
 UNION_K = [20, 24, 27, 31, 32]
@@ -355,14 +324,6 @@ def top32_case(k):
     return ["N".join(r).encode() for r in recs], [g // 16 for g in range(64)]
 
 
-def records_of(seqs, g):
-    return seqs[g].decode().split("N")
-
-
-def instances(seqs, k):
-    return sum(max(0, len(r) - k + 1) for g in range(len(seqs)) for r in records_of(seqs, g))
-
-
 # =========================================================================== CPU: the constructions
 def _src(name):
     with open(os.path.join(CSRC, name)) as fh:
@@ -475,8 +436,6 @@ def test_top32_family_preconditions(k):
 
 # =========================================================================== GPU
 KERNELS = ("skm_union", "skm_big", "skm_pack", "skm_phased", "union_tagged")
-SKM_SLOT = re.compile(r"\[skm\] k=(\d+) m=(\d+) .*slot: mean [\d.]+ max (\d+) cap (\d+) .*expanded: (\d+) k-mers \| "
-                      r"errors (\d+) spilled (\d+) overfull slots (\d+)")
 
 
 @pytest.fixture(scope="module")
@@ -490,47 +449,8 @@ def eng():
     e.close()
 
 
-def run(eng, seqs, group_of, k, cs, hist_len):
-    eng.profile(True)
-    st0 = eng.stats()
-    got = eng.exp1_run(seqs, group_of, k, cs=cs, hist_len=hist_len)
-    st1 = eng.stats()
-    eng.profile(False)
-    did = {n: st1["kernels"][n]["launches"] - st0["kernels"][n]["launches"] for n in KERNELS}
-    for n in ("retries", "big_slots"):
-        did[n] = st1[n] - st0[n]
-    return got, did
-
-
-def same(got, want):
-    for f in ("within_hist", "across_hist", "distinct_per_seq"):
-        assert got[f].shape == want[f].shape and (got[f] == want[f]).all(), f
-
-
 def check(eng, capfd, seqs, group_of, k, expect):
-    """The oracle's answer at every (cs, hist_len) of PAIRS, twice each with identical statistics; expect: {stat: n}
-    (exactly n) or {stat: (n, None)} (at least n).  Returns the engine's stderr of the first run of each pair."""
-    errs = []
-    for cs, hl in PAIRS:
-        want = CO.exp1(seqs, group_of, k, cs=cs, hist_len=hl)
-        capfd.readouterr()
-        got, did = run(eng, seqs, group_of, k, cs, hl)
-        errs.append(capfd.readouterr().err)
-        same(got, want)
-        for n, v in expect.items():
-            assert (did[n] >= v[0]) if isinstance(v, tuple) else (did[n] == v), (n, did, errs[-1][-3000:])
-        again, did2 = run(eng, seqs, group_of, k, cs, hl)
-        capfd.readouterr()
-        assert did2 == did
-        same(again, want)
-    return errs
-
-
-def skm_line(err):
-    lines = SKM_SLOT.findall(err)
-    assert len(lines) == 1, err
-    k, m, slot_max, cap, expanded, errors, spilled, overfull = (int(x) for x in lines[0])
-    return dict(k=k, m=m, slot_max=slot_max, cap=cap, expanded=expanded, errors=errors, spilled=spilled, overfull=overfull)
+    return util.exp1_check(eng, capfd, seqs, group_of, k, expect, KERNELS, ("retries", "big_slots"))
 
 
 UNION_ONLY = dict(skm_union=1, skm_big=0, skm_pack=0, skm_phased=0, union_tagged=0, retries=0, big_slots=0)

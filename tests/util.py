@@ -1,4 +1,6 @@
 """Shared helpers for the parity tests (oracle dict <-> engine arrays)."""
+import re
+
 import numpy as np
 
 MASK64 = (1 << 64) - 1
@@ -409,3 +411,111 @@ class Operand:
 def ref_hist(counts, hist_len):
     return np.bincount(np.minimum(np.asarray(counts, dtype=np.int64), hist_len - 1),
                        minlength=hist_len).astype(np.uint64)
+
+
+# ---------------------------------------------------------------- the hash-set modules of the super-k-mer form
+# What tests/test_gpu_skm_hashsets.py (one-word keys) and tests/test_gpu_skm2_hashsets.py (two-word keys) share: the
+# layout of chosen keys over genomes, the parser of the engine's [skm] debug line, and the comparison of one
+# kh_exp1_run call with the C restatement together with the kernels that did the work.
+COMP = {"A": "T", "C": "G", "G": "C", "T": "A"}
+PAIRS = [(5000, 80), (2, 5)]          # (cs, hist_len): nothing clamps / both clamp
+
+
+def revcomp(s):
+    return "".join(COMP[ch] for ch in reversed(s))
+
+
+def two_kmer(s, m):
+    """A record of two k-mers, s and a neighbour, both holding A^m: s + C, or C + s when A^m starts s."""
+    return s + "C" if s.find("A" * m) > 0 else "C" + s
+
+
+def skm_layout(keys, ngen, group_size, m, extra_records=()):
+    """Lone records of `keys` in ngen genomes (groups of group_size): key i in genome i % ngen; every third also in
+    genome (i + ngen // 2) % ngen (with 40 genomes: identical records in both halves of the 64-bit mask, which must
+    not merge); every even one again in its genome as its reverse complement (another record, the same key: a
+    repeat); every i % 4 == 1 again inside a two-k-mer record (two_kmer)."""
+    recs = [[] for _ in range(ngen)]
+    for i, s in enumerate(keys):
+        g = i % ngen
+        recs[g].append(s)
+        if i % 3 == 0:
+            recs[(g + ngen // 2) % ngen].append(s)
+        if i % 2 == 0:
+            recs[g].append(revcomp(s))
+        elif i % 4 == 1:
+            recs[g].append(two_kmer(s, m))
+    for j, r in enumerate(extra_records):
+        recs[(7 * j) % ngen].append(r)
+    return ["N".join(r).encode() for r in recs], [g // group_size for g in range(ngen)]
+
+
+def records_of(seqs, g):
+    return seqs[g].decode().split("N")
+
+
+def instances(seqs, k):
+    return sum(max(0, len(r) - k + 1) for g in range(len(seqs)) for r in records_of(seqs, g))
+
+
+def memo_in(cache):
+    """A decorator that keeps a case builder's results in `cache` (the CPU and the GPU tests use the same inputs)."""
+    def deco(fn):
+        def f(*a):
+            key = (fn.__name__,) + a
+            if key not in cache:
+                cache[key] = fn(*a)
+            return cache[key]
+        f.__name__ = fn.__name__
+        f.__doc__ = fn.__doc__
+        return f
+    return deco
+
+
+SKM_SLOT = re.compile(r"\[skm\] k=(\d+) m=(\d+) .*slot: mean [\d.]+ max (\d+) cap (\d+) .*expanded: (\d+) k-mers \| "
+                      r"errors (\d+) spilled (\d+) overfull slots (\d+)")
+
+
+def skm_line(err):
+    lines = SKM_SLOT.findall(err)
+    assert len(lines) == 1, err
+    k, m, slot_max, cap, expanded, errors, spilled, overfull = (int(x) for x in lines[0])
+    return dict(k=k, m=m, slot_max=slot_max, cap=cap, expanded=expanded, errors=errors, spilled=spilled, overfull=overfull)
+
+
+def exp1_run_stats(eng, seqs, group_of, k, cs, hist_len, kernels, counters):
+    """(result, {name: launches of the kernel class / growth of the counter during the call})"""
+    eng.profile(True)
+    st0 = eng.stats()
+    got = eng.exp1_run(seqs, group_of, k, cs=cs, hist_len=hist_len)
+    st1 = eng.stats()
+    eng.profile(False)
+    did = {n: st1["kernels"][n]["launches"] - st0["kernels"][n]["launches"] for n in kernels}
+    for n in counters:
+        did[n] = st1[n] - st0[n]
+    return got, did
+
+
+def exp1_same(got, want):
+    for f in ("within_hist", "across_hist", "distinct_per_seq"):
+        assert got[f].shape == want[f].shape and (got[f] == want[f]).all(), f
+
+
+def exp1_check(eng, capfd, seqs, group_of, k, expect, kernels, counters):
+    """The oracle's answer at every (cs, hist_len) of PAIRS, twice each with identical statistics; expect: {stat: n}
+    (exactly n) or {stat: (n, None)} (at least n).  Returns the engine's stderr of the first run of each pair."""
+    from oracle import c_oracle as CO
+    errs = []
+    for cs, hl in PAIRS:
+        want = CO.exp1(seqs, group_of, k, cs=cs, hist_len=hl)
+        capfd.readouterr()
+        got, did = exp1_run_stats(eng, seqs, group_of, k, cs, hl, kernels, counters)
+        errs.append(capfd.readouterr().err)
+        exp1_same(got, want)
+        for n, v in expect.items():
+            assert (did[n] >= v[0]) if isinstance(v, tuple) else (did[n] == v), (n, did, errs[-1][-3000:])
+        again, did2 = exp1_run_stats(eng, seqs, group_of, k, cs, hl, kernels, counters)
+        capfd.readouterr()
+        assert did2 == did
+        exp1_same(again, want)
+    return errs
