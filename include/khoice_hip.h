@@ -59,7 +59,8 @@ int kh_ctx_create(int device, kh_ctx **out);
 void kh_ctx_destroy(kh_ctx *ctx);
 const char *kh_last_error(void);
 int kh_device_count(void);
-/* JSON: device, op counts, bytes/keys processed, per-kernel-class time when profiling */
+/* JSON: device, op counts, bytes/keys processed, per-kernel-class time when profiling
+   (text_packed: bytes of sequence text copied into a batch buffer; a device text at a multiple of 16 adds none) */
 int kh_stats(kh_ctx *ctx, char *buf, size_t buflen);
 /* record HIP events around every kernel class (adds a sync when stats are read) */
 int kh_profile_enable(kh_ctx *ctx, int on);

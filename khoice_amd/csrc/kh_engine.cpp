@@ -285,9 +285,10 @@ extern "C" int kh_stats(kh_ctx* c, char* buf, size_t buflen) {
     snprintf(t, sizeof t, "\"device\":%d,\"arch\":\"%s\",\"cus\":%d,", c->dev, c->arch.c_str(), c->cus);
     s += t;
     snprintf(t, sizeof t,
-             "\"builds\":%llu,\"bases\":%llu,\"kmers\":%llu,\"distinct\":%llu,\"setops\":%llu,"
+             "\"builds\":%llu,\"bases\":%llu,\"text_packed\":%llu,\"kmers\":%llu,\"distinct\":%llu,\"setops\":%llu,"
              "\"setop_in\":%llu,\"setop_out\":%llu,\"retries\":%llu,\"order_fallbacks\":%llu,\"skm_records\":%llu,\"big_slots\":%llu,\"pool_bytes\":%zu,",
              (unsigned long long)c->stat.builds, (unsigned long long)c->stat.bases,
+             (unsigned long long)c->stat.text_packed,
              (unsigned long long)c->stat.kmers, (unsigned long long)c->stat.distinct,
              (unsigned long long)c->stat.setops, (unsigned long long)c->stat.setop_in,
              (unsigned long long)c->stat.setop_out, (unsigned long long)c->stat.retries,
@@ -553,6 +554,7 @@ static int build_once(kh_ctx* c, int nseq, const uint8_t* const* seqs, const uin
         if (!lens[i]) continue;
         HIPCHK(hipMemcpyAsync(d_seq.as<u8>() + pack_off[i], seqs[i], lens[i],
                               on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+        c->stat.text_packed += lens[i];
     }
     // Start order of pass C (KhBucketWork): buckets of up to 64 consecutive segments are
     // interleaved (bucket 0 of each, bucket 1 of each, ...), every segment writes into its own
@@ -1850,6 +1852,7 @@ static int skm_prepare(kh_ctx* c, int nseq, const uint8_t* const* seqs, const ui
         if (!segs[i].len) continue;
         HIPCHK(hipMemcpyAsync(s->d_seq.as<u8>() + pack_off[i], src, segs[i].len,
                               on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+        c->stat.text_packed += segs[i].len;
     }
     memcpy(h_up + (off_segs - off_ginfo), segs.data(), sizeof(KhSeg) * nseq);
     if (ntiles) memcpy(h_up + (off_tiles - off_ginfo), tiles.data(), sizeof(KhTile) * (size_t)ntiles);
@@ -2098,8 +2101,10 @@ static int bmp_copy_in(kh_ctx* c, BmpStage* s, const uint8_t* const* seqs, const
         const u8* dev = src;
         if (!(on_device && (reinterpret_cast<uintptr_t>(src) & 15) == 0)) {
             dev = d_seq + s->pack_off[i];
-            if (lens[i])
+            if (lens[i]) {
                 HIPCHK(hipMemcpyAsync(d_seq + s->pack_off[i], src, lens[i], on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->st));
+                c->stat.text_packed += lens[i];
+            }
         }
         for (u32 j = 0; j < s->ops[i].nsplits; ++j) s->splits[s->ops[i].split0 + j].seq = dev;
     }

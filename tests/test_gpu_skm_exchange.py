@@ -106,9 +106,10 @@ def test_decode_follows_insert_chunk():
 
 # ---------------------------------------------------------------------------------------------------- one simulated job
 class Job:
-    """R ranks packed on device 0 with the geometry they agreed on (dist.across_records_exchange)."""
+    """R ranks packed on device 0 with the geometry they agreed on (dist.across_records_exchange).  feed[r]: the form in
+    which rank r's texts are handed to the pack ((device pointer, length) pairs; default: the host bytes of `ranks`)."""
 
-    def __init__(self, eng, ranks, k, positions_max=None, fan_max=None):
+    def __init__(self, eng, ranks, k, positions_max=None, fan_max=None, feed=None):
         self.eng, self.ranks, self.k, self.R = eng, ranks, k, len(ranks)
         pmax = max(positions(s, k) for s, _ in ranks)
         self.positions_max = max(pmax, positions_max or 0)
@@ -116,14 +117,14 @@ class Job:
         self.nslots, self.spp, self.cap = eng.skm_exchange_plan(k, self.positions_max, self.fan_max, self.R)
         R, cap, spp, dev = self.R, self.cap, self.spp, torch.device("cuda", 0)
         self.rec, self.msk, self.cnt, self.off, self.part_n = [], [], [], [], []
-        for seqs, tags in ranks:
+        for r, (seqs, tags) in enumerate(ranks):
             rec = torch.full((R, cap, 2), POISON_REC, dtype=torch.int64, device=dev)
             msk = torch.full((R, cap), POISON_MASK, dtype=torch.int32, device=dev)
             cnt = torch.full((R, spp), POISON_TABLE, dtype=torch.int32, device=dev)
             off = torch.full((R, spp), POISON_TABLE, dtype=torch.int32, device=dev)
             torch.cuda.synchronize(dev)
-            pn = eng.skm_pack(seqs, tags, k, self.nslots, R, cap, rec.data_ptr(), msk.data_ptr(), cnt.data_ptr(),
-                              off.data_ptr())
+            pn = eng.skm_pack(feed[r] if feed else seqs, tags, k, self.nslots, R, cap, rec.data_ptr(), msk.data_ptr(),
+                              cnt.data_ptr(), off.data_ptr())
             self.rec.append(rec), self.msk.append(msk), self.cnt.append(cnt), self.off.append(off)
             self.part_n.append([int(x) for x in pn])
 

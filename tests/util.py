@@ -519,3 +519,74 @@ def exp1_check(eng, capfd, seqs, group_of, k, expect, kernels, counters):
         assert did2 == did
         exp1_same(again, want)
     return errs
+
+
+# ---------------------------------------------------------------- device-resident texts, read where they lie
+# tests/test_gpu_device_texts.py: the texts of a case lie in ONE array of random bases (the arena) at chosen byte
+# offsets from 256-byte aligned addresses, so a kernel that reads past a text's end reads valid bases of the same
+# allocation: an over-read shows as extra k-mers, never as a fault.
+ARENA_ALIGNED = (0, 16)          # offsets from a 256-aligned base that the library reads in place (pointer mod 16 == 0)
+ARENA_UNALIGNED = (1, 8, 15)     # offsets it packs with a device-to-device copy
+ARENA_TAIL = 4096                # bytes of the arena behind the end of the last text, at least
+ARENA_MAX = 1 << 20
+
+
+def canon_positions(text, k):
+    """The canonical code of every k-mer position of a text of ACGT, in order (rolling; plain ints, any k)."""
+    val = {65: 0, 67: 1, 71: 2, 84: 3}
+    mask, top = (1 << (2 * k)) - 1, 2 * (k - 1)
+    fw = rc = 0
+    out = []
+    for i, b in enumerate(text):
+        v = val[b]
+        fw = ((fw << 2) | v) & mask
+        rc = (rc >> 2) | ((3 - v) << top)
+        if i >= k - 1:
+            out.append(min(fw, rc))
+    return out
+
+
+class Arena:
+    """texts[i] (bytes, or None for the text given as pointer 0 with length 0) at offset classes[i] from a 256-byte
+    aligned address of its own; behind[i] (a byte value or None) is written right behind the text.  host: the arena;
+    at[i]: the text's offset in it (None for a None text)."""
+
+    def __init__(self, texts, classes, behind, seed):
+        rng = np.random.default_rng(seed)
+        self.texts, self.at, cursor = list(texts), [], 256
+        for t, c in zip(texts, classes):
+            if t is None:
+                self.at.append(None)
+                continue
+            self.at.append(((cursor + 255) & ~255) + c)
+            cursor = self.at[-1] + len(t) + 64
+        self.host = np.frombuffer(random_dna_np(rng, cursor + ARENA_TAIL + 256), dtype=np.uint8).copy()
+        for t, a, f in zip(texts, self.at, behind):
+            if t is None:
+                continue
+            self.host[a:a + len(t)] = np.frombuffer(t, dtype=np.uint8)
+            if f is not None:
+                self.host[a + len(t)] = f
+        self.dev = None
+
+    def upload(self):
+        """The arena in one device tensor whose first byte is 256-byte aligned -> [(pointer, length)] of the texts."""
+        import torch
+        n = self.host.shape[0]
+        dev = torch.from_numpy(self.host).to("cuda:0")
+        shift = (-dev.data_ptr()) & 255
+        if shift:                                    # offsets are counted from a 256-byte aligned address
+            dev2 = torch.empty(n + 256, dtype=torch.uint8, device="cuda:0")
+            shift = (-dev2.data_ptr()) & 255
+            dev2[shift:shift + n] = dev
+            dev = dev2
+        torch.cuda.synchronize()
+        self.dev, self.shift = dev, shift
+        base = dev.data_ptr() + shift
+        assert base % 256 == 0
+        return [(0, 0) if t is None else (base + a, len(t)) for t, a in zip(self.texts, self.at)]
+
+    def download(self):
+        import torch
+        torch.cuda.synchronize()
+        return self.dev[self.shift:self.shift + self.host.shape[0]].cpu().numpy()
