@@ -272,6 +272,41 @@ int kh_exp2_run(kh_ctx *ctx, int nseq, const uint8_t *const *seqs, const uint64_
                 uint64_t *within_only, uint64_t *across_only,
                 uint64_t *distinct_per_seq, uint64_t *distinct_per_pivot);
 
+/* ---------------------------------------------------------------- fused experiment type 4
+ * The device side of exp_type_4.smk:139-303 for one k on resident sequences: every pivot against the rest-of-set
+ * union of EVERY dataset (group), summed into one confusion-matrix row per pivot as src/merge_lists.py:101-141 does.
+ * Replaces per k: `kmc` per genome and pivot (:143,152), `set_counts 1` per genome (:164-168), the -cs{cs} `complex`
+ * union per dataset (:183) and its `transform histogram` (:191-196), `set_counts 1` of the unions (:205-209), the D x D
+ * `simple intersect -ocsum` databases (:226-228), every `dump -s` (:247-271) and the dictionaries of
+ * src/merge_lists.py:14-33.
+ *   seqs, lens, group_of, ngroups   the rest_of_set genomes, as for kh_exp1_run; every group needs a genome
+ *   pivot_seqs, pivot_lens          npivots pivot texts (host or device like seqs), each compared against ALL groups;
+ *                                   npivots need not equal ngroups and may be 0
+ *   within_hist [ngroups * hist_len]   histogram of the -cs{cs} union of group g: bins and clamps of kh_exp1_run
+ *   rows [npivots * ngroups], unique_pivot_count [npivots]
+ *                                   what kh_confusion_row returns for pivot p built with ci = 1, no cx and
+ *                                   counters saturating at pivot_cs (KH_KMC_DEFAULT_CS in the workflow) against the
+ *                                   `set_counts 1` unions of the groups: k-mers in ascending canonical key order,
+ *                                   1/len(M) then * count, one rounding each, no contraction
+ *                                   (src/merge_lists.py:122-141).  Bit-exact: the order of the sum is part of the contract.
+ *   distinct_per_seq [nseq], distinct_per_pivot [npivots]   distinct canonical k-mers of every text
+ * Any output may be NULL.  KH_E_ARG: a group outside [0, ngroups), a group without genome, hist_len < 2, k outside
+ * 1..64, cs == 0, pivot_cs == 0.
+ *
+ * Forms, the same numbers in each: k <= 12 and at most 64 groups presence bitmaps (kh_bmp.hip: the pivots are further
+ * genomes of the bitmap build; their multiplicities are added up in tables of 4^k cells, and one kernel writes a
+ * (membership mask, count) record per pivot k-mer in code order, which IS the dump order: nothing is sorted); otherwise,
+ * and whenever the bitmaps do not fit (1023 genomes per group, 4096 bins and counters, a pivot of 2^32 positions, the
+ * memory budget), builds, unions and the membership search on sets in device memory, whose keys the host sorts.
+ * Switches as for kh_exp1_run: KHOICE_NO_BMP, KHOICE_NO_SKM, KHOICE_BMP_MAX_K, KHOICE_BMP_MAX_BYTES. */
+int kh_exp4_run(kh_ctx *ctx, int nseq, const uint8_t *const *seqs, const uint64_t *lens, int on_device,
+                const int *group_of, int ngroups,
+                int npivots, const uint8_t *const *pivot_seqs, const uint64_t *pivot_lens,
+                int k, uint32_t cs, uint32_t pivot_cs,
+                uint64_t *within_hist, uint32_t hist_len,      /* [ngroups * hist_len] */
+                double *rows, uint64_t *unique_pivot_count,    /* [npivots * ngroups], [npivots] */
+                uint64_t *distinct_per_seq, uint64_t *distinct_per_pivot);
+
 /* ---------------------------------------------------------------- multi-GPU exchange (RCCL over xGMI)
  * Steps 7-8 of exp_type_1.smk:243-259 when the groups are sharded over several GPUs, one process
  * per GPU: every rank runs kh_exp1_run on its own groups asking for `across_set` (counter = number

@@ -15,6 +15,8 @@
 // There is no genome mask: any number of genomes and groups (up to 1023 per counter) is answered in one pass.
 //   k_bmp_pivot    experiment type 2 with the walk of k_bmp_readout: pivot genomes are further operands of the build;
 //                  a pivot's word masks the counter of its group and the counter over groups (see at the kernel).
+//   k_bmp_count, k_bmp_present, k_bmp_member   experiment type 4: the pivots' multiplicities, the groups' presence
+//                  words, and one (membership mask, count) record per pivot k-mer in code order (see at the kernels).
 #include "kh_device.h"
 #include "kh_launch.h"
 
@@ -383,12 +385,204 @@ __global__ __launch_bounds__(1024) void k_bmp_pivot(const KhBmpPivotJob jb) {
         if (bins[i]) atomicAdd(&rep[i], (unsigned long long)bins[i]);
 }
 
+// ------------------------------------------------------------------------------------------
+// experiment type 4: k_bmp_count, k_bmp_present, k_bmp_member
+// ------------------------------------------------------------------------------------------
+// k_bmp_count: how often every code occurs in a pivot.  A workgroup owns one split of a pivot and walks it with the
+// staging of k_bmp_build, all positions, no ranges and no bitmap in LDS: one device-scope add of 1 per valid position
+// into the pivot's table of 4^k cells, result unused.  The cells do not saturate; they are clamped where they are read.
+// LDS: [code: tile_pos / 16 + 1 u32][bad16: tile_pos / 16 + 1 u16]
+template <int K>
+__global__ __launch_bounds__(BMP_NT) void k_bmp_count(const KhBmpMemberJob jb) {
+    extern __shared__ __attribute__((aligned(16))) u8 lds_raw[];
+    const u32 tid = threadIdx.x;
+    const KhBmpSplit sp = jb.splits[jb.psplit0 + blockIdx.x];
+    const u32 twords = jb.tile_pos / BMP_CHUNK;
+    u32* code = reinterpret_cast<u32*>(lds_raw);
+    u16* bad16 = reinterpret_cast<u16*>(code + twords + 1);
+    u32* cnt = jb.cnt + (size_t)(sp.op - jb.ngenomes) * jb.ncells;
+    constexpr u32 KMASK = (1u << (2 * K)) - 1u;
+    const u32 swords = twords + 1;
+    kh_u32x4 pre[BMP_FETCH];
+    auto fetch = [&](const u64 t0) {
+#pragma unroll
+        for (u32 i = 0; i < BMP_FETCH; ++i) {
+            const u32 w = tid + i * BMP_NT;
+            pre[i] = codes_fetch(sp.seq, sp.len, t0 + 16ull * w, w < swords, jb.splits);
+        }
+    };
+    if (sp.p0 < sp.p1) fetch(sp.p0);
+    for (u64 t0 = sp.p0; t0 < sp.p1; t0 += jb.tile_pos) {
+        __syncthreads();                                         // the last tile has been read
+#pragma unroll
+        for (u32 i = 0; i < BMP_FETCH; ++i) {
+            const u32 w = tid + i * BMP_NT;
+            u32 codes, bad;
+            codes_decode(pre[i], sp.seq, sp.len, t0 + 16ull * w, codes, bad);
+            if (w < swords) {
+                code[w] = codes;
+                bad16[w] = (u16)bad;
+            }
+        }
+        __syncthreads();
+        if (t0 + jb.tile_pos < sp.p1) fetch(t0 + jb.tile_pos);
+        const u64 tend = t0 + jb.tile_pos < sp.p1 ? t0 + jb.tile_pos : sp.p1;
+        const u32 nch = (u32)((tend - t0 + BMP_CHUNK - 1) / BMP_CHUNK);
+        for (u32 c = tid; c < nch; c += BMP_NT) {
+            const u64 cw = (u64)code[c] | ((u64)code[c + 1] << 32);   // as in k_bmp_build
+            u32 inv = (u32)bad16[c] | ((u32)bad16[c + 1] << 16);
+            {
+                u32 w = 1;
+#pragma unroll
+                for (int s = 0; s < 3; ++s)
+                    if (2 * w <= (u32)K) { inv |= inv >> w; w *= 2; }
+                inv |= inv >> ((u32)K - w);
+            }
+            const u32 valid = ~inv & 0xffffu;
+            if (!valid) continue;
+            const u64 fwd = kh_revpairs64(cw);
+            const u64 rcw = ~cw;
+#pragma unroll
+            for (u32 j = 0; j < BMP_CHUNK; ++j) {
+                const u32 fw = (u32)(fwd >> (64 - 2 * (j + K))) & KMASK;
+                const u32 rc = (u32)(rcw >> (2 * j)) & KMASK;
+                if ((valid >> j) & 1u) atomicAdd(&cnt[fw < rc ? fw : rc], 1u);
+            }
+        }
+    }
+}
+
+// k_bmp_present: launch shape, LDS layout and walk of k_bmp_readout over the genomes (group-major), then the pivots.
+// A genome's word goes into its group's counter and into `any`; behind the group's last genome the bins of the counter
+// are added and `any` is stored to present[group] (every group, every word: nothing is cleared beforehand).  A
+// pivot's word is stored to pword[pivot], and the wave's popcount sum to blk[pivot][block of 64 words]: one writer per
+// word and per block, nothing atomic.  No counter over groups.
+__global__ __launch_bounds__(1024) void k_bmp_present(const KhBmpMemberJob jb) {
+    extern __shared__ __attribute__((aligned(16))) u8 lds_raw[];
+    u32* bins = reinterpret_cast<u32*>(lds_raw);
+    const u32 nb = jb.nbins + jb.nops;
+    u64* gx = reinterpret_cast<u64*>(lds_raw + ((4 * (size_t)nb + 15) & ~(size_t)15));   // [2][wy][64]
+    const u32 lane = threadIdx.x, y = threadIdx.y, wy = blockDim.y;
+    const u32 tid = y * KH_WAVE + lane, nt = wy * KH_WAVE;
+    for (u32 i = tid; i < nb; i += nt) bins[i] = 0;
+    __syncthreads();
+    u32 round = 0;
+    for (u64 wb = blockIdx.x; wb * KH_WAVE < jb.nwords; wb += gridDim.x) {
+        const u64 w = wb * KH_WAVE + lane;
+        const bool active = w < jb.nwords;
+        u32 g = 0;
+        KhBmpGroup gr = jb.groups[0];
+        u32 ns = bit_length(gr.size);
+        u64 c[BMP_SLICES], any = 0;
+#pragma unroll
+        for (int s = 0; s < BMP_SLICES; ++s) c[s] = 0;
+        for (u32 i0 = 0; i0 < jb.nops; i0 += wy, ++round) {
+            u64 x = 0;
+            if (i0 + y < jb.nops && active) {
+                const KhBmpOp op = jb.ops[i0 + y];
+                const u64* p = jb.partial + (size_t)op.split0 * jb.nwords + w;
+#pragma unroll 8
+                for (u32 s = 0; s < op.nsplits; ++s) x |= p[(size_t)s * jb.nwords];
+            }
+            u64* buf = gx + (size_t)(round & 1u) * wy * KH_WAVE;
+            buf[y * KH_WAVE + lane] = x;
+            __syncthreads();
+            if (y != 0) continue;
+            const u32 n = jb.nops - i0 < wy ? jb.nops - i0 : wy;
+            for (u32 j = 0; j < n; ++j) {
+                const u32 i = i0 + j;
+                const u64 xx = buf[j * KH_WAVE + lane];
+                const u32 sum = wave_scan_add((u32)__builtin_popcountll(xx));   // lane 63: the wave's distinct codes
+                if (lane == KH_WAVE - 1 && sum) atomicAdd(&bins[jb.nbins + i], sum);
+                if (i >= jb.ngenomes) {
+                    const u32 p = i - jb.ngenomes;
+                    if (active) jb.pword[(size_t)p * jb.nwords + w] = xx;
+                    if (lane == KH_WAVE - 1) jb.blk[(size_t)p * jb.nblocks + wb] = sum;
+                    continue;
+                }
+                any |= xx;
+                slices_add(c, xx, ns);
+                if (i + 1 == gr.first + gr.size) {   // the group is complete
+                    for (u32 v = 1; v <= gr.size; ++v)
+                        wave_add_to_bin(&bins[gr.bin0 + v], (u32)__builtin_popcountll(slices_equal(c, v, ns)));
+                    if (active) jb.present[(size_t)g * jb.nwords + w] = any;
+                    any = 0;
+#pragma unroll
+                    for (int s = 0; s < BMP_SLICES; ++s) c[s] = 0;
+                    if (++g < jb.ngroups) {
+                        gr = jb.groups[g];
+                        ns = bit_length(gr.size);
+                    }
+                }
+            }
+        }
+    }
+    __syncthreads();
+    unsigned long long* rep = jb.hist + (size_t)(blockIdx.x % jb.reps) * nb;
+    for (u32 i = tid; i < nb; i += nt)
+        if (bins[i]) atomicAdd(&rep[i], (unsigned long long)bins[i]);
+}
+
+// k_bmp_member: the records of a pivot in ascending code order.  blockDim = (64, BMP_MEMBER_WAVES); a workgroup owns
+// BMP_MEMBER_RUN consecutive blocks of 64 words of one pivot (blockIdx.y), a wave one block at a time, a lane one word.
+// Rank of a word's first record: the pivot's distinct codes in front of the run (blk, written by k_bmp_present, summed
+// by the whole workgroup in the prologue), the blocks of the run in front of this one, and the exclusive wave scan of
+// the popcounts.  The lane keeps its `present` words in LDS only to index them by group without scratch: it reads back
+// what it stored itself, so no barrier guards them.
+// LDS: [pres: waves x ngroups x 64 u64][part: waves u32][run: BMP_MEMBER_RUN u32]
+constexpr u32 BMP_MEMBER_WAVES = 4;
+constexpr u32 BMP_MEMBER_RUN = 16;
+__global__ __launch_bounds__(BMP_MEMBER_WAVES * KH_WAVE) void k_bmp_member(const KhBmpMemberJob jb) {
+    extern __shared__ __attribute__((aligned(16))) u8 lds_raw[];
+    const u32 lane = threadIdx.x, y = threadIdx.y, tid = y * KH_WAVE + lane;
+    u64* pres = reinterpret_cast<u64*>(lds_raw) + (size_t)y * jb.ngroups * KH_WAVE;
+    u32* part = reinterpret_cast<u32*>(lds_raw + 8 * (size_t)BMP_MEMBER_WAVES * jb.ngroups * KH_WAVE);
+    u32* run = part + BMP_MEMBER_WAVES;
+    const u32 p = blockIdx.y;
+    const u32 b0 = blockIdx.x * BMP_MEMBER_RUN, b1 = b0 + BMP_MEMBER_RUN < jb.nblocks ? b0 + BMP_MEMBER_RUN : jb.nblocks;
+    const u32* blk = jb.blk + (size_t)p * jb.nblocks;
+    u32 s = 0;
+    for (u32 i = tid; i < b0; i += BMP_MEMBER_WAVES * KH_WAVE) s += blk[i];
+    s = wave_scan_add(s);
+    if (lane == KH_WAVE - 1) part[y] = s;
+    if (tid < b1 - b0) run[tid] = blk[b0 + tid];
+    __syncthreads();
+    u32 front = 0;
+    for (u32 i = 0; i < BMP_MEMBER_WAVES; ++i) front += part[i];
+    const u32* cnt = jb.cnt + (size_t)p * jb.ncells;
+    const u64 r0 = jb.rec_off[p];
+    for (u32 b = b0 + y; b < b1; b += BMP_MEMBER_WAVES) {
+        u32 base = front;
+        for (u32 i = b0; i < b; ++i) base += run[i - b0];
+        const u64 w = (u64)b * KH_WAVE + lane;
+        const bool active = w < jb.nwords;
+        u64 pw = active ? jb.pword[(size_t)p * jb.nwords + w] : 0;
+        for (u32 d = 0; d < jb.ngroups; ++d) pres[d * KH_WAVE + lane] = active ? jb.present[(size_t)d * jb.nwords + w] : 0;
+        const u32 pc = (u32)__builtin_popcountll(pw);
+        u64 r = r0 + base + (wave_scan_add(pc) - pc);
+        while (pw) {
+            const u32 bit = (u32)__builtin_ctzll(pw);
+            pw &= pw - 1;
+            u64 m = 0;
+            for (u32 d = 0; d < jb.ngroups; ++d) m |= ((pres[d * KH_WAVE + lane] >> bit) & 1ull) << d;
+            const u32 n = cnt[64 * w + bit];
+            jb.rec_mask[r] = m;
+            jb.rec_count[r] = n < jb.pivot_cs ? n : jb.pivot_cs;
+            ++r;
+        }
+    }
+}
+
 template <class K> void bmp_allow_lds(K kern, size_t bytes) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
 template <int K> void launch_build(const KhBmpJob& job, u32 nsplits, size_t lds, hipStream_t st) {
     bmp_allow_lds(k_bmp_build<K>, lds);
     hipLaunchKernelGGL(k_bmp_build<K>, dim3(nsplits * job.nranges), dim3(BMP_NT), lds, st, job);
+}
+
+template <int K> void launch_count(const KhBmpMemberJob& job, size_t lds, hipStream_t st) {
+    hipLaunchKernelGGL(k_bmp_count<K>, dim3(job.npsplits), dim3(BMP_NT), lds, st, job);
 }
 
 }   // namespace
@@ -423,4 +617,30 @@ void kh_launch_bmp_pivot(const KhBmpPivotJob& job, u32 grid, u32 waves, hipStrea
     const size_t lds = kh_bmp_readout_lds_bytes(job.nbins, job.nops, waves);
     bmp_allow_lds(k_bmp_pivot, lds);
     hipLaunchKernelGGL(k_bmp_pivot, dim3(grid), dim3(KH_WAVE, waves), lds, st, job);
+}
+size_t kh_bmp_member_lds_bytes(u32 ngroups) {
+    return 8 * (size_t)BMP_MEMBER_WAVES * ngroups * KH_WAVE + 4 * (size_t)(BMP_MEMBER_WAVES + BMP_MEMBER_RUN);
+}
+void kh_launch_bmp_count(const KhBmpMemberJob& job, hipStream_t st) {
+    if (!job.npsplits) return;
+    const size_t lds = ((size_t)(job.tile_pos / BMP_CHUNK + 1) * 6 + 15) & ~(size_t)15;   // 24 KiB at most
+    switch (job.k) {
+#define BMP_K(KK) case KK: launch_count<KK>(job, lds, st); break;
+        BMP_K(1) BMP_K(2) BMP_K(3) BMP_K(4) BMP_K(5) BMP_K(6) BMP_K(7) BMP_K(8) BMP_K(9) BMP_K(10) BMP_K(11) BMP_K(12)
+        BMP_K(13)
+#undef BMP_K
+        default: break;
+    }
+}
+void kh_launch_bmp_present(const KhBmpMemberJob& job, u32 grid, u32 waves, hipStream_t st) {
+    const size_t lds = kh_bmp_readout_lds_bytes(job.nbins, job.nops, waves);
+    bmp_allow_lds(k_bmp_present, lds);
+    hipLaunchKernelGGL(k_bmp_present, dim3(grid), dim3(KH_WAVE, waves), lds, st, job);
+}
+void kh_launch_bmp_member(const KhBmpMemberJob& job, hipStream_t st) {
+    if (!job.npivots) return;
+    const size_t lds = kh_bmp_member_lds_bytes(job.ngroups);
+    bmp_allow_lds(k_bmp_member, lds);
+    hipLaunchKernelGGL(k_bmp_member, dim3((job.nblocks + BMP_MEMBER_RUN - 1) / BMP_MEMBER_RUN, job.npivots),
+                       dim3(KH_WAVE, BMP_MEMBER_WAVES), lds, st, job);
 }

@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <thread>
 #include <chrono>
 #include <cmath>
 #include <memory>
@@ -204,7 +205,7 @@ static const char* kClsNames[KC_COUNT] = {"extract_hist", "bucket_plan", "extrac
                                           "bucket_sort_rle", "range_bounds", "setop", "histogram",
                                           "remix", "copy_in", "union_tagged", "skm_scatter",
                                           "skm_regroup", "skm_union", "skm_big", "skm_pack", "skm_phased", "bmp_build",
-                                          "bmp_readout", "bmp_pivot"};
+                                          "bmp_readout", "bmp_pivot", "bmp_count", "bmp_present", "bmp_member"};
 
 // ------------------------------------------------------------------------------ ctx API
 extern "C" int kh_device_count(void) {
@@ -1280,23 +1281,22 @@ extern "C" int kh_membership(kh_ctx* c, const kh_set* pivot, const kh_set* const
 // up: k-mers in dump order; for a k-mer with count c held by the sets M (ascending index, the
 // order update_dictionary appends them, :26-33), row[m] += 1 / len(M) * c for m in M;
 // unique_pivot_count = sum of c over the k-mers no set holds (:122-126).
-extern "C" int kh_confusion_row(kh_ctx* c, const kh_set* pivot, const kh_set* const* sets, int nsets,
-                                double* row, uint64_t* unique_pivot_count) {
+// The sum itself, shared by kh_confusion_row and kh_exp4_run: record r (ascending canonical key) is masks[i * nwords ..]
+// and counts[i] with i = order ? order[r] : r.  One rounding per operation, no contraction, every partial sum stored.
+static void confusion_sum(const u64* masks, const u32* counts, const u32* order, u64 n, u32 nwords, int nsets,
+                          double* row, uint64_t* unique_pivot_count) {
 #pragma clang fp contract(off)
-    if (!row || !unique_pivot_count) return kh_fail(KH_E_ARG, "kh_confusion_row: NULL output");
-    Membership m;
-    KHCHK(membership_compute(c, pivot, sets, nsets, m));
     for (int d = 0; d < nsets; ++d) row[d] = 0.0;
     u64 uniq = 0;
-    for (u64 r = 0; r < pivot->n; ++r) {
-        const u64 i = m.order[r];
+    for (u64 r = 0; r < n; ++r) {
+        const u64 i = order ? order[r] : r;
         int len = 0;
-        for (u32 w = 0; w < m.nwords; ++w) len += __builtin_popcountll(m.masks[i * m.nwords + w]);
-        if (!len) { uniq += m.counts[i]; continue; }
+        for (u32 w = 0; w < nwords; ++w) len += __builtin_popcountll(masks[i * nwords + w]);
+        if (!len) { uniq += counts[i]; continue; }
         const double share = 1.0 / (double)len;              // Python: 1 / len(matches)
-        const double add = share * (double)m.counts[i];      //         ... * count
-        for (u32 w = 0; w < m.nwords; ++w) {
-            u64 bits = m.masks[i * m.nwords + w];
+        const double add = share * (double)counts[i];        //         ... * count
+        for (u32 w = 0; w < nwords; ++w) {
+            u64 bits = masks[i * nwords + w];
             while (bits) {
                 const int d = __builtin_ctzll(bits);
                 bits &= bits - 1;
@@ -1306,6 +1306,13 @@ extern "C" int kh_confusion_row(kh_ctx* c, const kh_set* pivot, const kh_set* co
         }
     }
     *unique_pivot_count = uniq;
+}
+extern "C" int kh_confusion_row(kh_ctx* c, const kh_set* pivot, const kh_set* const* sets, int nsets,
+                                double* row, uint64_t* unique_pivot_count) {
+    if (!row || !unique_pivot_count) return kh_fail(KH_E_ARG, "kh_confusion_row: NULL output");
+    Membership m;
+    KHCHK(membership_compute(c, pivot, sets, nsets, m));
+    confusion_sum(m.masks.data(), m.counts.data(), m.order.data(), pivot->n, m.nwords, nsets, row, unique_pivot_count);
     return KH_OK;
 }
 
@@ -3016,6 +3023,287 @@ extern "C" int kh_exp2_run(kh_ctx* c, int nseq, const uint8_t* const* seqs, cons
     KHCHK(exp2_bmp(c, in, out, &done));
     if (done) return KH_OK;
     return exp2_sets(c, in, out);
+}
+
+// ------------------------------------------------------------------------------ fused experiment type 4
+struct Exp4In {   // the arguments of kh_exp4_run that both forms read
+    int nseq; const uint8_t* const* seqs; const uint64_t* lens; int on_device;
+    const int* group_of; int ngroups;
+    int npivots; const uint8_t* const* pivot_seqs; const uint64_t* pivot_lens;
+    int k; u32 cs, pivot_cs, hist_len;
+};
+struct Exp4Out {   // any of them may be NULL
+    uint64_t* within_hist; double* rows; uint64_t *unique_pivot_count, *distinct_per_seq, *distinct_per_pivot;
+    void set_row(const Exp4In& in, int p, const double* row, uint64_t uniq) const {
+        if (rows) memcpy(rows + (size_t)p * in.ngroups, row, sizeof(double) * (size_t)in.ngroups);
+        if (unique_pivot_count) unique_pivot_count[p] = uniq;
+    }
+};
+// The presence-bitmap form (kh_bmp.hip): genomes (group-major) and pivots are the operands of the unchanged
+// k_bmp_build; k_bmp_count adds up the pivots' multiplicities, k_bmp_present leaves the within-group bins, the groups'
+// presence words and the pivots' words, k_bmp_member writes every pivot's (mask, count) records in code order, which is
+// the `dump -s` order: the host only copies them and sums.  *done == false: the form does not apply (nothing was
+// launched, no retry is counted).
+static int exp4_bmp(kh_ctx* c, const Exp4In& in, const Exp4Out& out, bool* done) {
+    *done = false;
+    const int k = in.k, nseq = in.nseq, ngroups = in.ngroups, npiv = in.npivots, nops = nseq + npiv;
+    if (!bmp_form_k(k) || (u32)ngroups > KH_BMP_MEMBER_GROUPS) return KH_OK;
+    // ---- operands: the genomes in group-major order, then the pivots
+    std::vector<KhBmpGroup> groups(ngroups, KhBmpGroup{0, 0, 0, 0});
+    for (int i = 0; i < nseq; ++i) groups[in.group_of[i]].size++;
+    u64 nbins = 0;
+    {
+        u32 first = 0;
+        for (KhBmpGroup& g : groups) {
+            if (g.size > KH_BMP_MAX_COUNT) return KH_OK;
+            g.first = first;
+            g.bin0 = (u32)nbins;
+            first += g.size;
+            nbins += g.size + 1;
+        }
+    }
+    if (nbins + (u64)nops > KH_BMP_MAX_BINS) return KH_OK;
+    std::vector<const uint8_t*> oseq(nops);
+    std::vector<uint64_t> olen(nops);
+    std::vector<int> op_of_seq(nseq);
+    {
+        std::vector<u32> at(ngroups);
+        for (int g = 0; g < ngroups; ++g) at[g] = groups[g].first;
+        for (int i = 0; i < nseq; ++i) {
+            const u32 o = at[in.group_of[i]]++;
+            op_of_seq[i] = (int)o; oseq[o] = in.seqs[i]; olen[o] = in.lens[i];
+        }
+        for (int p = 0; p < npiv; ++p) { oseq[nseq + p] = in.pivot_seqs[p]; olen[nseq + p] = in.pivot_lens[p]; }
+    }
+    // ---- memory beside the partial bitmaps, in rows of one bitmap: present, pword, the count tables (32 rows each:
+    // 4^k cells of 4 bytes) and the records (12 bytes each, at most one per position and per code of a pivot)
+    const u64 nwords = k >= 3 ? 1ull << (2 * k - 6) : 1, ncells = 64 * nwords, ncodes = 1ull << (2 * k);
+    std::vector<u64> rec_off(std::max(1, npiv), 0);
+    u64 nrec_max = 0;
+    for (int p = 0; p < npiv; ++p) {
+        const u64 npos = in.pivot_lens[p] >= (u64)k ? in.pivot_lens[p] - k + 1 : 0;
+        if (npos >> 32) return KH_OK;   // (the cells of the count table are 32 bits wide)
+        rec_off[p] = nrec_max;
+        nrec_max += std::min(npos, ncodes);
+    }
+    const u64 extra_rows = (u64)ngroups + 33ull * (u64)npiv + (12 * nrec_max + 8 * nwords - 1) / (8 * nwords);
+    BmpStage s;
+    bool fits = false;
+    KHCHK(bmp_plan(c, k, nops, oseq.data(), olen.data(), in.on_device, extra_rows, &s, &fits));
+    if (!fits) return KH_OK;
+
+    hipStream_t st = c->st;
+    const u32 nb = (u32)nbins + (u32)nops, nblocks = (u32)((nwords + 63) / 64);
+    const u32 reps = std::min<u32>(s.rgrid, std::max<u32>(1, std::min<u32>(64, 65536u / nb)));
+    // workspace: [hist: reps x nb u64][inst: nops u64] (zeroed, read back) [splits][ops][groups][rec_off] (one upload)
+    const size_t off_inst = 8 * (size_t)reps * nb, off_splits = off_inst + 8 * (size_t)nops,
+                 off_ops = off_splits + sizeof(KhBmpSplit) * s.splits.size(), off_groups = off_ops + sizeof(KhBmpOp) * (size_t)nops,
+                 off_rec = (off_groups + sizeof(KhBmpGroup) * (size_t)ngroups + 7) & ~(size_t)7,
+                 ws_bytes = off_rec + 8 * rec_off.size();
+    Tmp d_seq, d_ws, d_partial, d_present, d_pword, d_cnt, d_blk, d_rmask, d_rcount;
+    TMP_ALLOC(d_seq, c, s.need_pack ? s.seq_bytes : 256);
+    TMP_ALLOC(d_ws, c, ws_bytes);
+    TMP_ALLOC(d_partial, c, (size_t)(s.nsplits * s.nwords * 8));
+    TMP_ALLOC(d_present, c, (size_t)((u64)ngroups * nwords * 8));
+    TMP_ALLOC(d_pword, c, (size_t)(std::max<u64>(1, npiv) * nwords * 8));
+    TMP_ALLOC(d_cnt, c, (size_t)(std::max<u64>(1, npiv) * ncells * 4));
+    TMP_ALLOC(d_blk, c, (size_t)(std::max<u64>(1, npiv) * nblocks * 4));
+    TMP_ALLOC(d_rmask, c, (size_t)(std::max<u64>(1, nrec_max) * 8));
+    TMP_ALLOC(d_rcount, c, (size_t)(std::max<u64>(1, nrec_max) * 4));
+    const size_t up_bytes = ws_bytes - off_splits, down_bytes = off_splits;
+    Pinned pin{c};
+    PIN_ALLOC(pin, up_bytes + down_bytes + 64);
+    u8* h_up = static_cast<u8*>(pin.p);
+    u8* h_down = h_up + ((up_bytes + 63) & ~(size_t)63);
+    c->prof_begin(KC_COPY_IN);
+    KHCHK(bmp_copy_in(c, &s, oseq.data(), olen.data(), in.on_device, d_seq.as<u8>()));
+    memset(h_up, 0, up_bytes);
+    memcpy(h_up, s.splits.data(), sizeof(KhBmpSplit) * s.splits.size());
+    memcpy(h_up + (off_ops - off_splits), s.ops.data(), sizeof(KhBmpOp) * (size_t)nops);
+    memcpy(h_up + (off_groups - off_splits), groups.data(), sizeof(KhBmpGroup) * (size_t)ngroups);
+    memcpy(h_up + (off_rec - off_splits), rec_off.data(), 8 * rec_off.size());
+    u8* wsp = d_ws.as<u8>();
+    HIPCHK(hipMemsetAsync(wsp, 0, off_splits, st));
+    if (npiv) HIPCHK(hipMemsetAsync(d_cnt.b->p, 0, (size_t)((u64)npiv * ncells * 4), st));
+    HIPCHK(hipMemcpyAsync(wsp + off_splits, h_up, up_bytes, hipMemcpyHostToDevice, st));
+    c->prof_end();
+
+    const KhBmpJob build = bmp_build_job(s, k, reinterpret_cast<const KhBmpSplit*>(wsp + off_splits), d_partial.as<u64>(),
+                                         reinterpret_cast<unsigned long long*>(wsp + off_inst));
+    KhBmpMemberJob job{};
+    job.splits = build.splits;
+    job.ops = reinterpret_cast<const KhBmpOp*>(wsp + off_ops);
+    job.groups = reinterpret_cast<const KhBmpGroup*>(wsp + off_groups);
+    job.partial = d_partial.as<u64>();
+    job.present = d_present.as<u64>();
+    job.pword = d_pword.as<u64>();
+    job.cnt = d_cnt.as<u32>();
+    job.blk = d_blk.as<u32>();
+    job.hist = reinterpret_cast<unsigned long long*>(wsp);
+    job.rec_off = reinterpret_cast<const u64*>(wsp + off_rec);
+    job.rec_mask = d_rmask.as<u64>();
+    job.rec_count = d_rcount.as<u32>();
+    job.nwords = nwords; job.ncells = ncells;
+    job.nops = (u32)nops; job.ngenomes = (u32)nseq; job.ngroups = (u32)ngroups; job.npivots = (u32)npiv;
+    job.nbins = (u32)nbins; job.reps = reps; job.nblocks = nblocks;
+    job.psplit0 = npiv ? s.ops[nseq].split0 : (u32)s.nsplits;
+    job.npsplits = (u32)s.nsplits - job.psplit0;
+    job.tile_pos = s.tile_pos; job.pivot_cs = in.pivot_cs; job.k = k;
+    c->prof_begin(KC_BMP_BUILD);
+    kh_launch_bmp_build(build, (u32)s.nsplits, st);
+    c->prof_end();
+    HIPCHK(hipGetLastError());
+    if (npiv) {
+        c->prof_begin(KC_BMP_COUNT);
+        kh_launch_bmp_count(job, st);
+        c->prof_end();
+        HIPCHK(hipGetLastError());
+    }
+    c->prof_begin(KC_BMP_PRESENT);
+    kh_launch_bmp_present(job, s.rgrid, s.rwaves, st);
+    c->prof_end();
+    HIPCHK(hipGetLastError());
+    if (npiv) {
+        c->prof_begin(KC_BMP_MEMBER);
+        kh_launch_bmp_member(job, st);
+        c->prof_end();
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipMemcpyAsync(h_down, wsp, down_bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+
+    // ---- the replicas summed, the bins folded as exp1_bmp folds them
+    const u64* h_hist = reinterpret_cast<const u64*>(h_down);
+    const u64* h_inst = reinterpret_cast<const u64*>(h_down + off_inst);
+    std::vector<u64> bins(nb, 0);
+    for (u32 r = 0; r < reps; ++r)
+        for (u32 b = 0; b < nb; ++b) bins[b] += h_hist[(size_t)r * nb + b];
+    auto bin_of = [&](u32 cnt) { return std::min<u32>(std::min<u32>(cnt, in.cs), in.hist_len - 1); };
+    if (out.within_hist) {
+        memset(out.within_hist, 0, 8 * (size_t)ngroups * in.hist_len);
+        for (int g = 0; g < ngroups; ++g)
+            for (u32 cnt = 1; cnt <= groups[g].size; ++cnt)
+                out.within_hist[(size_t)g * in.hist_len + bin_of(cnt)] += bins[groups[g].bin0 + cnt];
+    }
+    u64 inst = 0, dsum = 0, nrec = 0;
+    for (int o = 0; o < nops; ++o) { inst += h_inst[o]; dsum += bins[nbins + o]; }
+    for (int i = 0; i < nseq; ++i)
+        if (out.distinct_per_seq) out.distinct_per_seq[i] = bins[nbins + op_of_seq[i]];
+    std::vector<u64> h_off(std::max(1, npiv), 0);   // the records in host memory: packed, the exact numbers
+    for (int p = 0; p < npiv; ++p) {
+        const u64 n = bins[nbins + nseq + p];
+        if (out.distinct_per_pivot) out.distinct_per_pivot[p] = n;
+        if (n > (p + 1 < npiv ? rec_off[p + 1] : nrec_max) - rec_off[p])
+            return kh_fail(KH_E_INTERNAL, "exp4_bmp: pivot %d has %llu records, more than its positions", p, (unsigned long long)n);
+        h_off[p] = nrec;
+        nrec += n;
+    }
+    // ---- every pivot's records copied, then summed in order: the pivots are independent, a few host threads share them
+    if (npiv && nrec && (out.rows || out.unique_pivot_count)) {
+        Pinned rpin{c};
+        const size_t off_cnt = (8 * (size_t)nrec + 63) & ~(size_t)63;
+        PIN_ALLOC(rpin, off_cnt + 4 * (size_t)nrec + 64);
+        u64* h_mask = static_cast<u64*>(rpin.p);
+        u32* h_cnt = reinterpret_cast<u32*>(static_cast<u8*>(rpin.p) + off_cnt);
+        for (int p = 0; p < npiv; ++p) {
+            const u64 n = bins[nbins + nseq + p];
+            if (!n) continue;
+            HIPCHK(hipMemcpyAsync(h_mask + h_off[p], job.rec_mask + rec_off[p], 8 * (size_t)n, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpyAsync(h_cnt + h_off[p], job.rec_count + rec_off[p], 4 * (size_t)n, hipMemcpyDeviceToHost, st));
+        }
+        HIPCHK(hipStreamSynchronize(st));
+        std::atomic<int> next{0};
+        auto work = [&]() {
+            std::vector<double> row(ngroups);
+            for (int p = next.fetch_add(1); p < npiv; p = next.fetch_add(1)) {
+                uint64_t uniq = 0;
+                confusion_sum(h_mask + h_off[p], h_cnt + h_off[p], nullptr, bins[nbins + nseq + p], 1, ngroups, row.data(), &uniq);
+                out.set_row(in, p, row.data(), uniq);
+            }
+        };
+        std::vector<std::thread> pool;
+        for (int t = 1; t < std::min(16, npiv); ++t) pool.emplace_back(work);
+        work();
+        for (std::thread& t : pool) t.join();
+    } else {
+        const std::vector<double> zero(ngroups, 0.0);
+        for (int p = 0; p < npiv; ++p) out.set_row(in, p, zero.data(), 0);
+    }
+    c->stat.bases += s.bases;
+    c->stat.builds += nops;
+    c->stat.kmers += inst;
+    c->stat.distinct += dsum;
+    c->stat.setop_in += dsum;
+    c->stat.setop_out += nrec;   // membership records
+    c->stat.setops++;
+    *done = true;
+    return KH_OK;
+}
+// The set form: the calls of workflow/exp_type_4.py::run_batched on sets that stay in device memory — one batched plain
+// build of the genomes, one counted build of the pivots, the -cs{cs} union of every group with its histogram,
+// set_counts 1, and per pivot the membership search and the sum of kh_confusion_row.
+static int exp4_sets(kh_ctx* c, const Exp4In& in, const Exp4Out& out) {
+    struct Bag {   // every intermediate set, freed on every way out
+        std::vector<kh_set*> v;
+        ~Bag() { for (kh_set* s : v) kh_set_free(s); }
+    } plain, pivots, unions, gsets;
+    const int nseq = in.nseq, ngroups = in.ngroups, npiv = in.npivots;
+    plain.v.assign(nseq, nullptr);
+    KHCHK(kh_build_batch(c, nseq, in.seqs, in.lens, in.on_device, in.k, 1, KH_NO_MAX, KH_KMC_DEFAULT_CS, 0, plain.v.data()));
+    pivots.v.assign(npiv, nullptr);
+    if (npiv)
+        KHCHK(kh_build_batch(c, npiv, in.pivot_seqs, in.pivot_lens, in.on_device, in.k, 1, KH_NO_MAX, in.pivot_cs, 1, pivots.v.data()));
+    for (int i = 0; i < nseq; ++i)
+        if (out.distinct_per_seq) out.distinct_per_seq[i] = plain.v[i]->n;
+    unions.v.assign(ngroups, nullptr);
+    gsets.v.assign(ngroups, nullptr);
+    for (int g = 0; g < ngroups; ++g) {
+        std::vector<const kh_set*> members;
+        for (int i = 0; i < nseq; ++i)
+            if (in.group_of[i] == g) members.push_back(plain.v[i]);
+        KHCHK(kh_union_sum(c, members.data(), (int)members.size(), in.cs, &unions.v[g],
+                           out.within_hist ? out.within_hist + (size_t)g * in.hist_len : nullptr, out.within_hist ? in.hist_len : 0));
+        KHCHK(kh_set_counts(c, unions.v[g], 1, &gsets.v[g]));
+    }
+    std::vector<double> row(ngroups);
+    for (int p = 0; p < npiv; ++p) {
+        const kh_set* pivot = pivots.v[p];
+        if (out.distinct_per_pivot) out.distinct_per_pivot[p] = pivot->n;
+        if (!out.rows && !out.unique_pivot_count) continue;
+        Membership m;
+        KHCHK(membership_compute(c, pivot, gsets.v.data(), ngroups, m));
+        uint64_t uniq = 0;
+        confusion_sum(m.masks.data(), m.counts.data(), m.order.data(), pivot->n, m.nwords, ngroups, row.data(), &uniq);
+        out.set_row(in, p, row.data(), uniq);
+    }
+    return KH_OK;
+}
+extern "C" int kh_exp4_run(kh_ctx* c, int nseq, const uint8_t* const* seqs, const uint64_t* lens, int on_device,
+                           const int* group_of, int ngroups, int npivots, const uint8_t* const* pivot_seqs,
+                           const uint64_t* pivot_lens, int k, uint32_t cs, uint32_t pivot_cs, uint64_t* within_hist,
+                           uint32_t hist_len, double* rows, uint64_t* unique_pivot_count, uint64_t* distinct_per_seq,
+                           uint64_t* distinct_per_pivot) {
+    if (!c || !seqs || !lens || !group_of || nseq <= 0 || ngroups <= 0 || npivots < 0 || (npivots && (!pivot_seqs || !pivot_lens)))
+        return kh_fail(KH_E_ARG, "kh_exp4_run: bad argument");
+    if (hist_len < 2) return kh_fail(KH_E_ARG, "hist_len must be >= 2");
+    KHCHK(check_k(k));
+    if (cs < 1) return kh_fail(KH_E_ARG, "cs must be >= 1");
+    if (pivot_cs < 1) return kh_fail(KH_E_ARG, "pivot_cs must be >= 1");
+    std::vector<int> gsize(ngroups, 0);
+    for (int i = 0; i < nseq; ++i) {
+        if (group_of[i] < 0 || group_of[i] >= ngroups)
+            return kh_fail(KH_E_ARG, "group_of[%d]=%d outside [0,%d)", i, group_of[i], ngroups);
+        gsize[group_of[i]]++;
+    }
+    for (int g = 0; g < ngroups; ++g)
+        if (!gsize[g]) return kh_fail(KH_E_ARG, "group %d has no sequences", g);
+    const Exp4In in{nseq, seqs, lens, on_device, group_of, ngroups, npivots, pivot_seqs, pivot_lens, k, cs, pivot_cs, hist_len};
+    const Exp4Out out{within_hist, rows, unique_pivot_count, distinct_per_seq, distinct_per_pivot};
+    HIPCHK(hipSetDevice(c->dev));
+    bool done = false;
+    KHCHK(exp4_bmp(c, in, out, &done));
+    if (done) return KH_OK;
+    return exp4_sets(c, in, out);
 }
 
 // ------------------------------------------------------------------------------ exchange form of steps 7-8

@@ -296,6 +296,36 @@ struct KhBmpPivotJob {
 };
 void kh_launch_bmp_pivot(const KhBmpPivotJob& job, u32 grid, u32 waves, hipStream_t st);   // launch shape and LDS of the read-out
 
+// ---- experiment type 4 from the same bitmaps (kh_exp4_run): the operands of k_bmp_build are the genomes in group-major
+// order, then all pivots.  k_bmp_count adds up the pivots' multiplicities in tables of 4^k cells, k_bmp_present walks the
+// bitmaps like k_bmp_readout (within-group bins, distinct counters, the groups' presence words, the pivots' own words and
+// their popcounts per block of 64 words), k_bmp_member writes one (membership mask, count) record per pivot k-mer in
+// ascending code order.  Bins: per group size + 1, then one distinct counter per operand.
+constexpr u32 KH_BMP_MEMBER_GROUPS = 64;   // one mask word per record
+struct KhBmpMemberJob {
+    const KhBmpSplit* splits;       // the build's table; the pivots' splits are its last npsplits entries
+    const KhBmpOp* ops;             // [nops]
+    const KhBmpGroup* groups;       // [ngroups]
+    const u64* partial;             // [splits][nwords], written by k_bmp_build
+    u64* present;                   // [ngroups][nwords]: codes any genome of the group holds
+    u64* pword;                     // [npivots][nwords]: the pivot's bitmap, its splits ORed
+    u32* cnt;                       // [npivots][ncells] zeroed: occurrences of every code in the pivot (not saturated)
+    u32* blk;                       // [npivots][nblocks]: distinct codes of the pivot in every block of 64 words
+    unsigned long long* hist;       // [reps][nbins + nops] zeroed
+    const u64* rec_off;             // [npivots]: the pivot's first record
+    u64* rec_mask;                  // records, struct of arrays: bit d = group d holds the k-mer
+    u32* rec_count;                 //                            min(occurrences, pivot_cs)
+    u64 nwords, ncells;             // ncells = 64 * nwords
+    u32 nops, ngenomes, ngroups, npivots, nbins, reps, nblocks;
+    u32 psplit0, npsplits;          // the pivots' splits
+    u32 tile_pos, pivot_cs;
+    int k;
+};
+size_t kh_bmp_member_lds_bytes(u32 ngroups);
+void kh_launch_bmp_count(const KhBmpMemberJob& job, hipStream_t st);     // one workgroup per split of a pivot
+void kh_launch_bmp_present(const KhBmpMemberJob& job, u32 grid, u32 waves, hipStream_t st);   // launch shape and LDS of the read-out
+void kh_launch_bmp_member(const KhBmpMemberJob& job, hipStream_t st);    // (runs of blocks) x pivots workgroups
+
 struct KhLookback {      // workspace of one ordered single-pass launch
     u64* desc;           // [nparts] tile descriptors, zeroed before launch
     u32* ticket;         // zeroed before launch

@@ -92,7 +92,14 @@ def confusion_from_sets(eng, pivots: Sequence, sets_per_pivot: Sequence[Sequence
         row, unique = eng.confusion_row(pv, list(sets))
         rows.append(row.tolist())
         uniques.append(unique)
-    cm, cm_ucol = assemble_matrices(rows, uniques, num_datasets)
+    return confusion_from_rows(rows, uniques, num_datasets, k)
+
+
+def confusion_from_rows(rows: Sequence[Sequence[float]], uniques: Sequence[int], num_datasets: int, k) -> dict:
+    """rows[p][d] and uniques[p] as `kh_confusion_row` / `kh_exp4_run` return them (lists or arrays) -> the texts of
+    the three files."""
+    rows = [[float(x) for x in row] for row in rows]
+    cm, cm_ucol = assemble_matrices(rows, [int(u) for u in uniques], num_datasets)
     return format_outputs(cm, cm_ucol, num_datasets, k)
 
 

@@ -8,6 +8,7 @@ the argv the reference gives KMC; the last rule calls the merge_lists drop-in
     run(work_root, k_values, num_datasets)            rule-per-process
     run_batched(...)                                  same final files from one resident engine:
                                                       no text dumps, no D x D intersections
+    run_fused(...)                                    the same again from one kh_exp4_run per k: no set is kept
 
 Staging of `input_type4/` out of DATABASE_ROOT (exp_type_4.smk:31-51) is data management, not
 k-mer work: both entries expect input_type4/{rest_of_set/dataset_N/*.fna.gz, pivot/pivot_N.fna.gz}.
@@ -200,5 +201,36 @@ def run_batched(work_root: str, k_values: Sequence, num_datasets: int, device: i
                 union.histogram_file(65535, os.path.join(hdir, f"dataset_{num + 1}.hist.txt"))
                 unions.append(union.set_counts(1))
             files = merge_lists.confusion_from_sets(eng, pivots, [unions] * num_datasets, num_datasets, k)
+            merge_lists.write_outputs(os.path.join(os.path.abspath(work_root), "accuracies_type_4") + "/", files)
+    return {"accuracy_values": concatenate_accuracies(work_root), "processes": 0}
+
+
+def run_fused(work_root: str, k_values: Sequence, num_datasets: int, device: int = 0):
+    """The files of run_batched from one Engine.exp4_run per k (kh_exp4_run: presence bitmaps and records in code
+    order for k <= 12, the set operations inside the library otherwise): the texts are read once, no set comes back
+    to Python."""
+    from .. import engine as E
+    from concurrent.futures import ThreadPoolExecutor
+    k_values = [str(k) for k in k_values]
+    prepare(work_root, k_values, num_datasets)
+    for d in ("accuracies_type_4/values", "accuracies_type_4/confusion_matrix"):
+        os.makedirs(os.path.join(work_root, d), exist_ok=True)
+    with E.Engine(device) as eng:
+        paths, owner = [], []
+        for num in range(1, num_datasets + 1):
+            for g in rest_of_set(work_root, num):
+                paths.append(os.path.join(work_root, f"input_type4/rest_of_set/dataset_{num}/{g}.fna.gz"))
+                owner.append(num - 1)
+        pivot_paths = [os.path.join(work_root, f"input_type4/pivot/pivot_{num}.fna.gz")
+                       for num in range(1, num_datasets + 1)]
+        with ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 1)) as pool:
+            texts = list(pool.map(eng.read_fasta, paths + pivot_paths))
+        for k in k_values:
+            res = eng.exp4_run(texts[:len(paths)], owner, texts[len(paths):], int(k), cs=5000, hist_len=5001)
+            for num in range(num_datasets):
+                hdir = os.path.join(work_root, f"unions_type_4/rest_of_set/k_{k}/dataset_{num + 1}")
+                os.makedirs(hdir, exist_ok=True)
+                eng.write_histogram_text(os.path.join(hdir, f"dataset_{num + 1}.hist.txt"), res["within_hist"][num], 65535)
+            files = merge_lists.confusion_from_rows(res["rows"], res["unique"], num_datasets, k)
             merge_lists.write_outputs(os.path.join(os.path.abspath(work_root), "accuracies_type_4") + "/", files)
     return {"accuracy_values": concatenate_accuracies(work_root), "processes": 0}
