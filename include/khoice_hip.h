@@ -272,6 +272,37 @@ int kh_exp2_run(kh_ctx *ctx, int nseq, const uint8_t *const *seqs, const uint64_
                 uint64_t *within_only, uint64_t *across_only,
                 uint64_t *distinct_per_seq, uint64_t *distinct_per_pivot);
 
+/* ---------------------------------------------------------------- fused experiment type 3
+ * The device side of exp_type_3.smk:176-277 for one k on resident sequences: the simulated reads of every pivot
+ * against the rest-of-set union of EVERY dataset (group): how many of the pivot's k-mers lie in exactly v genomes of
+ * the group.  Replaces per k: `kmc` per genome and per read set (:183,192), `set_counts 1` of both (:206,219), the
+ * -cs{cs} `complex` union per dataset (:233), the pivots x datasets `simple intersect -ocsum` databases (:248-250) and
+ * the `transform histogram` of each and of every pivot (:261-263, :274-276).
+ *   seqs, lens, group_of, ngroups   the rest_of_set genomes, as for kh_exp1_run; every group needs a genome
+ *   pivot_seqs, pivot_lens          npivots read sets (host or device like seqs): cleaned texts, the reads separated by
+ *                                   a line feed; a text may be empty or shorter than k; npivots may be 0
+ * With occ[v] = distinct canonical k-mers of pivot p in exactly v genomes of group g:
+ *   inter_hist [npivots * ngroups * hist_len]   inter_hist[p][g]: bin min(1 + min(v, cs), cs, hist_len - 1) += occ[v],
+ *                                   v >= 1: the histogram of the intersect -ocsum result (the pivot's counter 1 + the
+ *                                   union's, saturating), the fold of kh_exp2_run's within_hist
+ *   distinct_per_seq [nseq], distinct_per_pivot [npivots]   distinct canonical k-mers of every text (line 1 of the
+ *                                   pivot's own histogram)
+ * Any output may be NULL.  KH_E_ARG: a group outside [0, ngroups), a group without genome, hist_len < 2, k outside
+ * 1..64, cs == 0.
+ *
+ * Forms, the same numbers in each: k <= 12 presence bitmaps (kh_bmp.hip: the pivots are further genomes of the bitmap
+ * build; one read-out kernel per batch of pivots keeps their words in LDS and masks the bit-sliced counter of every
+ * group with them); otherwise, and whenever the bitmaps do not fit (1023 genomes per group, a pivot whose bins and the
+ * operand counters exceed 4096, the memory budget), one batched build, the unions and intersect + histogram on sets in
+ * device memory.  Switches as for kh_exp1_run: KHOICE_NO_BMP, KHOICE_NO_SKM, KHOICE_BMP_MAX_K, KHOICE_BMP_MAX_BYTES;
+ * KHOICE_BMP_MAX_BINS lowers the 4096 (more, smaller batches of pivots). */
+int kh_exp3_run(kh_ctx *ctx, int nseq, const uint8_t *const *seqs, const uint64_t *lens, int on_device,
+                const int *group_of, int ngroups,
+                int npivots, const uint8_t *const *pivot_seqs, const uint64_t *pivot_lens,
+                int k, uint32_t cs,
+                uint64_t *inter_hist, uint32_t hist_len,       /* [npivots * ngroups * hist_len] */
+                uint64_t *distinct_per_seq, uint64_t *distinct_per_pivot);
+
 /* ---------------------------------------------------------------- fused experiment type 4
  * The device side of exp_type_4.smk:139-303 for one k on resident sequences: every pivot against the rest-of-set
  * union of EVERY dataset (group), summed into one confusion-matrix row per pivot as src/merge_lists.py:101-141 does.

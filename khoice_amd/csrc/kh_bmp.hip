@@ -17,6 +17,8 @@
 //                  a pivot's word masks the counter of its group and the counter over groups (see at the kernel).
 //   k_bmp_count, k_bmp_present, k_bmp_member   experiment type 4: the pivots' multiplicities, the groups' presence
 //                  words, and one (membership mask, count) record per pivot k-mer in code order (see at the kernels).
+//   k_bmp_cross    experiment type 3 with the same walk: every pivot's word, kept in LDS, masks the counter of EVERY
+//                  group (see at the kernel).
 #include "kh_device.h"
 #include "kh_launch.h"
 
@@ -386,6 +388,83 @@ __global__ __launch_bounds__(1024) void k_bmp_pivot(const KhBmpPivotJob jb) {
 }
 
 // ------------------------------------------------------------------------------------------
+// k_bmp_cross
+// LDS: [bins: nbins + nops u32][gx: 2 x waves x 64 u64][pw: npivots x 64 u64]
+// ------------------------------------------------------------------------------------------
+// Experiment type 3 with the walk of k_bmp_readout: every pivot of the launch's batch against every group.  Operands of
+// the launch: the batch's pivots (build operands pop0 ..), then the genomes in group-major order (build operands 0 ..).
+// A pivot's word is kept in LDS as pw[q][lane]: the lane reads back only what it stored itself, so no barrier guards it.
+// A genome's word goes into the group's counter c; behind the last genome of group g the mask e = (c == v) is worked out
+// once per v = 1 .. size and bin(q, g, v) += popcount(pw[q] & e) for every pivot q.  Bins: per pivot one per genome
+// (group g: gr.bin0 + v - 1), then one distinct counter per operand of the launch.  No counter over groups, no device
+// scratch, one phase.
+__global__ __launch_bounds__(1024) void k_bmp_cross(const KhBmpCrossJob jb) {
+    extern __shared__ __attribute__((aligned(16))) u8 lds_raw[];
+    u32* bins = reinterpret_cast<u32*>(lds_raw);
+    const u32 nops = jb.npivots + jb.ngenomes, nb = jb.nbins + nops;
+    const u32 lane = threadIdx.x, y = threadIdx.y, wy = blockDim.y;
+    u64* gx = reinterpret_cast<u64*>(lds_raw + ((4 * (size_t)nb + 15) & ~(size_t)15));   // [2][wy][64]
+    u64* pw = gx + 2 * (size_t)wy * KH_WAVE;                                             // [npivots][64]
+    const u32 tid = y * KH_WAVE + lane, nt = wy * KH_WAVE;
+    for (u32 i = tid; i < nb; i += nt) bins[i] = 0;
+    __syncthreads();
+    u32 round = 0;
+    for (u64 wb = blockIdx.x; wb * KH_WAVE < jb.nwords; wb += gridDim.x) {
+        const u64 w = wb * KH_WAVE + lane;
+        const bool active = w < jb.nwords;
+        u32 g = 0;
+        KhBmpGroup gr = jb.groups[0];
+        u32 ns = bit_length(gr.size);
+        u64 c[BMP_SLICES];
+#pragma unroll
+        for (int s = 0; s < BMP_SLICES; ++s) c[s] = 0;
+        for (u32 i0 = 0; i0 < nops; i0 += wy, ++round) {
+            u64 x = 0;
+            if (i0 + y < nops && active) {
+                const u32 i = i0 + y;
+                const KhBmpOp op = jb.ops[i < jb.npivots ? jb.pop0 + i : i - jb.npivots];
+                const u64* p = jb.partial + (size_t)op.split0 * jb.nwords + w;
+#pragma unroll 8
+                for (u32 s = 0; s < op.nsplits; ++s) x |= p[(size_t)s * jb.nwords];
+            }
+            u64* buf = gx + (size_t)(round & 1u) * wy * KH_WAVE;
+            buf[y * KH_WAVE + lane] = x;
+            __syncthreads();
+            if (y != 0) continue;
+            const u32 n = nops - i0 < wy ? nops - i0 : wy;
+            for (u32 j = 0; j < n; ++j) {
+                const u32 i = i0 + j;
+                const u64 xx = buf[j * KH_WAVE + lane];
+                wave_add_to_bin(&bins[jb.nbins + i], (u32)__builtin_popcountll(xx));   // the operand's distinct k-mers
+                if (i < jb.npivots) {
+                    pw[i * KH_WAVE + lane] = xx;
+                    continue;
+                }
+                slices_add(c, xx, ns);
+                if (i - jb.npivots + 1 == gr.first + gr.size) {   // the group is complete: every pivot against its counter
+                    for (u32 v = 1; v <= gr.size; ++v) {
+                        const u64 e = slices_equal(c, v, ns);
+                        u32* bin = &bins[gr.bin0 + v - 1];
+                        for (u32 q = 0; q < jb.npivots; ++q, bin += jb.ngenomes)
+                            wave_add_to_bin(bin, (u32)__builtin_popcountll(pw[q * KH_WAVE + lane] & e));
+                    }
+#pragma unroll
+                    for (int s = 0; s < BMP_SLICES; ++s) c[s] = 0;
+                    if (++g < jb.ngroups) {
+                        gr = jb.groups[g];
+                        ns = bit_length(gr.size);
+                    }
+                }
+            }
+        }
+    }
+    __syncthreads();
+    unsigned long long* rep = jb.hist + (size_t)(blockIdx.x % jb.reps) * nb;
+    for (u32 i = tid; i < nb; i += nt)
+        if (bins[i]) atomicAdd(&rep[i], (unsigned long long)bins[i]);
+}
+
+// ------------------------------------------------------------------------------------------
 // experiment type 4: k_bmp_count, k_bmp_present, k_bmp_member
 // ------------------------------------------------------------------------------------------
 // k_bmp_count: how often every code occurs in a pivot.  A workgroup owns one split of a pivot and walks it with the
@@ -617,6 +696,14 @@ void kh_launch_bmp_pivot(const KhBmpPivotJob& job, u32 grid, u32 waves, hipStrea
     const size_t lds = kh_bmp_readout_lds_bytes(job.nbins, job.nops, waves);
     bmp_allow_lds(k_bmp_pivot, lds);
     hipLaunchKernelGGL(k_bmp_pivot, dim3(grid), dim3(KH_WAVE, waves), lds, st, job);
+}
+size_t kh_bmp_cross_lds_bytes(u32 nbins, u32 npivots, u32 ngenomes, u32 waves) {
+    return kh_bmp_readout_lds_bytes(nbins, npivots + ngenomes, waves) + (size_t)npivots * KH_WAVE * 8;
+}
+void kh_launch_bmp_cross(const KhBmpCrossJob& job, u32 grid, u32 waves, hipStream_t st) {
+    const size_t lds = kh_bmp_cross_lds_bytes(job.nbins, job.npivots, job.ngenomes, waves);
+    bmp_allow_lds(k_bmp_cross, lds);
+    hipLaunchKernelGGL(k_bmp_cross, dim3(grid), dim3(KH_WAVE, waves), lds, st, job);
 }
 size_t kh_bmp_member_lds_bytes(u32 ngroups) {
     return 8 * (size_t)BMP_MEMBER_WAVES * ngroups * KH_WAVE + 4 * (size_t)(BMP_MEMBER_WAVES + BMP_MEMBER_RUN);

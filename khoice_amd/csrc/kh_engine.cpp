@@ -205,7 +205,7 @@ static const char* kClsNames[KC_COUNT] = {"extract_hist", "bucket_plan", "extrac
                                           "bucket_sort_rle", "range_bounds", "setop", "histogram",
                                           "remix", "copy_in", "union_tagged", "skm_scatter",
                                           "skm_regroup", "skm_union", "skm_big", "skm_pack", "skm_phased", "bmp_build",
-                                          "bmp_readout", "bmp_pivot", "bmp_count", "bmp_present", "bmp_member"};
+                                          "bmp_readout", "bmp_pivot", "bmp_cross", "bmp_count", "bmp_present", "bmp_member"};
 
 // ------------------------------------------------------------------------------ ctx API
 extern "C" int kh_device_count(void) {
@@ -3304,6 +3304,228 @@ extern "C" int kh_exp4_run(kh_ctx* c, int nseq, const uint8_t* const* seqs, cons
     KHCHK(exp4_bmp(c, in, out, &done));
     if (done) return KH_OK;
     return exp4_sets(c, in, out);
+}
+
+// ------------------------------------------------------------------------------ fused experiment type 3
+struct Exp3In {   // the arguments of kh_exp3_run that both forms read
+    int nseq; const uint8_t* const* seqs; const uint64_t* lens; int on_device;
+    const int* group_of; int ngroups;
+    int npivots; const uint8_t* const* pivot_seqs; const uint64_t* pivot_lens;
+    int k; u32 cs, hist_len;
+};
+struct Exp3Out {   // any of them may be NULL
+    uint64_t *inter_hist, *distinct_per_seq, *distinct_per_pivot;
+    // occ k-mers of pivot p occur in v >= 1 genomes of group g: what `intersect -ocsum` with the -cs{cs} union, then
+    // `transform histogram`, make of them (the fold of Exp2Out::add)
+    void add(const Exp3In& in, int p, int g, u32 v, u64 occ) const {
+        if (inter_hist)
+            inter_hist[((size_t)p * in.ngroups + g) * in.hist_len + std::min(std::min(1 + std::min(v, in.cs), in.cs), in.hist_len - 1)] += occ;
+    }
+    void clear(const Exp3In& in) const {
+        if (inter_hist) memset(inter_hist, 0, 8 * (size_t)in.npivots * in.ngroups * in.hist_len);
+        if (distinct_per_pivot) memset(distinct_per_pivot, 0, 8 * (size_t)in.npivots);
+        if (distinct_per_seq) memset(distinct_per_seq, 0, 8 * (size_t)in.nseq);
+    }
+};
+// The presence-bitmap form (kh_bmp.hip): genomes (group-major) and pivots are the operands of the unchanged
+// k_bmp_build; k_bmp_cross counts a batch of pivots against the bit-sliced counter of every group, one launch and one
+// zeroed block of replicas per batch.  A batch holds as many pivots as fit the bins (KH_BMP_MAX_BINS, lowered by
+// KHOICE_BMP_MAX_BINS) and the LDS kept for their words (KH_BMP_CROSS_PIVOTS).  *done == false: the form does not apply
+// (nothing was launched, no retry is counted).
+static int exp3_bmp(kh_ctx* c, const Exp3In& in, const Exp3Out& out, bool* done) {
+    *done = false;
+    const int k = in.k, nseq = in.nseq, ngroups = in.ngroups, npiv = in.npivots, nops = nseq + npiv;
+    if (!bmp_form_k(k)) return KH_OK;
+    // ---- operands: the genomes in group-major order, then the pivots
+    std::vector<KhBmpGroup> groups(ngroups, KhBmpGroup{0, 0, 0, 0});
+    for (int i = 0; i < nseq; ++i) groups[in.group_of[i]].size++;
+    {
+        u32 first = 0;
+        for (KhBmpGroup& g : groups) {
+            if (g.size > KH_BMP_MAX_COUNT) return KH_OK;
+            g.first = g.bin0 = first;   // (a pivot has one bin per genome: count v of group g at bin0 + v - 1)
+            first += g.size;
+        }
+    }
+    u64 max_bins = KH_BMP_MAX_BINS;
+    if (const char* e = getenv("KHOICE_BMP_MAX_BINS")) max_bins = std::min<u64>(max_bins, strtoull(e, nullptr, 10));
+    // a launch of np pivots: np * nseq bins and np + nseq distinct counters
+    if ((u64)nseq + (npiv ? (u64)nseq + 1 : 0) > max_bins) return KH_OK;
+    const u32 batch = npiv ? (u32)std::min<u64>(std::min<u64>((max_bins - (u64)nseq) / ((u64)nseq + 1), KH_BMP_CROSS_PIVOTS), (u64)npiv) : 0;
+    const u32 nbatches = npiv ? ((u32)npiv + batch - 1) / batch : 1;
+    std::vector<const uint8_t*> oseq(nops);
+    std::vector<uint64_t> olen(nops);
+    std::vector<int> op_of_seq(nseq);
+    {
+        std::vector<u32> at(ngroups);
+        for (int g = 0; g < ngroups; ++g) at[g] = groups[g].first;
+        for (int i = 0; i < nseq; ++i) {
+            const u32 o = at[in.group_of[i]]++;
+            op_of_seq[i] = (int)o; oseq[o] = in.seqs[i]; olen[o] = in.lens[i];
+        }
+        for (int p = 0; p < npiv; ++p) { oseq[nseq + p] = in.pivot_seqs[p]; olen[nseq + p] = in.pivot_lens[p]; }
+    }
+    // ---- the batches' blocks of replicas count against the budget of the partial bitmaps, in rows of one bitmap
+    const u32 nb_max = batch * (u32)nseq + batch + (u32)nseq;   // bins and counters of a full batch
+    const u32 reps_max = std::max<u32>(1, std::min<u32>(64, 65536u / nb_max));
+    const u64 nwords = k >= 3 ? 1ull << (2 * k - 6) : 1;
+    const u64 extra_rows = ((u64)nbatches * reps_max * nb_max + nwords - 1) / nwords;
+    BmpStage s;
+    bool fits = false;
+    KHCHK(bmp_plan(c, k, nops, oseq.data(), olen.data(), in.on_device, extra_rows, &s, &fits));
+    if (!fits) return KH_OK;
+
+    hipStream_t st = c->st;
+    const u32 reps = std::min<u32>(s.rgrid, reps_max);
+    // workspace: [hist: nbatches x reps x nb_max u64][inst: nops u64] (zeroed, read back) [splits][ops][groups] (one upload)
+    const size_t hist_stride = 8 * (size_t)reps * nb_max;
+    const size_t off_inst = hist_stride * nbatches, off_splits = off_inst + 8 * (size_t)nops,
+                 off_ops = off_splits + sizeof(KhBmpSplit) * s.splits.size(), off_groups = off_ops + sizeof(KhBmpOp) * (size_t)nops,
+                 ws_bytes = off_groups + sizeof(KhBmpGroup) * (size_t)ngroups;
+    Tmp d_seq, d_ws, d_partial;
+    TMP_ALLOC(d_seq, c, s.need_pack ? s.seq_bytes : 256);
+    TMP_ALLOC(d_ws, c, ws_bytes);
+    TMP_ALLOC(d_partial, c, (size_t)(s.nsplits * s.nwords * 8));
+    const size_t up_bytes = ws_bytes - off_splits, down_bytes = off_splits;
+    Pinned pin{c};
+    PIN_ALLOC(pin, up_bytes + down_bytes + 64);
+    u8* h_up = static_cast<u8*>(pin.p);
+    u8* h_down = h_up + ((up_bytes + 63) & ~(size_t)63);
+    c->prof_begin(KC_COPY_IN);
+    KHCHK(bmp_copy_in(c, &s, oseq.data(), olen.data(), in.on_device, d_seq.as<u8>()));
+    memcpy(h_up, s.splits.data(), sizeof(KhBmpSplit) * s.splits.size());
+    memcpy(h_up + (off_ops - off_splits), s.ops.data(), sizeof(KhBmpOp) * (size_t)nops);
+    memcpy(h_up + (off_groups - off_splits), groups.data(), sizeof(KhBmpGroup) * (size_t)ngroups);
+    u8* wsp = d_ws.as<u8>();
+    HIPCHK(hipMemsetAsync(wsp, 0, off_splits, st));
+    HIPCHK(hipMemcpyAsync(wsp + off_splits, h_up, up_bytes, hipMemcpyHostToDevice, st));
+    c->prof_end();
+
+    const KhBmpJob build = bmp_build_job(s, k, reinterpret_cast<const KhBmpSplit*>(wsp + off_splits), d_partial.as<u64>(),
+                                         reinterpret_cast<unsigned long long*>(wsp + off_inst));
+    c->prof_begin(KC_BMP_BUILD);
+    kh_launch_bmp_build(build, (u32)s.nsplits, st);
+    c->prof_end();
+    HIPCHK(hipGetLastError());
+    KhBmpCrossJob job{};
+    job.ops = reinterpret_cast<const KhBmpOp*>(wsp + off_ops);
+    job.groups = reinterpret_cast<const KhBmpGroup*>(wsp + off_groups);
+    job.partial = d_partial.as<u64>();
+    job.nwords = s.nwords;
+    job.ngenomes = (u32)nseq; job.ngroups = (u32)ngroups; job.reps = reps;
+    for (u32 b = 0; b < nbatches; ++b) {
+        job.pop0 = (u32)nseq + b * batch;
+        job.npivots = std::min<u32>(batch, (u32)npiv - b * batch);   // (no pivots: one launch for the genomes' counters)
+        job.nbins = job.npivots * (u32)nseq;
+        job.hist = reinterpret_cast<unsigned long long*>(wsp + hist_stride * b);
+        c->prof_begin(KC_BMP_CROSS);
+        kh_launch_bmp_cross(job, s.rgrid, s.rwaves, st);
+        c->prof_end();
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipMemcpyAsync(h_down, wsp, down_bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+
+    // ---- per batch the replicas summed and the bins folded; the genomes' counters from the first batch
+    const u64* h_inst = reinterpret_cast<const u64*>(h_down + off_inst);
+    out.clear(in);
+    u64 inst = 0, dsum = 0, met = 0;
+    for (int o = 0; o < nops; ++o) inst += h_inst[o];
+    std::vector<u64> bins;
+    for (u32 b = 0; b < nbatches; ++b) {
+        const u32 p0 = b * batch, np = std::min<u32>(batch, (u32)npiv - p0), nbins = np * (u32)nseq, nb = nbins + np + (u32)nseq;
+        const u64* h_hist = reinterpret_cast<const u64*>(h_down + hist_stride * b);
+        bins.assign(nb, 0);
+        for (u32 r = 0; r < reps; ++r)
+            for (u32 i = 0; i < nb; ++i) bins[i] += h_hist[(size_t)r * nb + i];
+        if (b == 0)
+            for (int i = 0; i < nseq; ++i) {
+                const u64 d = bins[nbins + np + op_of_seq[i]];
+                dsum += d;
+                if (out.distinct_per_seq) out.distinct_per_seq[i] = d;
+            }
+        for (u32 q = 0; q < np; ++q) {
+            dsum += bins[nbins + q];
+            if (out.distinct_per_pivot) out.distinct_per_pivot[p0 + q] = bins[nbins + q];
+            for (int g = 0; g < ngroups; ++g)
+                for (u32 v = 1; v <= groups[g].size; ++v) {
+                    const u64 occ = bins[(size_t)q * nseq + groups[g].bin0 + v - 1];
+                    met += occ;
+                    out.add(in, (int)(p0 + q), g, v, occ);
+                }
+        }
+    }
+    c->stat.bases += s.bases;
+    c->stat.builds += nops;
+    c->stat.kmers += inst;
+    c->stat.distinct += dsum;
+    c->stat.setop_in += dsum;
+    c->stat.setop_out += met;   // pivot k-mers met in a group, summed over the groups
+    c->stat.setops++;
+    *done = true;
+    return KH_OK;
+}
+// The set form: the calls of workflow/exp_type_3.py::run_batched on sets that stay in device memory — one batched plain
+// build of genomes and pivots, the -cs{cs} union of every group, and intersect -ocsum + histogram of every pivot with
+// every union.  No kernel of its own.
+static int exp3_sets(kh_ctx* c, const Exp3In& in, const Exp3Out& out) {
+    struct Bag {   // every intermediate set, freed on every way out
+        std::vector<kh_set*> v;
+        ~Bag() { for (kh_set* s : v) kh_set_free(s); }
+    } plain, unions;
+    const int nseq = in.nseq, ngroups = in.ngroups, npiv = in.npivots, n = nseq + npiv;
+    std::vector<const uint8_t*> seqs(in.seqs, in.seqs + nseq);
+    std::vector<uint64_t> lens(in.lens, in.lens + nseq);
+    seqs.insert(seqs.end(), in.pivot_seqs, in.pivot_seqs + npiv);
+    lens.insert(lens.end(), in.pivot_lens, in.pivot_lens + npiv);
+    plain.v.assign(n, nullptr);   // genomes, then pivots
+    KHCHK(kh_build_batch(c, n, seqs.data(), lens.data(), in.on_device, in.k, 1, KH_NO_MAX, KH_KMC_DEFAULT_CS, 0, plain.v.data()));
+    out.clear(in);
+    for (int i = 0; i < nseq; ++i)
+        if (out.distinct_per_seq) out.distinct_per_seq[i] = plain.v[i]->n;
+    for (int p = 0; p < npiv; ++p)
+        if (out.distinct_per_pivot) out.distinct_per_pivot[p] = plain.v[nseq + p]->n;
+    if (!out.inter_hist || !npiv) return KH_OK;
+    unions.v.assign(ngroups, nullptr);
+    for (int g = 0; g < ngroups; ++g) {
+        std::vector<const kh_set*> members;
+        for (int i = 0; i < nseq; ++i)
+            if (in.group_of[i] == g) members.push_back(plain.v[i]);
+        KHCHK(kh_union_sum(c, members.data(), (int)members.size(), in.cs, &unions.v[g], nullptr, 0));
+    }
+    for (int p = 0; p < npiv; ++p)
+        for (int g = 0; g < ngroups; ++g) {
+            Bag r;
+            r.v.assign(1, nullptr);
+            KHCHK(kh_simple(c, plain.v[nseq + p], unions.v[g], KH_INTERSECT, KH_MODE_SUM, in.cs, &r.v[0]));
+            KHCHK(kh_histogram(c, r.v[0], out.inter_hist + ((size_t)p * ngroups + g) * in.hist_len, in.hist_len));
+        }
+    return KH_OK;
+}
+extern "C" int kh_exp3_run(kh_ctx* c, int nseq, const uint8_t* const* seqs, const uint64_t* lens, int on_device,
+                           const int* group_of, int ngroups, int npivots, const uint8_t* const* pivot_seqs,
+                           const uint64_t* pivot_lens, int k, uint32_t cs, uint64_t* inter_hist, uint32_t hist_len,
+                           uint64_t* distinct_per_seq, uint64_t* distinct_per_pivot) {
+    if (!c || !seqs || !lens || !group_of || nseq <= 0 || ngroups <= 0 || npivots < 0 || (npivots && (!pivot_seqs || !pivot_lens)))
+        return kh_fail(KH_E_ARG, "kh_exp3_run: bad argument");
+    if (hist_len < 2) return kh_fail(KH_E_ARG, "hist_len must be >= 2");
+    KHCHK(check_k(k));
+    if (cs < 1) return kh_fail(KH_E_ARG, "cs must be >= 1");
+    std::vector<int> gsize(ngroups, 0);
+    for (int i = 0; i < nseq; ++i) {
+        if (group_of[i] < 0 || group_of[i] >= ngroups)
+            return kh_fail(KH_E_ARG, "group_of[%d]=%d outside [0,%d)", i, group_of[i], ngroups);
+        gsize[group_of[i]]++;
+    }
+    for (int g = 0; g < ngroups; ++g)
+        if (!gsize[g]) return kh_fail(KH_E_ARG, "group %d has no sequences", g);
+    const Exp3In in{nseq, seqs, lens, on_device, group_of, ngroups, npivots, pivot_seqs, pivot_lens, k, cs, hist_len};
+    const Exp3Out out{inter_hist, distinct_per_seq, distinct_per_pivot};
+    HIPCHK(hipSetDevice(c->dev));
+    bool done = false;
+    KHCHK(exp3_bmp(c, in, out, &done));
+    if (done) return KH_OK;
+    return exp3_sets(c, in, out);
 }
 
 // ------------------------------------------------------------------------------ exchange form of steps 7-8

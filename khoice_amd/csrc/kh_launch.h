@@ -296,6 +296,24 @@ struct KhBmpPivotJob {
 };
 void kh_launch_bmp_pivot(const KhBmpPivotJob& job, u32 grid, u32 waves, hipStream_t st);   // launch shape and LDS of the read-out
 
+// ---- experiment type 3 from the same bitmaps (k_bmp_cross): the operands of k_bmp_build are the genomes in group-major
+// order, then all pivots (read sets).  A launch takes a batch of pivots against every group.  Bins of a launch: per pivot
+// of the batch one per genome (count 1 .. size of group g at groups[g].bin0 ..), then one distinct counter per operand
+// of the launch (the batch's pivots, then the genomes).
+constexpr u32 KH_BMP_CROSS_PIVOTS = 64;    // pivots of a launch at most: their words stay in LDS, 512 bytes each
+struct KhBmpCrossJob {
+    const KhBmpOp* ops;             // the build's table: genomes [0, ngenomes), then the pivots
+    const KhBmpGroup* groups;       // [ngroups]: first = the group's first genome, bin0 = genomes in front of it
+    const u64* partial;             // [splits][nwords], written by k_bmp_build
+    unsigned long long* hist;       // [reps][nbins + npivots + ngenomes] zeroed, this launch's own
+    u64 nwords;
+    u32 pop0, npivots;              // the batch: build operands [pop0, pop0 + npivots)
+    u32 ngenomes, ngroups;
+    u32 nbins, reps;                // nbins = npivots * ngenomes
+};
+size_t kh_bmp_cross_lds_bytes(u32 nbins, u32 npivots, u32 ngenomes, u32 waves);
+void kh_launch_bmp_cross(const KhBmpCrossJob& job, u32 grid, u32 waves, hipStream_t st);   // launch shape of the read-out
+
 // ---- experiment type 4 from the same bitmaps (kh_exp4_run): the operands of k_bmp_build are the genomes in group-major
 // order, then all pivots.  k_bmp_count adds up the pivots' multiplicities in tables of 4^k cells, k_bmp_present walks the
 // bitmaps like k_bmp_readout (within-group bins, distinct counters, the groups' presence words, the pivots' own words and

@@ -98,6 +98,8 @@ def load_library(path: Optional[str] = None):
         "kh_exp2_run": (C.c_int, [vp, C.c_int, C.POINTER(vp), u64p, C.c_int, C.POINTER(C.c_int), C.c_int,
                                   C.c_int, C.POINTER(vp), u64p, C.POINTER(C.c_int), C.c_int, C.c_uint32,
                                   u64p, u64p, C.c_uint32, u64p, u64p, u64p, u64p]),
+        "kh_exp3_run": (C.c_int, [vp, C.c_int, C.POINTER(vp), u64p, C.c_int, C.POINTER(C.c_int), C.c_int,
+                                  C.c_int, C.POINTER(vp), u64p, C.c_int, C.c_uint32, u64p, C.c_uint32, u64p, u64p]),
         "kh_exp4_run": (C.c_int, [vp, C.c_int, C.POINTER(vp), u64p, C.c_int, C.POINTER(C.c_int), C.c_int,
                                   C.c_int, C.POINTER(vp), u64p, C.c_int, C.c_uint32, C.c_uint32,
                                   u64p, C.c_uint32, C.POINTER(C.c_double), u64p, u64p, u64p]),
@@ -133,7 +135,7 @@ ABI_SYMBOLS = [
     "kh_set_upload", "kh_set_device_ptrs", "kh_set_from_device", "kh_set_export_device",
     "kh_set_export_range", "kh_set_wrap_device", "kh_set_partition_bounds",
     "kh_sets_partition_bounds",
-    "kh_save", "kh_load", "kh_exp1_run", "kh_exp2_run", "kh_exp4_run", "kh_comm_unique_id", "kh_comm_init", "kh_comm_destroy",
+    "kh_save", "kh_load", "kh_exp1_run", "kh_exp2_run", "kh_exp3_run", "kh_exp4_run", "kh_comm_unique_id", "kh_comm_init", "kh_comm_destroy",
     "kh_skm_exchange_plan", "kh_skm_pack", "kh_skm_phased_histogram",
     "kh_across_exchange_histogram", "kh_mix_host", "kh_unmix_host",
 ]
@@ -579,6 +581,29 @@ class Engine:
         _check(self._lib.kh_exp2_run(self._ctx, n, ptrs, _u64p(lens), on_dev, gof, ng, npv, pptrs, _u64p(plens), pgof,
                                      k, cs, arg["within_hist"], arg["across_hist"], hist_len, arg["within_only"],
                                      arg["across_only"], arg["distinct_per_seq"], arg["distinct_per_pivot"]))
+        return res
+
+    # -- fused experiment type 3
+    def exp3_run(self, seqs: Sequence, group_of: Sequence[int], pivots: Sequence, k: int, cs: int = 5000,
+                 hist_len: int = 5001):
+        """Device side of exp_type_3.smk:176-277 for one k: the read set of every pivot against the rest-of-set union of
+        every group.  Returns a dict with inter_hist[npivots, ngroups, hist_len] (the `intersect -ocsum` histograms),
+        distinct_per_seq[nseq] and distinct_per_pivot[npivots].  seqs and pivots: host bytes or device-resident texts."""
+        ptrs, lens, on_dev, keep = self._seq_args(seqs)
+        n, npv = len(seqs), len(pivots)
+        pptrs, plens, p_on_dev, pkeep = self._seq_args(pivots) if npv else (None, np.zeros(1, dtype=np.uint64), on_dev, [])
+        if p_on_dev != on_dev:
+            raise ValueError("mix of host and device sequences in one call")
+        if len(group_of) != n:
+            raise ValueError("one group per sequence")
+        ng = max(group_of) + 1
+        gof = (C.c_int * n)(*[int(g) for g in group_of])
+        res = {"inter_hist": np.zeros((npv, ng, hist_len), dtype=np.uint64),
+               "distinct_per_seq": np.zeros(n, dtype=np.uint64), "distinct_per_pivot": np.zeros(npv, dtype=np.uint64)}
+        arg = {f: (_u64p(a) if a.size else None) for f, a in res.items()}
+        _check(self._lib.kh_exp3_run(self._ctx, n, ptrs, _u64p(lens), on_dev, gof, ng, npv, pptrs, _u64p(plens),
+                                     k, cs, arg["inter_hist"], hist_len, arg["distinct_per_seq"],
+                                     arg["distinct_per_pivot"]))
         return res
 
     # -- fused experiment type 4

@@ -222,3 +222,32 @@ def pivot_across_groups_csv(hist_paths: Sequence[str], num_datasets: int) -> str
     """across_dataset_analysis_type_2/across_dataset_analysis.csv (exp_type_2.smk:521-554):
     the member count passed to the summariser is num_datasets (:536)."""
     return _rows_to_csv(PIVOT_ACROSS_HEADER, _pivot_rows(hist_paths, num_datasets, lambda _n: num_datasets, True))
+
+
+# --------------------------------------------------------------------------- experiment type 3
+INTERSECTION_PERCENT_HEADER = "read_type,pivot_num,k,dataset_num,intersection_percent\n"
+
+
+def intersection_percent_csv(hist_paths: Sequence[str], num_datasets: int) -> str:
+    """final_analysis_type3/final_analysis_type3.csv (exp_type_3.smk:286-320).  `hist_paths` in the order of
+    get_all_histogram_files (:102-112): read type, pivot, k, and within each the pivot's own histogram followed by one
+    intersect histogram per dataset; the fields are parsed from the path components as the rule does (:304-307).  A
+    pivot without k-mers divides by zero there, and here."""
+    rows: List[list] = []
+    pos = 0
+    while pos < len(hist_paths):
+        pivot_counts = read_histogram_file(hist_paths[pos])
+        pos += 1
+        assert sum(pivot_counts[1:]) == 0, "issue with pivot histogram file"
+        num_kmers_in_pivot = pivot_counts[0]
+        for path in hist_paths[pos:pos + num_datasets]:
+            parts = path.split("/")
+            read_type = parts[1]
+            pivot_num = parts[2].split("_")[1]
+            dataset_num = parts[4].split("_")[1]
+            k_value = parts[3].split("_")[1]
+            data_counts = read_histogram_file(path)
+            assert data_counts[0] == 0, "issue with histogram of intersection file"
+            rows.append([read_type, pivot_num, k_value, dataset_num, round(sum(data_counts) / num_kmers_in_pivot, 4)])
+        pos += num_datasets
+    return _rows_to_csv(INTERSECTION_PERCENT_HEADER, rows)

@@ -189,6 +189,65 @@ def write_type2_tree(root: str, n_species: int, n_genomes: int, length: int) -> 
                 fh.write(fasta_bytes(genome_records(s, g, length, anc)))
 
 
+def simulated_reads(codes: np.ndarray, n_reads: int, read_len: int, error_rate: float, seed: int,
+                    min_len: int | None = None) -> List[bytes]:
+    """A deterministic stand-in for the read simulators of experiment type 3 (art_illumina, pbsim:
+    exp_type_3.smk:121-147), NOT a model of either: n_reads reads of `codes` (base codes 0..3, 4 = N) whose starts a
+    SplitMix stream draws, each from the forward or the reverse-complement strand, with substitutions at `error_rate`
+    and nothing else.  Length read_len, or with min_len drawn between min_len and read_len; never longer than the
+    genome, never past its end."""
+    rng = SplitMix(SEED ^ 0x52454144 ^ (seed << 20))
+    size = int(codes.size)
+    hi = min(read_len, size)
+    lo = hi if min_len is None else min(min_len, hi)
+    draws = rng.take(3 * n_reads).reshape(n_reads, 3)
+    out = []
+    for i in range(n_reads):
+        ln = lo + int(draws[i, 0] % np.uint64(hi - lo + 1))
+        at = int(draws[i, 1] % np.uint64(size - ln + 1))
+        read = codes[at:at + ln]
+        if int(draws[i, 2]) & 1:                              # the other strand: complement (N stays N), reversed
+            read = np.where(read < 4, np.uint8(3) - read, read)[::-1]
+        hit = read < 4
+        if error_rate:
+            read = np.where(hit, _substitute(np.where(hit, read, 0).astype(np.uint8), error_rate, rng), read)
+        out.append(_LETTERS[read].tobytes())
+    return out
+
+
+def reads_fasta_bytes(reads: List[bytes], prefix: str) -> bytes:
+    """Plain FASTA as `seqtk seq -a` writes it: a header and one sequence line per read."""
+    return b"".join(b">" + f"{prefix}_{i + 1}".encode() + b"\n" + r + b"\n" for i, r in enumerate(reads))
+
+
+TYPE3_READS = {"illumina": dict(read_len=150, error_rate=0.002, min_len=None),       # -l 150 (exp_type_3.smk:129)
+               "ont": dict(read_len=8000, error_rate=0.05, min_len=200)}              # --accuracy-mean 0.95 --length-min 200 (:142)
+
+
+def write_type3_tree(root: str, n_species: int, n_genomes: int, length: int, n_reads: int) -> None:
+    """input_type3/{rest_of_set/dataset_{s}/*.fna.gz, pivot/dataset_{s}/pivot_{s}.fna.gz,
+    pivot_reads/{illumina,ont}/dataset_{s}/pivot_{s}_{read_type}_reads.fa} as exp_type_3.smk:33-55,149-171 leave them:
+    the pivot genome is NOT among its dataset's rest-of-set genomes, and the reads (simulated_reads of the pivot) are
+    plain FASTA."""
+    for s in range(1, n_species + 1):
+        d = os.path.join(root, "input_type3", "rest_of_set", f"dataset_{s}")
+        pd = os.path.join(root, "input_type3", "pivot", f"dataset_{s}")
+        os.makedirs(d, exist_ok=True)
+        os.makedirs(pd, exist_ok=True)
+        anc = ancestor(s, length)
+        for g in range(n_genomes + 1):
+            path = os.path.join(pd, f"pivot_{s}.fna.gz") if g == n_genomes else os.path.join(d, f"sp{s}_g{g}.fna.gz")
+            with gzip.open(path, "wb", compresslevel=1) as fh:
+                fh.write(fasta_bytes(genome_records(s, g, length, anc)))
+        pivot = genome_codes(s, n_genomes, length, anc)
+        for t, (read_type, kw) in enumerate(TYPE3_READS.items()):
+            rd = os.path.join(root, "input_type3", "pivot_reads", read_type, f"dataset_{s}")
+            os.makedirs(rd, exist_ok=True)
+            reads = simulated_reads(pivot, n_reads, seed=2 * s + t, **kw)
+            with open(os.path.join(rd, f"pivot_{s}_{read_type}_reads.fa"), "wb") as fh:
+                fh.write(reads_fasta_bytes(reads, f"pivot_{s}_{read_type}"))
+
+
 def species_set(n_species: int, n_genomes: int, length: int, first_species: int = 1):
     """[(species, genome, cleaned sequence text)] for the device-resident benchmarks."""
     out = []
