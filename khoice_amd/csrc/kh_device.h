@@ -43,14 +43,15 @@ constexpr int KH_HALO = 96;                                   // k-1 <= 63 bases
 
 // 16 ASCII bases -> 16 two-bit codes + 16 "not ACGTacgt" flags, four bytes at a time (SWAR):
 //   code = ((c >> 1) ^ (c >> 2)) & 3 maps A C G T (either case) to 0 1 2 3; the letter that code stands for is
-//   0x41 + {0, 2, 6, 0x13}[code], and a byte is a base iff its case-folded value equals that letter.
+//   "ACGT"[code]: a byte lookup in a four-entry table, which is what v_perm_b32 does with the four codes (one per
+//   byte, 0 .. 3: bytes of its second operand) as its selector; a byte is a base iff its case-folded value equals
+//   that letter.
 // The two multiplies gather the four 2-bit codes / the four flags of a word into its top byte / nibble
 // (the partial products land on distinct bits: no carries).
 __device__ __forceinline__ void decode4(const u32 x, u32& codes8, u32& bad4) {
     const u32 t = ((x >> 1) ^ (x >> 2)) & 0x03030303u;
     codes8 = (t * 0x01041040u) >> 24;
-    const u32 b0 = t & 0x01010101u, b1 = (t >> 1) & 0x01010101u, both = b0 & b1;
-    const u32 letter = 0x41414141u + ((b0 | b1) << 1) + ((b1 & ~b0) << 2) + both + (both << 4);
+    const u32 letter = __builtin_amdgcn_perm(0u, 0x54474341u, t);
     const u32 z = (x & 0xDFDFDFDFu) ^ letter;
     const u32 nz = (((z & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | z) & 0x80808080u;   // bit 7 of every byte that differs
     bad4 = ((nz >> 7) * 0x10204080u) >> 28;

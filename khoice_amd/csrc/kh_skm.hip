@@ -116,24 +116,23 @@ __global__ __launch_bounds__(SKM_NT, KH_TUNE_SKM_SCATTER_WAVES) void k_skm_scatt
 #if KH_TUNE_SKM_SCATTER_PREFETCH
         if (sub + 1 < subtiles && p0 + SKM_SUB < sg.npos) skm_fetch(sg.seq, sg.len, p0 + SKM_SUB, pre);
 #endif
-        // ---- hashes of the m-mers starting at the thread's 32 positions (32-bit rolling words)
-        u32 cw[6];   // bases p .. p + 95: a record starts in the thread's 32 positions and may run on into the next thread's
+        // ---- hashes of the m-mers starting at the thread's 32 positions
+        u32 cw[3];   // bases p .. p + 47: the last of the thread's m-mers ends at base p + 31 + 15
 #pragma unroll
-        for (int i = 0; i < 6; ++i) cw[i] = code[2 * tid + i];
+        for (int i = 0; i < 3; ++i) cw[i] = code[2 * tid + i];
         u32 cur[SKM_PPT + WW - 1];
-        {
-            const u32 pm = (u32)(m - 1);
-            const u32 pre_w = cw[0] & ((1u << (2 * pm)) - 1u);
-            u32 f = revpairs32(pre_w) >> (32 - 2 * pm);
-            u32 r = ((~pre_w) & ((1u << (2 * pm)) - 1u)) << 2;
-            u32 nw[2];
-            nw[0] = __builtin_amdgcn_alignbit(cw[1], cw[0], 2 * pm);
-            nw[1] = __builtin_amdgcn_alignbit(cw[2], cw[1], 2 * pm);
+        {   // Both strands of the m-mer at a compile-time position j are one funnel shift each: the reverse complement
+            // (base i at bits 2i, complemented) of the complemented words, the forward strand (first base on top) of the
+            // words with their 2-bit groups reversed — what the 64 tail threads below do from LDS.
+            u32 cv[3], rv[3];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) { cv[i] = ~cw[i]; rv[i] = revpairs32(cw[i]); }
+            const u32 fsh = 32u - 2u * (u32)m;
 #pragma unroll
             for (int j = 0; j < (int)SKM_PPT; ++j) {
-                const u32 c = (nw[j >> 4] >> (2 * (j & 15))) & 3u;
-                f = ((f << 2) | c) & mmask;
-                r = (r >> 2) | ((3u - c) << (2 * pm));
+                const int w = j >> 4, o = j & 15;
+                const u32 f = (o ? __builtin_amdgcn_alignbit(rv[w], rv[w + 1], 32 - 2 * o) : rv[w]) >> fsh;
+                const u32 r = __builtin_amdgcn_alignbit(cv[w + 1], cv[w], 2 * o) & mmask;
                 cur[j] = mmer_hash(f < r ? f : r);
             }
         }
@@ -351,7 +350,8 @@ __global__ __launch_bounds__(SKM_NT, KH_TUNE_SKM_SCATTER_WAVES) void k_skm_scatt
 //    instructions, but a chain of ~20 dependent LDS round trips per wave: 2.63 ms against 2.30.)
 // 4. Read-out: the thread whose compare-and-swap CREATED an entry remembers where; once all masks are final it
 //    turns its own entries into histogram bins (popcount per group / number of groups).  Nobody scans the table,
-//    no key is read again, waves without chunks have nothing to do.
+//    no key is read again, waves without chunks have nothing to do.  The read is an exchange that stores zero: the
+//    mask planes are clean for the next slot without being cleared (1.430 -> 1.407 ms).
 //
 // Geometry <NT, T>: threads and table entries of a workgroup.  <1024, 4096>: 79 KB of LDS, two workgroups per CU.
 // (<512, 2048> with four per CU and <640, 2560> with three were measured slower: DESIGN.md §3, §8.)
@@ -481,11 +481,23 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs) 
         uint4* k4 = reinterpret_cast<uint4*>(tkey);
         for (u32 i = tid; i < T / 2; i += NT) k4[i] = make_uint4(0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu);
     };
-    auto clear_masks = [&]() {
+    // The mask planes are NOT cleared per slot: the read-out takes every mask it evaluates by an exchange that stores
+    // zero (the invariant is stated there), so they are zero whenever an insertion phase begins.  Per slot only the
+    // second table's keys are reset.  (The timing variant without a read-out has to clear them.)
+#if !(defined(KH_ABLATE) && KH_ABLATE == 3)
+    constexpr bool MASKS_SELF_CLEAN = true;
+#else
+    constexpr bool MASKS_SELF_CLEAN = false;
+#endif
+    auto zero_masks = [&]() {
         for (u32 i = tid; i < T / 2; i += NT) reinterpret_cast<uint4*>(tmlo)[i] = make_uint4(0u, 0u, 0u, 0u);   // (both mask planes)
+        if (tid < T2) { omlo[tid] = 0u; omhi[tid] = 0u; }
+    };
+    auto clear_masks = [&]() {
+        if (!MASKS_SELF_CLEAN) zero_masks();
         unsigned long long e0 = EMPTY;   // (opaque, as `emptyv` below)
         asm volatile("" : "+v"(e0));
-        if (tid < T2) { okey[tid] = e0; omlo[tid] = 0u; omhi[tid] = 0u; }
+        if (tid < T2) okey[tid] = e0;
     };
     // the record counts were written by the regroup kernel and do not change here: read through the constant address
     // space, i.e. by SCALAR loads (inside the slot loop the compiler cannot prove that for a plain global pointer)
@@ -501,7 +513,9 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs) 
     SKM_MARK("init");
     // The read-out below is the twin of SkmReadout (kh_skm_device.h), kept in place: with the shared struct this kernel
     // had the same registers and 32 instructions fewer, and ran 1 % slower (1.431 -> 1.446 ms, three alternated runs
-    // each, the parent's spread 0.003).  A change of the bin rule has to be made in both.
+    // each, the parent's spread 0.003).  The BIN RULE is shared: a change of it has to be made in both.  The zeroing
+    // of the masks as they are read is this kernel's alone: the kernels built on SkmReadout clear their planes.
+    if (MASKS_SELF_CLEAN) zero_masks();   // (once: the first slot's first barrier comes before any mask is touched)
     if (tid < (u32)KH_TAG_MAX_OPS) {
         const u32 g = jb.ginfo[tid], g0 = g & 0xffu, gn = (g >> 8) & 0xffu;
         const u64 gm = gn ? (gn >= 64u ? ~0ull : ((1ull << gn) - 1ull)) << g0 : 0ull;
@@ -684,7 +698,9 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs) 
                 for (int e = 0; e < E; ++e) { kreg[e] = EMPTY; slot_[e] = 0; }
                 if (c < C) {
                     const u32 o = owner[c], ri = o >> SKM_OB, first = (o & ((1u << SKM_OB) - 1u)) * (u32)E;
-                    const uint4 r0 = reg[ri];   // an L2 hit: the records were read a moment ago
+                    // (an L2 hit: the records were read a moment ago.  Issued before the table clears instead, for the first
+                    // pass, it made the kernel slower: 1.430 -> 1.486 ms, same registers, three alternated runs each)
+                    const uint4 r0 = reg[ri];
                     bits = rmask[ri];
                     half = SkmRec1::half(r0.w);
                     const u32 left = SkmRec1::n(r0.w) - first;
@@ -823,7 +839,14 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs) 
             SKM_USTAMP(5);
             __syncthreads();
             SKM_USTAMP(6);
-            // ---- all masks are final: every thread turns the entries it created into histogram bins
+            // ---- all masks are final: every thread turns the entries it created into histogram bins.
+            // Invariant (MASKS_SELF_CLEAN): every non-zero mask has exactly one creator; it is read once, here, behind
+            // the barrier after the insertion, and the read stores zero — so both planes of both tables are zero when
+            // the next insertion phase (next subset, next slot) begins.  A mask is only ever ORed into behind a
+            // compare-and-swap that found its key or created it, and whoever created it recorded the place in `made`:
+            // in the probe rounds (`mk`), one key per lane (`where`, either table).  A key dropped under
+            // KH_ERR_CAPACITY touched no mask; a slot handed on inserts nothing (C = 0); with R > 1 each subset's
+            // read-out zeroes what that subset created before the barrier that precedes the next one.
 #pragma unroll
             for (u32 pass = 0; pass < SKM_PASSES; ++pass) {
                 u32 any = 0;
@@ -839,7 +862,15 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs) 
                     if (f & 0x8000u) {
                         const u32 at = f & 0x3fffu;
                         const bool second = f & 0x4000u;
-                        if (eval_mask((second ? omlo : tmlo)[at], (second ? omhi : tmhi)[at])) ++ones;
+                        u32 mlo, mhi;
+                        if (MASKS_SELF_CLEAN) {
+                            mlo = atomicExch((second ? omlo : tmlo) + at, 0u);
+                            mhi = atomicExch((second ? omhi : tmhi) + at, 0u);
+                        } else {
+                            mlo = (second ? omlo : tmlo)[at];
+                            mhi = (second ? omhi : tmhi)[at];
+                        }
+                        if (eval_mask(mlo, mhi)) ++ones;
                     }
                 }
             }

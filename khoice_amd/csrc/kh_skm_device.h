@@ -64,7 +64,9 @@ __device__ __forceinline__ u32 pick32(const u32 (&v)[SKM_PPT], u32 s) {
 
 // Sliding minimum over windows of WW positions, in registers: in: cur[0 .. PPT + WW - 2], out: cur[j] =
 // min(cur[j .. j + WW - 1]) for j < PPT.  Doubling up to the largest power of two L <= WW, then two
-// overlapping windows of L.
+// overlapping windows of L.  (Measured and taken out again: a ladder of three-input minimums — windows of 3, of 9, then
+// one step to WW: 116 v_min3_u32 / v_min_u32 instead of 162 at WW = 16 — left k_skm_scatter<16> where it was on its
+// own, 0.5357 -> 0.5353 ms with a spread of 0.002: profiles/README.md, round 5.)
 template <int WW>
 __device__ __forceinline__ void window_min(u32 (&cur)[SKM_PPT + WW - 1]) {
     constexpr int L = WW >= 32 ? 32 : (WW >= 16 ? 16 : (WW >= 8 ? 8 : (WW >= 4 ? 4 : (WW >= 2 ? 2 : 1))));
