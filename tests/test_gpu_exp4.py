@@ -242,11 +242,11 @@ def order_case():
     return seqs, list(range(7)), [b"N".join(pieces)]
 
 
-def order_addends():
+def order_addends(k=ORDER_K):
     """[(code, groups holding it, addend)] of the order case's pivot, as the reference forms them."""
     seqs, group_of, pivots = order_case()
-    db = counted(pivots[0], ORDER_K, KMC_CS)
-    sets = [plain_set(t, ORDER_K) for t in seqs]
+    db = counted(pivots[0], k, KMC_CS)
+    sets = [plain_set(t, k) for t in seqs]
     out = []
     for code in sorted(db):
         m = [g for g, s in enumerate(sets) if code in s]
@@ -495,24 +495,34 @@ def test_planted_case_holds_every_multiplicity_and_membership(k):
     assert sum(1 for t in seqs for w in t.decode().split("N") if not is_canonical(O.encode(w), k)) > 0   # genomes spell the other strand too
 
 
-def test_order_case_sums_differently_in_another_order():
-    adds = order_addends()
+def summed(adds):
+    row = [0.0] * 7
+    for _, m, a in adds:
+        for g in m:
+            row[g] += a
+    return row
+
+
+@pytest.mark.parametrize("k", (ORDER_K, 21, 41))
+def test_order_case_sums_differently_in_another_order(k):
+    adds = order_addends(k)
     seqs, group_of, pivots = order_case()
-    want = oracle(seqs, group_of, pivots, ORDER_K)["rows"][0]
+    want = oracle(seqs, group_of, pivots, k)["rows"][0]
     sizes = {len(m) for _, m, _ in adds}
     assert sizes >= set(ORDER_SIZES) and 4_000 < len(pivots[0]) < 6_000
     assert min(sum(1 for _, m, _ in adds if g in m) for g in range(7)) >= 200
-    fwd, rev = [0.0] * 7, [0.0] * 7
-    for _, m, a in adds:
-        for g in m:
-            fwd[g] += a
-    for _, m, a in reversed(adds):
-        for g in m:
-            rev[g] += a
+    assert [code for code, _, _ in adds] == sorted(code for code, _, _ in adds)
+    fwd, rev = summed(adds), summed(reversed(adds))
     by_numpy = [float(np.sum(np.array([a for _, m, a in adds if g in m]))) for g in range(7)]
     assert fwd == want.tolist()
     assert any(r != w for r, w in zip(rev, want.tolist()))
     assert any(r != w for r, w in zip(by_numpy, want.tolist()))
+    if k > 32:   # two-word keys: an order that compared the low 64-bit word first is another order, and another row
+        low_first = sorted(adds, key=lambda t: (t[0] & (2 ** 64 - 1), t[0] >> 64))
+        low_only = sorted(adds, key=lambda t: t[0] & (2 ** 64 - 1))
+        assert [c for c, _, _ in low_first] != [c for c, _, _ in adds] and {c >> 64 for c, _, _ in adds} != {0}
+        assert any(r != w for r, w in zip(summed(low_first), want.tolist()))
+        assert any(r != w for r, w in zip(summed(low_only), want.tolist()))
 
 
 def test_shape_cases_are_what_they_claim():
