@@ -1,24 +1,24 @@
-// khoice_amd — presence-bitmap form of the fused experiment-type-1 and type-2 steps for small k (gfx950).
+// khoice_amd — presence-bitmap forms of the fused experiment types 1-4 for small k (gfx950).
 //
 // A k-mer of k <= 13 is a number below 2^26: "which genomes hold it" is one bit per genome in a directly addressed
-// bitmap of 4^k bits, and every histogram of the step is a count over those bits.  Three kernels:
-//   k_bmp_build    text -> presence bitmaps.  A workgroup owns one (genome, split, code range): it keeps the bitmap of
-//                  its range in LDS, walks its split tile by tile (the staging of load_codes, canonical code of every valid position,
-//                  one LDS OR where the code falls in the range) and then stores every word of the range, zeros
-//                  included, with plain vector stores: every word of the partial bitmaps [split][4^k bits] is written
-//                  by exactly one workgroup, so nothing is cleared beforehand and nothing in device memory is atomic.
-//   k_bmp_readout  bit-sliced counting.  A lane owns one 64-bit word (64 consecutive codes): per group it ORs the
-//                  splits of every genome, adds the genome's word into a bit-sliced counter (ripple carry over the
-//                  slices), and reads the counter out as one equality mask per count value, whose popcount goes to the
-//                  LDS bin of (group, count).  The groups' "present" words feed a second bit-sliced counter over
-//                  groups: the across-group bins.  The popcount of a genome's own word is its distinct k-mers.
-// There is no genome mask: any number of genomes and groups (up to 1023 per counter) is answered in one pass.
-//   k_bmp_pivot    experiment type 2 with the walk of k_bmp_readout: pivot genomes are further operands of the build;
-//                  a pivot's word masks the counter of its group and the counter over groups (see at the kernel).
-//   k_bmp_count, k_bmp_present, k_bmp_member   experiment type 4: the pivots' multiplicities, the groups' presence
-//                  words, and one (membership mask, count) record per pivot k-mer in code order (see at the kernels).
-//   k_bmp_cross    experiment type 3 with the same walk: every pivot's word, kept in LDS, masks the counter of EVERY
-//                  group (see at the kernel).
+// bitmap of 4^k bits, and every histogram of the forms is a count over those bits.  There is no genome mask: any number
+// of genomes and groups (up to 1023 per counter) is answered in one pass.
+//
+// Two kernels read text, tile by tile with the same staging, written out in each:
+//   k_bmp_build<K>  text -> presence bitmaps, one partial bitmap per split of an operand (every form)
+//   k_bmp_count<K>  text -> how often every code occurs in a pivot (type 4)
+// Four kernels walk the bitmaps with the same walk, written out in each (the comment above k_bmp_readout describes it):
+// a lane owns one 64-bit word, the operands' words are handed to wave 0, which counts them with bit-sliced counters
+// into bins in LDS.
+//   k_bmp_readout   type 1: the bins per count of every group and the bins of the counter over groups
+//   k_bmp_pivot     type 2: a pivot's word masks the counter of its group, then the counter over groups
+//   k_bmp_cross     type 3: every pivot's word, kept in LDS, masks the counter of every group
+//   k_bmp_present   type 4: the within-group bins, the groups' presence words, the pivots' words and popcounts
+// And one kernel of its own shape:
+//   k_bmp_member    type 4: one (membership mask, count) record per pivot k-mer in code order
+// The launchers share one dispatch on k (bmp_for_k) and one body for the four walk kernels (launch_walk).
+#include <type_traits>
+
 #include "kh_device.h"
 #include "kh_launch.h"
 
@@ -29,6 +29,8 @@ constexpr u32 BMP_CHUNK = 16;         // positions per thread and round: one sta
 constexpr u32 BMP_FETCH = (KH_BMP_TILE / BMP_CHUNK + 1 + BMP_NT - 1) / BMP_NT;   // staged words a thread fetches per tile
 constexpr u32 BMP_PREFILTER_RANGES = 16;   // from this many ranges on, candidates are picked by their leading bases first
 constexpr u32 BMP_MAX_LEAD = 5;       // leading bases of a range at most (k = 13 with ranges of 2^16 codes)
+// LDS of a tile's staging: [code: tile_pos / 16 + 1 u32][bad16: tile_pos / 16 + 1 u16]
+constexpr size_t bmp_stage_lds_bytes(u32 tile_pos) { return ((size_t)(tile_pos / BMP_CHUNK + 1) * 6 + 15) & ~(size_t)15; }
 
 // ------------------------------------------------------------------------------------------
 // k_bmp_build
@@ -655,13 +657,21 @@ __global__ __launch_bounds__(BMP_MEMBER_WAVES * KH_WAVE) void k_bmp_member(const
 template <class K> void bmp_allow_lds(K kern, size_t bytes) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
-template <int K> void launch_build(const KhBmpJob& job, u32 nsplits, size_t lds, hipStream_t st) {
-    bmp_allow_lds(k_bmp_build<K>, lds);
-    hipLaunchKernelGGL(k_bmp_build<K>, dim3(nsplits * job.nranges), dim3(BMP_NT), lds, st, job);
+// f(std::integral_constant<int, k>) for the k the kernels are instantiated for; another k: nothing (the host asks for
+// k <= KH_BMP_INST_MAX_K only)
+template <class F> void bmp_for_k(u32 k, F f) {
+    switch (k) {
+#define BMP_K(KK) case KK: f(std::integral_constant<int, KK>{}); break;
+        BMP_K(1) BMP_K(2) BMP_K(3) BMP_K(4) BMP_K(5) BMP_K(6) BMP_K(7) BMP_K(8) BMP_K(9) BMP_K(10) BMP_K(11) BMP_K(12)
+        BMP_K(13)
+#undef BMP_K
+        default: break;
+    }
 }
-
-template <int K> void launch_count(const KhBmpMemberJob& job, size_t lds, hipStream_t st) {
-    hipLaunchKernelGGL(k_bmp_count<K>, dim3(job.npsplits), dim3(BMP_NT), lds, st, job);
+// a kernel of the walk: grid workgroups of `waves` waves
+template <class Job> void launch_walk(void (*kern)(Job), const Job& job, size_t lds, u32 grid, u32 waves, hipStream_t st) {
+    bmp_allow_lds(kern, lds);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(KH_WAVE, waves), lds, st, job);
 }
 
 }   // namespace
@@ -670,59 +680,41 @@ template <int K> void launch_count(const KhBmpMemberJob& job, size_t lds, hipStr
 // launchers
 // ------------------------------------------------------------------------------------------
 size_t kh_bmp_build_lds_bytes(u32 range_bits, u32 tile_pos) {
-    const size_t stage = ((size_t)(tile_pos / BMP_CHUNK + 1) * 6 + 15) & ~(size_t)15;
-    return ((size_t)1 << (range_bits - 3)) + stage + 16;
+    return ((size_t)1 << (range_bits - 3)) + bmp_stage_lds_bytes(tile_pos) + 16;
 }
 size_t kh_bmp_readout_lds_bytes(u32 nbins, u32 nops, u32 waves) {
     return ((4 * ((size_t)nbins + nops) + 15) & ~(size_t)15) + 2 * (size_t)waves * KH_WAVE * 8;
 }
-void kh_launch_bmp_build(const KhBmpJob& job, u32 nsplits, hipStream_t st) {
-    if (!nsplits) return;
-    const size_t lds = kh_bmp_build_lds_bytes(job.range_bits, job.tile_pos);
-    switch (job.k) {
-#define BMP_K(KK) case KK: launch_build<KK>(job, nsplits, lds, st); break;
-        BMP_K(1) BMP_K(2) BMP_K(3) BMP_K(4) BMP_K(5) BMP_K(6) BMP_K(7) BMP_K(8) BMP_K(9) BMP_K(10) BMP_K(11) BMP_K(12)
-        BMP_K(13)
-#undef BMP_K
-        default: break;   // the host asks for k <= KH_BMP_INST_MAX_K only
-    }
-}
-void kh_launch_bmp_readout(const KhBmpJob& job, u32 grid, u32 waves, hipStream_t st) {
-    const size_t lds = kh_bmp_readout_lds_bytes(job.nbins, job.nops, waves);
-    bmp_allow_lds(k_bmp_readout, lds);
-    hipLaunchKernelGGL(k_bmp_readout, dim3(grid), dim3(KH_WAVE, waves), lds, st, job);
-}
-void kh_launch_bmp_pivot(const KhBmpPivotJob& job, u32 grid, u32 waves, hipStream_t st) {
-    const size_t lds = kh_bmp_readout_lds_bytes(job.nbins, job.nops, waves);
-    bmp_allow_lds(k_bmp_pivot, lds);
-    hipLaunchKernelGGL(k_bmp_pivot, dim3(grid), dim3(KH_WAVE, waves), lds, st, job);
-}
 size_t kh_bmp_cross_lds_bytes(u32 nbins, u32 npivots, u32 ngenomes, u32 waves) {
     return kh_bmp_readout_lds_bytes(nbins, npivots + ngenomes, waves) + (size_t)npivots * KH_WAVE * 8;
-}
-void kh_launch_bmp_cross(const KhBmpCrossJob& job, u32 grid, u32 waves, hipStream_t st) {
-    const size_t lds = kh_bmp_cross_lds_bytes(job.nbins, job.npivots, job.ngenomes, waves);
-    bmp_allow_lds(k_bmp_cross, lds);
-    hipLaunchKernelGGL(k_bmp_cross, dim3(grid), dim3(KH_WAVE, waves), lds, st, job);
 }
 size_t kh_bmp_member_lds_bytes(u32 ngroups) {
     return 8 * (size_t)BMP_MEMBER_WAVES * ngroups * KH_WAVE + 4 * (size_t)(BMP_MEMBER_WAVES + BMP_MEMBER_RUN);
 }
+void kh_launch_bmp_build(const KhBmpJob& job, u32 nsplits, hipStream_t st) {
+    if (!nsplits) return;
+    const size_t lds = kh_bmp_build_lds_bytes(job.range_bits, job.tile_pos);
+    bmp_for_k(job.k, [&](auto k) {
+        bmp_allow_lds(k_bmp_build<k()>, lds);
+        hipLaunchKernelGGL(k_bmp_build<k()>, dim3(nsplits * job.nranges), dim3(BMP_NT), lds, st, job);
+    });
+}
 void kh_launch_bmp_count(const KhBmpMemberJob& job, hipStream_t st) {
     if (!job.npsplits) return;
-    const size_t lds = ((size_t)(job.tile_pos / BMP_CHUNK + 1) * 6 + 15) & ~(size_t)15;   // 24 KiB at most
-    switch (job.k) {
-#define BMP_K(KK) case KK: launch_count<KK>(job, lds, st); break;
-        BMP_K(1) BMP_K(2) BMP_K(3) BMP_K(4) BMP_K(5) BMP_K(6) BMP_K(7) BMP_K(8) BMP_K(9) BMP_K(10) BMP_K(11) BMP_K(12)
-        BMP_K(13)
-#undef BMP_K
-        default: break;
-    }
+    const size_t lds = bmp_stage_lds_bytes(job.tile_pos);   // 24 KiB at most
+    bmp_for_k(job.k, [&](auto k) { hipLaunchKernelGGL(k_bmp_count<k()>, dim3(job.npsplits), dim3(BMP_NT), lds, st, job); });
+}
+void kh_launch_bmp_readout(const KhBmpJob& job, u32 grid, u32 waves, hipStream_t st) {
+    launch_walk(k_bmp_readout, job, kh_bmp_readout_lds_bytes(job.nbins, job.nops, waves), grid, waves, st);
+}
+void kh_launch_bmp_pivot(const KhBmpPivotJob& job, u32 grid, u32 waves, hipStream_t st) {
+    launch_walk(k_bmp_pivot, job, kh_bmp_readout_lds_bytes(job.nbins, job.nops, waves), grid, waves, st);
+}
+void kh_launch_bmp_cross(const KhBmpCrossJob& job, u32 grid, u32 waves, hipStream_t st) {
+    launch_walk(k_bmp_cross, job, kh_bmp_cross_lds_bytes(job.nbins, job.npivots, job.ngenomes, waves), grid, waves, st);
 }
 void kh_launch_bmp_present(const KhBmpMemberJob& job, u32 grid, u32 waves, hipStream_t st) {
-    const size_t lds = kh_bmp_readout_lds_bytes(job.nbins, job.nops, waves);
-    bmp_allow_lds(k_bmp_present, lds);
-    hipLaunchKernelGGL(k_bmp_present, dim3(grid), dim3(KH_WAVE, waves), lds, st, job);
+    launch_walk(k_bmp_present, job, kh_bmp_readout_lds_bytes(job.nbins, job.nops, waves), grid, waves, st);
 }
 void kh_launch_bmp_member(const KhBmpMemberJob& job, hipStream_t st) {
     if (!job.npivots) return;

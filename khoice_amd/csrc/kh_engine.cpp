@@ -1509,17 +1509,21 @@ extern "C" int kh_sets_partition_bounds(kh_ctx* c, const kh_set* const* sets, in
 // its genomes are built in sub-waves, each summed into a running union that carries counters
 // (no saturation until the end), so the memory in flight is one sub-wave + the union.  The
 // final pass applies `cs` and takes the histogram.  Same result as the one-wave path.
-struct SetsGuard {
-    std::vector<kh_set*>& v;
-    ~SetsGuard() { for (auto* s : v) kh_set_free(s); }
+struct SetBag {   // sets that are freed on every way out
+    std::vector<kh_set*> v;
+    ~SetBag() { clear(); }
+    void clear() {
+        for (kh_set* s : v) kh_set_free(s);
+        v.clear();
+    }
+    kh_set** slot() { v.push_back(nullptr); return &v.back(); }   // (valid until the next slot())
 };
 static int group_union_incremental(kh_ctx* c, const std::vector<int>& members, const uint8_t* const* seqs,
                                    const uint64_t* lens, int on_device, int k, u32 cs, u64 budget,
                                    uint64_t* hist, u32 hist_len, uint64_t* distinct_per_seq,
                                    kh_set** out_union) {
     kh_set* running = nullptr;
-    std::vector<kh_set*> wsets;
-    SetsGuard free_wsets{wsets};
+    SetBag wsets;
     size_t i0 = 0;
     while (i0 < members.size()) {
         size_t i1 = i0;
@@ -1529,21 +1533,20 @@ static int group_union_incremental(kh_ctx* c, const std::vector<int>& members, c
             acc += lens[members[i1++]];
         std::vector<const uint8_t*> wseqs(i1 - i0);
         std::vector<uint64_t> wlens(i1 - i0);
-        wsets.assign(i1 - i0, nullptr);
+        wsets.v.assign(i1 - i0, nullptr);
         for (size_t j = i0; j < i1; ++j) { wseqs[j - i0] = seqs[members[j]]; wlens[j - i0] = lens[members[j]]; }
         int r = kh_build_batch(c, (int)(i1 - i0), wseqs.data(), wlens.data(), on_device, k, 1, KH_NO_MAX,
-                               KH_KMC_DEFAULT_CS, 0, wsets.data());
+                               KH_KMC_DEFAULT_CS, 0, wsets.v.data());
         if (r != KH_OK) { kh_set_free(running); return r; }
         std::vector<const kh_set*> in;
         if (running) in.push_back(running);
         for (size_t j = i0; j < i1; ++j) {
-            if (distinct_per_seq) distinct_per_seq[members[j]] = wsets[j - i0]->n;
-            in.push_back(wsets[j - i0]);
+            if (distinct_per_seq) distinct_per_seq[members[j]] = wsets.v[j - i0]->n;
+            in.push_back(wsets.v[j - i0]);
         }
         kh_set* next = nullptr;
         r = run_setop(c, in, KH_OP_UNION, KH_OC_SUM, 0x7fffffffu, &next, nullptr, 0);
         if (r != KH_OK) { kh_set_free(running); return r; }
-        for (auto* s : wsets) kh_set_free(s);
         wsets.clear();
         kh_set_free(running);
         running = next;
@@ -2002,8 +2005,8 @@ static int exp1_skm(kh_ctx* c, const Exp1In& in, uint64_t* within_hist, uint64_t
     *done = true;
     return KH_OK;
 }
-// What the presence-bitmap forms (exp1_bmp, exp2_bmp) share: the switches, the geometry of the build, the tables of
-// splits and operands, and the copy-in of the texts.
+// What the presence-bitmap forms (exp1_bmp .. exp4_bmp) share: the switches, the geometry of the build, the tables of
+// splits and operands, the copy-in of the texts, and the run that strings them together (BmpRun).
 static bool bmp_form_k(int k) {
     int max_k = KH_BMP_MAX_K;
     if (const char* e = getenv("KHOICE_BMP_MAX_K")) max_k = std::min(KH_BMP_INST_MAX_K, atoi(e));
@@ -2117,17 +2120,240 @@ static int bmp_copy_in(kh_ctx* c, BmpStage* s, const uint8_t* const* seqs, const
     }
     return KH_OK;
 }
-static KhBmpJob bmp_build_job(const BmpStage& s, int k, const KhBmpSplit* d_splits, u64* d_partial, unsigned long long* d_inst) {
-    KhBmpJob job{};
-    job.splits = d_splits;
-    job.partial = d_partial;
-    job.inst = d_inst;
-    job.nwords = s.nwords;
-    job.tile_pos = s.tile_pos;
-    job.range_bits = s.range_bits; job.nranges = s.nranges;
-    job.nops = (u32)s.ops.size();
-    job.k = k;
-    return job;
+// a launch under its profiling class, and the error it may have left
+template <class F> static int timed_launch(kh_ctx* c, int cls, F launch) {
+    c->prof_begin(cls);
+    launch();
+    c->prof_end();
+    HIPCHK(hipGetLastError());
+    return KH_OK;
+}
+// The operands of a bitmap run: the genomes in group-major order (within a group in the caller's order), then the
+// pivots — with pivot_group, each behind the genomes of the group it was held out of.
+struct BmpOperands {
+    std::vector<const uint8_t*> seq;
+    std::vector<uint64_t> len;
+    std::vector<int> op_of_seq, op_of_pivot;
+    std::vector<u32> first, size;         // per group: its first operand, its genomes
+};
+static BmpOperands bmp_operands(int nseq, const uint8_t* const* seqs, const uint64_t* lens, const int* group_of, int ngroups,
+                                int npiv = 0, const uint8_t* const* pivot_seqs = nullptr, const uint64_t* pivot_lens = nullptr,
+                                const int* pivot_group = nullptr) {
+    BmpOperands o;
+    o.seq.resize(nseq + npiv);
+    o.len.resize(nseq + npiv);
+    o.op_of_seq.resize(nseq);
+    o.op_of_pivot.resize(npiv);
+    o.first.resize(ngroups);
+    o.size.assign(ngroups, 0);
+    std::vector<u32> held(ngroups, 0), at(ngroups);
+    for (int i = 0; i < nseq; ++i) o.size[group_of[i]]++;
+    for (int p = 0; p < npiv && pivot_group; ++p) held[pivot_group[p]]++;
+    u32 next = 0;
+    for (int g = 0; g < ngroups; ++g) {
+        o.first[g] = at[g] = next;
+        next += o.size[g] + held[g];
+    }
+    auto place = [&](u32 op, const uint8_t* s, uint64_t l) {
+        o.seq[op] = s;
+        o.len[op] = l;
+        return (int)op;
+    };
+    for (int i = 0; i < nseq; ++i) o.op_of_seq[i] = place(at[group_of[i]]++, seqs[i], lens[i]);
+    for (int p = 0; p < npiv; ++p) o.op_of_pivot[p] = place(pivot_group ? at[pivot_group[p]]++ : next++, pivot_seqs[p], pivot_lens[p]);
+    return o;
+}
+// The groups' table entries of types 1 and 4: one bin per count 0 .. size of every group, one group's bins behind the
+// other's; *nbins: the bins in all.  false: a group has more genomes than a counter takes.
+static bool bmp_group_table(const BmpOperands& o, std::vector<KhBmpGroup>* groups, u64* nbins) {
+    groups->resize(o.size.size());
+    *nbins = 0;
+    for (size_t g = 0; g < o.size.size(); ++g) {
+        if (o.size[g] > KH_BMP_MAX_COUNT) return false;
+        (*groups)[g] = KhBmpGroup{o.first[g], o.size[g], (u32)*nbins, 0};
+        *nbins += o.size[g] + 1;
+    }
+    return true;
+}
+// One run of a presence-bitmap form, what exp1_bmp .. exp4_bmp do alike.  In this order: plan(); layout(); table() for
+// every table of the form's own; upload(); build(); the form's launches (timed_launch); download(); then bins(), inst()
+// and account().
+// Workspace: [hist: blocks x reps x nb u64][inst: nops u64] (zeroed, read back) [splits][ops][the form's tables] (one
+// upload, zero where a table's alignment leaves a gap)
+struct BmpRun {
+    kh_ctx* c;
+    int k, on_device;
+    const BmpOperands& o;
+    BmpStage s;
+    u32 nb = 0, reps = 0;                 // bins and counters of a block of replicas (the largest launch's), replicas
+    size_t hist_stride = 0, off_inst = 0, off_splits = 0, off_ops = 0, ws_bytes = 0;
+    struct Table { size_t off; const void* src; size_t bytes; };
+    std::vector<Table> tables;
+    Tmp d_seq, d_ws, d_partial;
+    Pinned pin;
+    u8 *h_up = nullptr, *h_down = nullptr;
+
+    BmpRun(kh_ctx* ctx, int k_, int on_dev, const BmpOperands& ops) : c(ctx), k(k_), on_device(on_dev), o(ops), pin{ctx} {}
+    int nops() const { return (int)o.seq.size(); }
+    static u32 reps_max(u32 nb) { return std::max<u32>(1, std::min<u32>(64, 65536u / nb)); }
+    // *fits == false: the form declines
+    int plan(u64 extra_rows, bool* fits) { return bmp_plan(c, k, nops(), o.seq.data(), o.len.data(), on_device, extra_rows, &s, fits); }
+    void layout(u32 blocks, u32 nb_of_block) {
+        nb = nb_of_block;
+        reps = std::min(s.rgrid, reps_max(nb));
+        hist_stride = 8 * (size_t)reps * nb;
+        off_inst = hist_stride * blocks;
+        ws_bytes = off_inst + 8 * (size_t)nops();
+        off_splits = table(s.splits);     // (their texts are filled in by upload())
+        off_ops = table(s.ops);
+    }
+    // a table behind the ones laid out so far; returns its offset in the workspace (dev()).  v stays until upload().
+    template <class T> size_t table(const std::vector<T>& v) {
+        const size_t off = (ws_bytes + alignof(T) - 1) & ~(alignof(T) - 1);
+        tables.push_back(Table{off, v.data(), sizeof(T) * v.size()});
+        ws_bytes = off + sizeof(T) * v.size();
+        return off;
+    }
+    // the device memory, the texts copied in, the zeroed region zeroed and the tables uploaded; `also` runs among the copies
+    template <class F> int upload(F also) {
+        TMP_ALLOC(d_seq, c, s.need_pack ? s.seq_bytes : 256);
+        TMP_ALLOC(d_ws, c, ws_bytes);
+        TMP_ALLOC(d_partial, c, (size_t)(s.nsplits * s.nwords * 8));
+        const size_t up_bytes = ws_bytes - off_splits;
+        PIN_ALLOC(pin, up_bytes + off_splits + 64);
+        h_up = static_cast<u8*>(pin.p);
+        h_down = h_up + ((up_bytes + 63) & ~(size_t)63);
+        c->prof_begin(KC_COPY_IN);
+        KHCHK(bmp_copy_in(c, &s, o.seq.data(), o.len.data(), on_device, d_seq.as<u8>()));
+        memset(h_up, 0, up_bytes);
+        for (const Table& t : tables)
+            if (t.bytes) memcpy(h_up + (t.off - off_splits), t.src, t.bytes);
+        HIPCHK(hipMemsetAsync(d_ws.b->p, 0, off_splits, c->st));
+        KHCHK(also());
+        HIPCHK(hipMemcpyAsync(d_ws.as<u8>() + off_splits, h_up, up_bytes, hipMemcpyHostToDevice, c->st));
+        c->prof_end();
+        return KH_OK;
+    }
+    int upload() { return upload([] { return (int)KH_OK; }); }
+    template <class T> T* dev(size_t off) const { return reinterpret_cast<T*>(d_ws.as<u8>() + off); }
+    const KhBmpOp* ops() const { return dev<const KhBmpOp>(off_ops); }
+    unsigned long long* hist(u32 block) const { return dev<unsigned long long>(hist_stride * block); }
+    KhBmpJob build_job() const {
+        KhBmpJob job{};
+        job.splits = dev<const KhBmpSplit>(off_splits);
+        job.partial = d_partial.as<u64>();
+        job.inst = dev<unsigned long long>(off_inst);
+        job.nwords = s.nwords;
+        job.tile_pos = s.tile_pos;
+        job.range_bits = s.range_bits; job.nranges = s.nranges;
+        job.nops = (u32)nops();
+        job.k = k;
+        return job;
+    }
+    int build() {
+        const KhBmpJob job = build_job();
+        return timed_launch(c, KC_BMP_BUILD, [&] { kh_launch_bmp_build(job, (u32)s.nsplits, c->st); });
+    }
+    int download() {
+        HIPCHK(hipMemcpyAsync(h_down, d_ws.b->p, off_splits, hipMemcpyDeviceToHost, c->st));
+        HIPCHK(hipStreamSynchronize(c->st));
+        return KH_OK;
+    }
+    const u64* inst() const { return reinterpret_cast<const u64*>(h_down + off_inst); }   // [nops] valid positions
+    // the replicas of a block summed; nb_of_launch: the bins and counters of the launch that filled it
+    void bins(u32 block, u32 nb_of_launch, std::vector<u64>* out) const {
+        const u64* h = reinterpret_cast<const u64*>(h_down + hist_stride * block);
+        out->assign(nb_of_launch, 0);
+        for (u32 r = 0; r < reps; ++r)
+            for (u32 b = 0; b < nb_of_launch; ++b) (*out)[b] += h[(size_t)r * nb_of_launch + b];
+    }
+    // the operands' distinct k-mers, counters first_counter .. of `bins`: their sum; every sequence's into per_seq (or null)
+    u64 distinct(const std::vector<u64>& bins, u64 first_counter, uint64_t* per_seq) const {
+        u64 sum = 0;
+        for (int op = 0; op < nops(); ++op) sum += bins[first_counter + op];
+        for (size_t i = 0; i < o.op_of_seq.size() && per_seq; ++i) per_seq[i] = bins[first_counter + o.op_of_seq[i]];
+        return sum;
+    }
+    // distinct: the operands' distinct k-mers summed; setop_out: what the form counts as its set operations' output
+    void account(u64 distinct, u64 setop_out) const {
+        u64 kmers = 0;
+        for (int i = 0; i < nops(); ++i) kmers += inst()[i];
+        c->stat.bases += s.bases;
+        c->stat.builds += nops();
+        c->stat.kmers += kmers;
+        c->stat.distinct += distinct;
+        c->stat.setop_in += distinct;
+        c->stat.setop_out += setop_out;
+        c->stat.setops++;
+    }
+};
+// The bin of a count in a histogram of a -cs{cs} union: counts saturate at cs and at the last bin.
+static u32 count_bin(u32 cnt, u32 cs, u32 hist_len) { return std::min(std::min(cnt, cs), hist_len - 1); }
+// The bin of pivot k-mers that v genomes hold, in the histogram of `intersect -ocsum` with the -cs{cs} union: the
+// pivot's own 1 is added to the union's saturated counter, and the sum saturates again.
+static u32 ocsum_bin(u32 v, u32 cs, u32 hist_len) { return std::min(std::min(1 + std::min(v, cs), cs), hist_len - 1); }
+// within_hist[g]: the bins of group g's counter (bins[bin0 + cnt], cnt = 1 .. size) folded
+static void fold_within(const std::vector<KhBmpGroup>& groups, const std::vector<u64>& bins, u32 cs, uint64_t* within_hist, u32 hist_len) {
+    if (!within_hist) return;
+    memset(within_hist, 0, 8 * groups.size() * hist_len);
+    for (size_t g = 0; g < groups.size(); ++g)
+        for (u32 cnt = 1; cnt <= groups[g].size; ++cnt)
+            within_hist[g * hist_len + count_bin(cnt, cs, hist_len)] += bins[groups[g].bin0 + cnt];
+}
+// What the set forms of types 2-4 do alike.  genomes (and pivots behind them) in one plain batched build:
+static int build_plain(kh_ctx* c, int nseq, const uint8_t* const* seqs, const uint64_t* lens, int npiv, const uint8_t* const* pivot_seqs,
+                       const uint64_t* pivot_lens, int on_device, int k, SetBag* plain) {
+    std::vector<const uint8_t*> s(seqs, seqs + nseq);
+    std::vector<uint64_t> l(lens, lens + nseq);
+    s.insert(s.end(), pivot_seqs, pivot_seqs + npiv);
+    l.insert(l.end(), pivot_lens, pivot_lens + npiv);
+    plain->v.assign(nseq + npiv, nullptr);
+    return kh_build_batch(c, nseq + npiv, s.data(), l.data(), on_device, k, 1, KH_NO_MAX, KH_KMC_DEFAULT_CS, 0, plain->v.data());
+}
+// unions->v[g]: the -cs{cs} union of group g's genomes (plain[i], i < nseq); hist: [ngroups][hist_len] the unions'
+// histograms, or null
+static int group_unions(kh_ctx* c, kh_set* const* plain, int nseq, const int* group_of, int ngroups, u32 cs, SetBag* unions,
+                        uint64_t* hist, u32 hist_len) {
+    unions->v.assign(ngroups, nullptr);
+    for (int g = 0; g < ngroups; ++g) {
+        std::vector<const kh_set*> members;
+        for (int i = 0; i < nseq; ++i)
+            if (group_of[i] == g) members.push_back(plain[i]);
+        KHCHK(kh_union_sum(c, members.data(), (int)members.size(), cs, &unions->v[g], hist ? hist + (size_t)g * hist_len : nullptr,
+                           hist ? hist_len : 0));
+    }
+    return KH_OK;
+}
+// ones->v[g]: unions.v[g] with every counter 1 (`set_counts 1`)
+static int group_ones(kh_ctx* c, const SetBag& unions, SetBag* ones) {
+    ones->v.assign(unions.v.size(), nullptr);
+    for (size_t g = 0; g < unions.v.size(); ++g) KHCHK(kh_set_counts(c, unions.v[g], 1, &ones->v[g]));
+    return KH_OK;
+}
+// What kh_exp2_run, kh_exp3_run and kh_exp4_run check alike, in the order they check it.  has_pivot_group: the call
+// has a pivot_group; pivot_cs: null where the call has none.
+static int exp_check_args(const char* who, const kh_ctx* c, int nseq, const void* seqs, const void* lens, const int* group_of, int ngroups,
+                          int npivots, const void* pivot_seqs, const void* pivot_lens, bool has_pivot_group, const int* pivot_group,
+                          u32 hist_len, int k, u32 cs, const u32* pivot_cs) {
+    if (!c || !seqs || !lens || !group_of || nseq <= 0 || ngroups <= 0 || npivots < 0 ||
+        (npivots && (!pivot_seqs || !pivot_lens || (has_pivot_group && !pivot_group))))
+        return kh_fail(KH_E_ARG, "%s: bad argument", who);
+    if (hist_len < 2) return kh_fail(KH_E_ARG, "hist_len must be >= 2");
+    KHCHK(check_k(k));
+    if (cs < 1) return kh_fail(KH_E_ARG, "cs must be >= 1");
+    if (pivot_cs && *pivot_cs < 1) return kh_fail(KH_E_ARG, "pivot_cs must be >= 1");
+    std::vector<int> gsize(ngroups, 0);
+    for (int i = 0; i < nseq; ++i) {
+        if (group_of[i] < 0 || group_of[i] >= ngroups)
+            return kh_fail(KH_E_ARG, "group_of[%d]=%d outside [0,%d)", i, group_of[i], ngroups);
+        gsize[group_of[i]]++;
+    }
+    for (int g = 0; g < ngroups; ++g)
+        if (!gsize[g]) return kh_fail(KH_E_ARG, "group %d has no sequences", g);
+    for (int p = 0; p < npivots && has_pivot_group; ++p)
+        if (pivot_group[p] < 0 || pivot_group[p] >= ngroups)
+            return kh_fail(KH_E_ARG, "pivot_group[%d]=%d outside [0,%d)", p, pivot_group[p], ngroups);
+    return KH_OK;
 }
 // The presence-bitmap form of the fused path (kh_bmp.hip) for k <= KH_BMP_MAX_K, histograms and distinct counts only: a
 // k-mer is a number below 4^k, so "which genomes hold it" is one bit per genome in a directly addressed bitmap.
@@ -2138,105 +2364,44 @@ static int exp1_bmp(kh_ctx* c, const Exp1In& in, uint64_t* within_hist, uint64_t
                     bool* done) {
     *done = false;
     const int k = in.k, nseq = in.nseq, ngroups = in.ngroups;
-    if (!bmp_form_k(k)) return KH_OK;
-    if ((u32)ngroups > KH_BMP_MAX_COUNT) return KH_OK;
-    {
-        std::vector<u32> gsize(ngroups, 0);
-        u64 nbins = (u64)ngroups + 1;
-        for (int i = 0; i < nseq; ++i) gsize[in.group_of[i]]++;
-        for (int g = 0; g < ngroups; ++g) {
-            if (!gsize[g] || gsize[g] > KH_BMP_MAX_COUNT) return KH_OK;   // (a group without genomes: the general path reports it)
-            nbins += gsize[g] + 1;
-        }
-        if (nbins > KH_BMP_MAX_BINS) return KH_OK;
-    }
-    TagLayout L;
-    KHCHK(tag_layout(&L, nseq, in.group_of, ngroups, false));
-    std::vector<const uint8_t*> oseq(nseq);   // the operands: group-major order
-    std::vector<uint64_t> olen(nseq);
-    for (int i = 0; i < nseq; ++i) { oseq[i] = in.seqs[L.perm[i]]; olen[i] = in.lens[L.perm[i]]; }
-    BmpStage s;
+    if (!bmp_form_k(k) || (u32)ngroups > KH_BMP_MAX_COUNT) return KH_OK;
+    const BmpOperands o = bmp_operands(nseq, in.seqs, in.lens, in.group_of, ngroups);
+    // ---- bins: per group one per count of its genomes, then one per count of groups (across)
+    std::vector<KhBmpGroup> groups;
+    u64 nbins = 0;
+    if (!bmp_group_table(o, &groups, &nbins)) return KH_OK;
+    for (int g = 0; g < ngroups; ++g)
+        if (!o.size[g]) return KH_OK;   // (a group without genomes: the general path reports it)
+    const u32 abase = (u32)nbins;
+    nbins += (u64)ngroups + 1;
+    if (nbins > KH_BMP_MAX_BINS) return KH_OK;
+    BmpRun run(c, k, in.on_device, o);
     bool fits = false;
-    KHCHK(bmp_plan(c, k, nseq, oseq.data(), olen.data(), in.on_device, 0, &s, &fits));
+    KHCHK(run.plan(0, &fits));
     if (!fits) return KH_OK;
+    run.layout(1, (u32)nbins + (u32)nseq);   // the bins, then one distinct counter per operand
+    const size_t off_groups = run.table(groups);
+    KHCHK(run.upload());
+    KHCHK(run.build());
+    KhBmpJob job = run.build_job();
+    job.ops = run.ops();
+    job.groups = run.dev<const KhBmpGroup>(off_groups);
+    job.hist = run.hist(0);
+    job.ngroups = (u32)ngroups; job.nbins = (u32)nbins; job.abase = abase; job.reps = run.reps;
+    KHCHK(timed_launch(c, KC_BMP_READOUT, [&] { kh_launch_bmp_readout(job, run.s.rgrid, run.s.rwaves, c->st); }));
+    KHCHK(run.download());
 
-    hipStream_t st = c->st;
-    std::vector<KhBmpGroup> groups(ngroups);
-    for (int g = 0; g < ngroups; ++g) groups[g] = KhBmpGroup{(u32)L.gstart[g], (u32)L.gsize[g], L.bin0[g], 0};
-    const u32 nb = L.nbins + (u32)nseq;   // the bins, then one distinct counter per operand
-    const u32 reps = std::min<u32>(s.rgrid, std::max<u32>(1, std::min<u32>(64, 65536u / nb)));
-    // workspace: [hist: reps x nb u64][inst: nseq u64] (zeroed, read back) [splits][ops][groups] (one upload)
-    const size_t off_inst = 8 * (size_t)reps * nb, off_splits = off_inst + 8 * (size_t)nseq,
-                 off_ops = off_splits + sizeof(KhBmpSplit) * s.splits.size(), off_groups = off_ops + sizeof(KhBmpOp) * (size_t)nseq,
-                 ws_bytes = off_groups + sizeof(KhBmpGroup) * (size_t)ngroups;
-    Tmp d_seq, d_ws, d_partial;
-    TMP_ALLOC(d_seq, c, s.need_pack ? s.seq_bytes : 256);
-    TMP_ALLOC(d_ws, c, ws_bytes);
-    TMP_ALLOC(d_partial, c, (size_t)(s.nsplits * s.nwords * 8));
-    const size_t up_bytes = ws_bytes - off_splits, down_bytes = off_splits;
-    Pinned pin{c};
-    PIN_ALLOC(pin, up_bytes + down_bytes + 64);
-    u8* h_up = static_cast<u8*>(pin.p);
-    u8* h_down = h_up + ((up_bytes + 63) & ~(size_t)63);
-    c->prof_begin(KC_COPY_IN);
-    KHCHK(bmp_copy_in(c, &s, oseq.data(), olen.data(), in.on_device, d_seq.as<u8>()));
-    memcpy(h_up, s.splits.data(), sizeof(KhBmpSplit) * s.splits.size());
-    memcpy(h_up + (off_ops - off_splits), s.ops.data(), sizeof(KhBmpOp) * (size_t)nseq);
-    memcpy(h_up + (off_groups - off_splits), groups.data(), sizeof(KhBmpGroup) * (size_t)ngroups);
-    u8* wsp = d_ws.as<u8>();
-    HIPCHK(hipMemsetAsync(wsp, 0, off_splits, st));
-    HIPCHK(hipMemcpyAsync(wsp + off_splits, h_up, up_bytes, hipMemcpyHostToDevice, st));
-    c->prof_end();
-
-    KhBmpJob job = bmp_build_job(s, k, reinterpret_cast<const KhBmpSplit*>(wsp + off_splits), d_partial.as<u64>(),
-                                 reinterpret_cast<unsigned long long*>(wsp + off_inst));
-    job.ops = reinterpret_cast<const KhBmpOp*>(wsp + off_ops);
-    job.groups = reinterpret_cast<const KhBmpGroup*>(wsp + off_groups);
-    job.hist = reinterpret_cast<unsigned long long*>(wsp);
-    job.ngroups = (u32)ngroups; job.nbins = L.nbins; job.abase = L.abase; job.reps = reps;
-    c->prof_begin(KC_BMP_BUILD);
-    kh_launch_bmp_build(job, (u32)s.nsplits, st);
-    c->prof_end();
-    HIPCHK(hipGetLastError());
-    c->prof_begin(KC_BMP_READOUT);
-    kh_launch_bmp_readout(job, s.rgrid, s.rwaves, st);
-    c->prof_end();
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(h_down, wsp, down_bytes, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-
-    // ---- the replicas summed; counts saturate at cs and at the last bin
-    const u64* h_hist = reinterpret_cast<const u64*>(h_down);
-    const u64* h_inst = reinterpret_cast<const u64*>(h_down + off_inst);
-    std::vector<u64> bins(nb, 0);
-    for (u32 r = 0; r < reps; ++r)
-        for (u32 b = 0; b < nb; ++b) bins[b] += h_hist[(size_t)r * nb + b];
-    auto bin_of = [&](int cnt) { return std::min<u32>(std::min<u32>((u32)cnt, in.cs), in.hist_len - 1); };
-    if (within_hist) {
-        memset(within_hist, 0, 8 * (size_t)ngroups * in.hist_len);
-        for (int g = 0; g < ngroups; ++g)
-            for (int cnt = 1; cnt <= L.gsize[g]; ++cnt) within_hist[(size_t)g * in.hist_len + bin_of(cnt)] += bins[L.bin0[g] + cnt];
-    }
+    // ---- the bins folded: counts saturate at cs and at the last bin
+    std::vector<u64> bins;
+    run.bins(0, run.nb, &bins);
+    fold_within(groups, bins, in.cs, within_hist, in.hist_len);
     u64 across_n = 0;
     if (across_hist) memset(across_hist, 0, 8 * (size_t)in.hist_len);
-    for (int cnt = 1; cnt <= ngroups; ++cnt) {
-        across_n += bins[L.abase + cnt];
-        if (across_hist) across_hist[bin_of(cnt)] += bins[L.abase + cnt];
+    for (u32 cnt = 1; cnt <= (u32)ngroups; ++cnt) {
+        across_n += bins[abase + cnt];
+        if (across_hist) across_hist[count_bin(cnt, in.cs, in.hist_len)] += bins[abase + cnt];
     }
-    u64 inst = 0, dsum = 0;
-    for (int i = 0; i < nseq; ++i) {
-        const u64 d = bins[L.nbins + i];
-        inst += h_inst[i];
-        dsum += d;
-        if (distinct_per_seq) distinct_per_seq[L.perm[i]] = d;
-    }
-    c->stat.bases += s.bases;
-    c->stat.builds += nseq;
-    c->stat.kmers += inst;
-    c->stat.distinct += dsum;
-    c->stat.setop_in += dsum;
-    c->stat.setop_out += across_n;
-    c->stat.setops++;
+    run.account(run.distinct(bins, nbins, distinct_per_seq), across_n);
     *done = true;
     return KH_OK;
 }
@@ -2268,8 +2433,7 @@ static int exp1_fused(kh_ctx* c, int nseq, const uint8_t* const* seqs, const uin
 
     std::vector<u64> bins(L.nbins, 0), dist_acc(nseq, 0);
     const bool emit = across_set != nullptr;
-    std::vector<kh_set*> wave_sets;   // emitted across-group sets, one per wave (disjoint, ascending key ranges)
-    SetsGuard sets_guard{wave_sets};
+    SetBag wave_sets;   // emitted across-group sets, one per wave (disjoint, ascending key ranges)
     for (u32 wave = 0; wave < nwaves; ++wave) {
     GridBuild gb;
     gb.fan = std::max(L.fan, fan_hint);   // (fan_hint: genomes that are related although every one is a group of its own here)
@@ -2377,18 +2541,18 @@ static int exp1_fused(kh_ctx* c, int nseq, const uint8_t* const* seqs, const uin
         const u64 n = *reinterpret_cast<const u64*>(h_ctl + 8);
         buf_ref(okeys);
         buf_ref(ocnt);
-        wave_sets.push_back(make_set(k, n, okeys, 0, ocnt, 0, 1, cs));
+        wave_sets.v.push_back(make_set(k, n, okeys, 0, ocnt, 0, 1, cs));
     }
     }   // waves
     if (distinct_per_seq)
         for (int i = 0; i < nseq; ++i) distinct_per_seq[L.perm[i]] = dist_acc[i];
     L.fold(c, bins, within_hist, across_hist, hist_len);
     if (across_set) {
-        if (wave_sets.size() == 1) {
-            *across_set = wave_sets[0];
-            wave_sets.clear();
+        if (wave_sets.v.size() == 1) {
+            *across_set = wave_sets.v[0];
+            wave_sets.v.clear();
         } else {   // the waves' sets cover disjoint key ranges: their union is their concatenation
-            KHCHK(kh_union_sum(c, wave_sets.data(), (int)wave_sets.size(), cs, across_set, nullptr, 0));
+            KHCHK(kh_union_sum(c, wave_sets.v.data(), (int)wave_sets.v.size(), cs, across_set, nullptr, 0));
         }
     }
     *done = true;
@@ -2492,8 +2656,7 @@ static int exp1_big_group(kh_ctx* c, const Exp1In& in, int g, u64 budget, uint64
         }
         cp.rollback();
     }
-    std::vector<kh_set*> subs;
-    SetsGuard guard{subs};
+    SetBag subs;
     for (size_t i0 = 0; i0 < all.idx.size(); i0 += KH_TAG_MAX_OPS) {
         const size_t m = std::min<size_t>(KH_TAG_MAX_OPS, all.idx.size() - i0);
         SubBatch b;   // every genome a group of its own
@@ -2504,11 +2667,11 @@ static int exp1_big_group(kh_ctx* c, const Exp1In& in, int g, u64 budget, uint64
         const StatCheckpoint cp{c};
         KHCHK(exp1_fused_rescaled(c, in, b, 0x7fffffffu, nullptr, nullptr, &aset, exp1_waves(b.bases, budget), (u32)m, &cp, &d));
         if (!d) return KH_OK;
-        subs.push_back(aset);
+        subs.v.push_back(aset);
         b.scatter(dist_out);
     }
-    if (group_set) KHCHK(kh_union_sum(c, subs.data(), (int)subs.size(), in.cs, group_set, whist, whist ? in.hist_len : 0));
-    else if (whist) KHCHK(kh_union_histogram(c, subs.data(), (int)subs.size(), in.cs, whist, in.hist_len));
+    if (group_set) KHCHK(kh_union_sum(c, subs.v.data(), (int)subs.v.size(), in.cs, group_set, whist, whist ? in.hist_len : 0));
+    else if (whist) KHCHK(kh_union_histogram(c, subs.v.data(), (int)subs.v.size(), in.cs, whist, in.hist_len));
     *done = true;
     return KH_OK;
 }
@@ -2579,8 +2742,7 @@ static int exp1_batched(kh_ctx* c, const Exp1In& in, const std::vector<Exp1Batch
                         uint64_t* across_hist, uint64_t* distinct_per_seq, kh_set** across_set, bool* done) {
     const StatCheckpoint cp{c};
     const bool want_across = across_hist || across_set;
-    std::vector<kh_set*> asets;
-    SetsGuard guard{asets};
+    SetBag asets;
     for (const Exp1Batch& bt : batches) {
         uint64_t* wh = within_hist ? within_hist + (size_t)bt.g0 * in.hist_len : nullptr;
         bool d = false;
@@ -2592,7 +2754,7 @@ static int exp1_batched(kh_ctx* c, const Exp1In& in, const std::vector<Exp1Batch
                 const int r = kh_set_counts(c, gs, 1, &one);
                 kh_set_free(gs);
                 KHCHK(r);
-                asets.push_back(one);
+                asets.v.push_back(one);
             }
         } else {
             SubBatch b = groups_batch(in, bt.g0, bt.g1);
@@ -2603,7 +2765,7 @@ static int exp1_batched(kh_ctx* c, const Exp1In& in, const std::vector<Exp1Batch
                 KHCHK(exp1_fused(c, b.n(), b.seqs.data(), b.lens.data(), in.on_device, b.group.data(), b.ngroups, in.k, in.cs, wh,
                                  nullptr, in.hist_len, b.dist.data(), want_across ? &aset : nullptr, &d, exp1_waves(b.bases, budget)));
             if (d) {
-                if (aset) asets.push_back(aset);
+                if (aset) asets.v.push_back(aset);
                 b.scatter(distinct_per_seq);
             }
         }
@@ -2613,8 +2775,8 @@ static int exp1_batched(kh_ctx* c, const Exp1In& in, const std::vector<Exp1Batch
         }
     }
     *done = true;
-    if (across_set) return kh_union_sum(c, asets.data(), (int)asets.size(), in.cs, across_set, across_hist, in.hist_len);
-    if (across_hist) return kh_union_histogram(c, asets.data(), (int)asets.size(), in.cs, across_hist, in.hist_len);
+    if (across_set) return kh_union_sum(c, asets.v.data(), (int)asets.v.size(), in.cs, across_set, across_hist, in.hist_len);
+    if (across_hist) return kh_union_histogram(c, asets.v.data(), (int)asets.v.size(), in.cs, across_hist, in.hist_len);
     return KH_OK;
 }
 // The general path: per-genome sets, per-group unions (steps 1-6), then steps 7+8 over the group sets.
@@ -2622,8 +2784,10 @@ static int exp1_general(kh_ctx* c, const Exp1In& in, uint64_t* within_hist, uint
                         kh_set** group_sets, kh_set** across_set) {
     const int nseq = in.nseq, ngroups = in.ngroups, k = in.k;
     const u32 cs = in.cs, hist_len = in.hist_len;
-    std::vector<kh_set*> gsets(nseq, nullptr), unions(ngroups, nullptr), usets(ngroups, nullptr);
-    SetsGuard free_usets{usets}, free_unions{unions}, free_gsets{gsets};
+    SetBag usets, unions, gsets;   // every intermediate set, freed on every way out
+    gsets.v.assign(nseq, nullptr);
+    unions.v.assign(ngroups, nullptr);
+    usets.v.assign(ngroups, nullptr);
     // Groups are independent until step 7, so they are processed in waves that fit a device
     // memory budget (all groups at once for the benchmark sizes; wave by wave for inputs whose
     // k-mers would not fit HBM together): per wave, steps 1+2 build every genome of the wave as
@@ -2639,8 +2803,8 @@ static int exp1_general(kh_ctx* c, const Exp1In& in, uint64_t* within_hist, uint
         if (group_bases[g0] > budget) {             // one group larger than a wave: sub-waves of genomes
             r = group_union_incremental(c, groups_batch(in, g0, g0 + 1).idx, in.seqs, in.lens, in.on_device, k, cs, budget,
                                         within_hist ? within_hist + (size_t)g0 * hist_len : nullptr, hist_len,
-                                        distinct_per_seq, &unions[g0]);
-            if (r == KH_OK) r = kh_set_counts(c, unions[g0], 1, &usets[g0]);
+                                        distinct_per_seq, &unions.v[g0]);
+            if (r == KH_OK) r = kh_set_counts(c, unions.v[g0], 1, &usets.v[g0]);
             if (r != KH_OK) return r;
             ++g0;
             continue;
@@ -2654,7 +2818,7 @@ static int exp1_general(kh_ctx* c, const Exp1In& in, uint64_t* within_hist, uint
         KHCHK(kh_build_batch(c, b.n(), b.seqs.data(), b.lens.data(), in.on_device, k, 1, KH_NO_MAX,
                              KH_KMC_DEFAULT_CS, 0, wsets.data()));
         for (size_t j = 0; j < idx.size(); ++j) {
-            gsets[idx[j]] = wsets[j];
+            gsets.v[idx[j]] = wsets[j];
             if (distinct_per_seq) distinct_per_seq[idx[j]] = wsets[j]->n;
         }
         std::vector<SetopJob> jobs(g1 - g0);
@@ -2664,10 +2828,10 @@ static int exp1_general(kh_ctx* c, const Exp1In& in, uint64_t* within_hist, uint
             j.hist = within_hist ? within_hist + (size_t)g * hist_len : nullptr;
             j.hist_len = hist_len;
             for (int i : idx)
-                if (in.group_of[i] == g) j.in.push_back(gsets[i]);
+                if (in.group_of[i] == g) j.in.push_back(gsets.v[i]);
             if (j.in.empty()) return kh_fail(KH_E_ARG, "group %d has no sequences", g);
             if ((int)j.in.size() > KH_MAX_INPUT_SETS) {   // beyond one launch's fan-in: the general path
-                KHCHK(kh_union_sum(c, j.in.data(), (int)j.in.size(), cs, &unions[g], j.hist, hist_len));
+                KHCHK(kh_union_sum(c, j.in.data(), (int)j.in.size(), cs, &unions.v[g], j.hist, hist_len));
                 j.in.clear();
                 continue;
             }
@@ -2689,18 +2853,18 @@ static int exp1_general(kh_ctx* c, const Exp1In& in, uint64_t* within_hist, uint
         if (hipStreamSynchronize(c->st) != hipSuccess) return kh_fail(KH_E_HIP, "stream sync failed");
         if (g_trace) t_unions_synced = now_ms();
         for (int g = g0; g < g1; ++g) {
-            if (!jobs[g - g0].in.empty()) KHCHK(setop_finish(jobs[g - g0], &unions[g]));
+            if (!jobs[g - g0].in.empty()) KHCHK(setop_finish(jobs[g - g0], &unions.v[g]));
         }
         jobs.clear();
-        for (int g = g0; g < g1; ++g) KHCHK(kh_set_counts(c, unions[g], 1, &usets[g]));
-        for (int i : idx) { kh_set_free(gsets[i]); gsets[i] = nullptr; }   // genome sets of this wave
+        for (int g = g0; g < g1; ++g) KHCHK(kh_set_counts(c, unions.v[g], 1, &usets.v[g]));
+        for (int i : idx) { kh_set_free(gsets.v[i]); gsets.v[i] = nullptr; }   // genome sets of this wave
         g0 = g1;
     }
     // steps 7+8 (skipped when the caller wants neither output: the multi-GPU path does them
     // after exchanging the group sets, khoice_amd/dist.py)
     if (g_trace) t_groups_done = now_ms();
-    if (across_set) KHCHK(kh_union_sum(c, usets.data(), ngroups, cs, across_set, across_hist, hist_len));   // (nothing fails after it)
-    else if (across_hist) KHCHK(kh_union_histogram(c, usets.data(), ngroups, cs, across_hist, hist_len));
+    if (across_set) KHCHK(kh_union_sum(c, usets.v.data(), ngroups, cs, across_set, across_hist, hist_len));   // (nothing fails after it)
+    else if (across_hist) KHCHK(kh_union_histogram(c, usets.v.data(), ngroups, cs, across_hist, hist_len));
     if (g_trace)
         fprintf(stderr, "[khoice trace] build submit %.3f wait %.3f | unions submit %.3f wait %.3f finish %.3f | "
                         "across %.3f | total %.3f ms\n",
@@ -2708,7 +2872,7 @@ static int exp1_general(kh_ctx* c, const Exp1In& in, uint64_t* within_hist, uint
                 t_unions_submitted - g_t_build_synced, t_unions_synced - t_unions_submitted,
                 t_groups_done - t_unions_synced, now_ms() - t_groups_done, now_ms() - t_begin);
     if (group_sets)
-        for (int g = 0; g < ngroups; ++g) { group_sets[g] = unions[g]; unions[g] = nullptr; }
+        for (int g = 0; g < ngroups; ++g) { group_sets[g] = unions.v[g]; unions.v[g] = nullptr; }
     return KH_OK;
 }
 extern "C" int kh_exp1_run(kh_ctx* c, int nseq, const uint8_t* const* seqs, const uint64_t* lens,
@@ -2778,7 +2942,7 @@ struct Exp2Out {   // any of them may be NULL
         if (v == 0) {
             if (only) only[p] += occ;
         } else if (hist) {
-            hist[(size_t)p * in.hist_len + std::min(std::min(1 + std::min(v, in.cs), in.cs), in.hist_len - 1)] += occ;
+            hist[(size_t)p * in.hist_len + ocsum_bin(v, in.cs, in.hist_len)] += occ;
         }
     }
     void clear(const Exp2In& in) const {
@@ -2797,40 +2961,31 @@ static int exp2_bmp(kh_ctx* c, const Exp2In& in, const Exp2Out& out, bool* done)
     const int k = in.k, nseq = in.nseq, ngroups = in.ngroups, npiv = in.npivots, nops = nseq + npiv;
     if (!bmp_form_k(k) || (u32)ngroups > KH_BMP_MAX_COUNT) return KH_OK;
     // ---- operands in group-major order: the genomes of a group, then its pivots
+    const BmpOperands o = bmp_operands(nseq, in.seqs, in.lens, in.group_of, ngroups, npiv, in.pivot_seqs, in.pivot_lens, in.pivot_group);
     std::vector<KhBmpPivotGroup> groups(ngroups, KhBmpPivotGroup{0, 0, 0, 0, 0, 0});
-    for (int i = 0; i < nseq; ++i) groups[in.group_of[i]].size++;
     for (int p = 0; p < npiv; ++p) groups[in.pivot_group[p]].npiv++;
-    u32 prows = 0;
+    u32 prows = 0, q0 = 0;
     u64 nbins = 0;
-    {
-        u32 first = 0, q0 = 0;
-        for (KhBmpPivotGroup& g : groups) {
-            if (g.size > KH_BMP_MAX_COUNT) return KH_OK;
-            g.first = first;
-            g.q0 = q0;
-            if (g.npiv) g.prow = prows++;
-            first += g.size + g.npiv;
-            q0 += g.npiv;
-            nbins += (u64)g.npiv * (g.size + 1 + (u32)ngroups);
-        }
+    for (int g = 0; g < ngroups; ++g) {
+        KhBmpPivotGroup& gr = groups[g];
+        if (o.size[g] > KH_BMP_MAX_COUNT) return KH_OK;
+        gr.first = o.first[g];
+        gr.size = o.size[g];
+        gr.q0 = q0;
+        if (gr.npiv) gr.prow = prows++;
+        q0 += gr.npiv;
+        nbins += (u64)gr.npiv * (gr.size + 1 + (u32)ngroups);
     }
     if (nbins + (u64)nops > KH_BMP_MAX_BINS) return KH_OK;
-    std::vector<const uint8_t*> oseq(nops);
-    std::vector<uint64_t> olen(nops);
-    std::vector<int> op_of_seq(nseq), q_of_pivot(npiv);
+    std::vector<int> q_of_pivot(npiv);   // pivots in group-major order, with their bins
     std::vector<KhBmpPivot> pivots(npiv);
     {
-        std::vector<u32> at(ngroups), qat(ngroups);
-        for (int g = 0; g < ngroups; ++g) { at[g] = groups[g].first; qat[g] = groups[g].q0; }
-        for (int i = 0; i < nseq; ++i) {
-            const u32 o = at[in.group_of[i]]++;
-            op_of_seq[i] = (int)o; oseq[o] = in.seqs[i]; olen[o] = in.lens[i];
-        }
+        std::vector<u32> qat(ngroups);
+        for (int g = 0; g < ngroups; ++g) qat[g] = groups[g].q0;
         for (int p = 0; p < npiv; ++p) {
             const int g = in.pivot_group[p];
-            const u32 o = at[g]++, q = qat[g]++;
-            q_of_pivot[p] = (int)q; oseq[o] = in.pivot_seqs[p]; olen[o] = in.pivot_lens[p];
-            pivots[q] = KhBmpPivot{o, (u32)g, 0, 0};
+            q_of_pivot[p] = (int)qat[g]++;
+            pivots[q_of_pivot[p]] = KhBmpPivot{(u32)o.op_of_pivot[p], (u32)g, 0, 0};
         }
         u32 b = 0;
         for (KhBmpPivot& pv : pivots) {
@@ -2839,73 +2994,34 @@ static int exp2_bmp(kh_ctx* c, const Exp2In& in, const Exp2Out& out, bool* done)
             b = pv.abin0 + (u32)ngroups;
         }
     }
-    BmpStage s;
+    BmpRun run(c, k, in.on_device, o);
     bool fits = false;
-    KHCHK(bmp_plan(c, k, nops, oseq.data(), olen.data(), in.on_device, prows, &s, &fits));
+    KHCHK(run.plan(prows, &fits));
     if (!fits) return KH_OK;
-
-    hipStream_t st = c->st;
-    const u32 nb = (u32)nbins + (u32)nops;
-    const u32 reps = std::min<u32>(s.rgrid, std::max<u32>(1, std::min<u32>(64, 65536u / nb)));
-    // workspace: [hist: reps x nb u64][inst: nops u64] (zeroed, read back) [splits][ops][groups][pivots] (one upload)
-    const size_t off_inst = 8 * (size_t)reps * nb, off_splits = off_inst + 8 * (size_t)nops,
-                 off_ops = off_splits + sizeof(KhBmpSplit) * s.splits.size(), off_groups = off_ops + sizeof(KhBmpOp) * (size_t)nops,
-                 off_pivots = off_groups + sizeof(KhBmpPivotGroup) * (size_t)ngroups,
-                 ws_bytes = off_pivots + sizeof(KhBmpPivot) * (size_t)npiv;
-    Tmp d_seq, d_ws, d_partial, d_present;
-    TMP_ALLOC(d_seq, c, s.need_pack ? s.seq_bytes : 256);
-    TMP_ALLOC(d_ws, c, ws_bytes);
-    TMP_ALLOC(d_partial, c, (size_t)(s.nsplits * s.nwords * 8));
-    TMP_ALLOC(d_present, c, (size_t)(std::max<u64>(1, prows) * s.nwords * 8));
-    const size_t up_bytes = ws_bytes - off_splits, down_bytes = off_splits;
-    Pinned pin{c};
-    PIN_ALLOC(pin, up_bytes + down_bytes + 64);
-    u8* h_up = static_cast<u8*>(pin.p);
-    u8* h_down = h_up + ((up_bytes + 63) & ~(size_t)63);
-    c->prof_begin(KC_COPY_IN);
-    KHCHK(bmp_copy_in(c, &s, oseq.data(), olen.data(), in.on_device, d_seq.as<u8>()));
-    memcpy(h_up, s.splits.data(), sizeof(KhBmpSplit) * s.splits.size());
-    memcpy(h_up + (off_ops - off_splits), s.ops.data(), sizeof(KhBmpOp) * (size_t)nops);
-    memcpy(h_up + (off_groups - off_splits), groups.data(), sizeof(KhBmpPivotGroup) * (size_t)ngroups);
-    if (npiv) memcpy(h_up + (off_pivots - off_splits), pivots.data(), sizeof(KhBmpPivot) * (size_t)npiv);
-    u8* wsp = d_ws.as<u8>();
-    HIPCHK(hipMemsetAsync(wsp, 0, off_splits, st));
-    HIPCHK(hipMemcpyAsync(wsp + off_splits, h_up, up_bytes, hipMemcpyHostToDevice, st));
-    c->prof_end();
-
-    const KhBmpJob build = bmp_build_job(s, k, reinterpret_cast<const KhBmpSplit*>(wsp + off_splits), d_partial.as<u64>(),
-                                         reinterpret_cast<unsigned long long*>(wsp + off_inst));
+    run.layout(1, (u32)nbins + (u32)nops);
+    const size_t off_groups = run.table(groups), off_pivots = run.table(pivots);
+    Tmp d_present;
+    TMP_ALLOC(d_present, c, (size_t)(std::max<u64>(1, prows) * run.s.nwords * 8));
+    KHCHK(run.upload());
+    KHCHK(run.build());
     KhBmpPivotJob job;
-    job.ops = reinterpret_cast<const KhBmpOp*>(wsp + off_ops);
-    job.groups = reinterpret_cast<const KhBmpPivotGroup*>(wsp + off_groups);
-    job.pivots = reinterpret_cast<const KhBmpPivot*>(wsp + off_pivots);
-    job.partial = d_partial.as<u64>();
+    job.ops = run.ops();
+    job.groups = run.dev<const KhBmpPivotGroup>(off_groups);
+    job.pivots = run.dev<const KhBmpPivot>(off_pivots);
+    job.partial = run.d_partial.as<u64>();
     job.present = d_present.as<u64>();
-    job.hist = reinterpret_cast<unsigned long long*>(wsp);
-    job.nwords = s.nwords;
-    job.nops = (u32)nops; job.ngroups = (u32)ngroups; job.npivots = (u32)npiv; job.nbins = (u32)nbins; job.reps = reps;
-    c->prof_begin(KC_BMP_BUILD);
-    kh_launch_bmp_build(build, (u32)s.nsplits, st);
-    c->prof_end();
-    HIPCHK(hipGetLastError());
-    c->prof_begin(KC_BMP_PIVOT);
-    kh_launch_bmp_pivot(job, s.rgrid, s.rwaves, st);
-    c->prof_end();
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(h_down, wsp, down_bytes, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    job.hist = run.hist(0);
+    job.nwords = run.s.nwords;
+    job.nops = (u32)nops; job.ngroups = (u32)ngroups; job.npivots = (u32)npiv; job.nbins = (u32)nbins; job.reps = run.reps;
+    KHCHK(timed_launch(c, KC_BMP_PIVOT, [&] { kh_launch_bmp_pivot(job, run.s.rgrid, run.s.rwaves, c->st); }));
+    KHCHK(run.download());
 
-    // ---- the replicas summed, the bins folded
-    const u64* h_hist = reinterpret_cast<const u64*>(h_down);
-    const u64* h_inst = reinterpret_cast<const u64*>(h_down + off_inst);
-    std::vector<u64> bins(nb, 0);
-    for (u32 r = 0; r < reps; ++r)
-        for (u32 b = 0; b < nb; ++b) bins[b] += h_hist[(size_t)r * nb + b];
+    // ---- the bins folded
+    std::vector<u64> bins;
+    run.bins(0, run.nb, &bins);
     out.clear(in);
-    u64 inst = 0, dsum = 0, held = 0;
-    for (int o = 0; o < nops; ++o) { inst += h_inst[o]; dsum += bins[nbins + o]; }
-    for (int i = 0; i < nseq; ++i)
-        if (out.distinct_per_seq) out.distinct_per_seq[i] = bins[nbins + op_of_seq[i]];
+    const u64 dsum = run.distinct(bins, nbins, out.distinct_per_seq);
+    u64 held = 0;
     for (int p = 0; p < npiv; ++p) {
         const KhBmpPivot& pv = pivots[q_of_pivot[p]];
         if (out.distinct_per_pivot) out.distinct_per_pivot[p] = bins[nbins + pv.op];
@@ -2913,13 +3029,7 @@ static int exp2_bmp(kh_ctx* c, const Exp2In& in, const Exp2Out& out, bool* done)
         for (u32 v = 0; v < (u32)ngroups; ++v) out.add(in, p, true, v, bins[pv.abin0 + v]);
         held += bins[nbins + pv.op] - bins[pv.bin0];
     }
-    c->stat.bases += s.bases;
-    c->stat.builds += nops;
-    c->stat.kmers += inst;
-    c->stat.distinct += dsum;
-    c->stat.setop_in += dsum;
-    c->stat.setop_out += held;   // pivot k-mers their own group holds
-    c->stat.setops++;
+    run.account(dsum, held);   // pivot k-mers their own group holds
     *done = true;
     return KH_OK;
 }
@@ -2927,52 +3037,31 @@ static int exp2_bmp(kh_ctx* c, const Exp2In& in, const Exp2Out& out, bool* done)
 // genomes and pivots, the -cs{cs} union of every group, set_counts 1, per pivot group the union of the other groups,
 // and intersect -ocsum / kmers_subtract of every pivot with both.
 static int exp2_sets(kh_ctx* c, const Exp2In& in, const Exp2Out& out) {
-    struct Bag {   // every intermediate set, freed on every way out
-        std::vector<kh_set*> v;
-        ~Bag() { for (kh_set* s : v) kh_set_free(s); }
-        kh_set** slot() { v.push_back(nullptr); return &v.back(); }
-    } bag;
-    const int nseq = in.nseq, ngroups = in.ngroups, npiv = in.npivots, n = nseq + npiv;
-    std::vector<const uint8_t*> seqs(in.seqs, in.seqs + nseq);
-    std::vector<uint64_t> lens(in.lens, in.lens + nseq);
-    seqs.insert(seqs.end(), in.pivot_seqs, in.pivot_seqs + npiv);
-    lens.insert(lens.end(), in.pivot_lens, in.pivot_lens + npiv);
-    bag.v.assign(n, nullptr);
-    KHCHK(kh_build_batch(c, n, seqs.data(), lens.data(), in.on_device, in.k, 1, KH_NO_MAX, KH_KMC_DEFAULT_CS, 0, bag.v.data()));
-    auto plain = [&](int i) { return bag.v[i]; };   // genomes, then pivots
+    const int nseq = in.nseq, ngroups = in.ngroups, npiv = in.npivots;
+    SetBag plain, unions, gsets, others;   // every intermediate set, freed on every way out
+    KHCHK(build_plain(c, nseq, in.seqs, in.lens, npiv, in.pivot_seqs, in.pivot_lens, in.on_device, in.k, &plain));
     out.clear(in);
     for (int i = 0; i < nseq; ++i)
-        if (out.distinct_per_seq) out.distinct_per_seq[i] = plain(i)->n;
+        if (out.distinct_per_seq) out.distinct_per_seq[i] = plain.v[i]->n;
     std::vector<int> has_pivot(ngroups, 0);
     for (int p = 0; p < npiv; ++p) has_pivot[in.pivot_group[p]] = 1;
-    std::vector<kh_set*> unions(ngroups, nullptr), gsets(ngroups, nullptr), others(ngroups, nullptr);
-    for (int g = 0; g < ngroups; ++g) {
-        std::vector<const kh_set*> members;
-        for (int i = 0; i < nseq; ++i)
-            if (in.group_of[i] == g) members.push_back(plain(i));
-        kh_set** u = bag.slot();
-        KHCHK(kh_union_sum(c, members.data(), (int)members.size(), in.cs, u, nullptr, 0));
-        unions[g] = *u;
-        kh_set** gs = bag.slot();
-        KHCHK(kh_set_counts(c, unions[g], 1, gs));
-        gsets[g] = *gs;
-    }
+    KHCHK(group_unions(c, plain.v.data(), nseq, in.group_of, ngroups, in.cs, &unions, nullptr, 0));
+    KHCHK(group_ones(c, unions, &gsets));
+    others.v.assign(ngroups, nullptr);
     for (int g = 0; g < ngroups && ngroups > 1; ++g) {
         if (!has_pivot[g]) continue;
         std::vector<const kh_set*> rest;
         for (int h = 0; h < ngroups; ++h)
-            if (h != g) rest.push_back(gsets[h]);
-        kh_set** o = bag.slot();
-        KHCHK(kh_union_sum(c, rest.data(), (int)rest.size(), in.cs, o, nullptr, 0));
-        others[g] = *o;
+            if (h != g) rest.push_back(gsets.v[h]);
+        KHCHK(kh_union_sum(c, rest.data(), (int)rest.size(), in.cs, &others.v[g], nullptr, 0));
     }
     std::vector<uint64_t> hist(in.hist_len);
     for (int p = 0; p < npiv; ++p) {
-        const kh_set* pivot = plain(nseq + p);
+        const kh_set* pivot = plain.v[nseq + p];
         const int g = in.pivot_group[p];
         if (out.distinct_per_pivot) out.distinct_per_pivot[p] = pivot->n;
         for (int across = 0; across < 2; ++across) {
-            const kh_set* other = across ? others[g] : unions[g];
+            const kh_set* other = across ? others.v[g] : unions.v[g];
             uint64_t* h = across ? out.across_hist : out.within_hist;
             uint64_t* only = across ? out.across_only : out.within_only;
             if (!other) {   // one group: nothing to meet, the pivot's k-mers are all its own
@@ -2980,13 +3069,13 @@ static int exp2_sets(kh_ctx* c, const Exp2In& in, const Exp2Out& out) {
                 continue;
             }
             if (h) {
-                Bag r;
+                SetBag r;
                 KHCHK(kh_simple(c, pivot, other, KH_INTERSECT, KH_MODE_SUM, in.cs, r.slot()));
                 KHCHK(kh_histogram(c, r.v[0], hist.data(), in.hist_len));
                 memcpy(h + (size_t)p * in.hist_len, hist.data(), 8 * (size_t)in.hist_len);
             }
             if (only) {
-                Bag r;
+                SetBag r;
                 KHCHK(kh_simple(c, pivot, other, KH_KMERS_SUBTRACT, KH_MODE_LEFT, in.cs, r.slot()));
                 only[p] = r.v[0]->n;
             }
@@ -2999,23 +3088,8 @@ extern "C" int kh_exp2_run(kh_ctx* c, int nseq, const uint8_t* const* seqs, cons
                            const uint64_t* pivot_lens, const int* pivot_group, int k, uint32_t cs, uint64_t* within_hist,
                            uint64_t* across_hist, uint32_t hist_len, uint64_t* within_only, uint64_t* across_only,
                            uint64_t* distinct_per_seq, uint64_t* distinct_per_pivot) {
-    if (!c || !seqs || !lens || !group_of || nseq <= 0 || ngroups <= 0 || npivots < 0 ||
-        (npivots && (!pivot_seqs || !pivot_lens || !pivot_group)))
-        return kh_fail(KH_E_ARG, "kh_exp2_run: bad argument");
-    if (hist_len < 2) return kh_fail(KH_E_ARG, "hist_len must be >= 2");
-    KHCHK(check_k(k));
-    if (cs < 1) return kh_fail(KH_E_ARG, "cs must be >= 1");
-    std::vector<int> gsize(ngroups, 0);
-    for (int i = 0; i < nseq; ++i) {
-        if (group_of[i] < 0 || group_of[i] >= ngroups)
-            return kh_fail(KH_E_ARG, "group_of[%d]=%d outside [0,%d)", i, group_of[i], ngroups);
-        gsize[group_of[i]]++;
-    }
-    for (int g = 0; g < ngroups; ++g)
-        if (!gsize[g]) return kh_fail(KH_E_ARG, "group %d has no sequences", g);
-    for (int p = 0; p < npivots; ++p)
-        if (pivot_group[p] < 0 || pivot_group[p] >= ngroups)
-            return kh_fail(KH_E_ARG, "pivot_group[%d]=%d outside [0,%d)", p, pivot_group[p], ngroups);
+    KHCHK(exp_check_args("kh_exp2_run", c, nseq, seqs, lens, group_of, ngroups, npivots, pivot_seqs, pivot_lens, true, pivot_group,
+                         hist_len, k, cs, nullptr));
     const Exp2In in{nseq, seqs, lens, on_device, group_of, ngroups, npivots, pivot_seqs, pivot_lens, pivot_group, k, cs, hist_len};
     const Exp2Out out{within_hist, across_hist, within_only, across_only, distinct_per_seq, distinct_per_pivot};
     HIPCHK(hipSetDevice(c->dev));
@@ -3049,32 +3123,11 @@ static int exp4_bmp(kh_ctx* c, const Exp4In& in, const Exp4Out& out, bool* done)
     const int k = in.k, nseq = in.nseq, ngroups = in.ngroups, npiv = in.npivots, nops = nseq + npiv;
     if (!bmp_form_k(k) || (u32)ngroups > KH_BMP_MEMBER_GROUPS) return KH_OK;
     // ---- operands: the genomes in group-major order, then the pivots
-    std::vector<KhBmpGroup> groups(ngroups, KhBmpGroup{0, 0, 0, 0});
-    for (int i = 0; i < nseq; ++i) groups[in.group_of[i]].size++;
+    const BmpOperands o = bmp_operands(nseq, in.seqs, in.lens, in.group_of, ngroups, npiv, in.pivot_seqs, in.pivot_lens);
+    std::vector<KhBmpGroup> groups;
     u64 nbins = 0;
-    {
-        u32 first = 0;
-        for (KhBmpGroup& g : groups) {
-            if (g.size > KH_BMP_MAX_COUNT) return KH_OK;
-            g.first = first;
-            g.bin0 = (u32)nbins;
-            first += g.size;
-            nbins += g.size + 1;
-        }
-    }
+    if (!bmp_group_table(o, &groups, &nbins)) return KH_OK;
     if (nbins + (u64)nops > KH_BMP_MAX_BINS) return KH_OK;
-    std::vector<const uint8_t*> oseq(nops);
-    std::vector<uint64_t> olen(nops);
-    std::vector<int> op_of_seq(nseq);
-    {
-        std::vector<u32> at(ngroups);
-        for (int g = 0; g < ngroups; ++g) at[g] = groups[g].first;
-        for (int i = 0; i < nseq; ++i) {
-            const u32 o = at[in.group_of[i]]++;
-            op_of_seq[i] = (int)o; oseq[o] = in.seqs[i]; olen[o] = in.lens[i];
-        }
-        for (int p = 0; p < npiv; ++p) { oseq[nseq + p] = in.pivot_seqs[p]; olen[nseq + p] = in.pivot_lens[p]; }
-    }
     // ---- memory beside the partial bitmaps, in rows of one bitmap: present, pword, the count tables (32 rows each:
     // 4^k cells of 4 bytes) and the records (12 bytes each, at most one per position and per code of a pivot)
     const u64 nwords = k >= 3 ? 1ull << (2 * k - 6) : 1, ncells = 64 * nwords, ncodes = 1ull << (2 * k);
@@ -3087,108 +3140,57 @@ static int exp4_bmp(kh_ctx* c, const Exp4In& in, const Exp4Out& out, bool* done)
         nrec_max += std::min(npos, ncodes);
     }
     const u64 extra_rows = (u64)ngroups + 33ull * (u64)npiv + (12 * nrec_max + 8 * nwords - 1) / (8 * nwords);
-    BmpStage s;
+    BmpRun run(c, k, in.on_device, o);
     bool fits = false;
-    KHCHK(bmp_plan(c, k, nops, oseq.data(), olen.data(), in.on_device, extra_rows, &s, &fits));
+    KHCHK(run.plan(extra_rows, &fits));
     if (!fits) return KH_OK;
 
     hipStream_t st = c->st;
-    const u32 nb = (u32)nbins + (u32)nops, nblocks = (u32)((nwords + 63) / 64);
-    const u32 reps = std::min<u32>(s.rgrid, std::max<u32>(1, std::min<u32>(64, 65536u / nb)));
-    // workspace: [hist: reps x nb u64][inst: nops u64] (zeroed, read back) [splits][ops][groups][rec_off] (one upload)
-    const size_t off_inst = 8 * (size_t)reps * nb, off_splits = off_inst + 8 * (size_t)nops,
-                 off_ops = off_splits + sizeof(KhBmpSplit) * s.splits.size(), off_groups = off_ops + sizeof(KhBmpOp) * (size_t)nops,
-                 off_rec = (off_groups + sizeof(KhBmpGroup) * (size_t)ngroups + 7) & ~(size_t)7,
-                 ws_bytes = off_rec + 8 * rec_off.size();
-    Tmp d_seq, d_ws, d_partial, d_present, d_pword, d_cnt, d_blk, d_rmask, d_rcount;
-    TMP_ALLOC(d_seq, c, s.need_pack ? s.seq_bytes : 256);
-    TMP_ALLOC(d_ws, c, ws_bytes);
-    TMP_ALLOC(d_partial, c, (size_t)(s.nsplits * s.nwords * 8));
+    const u32 nblocks = (u32)((nwords + 63) / 64);
+    run.layout(1, (u32)nbins + (u32)nops);
+    const size_t off_groups = run.table(groups), off_rec = run.table(rec_off);
+    Tmp d_present, d_pword, d_cnt, d_blk, d_rmask, d_rcount;
     TMP_ALLOC(d_present, c, (size_t)((u64)ngroups * nwords * 8));
     TMP_ALLOC(d_pword, c, (size_t)(std::max<u64>(1, npiv) * nwords * 8));
     TMP_ALLOC(d_cnt, c, (size_t)(std::max<u64>(1, npiv) * ncells * 4));
     TMP_ALLOC(d_blk, c, (size_t)(std::max<u64>(1, npiv) * nblocks * 4));
     TMP_ALLOC(d_rmask, c, (size_t)(std::max<u64>(1, nrec_max) * 8));
     TMP_ALLOC(d_rcount, c, (size_t)(std::max<u64>(1, nrec_max) * 4));
-    const size_t up_bytes = ws_bytes - off_splits, down_bytes = off_splits;
-    Pinned pin{c};
-    PIN_ALLOC(pin, up_bytes + down_bytes + 64);
-    u8* h_up = static_cast<u8*>(pin.p);
-    u8* h_down = h_up + ((up_bytes + 63) & ~(size_t)63);
-    c->prof_begin(KC_COPY_IN);
-    KHCHK(bmp_copy_in(c, &s, oseq.data(), olen.data(), in.on_device, d_seq.as<u8>()));
-    memset(h_up, 0, up_bytes);
-    memcpy(h_up, s.splits.data(), sizeof(KhBmpSplit) * s.splits.size());
-    memcpy(h_up + (off_ops - off_splits), s.ops.data(), sizeof(KhBmpOp) * (size_t)nops);
-    memcpy(h_up + (off_groups - off_splits), groups.data(), sizeof(KhBmpGroup) * (size_t)ngroups);
-    memcpy(h_up + (off_rec - off_splits), rec_off.data(), 8 * rec_off.size());
-    u8* wsp = d_ws.as<u8>();
-    HIPCHK(hipMemsetAsync(wsp, 0, off_splits, st));
-    if (npiv) HIPCHK(hipMemsetAsync(d_cnt.b->p, 0, (size_t)((u64)npiv * ncells * 4), st));
-    HIPCHK(hipMemcpyAsync(wsp + off_splits, h_up, up_bytes, hipMemcpyHostToDevice, st));
-    c->prof_end();
-
-    const KhBmpJob build = bmp_build_job(s, k, reinterpret_cast<const KhBmpSplit*>(wsp + off_splits), d_partial.as<u64>(),
-                                         reinterpret_cast<unsigned long long*>(wsp + off_inst));
+    KHCHK(run.upload([&] {
+        if (npiv) HIPCHK(hipMemsetAsync(d_cnt.b->p, 0, (size_t)((u64)npiv * ncells * 4), st));
+        return (int)KH_OK;
+    }));
+    KHCHK(run.build());
     KhBmpMemberJob job{};
-    job.splits = build.splits;
-    job.ops = reinterpret_cast<const KhBmpOp*>(wsp + off_ops);
-    job.groups = reinterpret_cast<const KhBmpGroup*>(wsp + off_groups);
-    job.partial = d_partial.as<u64>();
+    job.splits = run.dev<const KhBmpSplit>(run.off_splits);
+    job.ops = run.ops();
+    job.groups = run.dev<const KhBmpGroup>(off_groups);
+    job.partial = run.d_partial.as<u64>();
     job.present = d_present.as<u64>();
     job.pword = d_pword.as<u64>();
     job.cnt = d_cnt.as<u32>();
     job.blk = d_blk.as<u32>();
-    job.hist = reinterpret_cast<unsigned long long*>(wsp);
-    job.rec_off = reinterpret_cast<const u64*>(wsp + off_rec);
+    job.hist = run.hist(0);
+    job.rec_off = run.dev<const u64>(off_rec);
     job.rec_mask = d_rmask.as<u64>();
     job.rec_count = d_rcount.as<u32>();
     job.nwords = nwords; job.ncells = ncells;
     job.nops = (u32)nops; job.ngenomes = (u32)nseq; job.ngroups = (u32)ngroups; job.npivots = (u32)npiv;
-    job.nbins = (u32)nbins; job.reps = reps; job.nblocks = nblocks;
-    job.psplit0 = npiv ? s.ops[nseq].split0 : (u32)s.nsplits;
-    job.npsplits = (u32)s.nsplits - job.psplit0;
-    job.tile_pos = s.tile_pos; job.pivot_cs = in.pivot_cs; job.k = k;
-    c->prof_begin(KC_BMP_BUILD);
-    kh_launch_bmp_build(build, (u32)s.nsplits, st);
-    c->prof_end();
-    HIPCHK(hipGetLastError());
-    if (npiv) {
-        c->prof_begin(KC_BMP_COUNT);
-        kh_launch_bmp_count(job, st);
-        c->prof_end();
-        HIPCHK(hipGetLastError());
-    }
-    c->prof_begin(KC_BMP_PRESENT);
-    kh_launch_bmp_present(job, s.rgrid, s.rwaves, st);
-    c->prof_end();
-    HIPCHK(hipGetLastError());
-    if (npiv) {
-        c->prof_begin(KC_BMP_MEMBER);
-        kh_launch_bmp_member(job, st);
-        c->prof_end();
-        HIPCHK(hipGetLastError());
-    }
-    HIPCHK(hipMemcpyAsync(h_down, wsp, down_bytes, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    job.nbins = (u32)nbins; job.reps = run.reps; job.nblocks = nblocks;
+    job.psplit0 = npiv ? run.s.ops[nseq].split0 : (u32)run.s.nsplits;
+    job.npsplits = (u32)run.s.nsplits - job.psplit0;
+    job.tile_pos = run.s.tile_pos; job.pivot_cs = in.pivot_cs; job.k = k;
+    if (npiv) KHCHK(timed_launch(c, KC_BMP_COUNT, [&] { kh_launch_bmp_count(job, st); }));
+    KHCHK(timed_launch(c, KC_BMP_PRESENT, [&] { kh_launch_bmp_present(job, run.s.rgrid, run.s.rwaves, st); }));
+    if (npiv) KHCHK(timed_launch(c, KC_BMP_MEMBER, [&] { kh_launch_bmp_member(job, st); }));
+    KHCHK(run.download());
 
-    // ---- the replicas summed, the bins folded as exp1_bmp folds them
-    const u64* h_hist = reinterpret_cast<const u64*>(h_down);
-    const u64* h_inst = reinterpret_cast<const u64*>(h_down + off_inst);
-    std::vector<u64> bins(nb, 0);
-    for (u32 r = 0; r < reps; ++r)
-        for (u32 b = 0; b < nb; ++b) bins[b] += h_hist[(size_t)r * nb + b];
-    auto bin_of = [&](u32 cnt) { return std::min<u32>(std::min<u32>(cnt, in.cs), in.hist_len - 1); };
-    if (out.within_hist) {
-        memset(out.within_hist, 0, 8 * (size_t)ngroups * in.hist_len);
-        for (int g = 0; g < ngroups; ++g)
-            for (u32 cnt = 1; cnt <= groups[g].size; ++cnt)
-                out.within_hist[(size_t)g * in.hist_len + bin_of(cnt)] += bins[groups[g].bin0 + cnt];
-    }
-    u64 inst = 0, dsum = 0, nrec = 0;
-    for (int o = 0; o < nops; ++o) { inst += h_inst[o]; dsum += bins[nbins + o]; }
-    for (int i = 0; i < nseq; ++i)
-        if (out.distinct_per_seq) out.distinct_per_seq[i] = bins[nbins + op_of_seq[i]];
+    // ---- the bins folded as exp1_bmp folds them
+    std::vector<u64> bins;
+    run.bins(0, run.nb, &bins);
+    fold_within(groups, bins, in.cs, out.within_hist, in.hist_len);
+    const u64 dsum = run.distinct(bins, nbins, out.distinct_per_seq);
+    u64 nrec = 0;
     std::vector<u64> h_off(std::max(1, npiv), 0);   // the records in host memory: packed, the exact numbers
     for (int p = 0; p < npiv; ++p) {
         const u64 n = bins[nbins + nseq + p];
@@ -3229,13 +3231,7 @@ static int exp4_bmp(kh_ctx* c, const Exp4In& in, const Exp4Out& out, bool* done)
         const std::vector<double> zero(ngroups, 0.0);
         for (int p = 0; p < npiv; ++p) out.set_row(in, p, zero.data(), 0);
     }
-    c->stat.bases += s.bases;
-    c->stat.builds += nops;
-    c->stat.kmers += inst;
-    c->stat.distinct += dsum;
-    c->stat.setop_in += dsum;
-    c->stat.setop_out += nrec;   // membership records
-    c->stat.setops++;
+    run.account(dsum, nrec);   // membership records
     *done = true;
     return KH_OK;
 }
@@ -3243,28 +3239,16 @@ static int exp4_bmp(kh_ctx* c, const Exp4In& in, const Exp4Out& out, bool* done)
 // build of the genomes, one counted build of the pivots, the -cs{cs} union of every group with its histogram,
 // set_counts 1, and per pivot the membership search and the sum of kh_confusion_row.
 static int exp4_sets(kh_ctx* c, const Exp4In& in, const Exp4Out& out) {
-    struct Bag {   // every intermediate set, freed on every way out
-        std::vector<kh_set*> v;
-        ~Bag() { for (kh_set* s : v) kh_set_free(s); }
-    } plain, pivots, unions, gsets;
     const int nseq = in.nseq, ngroups = in.ngroups, npiv = in.npivots;
-    plain.v.assign(nseq, nullptr);
-    KHCHK(kh_build_batch(c, nseq, in.seqs, in.lens, in.on_device, in.k, 1, KH_NO_MAX, KH_KMC_DEFAULT_CS, 0, plain.v.data()));
+    SetBag plain, pivots, unions, gsets;   // every intermediate set, freed on every way out
+    KHCHK(build_plain(c, nseq, in.seqs, in.lens, 0, nullptr, nullptr, in.on_device, in.k, &plain));
     pivots.v.assign(npiv, nullptr);
     if (npiv)
         KHCHK(kh_build_batch(c, npiv, in.pivot_seqs, in.pivot_lens, in.on_device, in.k, 1, KH_NO_MAX, in.pivot_cs, 1, pivots.v.data()));
     for (int i = 0; i < nseq; ++i)
         if (out.distinct_per_seq) out.distinct_per_seq[i] = plain.v[i]->n;
-    unions.v.assign(ngroups, nullptr);
-    gsets.v.assign(ngroups, nullptr);
-    for (int g = 0; g < ngroups; ++g) {
-        std::vector<const kh_set*> members;
-        for (int i = 0; i < nseq; ++i)
-            if (in.group_of[i] == g) members.push_back(plain.v[i]);
-        KHCHK(kh_union_sum(c, members.data(), (int)members.size(), in.cs, &unions.v[g],
-                           out.within_hist ? out.within_hist + (size_t)g * in.hist_len : nullptr, out.within_hist ? in.hist_len : 0));
-        KHCHK(kh_set_counts(c, unions.v[g], 1, &gsets.v[g]));
-    }
+    KHCHK(group_unions(c, plain.v.data(), nseq, in.group_of, ngroups, in.cs, &unions, out.within_hist, in.hist_len));
+    KHCHK(group_ones(c, unions, &gsets));
     std::vector<double> row(ngroups);
     for (int p = 0; p < npiv; ++p) {
         const kh_set* pivot = pivots.v[p];
@@ -3283,20 +3267,8 @@ extern "C" int kh_exp4_run(kh_ctx* c, int nseq, const uint8_t* const* seqs, cons
                            const uint64_t* pivot_lens, int k, uint32_t cs, uint32_t pivot_cs, uint64_t* within_hist,
                            uint32_t hist_len, double* rows, uint64_t* unique_pivot_count, uint64_t* distinct_per_seq,
                            uint64_t* distinct_per_pivot) {
-    if (!c || !seqs || !lens || !group_of || nseq <= 0 || ngroups <= 0 || npivots < 0 || (npivots && (!pivot_seqs || !pivot_lens)))
-        return kh_fail(KH_E_ARG, "kh_exp4_run: bad argument");
-    if (hist_len < 2) return kh_fail(KH_E_ARG, "hist_len must be >= 2");
-    KHCHK(check_k(k));
-    if (cs < 1) return kh_fail(KH_E_ARG, "cs must be >= 1");
-    if (pivot_cs < 1) return kh_fail(KH_E_ARG, "pivot_cs must be >= 1");
-    std::vector<int> gsize(ngroups, 0);
-    for (int i = 0; i < nseq; ++i) {
-        if (group_of[i] < 0 || group_of[i] >= ngroups)
-            return kh_fail(KH_E_ARG, "group_of[%d]=%d outside [0,%d)", i, group_of[i], ngroups);
-        gsize[group_of[i]]++;
-    }
-    for (int g = 0; g < ngroups; ++g)
-        if (!gsize[g]) return kh_fail(KH_E_ARG, "group %d has no sequences", g);
+    KHCHK(exp_check_args("kh_exp4_run", c, nseq, seqs, lens, group_of, ngroups, npivots, pivot_seqs, pivot_lens, false, nullptr,
+                         hist_len, k, cs, &pivot_cs));
     const Exp4In in{nseq, seqs, lens, on_device, group_of, ngroups, npivots, pivot_seqs, pivot_lens, k, cs, pivot_cs, hist_len};
     const Exp4Out out{within_hist, rows, unique_pivot_count, distinct_per_seq, distinct_per_pivot};
     HIPCHK(hipSetDevice(c->dev));
@@ -3319,7 +3291,7 @@ struct Exp3Out {   // any of them may be NULL
     // `transform histogram`, make of them (the fold of Exp2Out::add)
     void add(const Exp3In& in, int p, int g, u32 v, u64 occ) const {
         if (inter_hist)
-            inter_hist[((size_t)p * in.ngroups + g) * in.hist_len + std::min(std::min(1 + std::min(v, in.cs), in.cs), in.hist_len - 1)] += occ;
+            inter_hist[((size_t)p * in.ngroups + g) * in.hist_len + ocsum_bin(v, in.cs, in.hist_len)] += occ;
     }
     void clear(const Exp3In& in) const {
         if (inter_hist) memset(inter_hist, 0, 8 * (size_t)in.npivots * in.ngroups * in.hist_len);
@@ -3334,18 +3306,14 @@ struct Exp3Out {   // any of them may be NULL
 // (nothing was launched, no retry is counted).
 static int exp3_bmp(kh_ctx* c, const Exp3In& in, const Exp3Out& out, bool* done) {
     *done = false;
-    const int k = in.k, nseq = in.nseq, ngroups = in.ngroups, npiv = in.npivots, nops = nseq + npiv;
+    const int k = in.k, nseq = in.nseq, ngroups = in.ngroups, npiv = in.npivots;
     if (!bmp_form_k(k)) return KH_OK;
     // ---- operands: the genomes in group-major order, then the pivots
-    std::vector<KhBmpGroup> groups(ngroups, KhBmpGroup{0, 0, 0, 0});
-    for (int i = 0; i < nseq; ++i) groups[in.group_of[i]].size++;
-    {
-        u32 first = 0;
-        for (KhBmpGroup& g : groups) {
-            if (g.size > KH_BMP_MAX_COUNT) return KH_OK;
-            g.first = g.bin0 = first;   // (a pivot has one bin per genome: count v of group g at bin0 + v - 1)
-            first += g.size;
-        }
+    const BmpOperands o = bmp_operands(nseq, in.seqs, in.lens, in.group_of, ngroups, npiv, in.pivot_seqs, in.pivot_lens);
+    std::vector<KhBmpGroup> groups(ngroups);
+    for (int g = 0; g < ngroups; ++g) {
+        if (o.size[g] > KH_BMP_MAX_COUNT) return KH_OK;
+        groups[g] = KhBmpGroup{o.first[g], o.size[g], o.first[g], 0};   // (a pivot has one bin per genome: count v of group g at bin0 + v - 1)
     }
     u64 max_bins = KH_BMP_MAX_BINS;
     if (const char* e = getenv("KHOICE_BMP_MAX_BINS")) max_bins = std::min<u64>(max_bins, strtoull(e, nullptr, 10));
@@ -3353,94 +3321,43 @@ static int exp3_bmp(kh_ctx* c, const Exp3In& in, const Exp3Out& out, bool* done)
     if ((u64)nseq + (npiv ? (u64)nseq + 1 : 0) > max_bins) return KH_OK;
     const u32 batch = npiv ? (u32)std::min<u64>(std::min<u64>((max_bins - (u64)nseq) / ((u64)nseq + 1), KH_BMP_CROSS_PIVOTS), (u64)npiv) : 0;
     const u32 nbatches = npiv ? ((u32)npiv + batch - 1) / batch : 1;
-    std::vector<const uint8_t*> oseq(nops);
-    std::vector<uint64_t> olen(nops);
-    std::vector<int> op_of_seq(nseq);
-    {
-        std::vector<u32> at(ngroups);
-        for (int g = 0; g < ngroups; ++g) at[g] = groups[g].first;
-        for (int i = 0; i < nseq; ++i) {
-            const u32 o = at[in.group_of[i]]++;
-            op_of_seq[i] = (int)o; oseq[o] = in.seqs[i]; olen[o] = in.lens[i];
-        }
-        for (int p = 0; p < npiv; ++p) { oseq[nseq + p] = in.pivot_seqs[p]; olen[nseq + p] = in.pivot_lens[p]; }
-    }
     // ---- the batches' blocks of replicas count against the budget of the partial bitmaps, in rows of one bitmap
     const u32 nb_max = batch * (u32)nseq + batch + (u32)nseq;   // bins and counters of a full batch
-    const u32 reps_max = std::max<u32>(1, std::min<u32>(64, 65536u / nb_max));
     const u64 nwords = k >= 3 ? 1ull << (2 * k - 6) : 1;
-    const u64 extra_rows = ((u64)nbatches * reps_max * nb_max + nwords - 1) / nwords;
-    BmpStage s;
+    const u64 extra_rows = ((u64)nbatches * BmpRun::reps_max(nb_max) * nb_max + nwords - 1) / nwords;
+    BmpRun run(c, k, in.on_device, o);
     bool fits = false;
-    KHCHK(bmp_plan(c, k, nops, oseq.data(), olen.data(), in.on_device, extra_rows, &s, &fits));
+    KHCHK(run.plan(extra_rows, &fits));
     if (!fits) return KH_OK;
-
-    hipStream_t st = c->st;
-    const u32 reps = std::min<u32>(s.rgrid, reps_max);
-    // workspace: [hist: nbatches x reps x nb_max u64][inst: nops u64] (zeroed, read back) [splits][ops][groups] (one upload)
-    const size_t hist_stride = 8 * (size_t)reps * nb_max;
-    const size_t off_inst = hist_stride * nbatches, off_splits = off_inst + 8 * (size_t)nops,
-                 off_ops = off_splits + sizeof(KhBmpSplit) * s.splits.size(), off_groups = off_ops + sizeof(KhBmpOp) * (size_t)nops,
-                 ws_bytes = off_groups + sizeof(KhBmpGroup) * (size_t)ngroups;
-    Tmp d_seq, d_ws, d_partial;
-    TMP_ALLOC(d_seq, c, s.need_pack ? s.seq_bytes : 256);
-    TMP_ALLOC(d_ws, c, ws_bytes);
-    TMP_ALLOC(d_partial, c, (size_t)(s.nsplits * s.nwords * 8));
-    const size_t up_bytes = ws_bytes - off_splits, down_bytes = off_splits;
-    Pinned pin{c};
-    PIN_ALLOC(pin, up_bytes + down_bytes + 64);
-    u8* h_up = static_cast<u8*>(pin.p);
-    u8* h_down = h_up + ((up_bytes + 63) & ~(size_t)63);
-    c->prof_begin(KC_COPY_IN);
-    KHCHK(bmp_copy_in(c, &s, oseq.data(), olen.data(), in.on_device, d_seq.as<u8>()));
-    memcpy(h_up, s.splits.data(), sizeof(KhBmpSplit) * s.splits.size());
-    memcpy(h_up + (off_ops - off_splits), s.ops.data(), sizeof(KhBmpOp) * (size_t)nops);
-    memcpy(h_up + (off_groups - off_splits), groups.data(), sizeof(KhBmpGroup) * (size_t)ngroups);
-    u8* wsp = d_ws.as<u8>();
-    HIPCHK(hipMemsetAsync(wsp, 0, off_splits, st));
-    HIPCHK(hipMemcpyAsync(wsp + off_splits, h_up, up_bytes, hipMemcpyHostToDevice, st));
-    c->prof_end();
-
-    const KhBmpJob build = bmp_build_job(s, k, reinterpret_cast<const KhBmpSplit*>(wsp + off_splits), d_partial.as<u64>(),
-                                         reinterpret_cast<unsigned long long*>(wsp + off_inst));
-    c->prof_begin(KC_BMP_BUILD);
-    kh_launch_bmp_build(build, (u32)s.nsplits, st);
-    c->prof_end();
-    HIPCHK(hipGetLastError());
+    run.layout(nbatches, nb_max);
+    const size_t off_groups = run.table(groups);
+    KHCHK(run.upload());
+    KHCHK(run.build());
     KhBmpCrossJob job{};
-    job.ops = reinterpret_cast<const KhBmpOp*>(wsp + off_ops);
-    job.groups = reinterpret_cast<const KhBmpGroup*>(wsp + off_groups);
-    job.partial = d_partial.as<u64>();
-    job.nwords = s.nwords;
-    job.ngenomes = (u32)nseq; job.ngroups = (u32)ngroups; job.reps = reps;
+    job.ops = run.ops();
+    job.groups = run.dev<const KhBmpGroup>(off_groups);
+    job.partial = run.d_partial.as<u64>();
+    job.nwords = run.s.nwords;
+    job.ngenomes = (u32)nseq; job.ngroups = (u32)ngroups; job.reps = run.reps;
     for (u32 b = 0; b < nbatches; ++b) {
         job.pop0 = (u32)nseq + b * batch;
         job.npivots = std::min<u32>(batch, (u32)npiv - b * batch);   // (no pivots: one launch for the genomes' counters)
         job.nbins = job.npivots * (u32)nseq;
-        job.hist = reinterpret_cast<unsigned long long*>(wsp + hist_stride * b);
-        c->prof_begin(KC_BMP_CROSS);
-        kh_launch_bmp_cross(job, s.rgrid, s.rwaves, st);
-        c->prof_end();
-        HIPCHK(hipGetLastError());
+        job.hist = run.hist(b);
+        KHCHK(timed_launch(c, KC_BMP_CROSS, [&] { kh_launch_bmp_cross(job, run.s.rgrid, run.s.rwaves, c->st); }));
     }
-    HIPCHK(hipMemcpyAsync(h_down, wsp, down_bytes, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    KHCHK(run.download());
 
-    // ---- per batch the replicas summed and the bins folded; the genomes' counters from the first batch
-    const u64* h_inst = reinterpret_cast<const u64*>(h_down + off_inst);
+    // ---- per batch the bins folded; the genomes' counters from the first batch
     out.clear(in);
-    u64 inst = 0, dsum = 0, met = 0;
-    for (int o = 0; o < nops; ++o) inst += h_inst[o];
+    u64 dsum = 0, met = 0;
     std::vector<u64> bins;
     for (u32 b = 0; b < nbatches; ++b) {
-        const u32 p0 = b * batch, np = std::min<u32>(batch, (u32)npiv - p0), nbins = np * (u32)nseq, nb = nbins + np + (u32)nseq;
-        const u64* h_hist = reinterpret_cast<const u64*>(h_down + hist_stride * b);
-        bins.assign(nb, 0);
-        for (u32 r = 0; r < reps; ++r)
-            for (u32 i = 0; i < nb; ++i) bins[i] += h_hist[(size_t)r * nb + i];
+        const u32 p0 = b * batch, np = std::min<u32>(batch, (u32)npiv - p0), nbins = np * (u32)nseq;
+        run.bins(b, nbins + np + (u32)nseq, &bins);
         if (b == 0)
             for (int i = 0; i < nseq; ++i) {
-                const u64 d = bins[nbins + np + op_of_seq[i]];
+                const u64 d = bins[nbins + np + o.op_of_seq[i]];
                 dsum += d;
                 if (out.distinct_per_seq) out.distinct_per_seq[i] = d;
             }
@@ -3455,13 +3372,7 @@ static int exp3_bmp(kh_ctx* c, const Exp3In& in, const Exp3Out& out, bool* done)
                 }
         }
     }
-    c->stat.bases += s.bases;
-    c->stat.builds += nops;
-    c->stat.kmers += inst;
-    c->stat.distinct += dsum;
-    c->stat.setop_in += dsum;
-    c->stat.setop_out += met;   // pivot k-mers met in a group, summed over the groups
-    c->stat.setops++;
+    run.account(dsum, met);   // pivot k-mers met in a group, summed over the groups
     *done = true;
     return KH_OK;
 }
@@ -3469,35 +3380,20 @@ static int exp3_bmp(kh_ctx* c, const Exp3In& in, const Exp3Out& out, bool* done)
 // build of genomes and pivots, the -cs{cs} union of every group, and intersect -ocsum + histogram of every pivot with
 // every union.  No kernel of its own.
 static int exp3_sets(kh_ctx* c, const Exp3In& in, const Exp3Out& out) {
-    struct Bag {   // every intermediate set, freed on every way out
-        std::vector<kh_set*> v;
-        ~Bag() { for (kh_set* s : v) kh_set_free(s); }
-    } plain, unions;
-    const int nseq = in.nseq, ngroups = in.ngroups, npiv = in.npivots, n = nseq + npiv;
-    std::vector<const uint8_t*> seqs(in.seqs, in.seqs + nseq);
-    std::vector<uint64_t> lens(in.lens, in.lens + nseq);
-    seqs.insert(seqs.end(), in.pivot_seqs, in.pivot_seqs + npiv);
-    lens.insert(lens.end(), in.pivot_lens, in.pivot_lens + npiv);
-    plain.v.assign(n, nullptr);   // genomes, then pivots
-    KHCHK(kh_build_batch(c, n, seqs.data(), lens.data(), in.on_device, in.k, 1, KH_NO_MAX, KH_KMC_DEFAULT_CS, 0, plain.v.data()));
+    const int nseq = in.nseq, ngroups = in.ngroups, npiv = in.npivots;
+    SetBag plain, unions;   // every intermediate set, freed on every way out
+    KHCHK(build_plain(c, nseq, in.seqs, in.lens, npiv, in.pivot_seqs, in.pivot_lens, in.on_device, in.k, &plain));
     out.clear(in);
     for (int i = 0; i < nseq; ++i)
         if (out.distinct_per_seq) out.distinct_per_seq[i] = plain.v[i]->n;
     for (int p = 0; p < npiv; ++p)
         if (out.distinct_per_pivot) out.distinct_per_pivot[p] = plain.v[nseq + p]->n;
     if (!out.inter_hist || !npiv) return KH_OK;
-    unions.v.assign(ngroups, nullptr);
-    for (int g = 0; g < ngroups; ++g) {
-        std::vector<const kh_set*> members;
-        for (int i = 0; i < nseq; ++i)
-            if (in.group_of[i] == g) members.push_back(plain.v[i]);
-        KHCHK(kh_union_sum(c, members.data(), (int)members.size(), in.cs, &unions.v[g], nullptr, 0));
-    }
+    KHCHK(group_unions(c, plain.v.data(), nseq, in.group_of, ngroups, in.cs, &unions, nullptr, 0));
     for (int p = 0; p < npiv; ++p)
         for (int g = 0; g < ngroups; ++g) {
-            Bag r;
-            r.v.assign(1, nullptr);
-            KHCHK(kh_simple(c, plain.v[nseq + p], unions.v[g], KH_INTERSECT, KH_MODE_SUM, in.cs, &r.v[0]));
+            SetBag r;
+            KHCHK(kh_simple(c, plain.v[nseq + p], unions.v[g], KH_INTERSECT, KH_MODE_SUM, in.cs, r.slot()));
             KHCHK(kh_histogram(c, r.v[0], out.inter_hist + ((size_t)p * ngroups + g) * in.hist_len, in.hist_len));
         }
     return KH_OK;
@@ -3506,19 +3402,8 @@ extern "C" int kh_exp3_run(kh_ctx* c, int nseq, const uint8_t* const* seqs, cons
                            const int* group_of, int ngroups, int npivots, const uint8_t* const* pivot_seqs,
                            const uint64_t* pivot_lens, int k, uint32_t cs, uint64_t* inter_hist, uint32_t hist_len,
                            uint64_t* distinct_per_seq, uint64_t* distinct_per_pivot) {
-    if (!c || !seqs || !lens || !group_of || nseq <= 0 || ngroups <= 0 || npivots < 0 || (npivots && (!pivot_seqs || !pivot_lens)))
-        return kh_fail(KH_E_ARG, "kh_exp3_run: bad argument");
-    if (hist_len < 2) return kh_fail(KH_E_ARG, "hist_len must be >= 2");
-    KHCHK(check_k(k));
-    if (cs < 1) return kh_fail(KH_E_ARG, "cs must be >= 1");
-    std::vector<int> gsize(ngroups, 0);
-    for (int i = 0; i < nseq; ++i) {
-        if (group_of[i] < 0 || group_of[i] >= ngroups)
-            return kh_fail(KH_E_ARG, "group_of[%d]=%d outside [0,%d)", i, group_of[i], ngroups);
-        gsize[group_of[i]]++;
-    }
-    for (int g = 0; g < ngroups; ++g)
-        if (!gsize[g]) return kh_fail(KH_E_ARG, "group %d has no sequences", g);
+    KHCHK(exp_check_args("kh_exp3_run", c, nseq, seqs, lens, group_of, ngroups, npivots, pivot_seqs, pivot_lens, false, nullptr,
+                         hist_len, k, cs, nullptr));
     const Exp3In in{nseq, seqs, lens, on_device, group_of, ngroups, npivots, pivot_seqs, pivot_lens, k, cs, hist_len};
     const Exp3Out out{inter_hist, distinct_per_seq, distinct_per_pivot};
     HIPCHK(hipSetDevice(c->dev));
