@@ -89,10 +89,31 @@ void Pool::trim() {
     cached_bytes = 0;
 }
 
+// KHOICE_DEBUG_POISON=<0..255> (tests): every block handed out, fresh or recycled, is filled with
+// that byte first, so that no form can lean on what a block held before.  Read at every call, like
+// the other knobs; unset, nothing is queued.  -1 = unset or not a byte.
+static int debug_poison() {
+    const char* e = getenv("KHOICE_DEBUG_POISON");
+    if (!e || !*e) return -1;
+    char* end = nullptr;
+    const long v = strtol(e, &end, 0);
+    return (*end || v < 0 || v > 255) ? -1 : (int)v;
+}
+
 DevBuf* kh_ctx::buf_alloc(size_t bytes) {
     size_t got = 0;
     void* p = pool.alloc(bytes, &got);
     if (!p) return nullptr;
+    const int poison = debug_poison();
+    if (poison >= 0) {
+        // Every user of the block runs on `st`, which exists from kh_ctx_create on (no allocation
+        // precedes it), so the fill is ordered before them and after the block's last user.
+        if (hipMemsetAsync(p, poison, got, st) != hipSuccess) {
+            pool.release(p, got);
+            return nullptr;
+        }
+        stat.poisoned_bytes += got;
+    }
     DevBuf* b = new DevBuf;
     b->p = p;
     b->bytes = got;
@@ -146,15 +167,20 @@ struct Pinned {
 void* kh_ctx::pin_alloc(size_t bytes, size_t* got) {
     bytes = (bytes + 4095) & ~(size_t)4095;
     auto it = pinned_free.lower_bound(bytes);
+    void* p = nullptr;
     if (it != pinned_free.end() && it->first <= 4 * bytes) {
-        void* p = it->second;
+        p = it->second;
         *got = it->first;
         pinned_free.erase(it);
-        return p;
+    } else {
+        if (hipHostMalloc(&p, bytes, hipHostMallocDefault) != hipSuccess) return nullptr;
+        *got = bytes;
     }
-    void* p = nullptr;
-    if (hipHostMalloc(&p, bytes, hipHostMallocDefault) != hipSuccess) return nullptr;
-    *got = bytes;
+    const int poison = debug_poison();   // a released staging block has no copy in flight: its user synchronised
+    if (poison >= 0) {
+        memset(p, poison, *got);
+        stat.poisoned_bytes += *got;
+    }
     return p;
 }
 void kh_ctx::pin_release(void* p, size_t bytes) {
@@ -282,19 +308,20 @@ extern "C" int kh_stats(kh_ctx* c, char* buf, size_t buflen) {
     if (!c || !buf) return kh_fail(KH_E_ARG, "kh_stats: NULL argument");
     c->prof_collect();
     std::string s = "{";
-    char t[384];
+    char t[512];
     snprintf(t, sizeof t, "\"device\":%d,\"arch\":\"%s\",\"cus\":%d,", c->dev, c->arch.c_str(), c->cus);
     s += t;
     snprintf(t, sizeof t,
              "\"builds\":%llu,\"bases\":%llu,\"text_packed\":%llu,\"kmers\":%llu,\"distinct\":%llu,\"setops\":%llu,"
-             "\"setop_in\":%llu,\"setop_out\":%llu,\"retries\":%llu,\"order_fallbacks\":%llu,\"skm_records\":%llu,\"big_slots\":%llu,\"pool_bytes\":%zu,",
+             "\"setop_in\":%llu,\"setop_out\":%llu,\"retries\":%llu,\"order_fallbacks\":%llu,\"skm_records\":%llu,\"big_slots\":%llu,\"poisoned_bytes\":%llu,\"pool_bytes\":%zu,",
              (unsigned long long)c->stat.builds, (unsigned long long)c->stat.bases,
              (unsigned long long)c->stat.text_packed,
              (unsigned long long)c->stat.kmers, (unsigned long long)c->stat.distinct,
              (unsigned long long)c->stat.setops, (unsigned long long)c->stat.setop_in,
              (unsigned long long)c->stat.setop_out, (unsigned long long)c->stat.retries,
              (unsigned long long)c->stat.order_fallbacks, (unsigned long long)c->stat.skm_records,
-             (unsigned long long)c->stat.big_slots, c->pool.total_bytes);
+             (unsigned long long)c->stat.big_slots, (unsigned long long)c->stat.poisoned_bytes,
+             c->pool.total_bytes);
     s += t;
     s += "\"kernels\":{";
     for (int i = 0; i < KC_COUNT; ++i) {

@@ -38,7 +38,8 @@ struct ProfEvt { int cls; hipEvent_t a, b; };
 struct Stats {
     u64 builds = 0, bases = 0, kmers = 0, distinct = 0, setops = 0, setop_in = 0, setop_out = 0,
         retries = 0, order_fallbacks = 0, skm_records = 0, big_slots = 0,
-        text_packed = 0;   // bytes of sequence text copied into a batch buffer (0 for a text read in place)
+        text_packed = 0,   // bytes of sequence text copied into a batch buffer (0 for a text read in place)
+        poisoned_bytes = 0;   // device and pinned bytes filled under KHOICE_DEBUG_POISON (0 when unset)
 };
 
 struct kh_ctx {
