@@ -436,6 +436,29 @@ static void report_stamps(kh_ctx* c, const char* what, DevBuf* sb, u64 nparts) {
         fprintf(stderr, "[stamps] %s offsets from t0:%s\n", what, line.c_str());
     }
 }
+#ifdef KH_STAMPS_WG
+void kh_debug_set_stamps_skm2(u64* p);
+// -DKH_STAMPS_WG: when every workgroup of the persistent union began and ended its walk, one line per workgroup
+// appended to $KHOICE_WG_DUMP (tools/wg_ends.py reads it): call, workgroup, hardware id, XCC, shader clock at the
+// beginning and the end, constant-rate clock at the beginning and the end
+static void dump_wg_ends(kh_ctx* c, DevBuf* sb, u32 grid) {
+    const char* path = getenv("KHOICE_WG_DUMP");
+    if (!path) return;
+    static int call = 0;
+    std::vector<u64> h((size_t)grid * 16);
+    (void)hipMemcpyAsync(h.data(), sb->p, (size_t)grid * 128, hipMemcpyDeviceToHost, c->st);
+    (void)hipStreamSynchronize(c->st);
+    FILE* f = fopen(path, "a");
+    if (!f) return;
+    for (u32 b = 0; b < grid; ++b) {
+        const u64* t = &h[(size_t)b * 16];
+        fprintf(f, "%d %u %llu %llu %llu %llu %llu %llu\n", call, b, (unsigned long long)t[1], (unsigned long long)t[2],
+                (unsigned long long)t[0], (unsigned long long)t[8], (unsigned long long)t[3], (unsigned long long)t[11]);
+    }
+    fclose(f);
+    ++call;
+}
+#endif
 #endif
 
 // ------------------------------------------------------------------------------ K1 build
@@ -1860,10 +1883,12 @@ static int skm_prepare(kh_ctx* c, int nseq, const uint8_t* const* seqs, const ui
     const u32 ntiles = (u32)tiles.size();
     const u32 reps = g.ugrid;
     const size_t hist_words = (size_t)reps * L->nbins;
-    // workspace: [hist][ctl: 8 u32][inst: nseq u64][dup: 64 u64][cur1: nb1 u32][cur2: nslots u32] (zeroed) [ginfo: 64 u32]
+    // workspace: [hist][ctl: 8 u32][inst: nseq u64][dup: 64 u64][cur1: nb1 u32][cur2: nslots u32][claim: a 128-byte
+    // line of its own] (zeroed) [ginfo: 64 u32]
     const size_t off_ctl = 8 * hist_words, off_inst = off_ctl + 32, off_dup = off_inst + 8 * (size_t)nseq,
                  off_cur1 = off_dup + 8 * 64, off_cur2 = off_cur1 + 4 * (size_t)KH_SKM_CUR1_STRIDE * g.nb1,
-                 off_ginfo = off_cur2 + 4 * (size_t)((g.nslots + 3) & ~3u), off_tags = off_ginfo + 256,
+                 off_claim = (off_cur2 + 4 * (size_t)g.nslots + 127) & ~(size_t)127,
+                 off_ginfo = off_claim + 128, off_tags = off_ginfo + 256,
                  off_segs = off_tags + (((size_t)nseq + 15) & ~(size_t)15), off_tiles = off_segs + sizeof(KhSeg) * nseq,
                  ws_bytes = off_tiles + sizeof(KhTile) * (size_t)std::max<u32>(1, ntiles);   // [ginfo .. tiles]: one upload
     const u32 spill_cap = SkmStage::spill_cap;
@@ -1912,6 +1937,7 @@ static int skm_prepare(kh_ctx* c, int nseq, const uint8_t* const* seqs, const ui
     job.ginfo = reinterpret_cast<const u32*>(wsp + off_ginfo);
     job.hist = reinterpret_cast<unsigned long long*>(wsp);
     job.ctl = reinterpret_cast<u32*>(wsp + off_ctl);
+    job.claim = reinterpret_cast<u32*>(wsp + off_claim);
     job.tile_pos = tile_pos;
     job.k = k; job.m = g.m; job.w = g.w; job.nmax = g.nmax;
     job.nslots = g.nslots; job.S = g.S; job.nb1 = g.nb1; job.cap1 = g.cap1; job.cap2 = g.cap2;
@@ -1943,6 +1969,9 @@ static int skm_prepare(kh_ctx* c, int nseq, const uint8_t* const* seqs, const ui
     c->prof_end();
 #ifdef KH_STAMPS
     kh_debug_set_stamps_skm(s->d_stamps.as<u64>());
+#ifdef KH_STAMPS_WG
+    kh_debug_set_stamps_skm2(s->d_stamps.as<u64>());
+#endif
 #endif
     s->staged = true;
     return KH_OK;
@@ -1963,7 +1992,11 @@ static int exp1_skm(kh_ctx* c, const Exp1In& in, uint64_t* within_hist, uint64_t
     else kh_launch_skm_union(job, in.cs, g.ugrid, st);
     c->prof_end();
     HIPCHK(hipGetLastError());
-#ifdef KH_STAMPS
+#if defined(KH_STAMPS) && defined(KH_STAMPS_WG)
+    dump_wg_ends(c, s.d_stamps.b, g.ugrid);
+    kh_debug_set_stamps_skm(nullptr);
+    kh_debug_set_stamps_skm2(nullptr);
+#elif defined(KH_STAMPS)
     report_stamps(c, "skm_union (scan barrier / owner / expand / insert / barrier / read-out / barrier / flush)", s.d_stamps.b, g.nslots);
     kh_debug_set_stamps_skm(nullptr);
 #endif

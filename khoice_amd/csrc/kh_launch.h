@@ -148,6 +148,7 @@ struct KhSkmJob {
     const u32* ginfo;               // as KhTagJob
     unsigned long long* hist;       // [reps][nbins]
     u32* ctl;                       // [0] error bits, [1] fullest slot seen, [2] records written by the scatter
+    u32* claim;                     // zeroed, a 128-byte line of its own: the unions' slot claims (SkmSlotFeed, kh_skm_device.h)
     u32 tile_pos;
     int k, m;                       // m-mer length of the minimizer (<= 16)
     u32 w;                          // m-mers per k-mer: k - m + 1

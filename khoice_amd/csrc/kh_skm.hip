@@ -429,7 +429,27 @@ struct SkmClaim1 {
     }
 };
 
-#ifdef KH_STAMPS
+// (-DKH_STAMPS_WG with -DKH_STAMPS: two stamps per workgroup, the beginning and the end of its walk, instead of the
+// per-slot ones: when do the workgroups of the persistent union finish?  Word 1: the hardware id of the wave, word 2:
+// the XCC; words 3 and 11: the constant-rate clock, which all XCCs share.)
+#if defined(KH_STAMPS) && defined(KH_STAMPS_WG)
+#define SKM_USTAMP(idx) do {} while (0)
+#define SKM_WGSTAMP(idx)                                                                   \
+    do {                                                                                   \
+        __builtin_amdgcn_sched_barrier(0);                                                 \
+        if (threadIdx.x == 0 && g_skm_stamps) {                                            \
+            u64* const sp_ = g_skm_stamps + (u64)blockIdx.x * 16;                          \
+            sp_[(idx)] = __builtin_amdgcn_s_memtime();                                     \
+            sp_[(idx) + 3] = wall_clock64();                                               \
+            if ((idx) == 0) {                                                              \
+                sp_[1] = __builtin_amdgcn_s_getreg(4 | (31 << 11));                        \
+                sp_[2] = __builtin_amdgcn_s_getreg(20 | (31 << 11));                       \
+            }                                                                              \
+        }                                                                                  \
+        __builtin_amdgcn_sched_barrier(0);                                                 \
+    } while (0)
+#elif defined(KH_STAMPS)
+#define SKM_WGSTAMP(idx) do {} while (0)
 #define SKM_USTAMP(idx)                                                                    \
     do {                                                                                   \
         __builtin_amdgcn_sched_barrier(0);                                                 \
@@ -438,15 +458,19 @@ struct SkmClaim1 {
     } while (0)
 #else
 #define SKM_USTAMP(idx) do {} while (0)
+#define SKM_WGSTAMP(idx) do {} while (0)
 #endif
 
 // PERSISTENT: the grid is two workgroups per CU (what the LDS allows); a workgroup walks slots blockIdx.x,
-// blockIdx.x + gridDim.x, ...  While it works on one slot the record of the next one is already on its way to the
+// blockIdx.x + gridDim.x, ... for the first half of its rounds and takes the rest by claim from a device counter
+// (SkmSlotFeed, kh_skm_device.h: the two workgroups of a CU do not run at the same speed; with equal shares the one
+// dispatched first left at 0.75 of the kernel's time and the other finished alone, 13 % of the wave-slots stood
+// empty).  While it works on one slot the record of the next one is already on its way to the
 // thread's registers and the count of the one after to a scalar register: a workgroup that started with "load the
 // count, then load the records" spent 2.5 of its 6 microseconds waiting for memory with nothing else to do.  The
 // histogram bins and the repeat counters stay in LDS over all slots of the workgroup and are written once.
 template <u32 NT, u32 T>
-__global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs) {
+__global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs, u32 first_claimed) {
     extern __shared__ __attribute__((aligned(16))) u8 lds_raw[];
     using G = SkmUnionGeo<NT, T>;
     constexpr u32 T2 = G::T2, NW = NT / 64;
@@ -474,7 +498,7 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs) 
     u32* dd = reinterpret_cast<u32*>(tkey) + T;
     const u32 tid0 = threadIdx.x, wid = __builtin_amdgcn_readfirstlane(tid0 >> 6);
     u32 tid = tid0, lane = lane_id();
-    const u32 nbins = jb.nbins, cap2 = jb.cap2, nslots = jb.nslots, stride = gridDim.x;
+    const u32 nbins = jb.nbins, cap2 = jb.cap2, nslots = jb.nslots;
     const int k = jb.k;
     const u32 sshift = nbins <= 72u ? 2u : (nbins <= 144u ? 1u : 0u), smask = (1u << sshift) - 1u;
     auto clear_keys = [&]() {
@@ -523,7 +547,7 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs) 
         dupc[tid] = 0;
     }
     if (tid < SKM_HSTRIPE_WORDS) hstripe[tid] = 0;
-    if (tid == 0) scratch[0] = 0;
+    if (tid == 0) { scratch[0] = 0; scratch[1] = ~0u; }   // ([1]: the claim that is handed over, SkmSlotFeed)
     // the 2k-bit mask and where the last base of a k-mer sits, as 32-bit halves (15 <= k <= 32)
     const u32 kml = (u32)kh_mask(2 * k), kmh = (u32)(kh_mask(2 * k) >> 32);
     const u32 fsh = 64u - 2u * (u32)k;          // right-aligns a reversed window
@@ -552,18 +576,19 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs) 
     };
     u32 st_full = 0, st_exp = 0;   // fullest slot seen, k-mer instances expanded (uniform)
     // ---- pipeline prologue: this slot's record, the next slot's count
-    u32 slot = blockIdx.x;
+    SkmSlotFeed feed(gridDim.x, nslots, first_claimed);
+    u32 slot = blockIdx.x, slot_next = slot + gridDim.x;
     u32 nrec = count_of(slot);
-    u32 nrec_next = count_of(slot + stride);
+    u32 nrec_next = count_of(slot_next);
     uint4 rr = tid < nrec ? (jb.reg2 + (u64)slot * cap2)[tid] : make_uint4(0, 0, 0, 0);
-    for (; slot < nslots; slot += stride) {
+    SKM_WGSTAMP(0);
+    while (slot < nslots) {
         // (the thread number through an opaque copy, per slot: the many LDS addresses formed from it are worked out
         // where they are used instead of being kept in registers — and spilled — across the whole loop)
         tid = tid0;
         asm volatile("" : "+v"(tid));
         lane = tid & (KH_WAVE - 1u);
         const uint4* __restrict__ reg = jb.reg2 + (u64)slot * cap2;
-        const u32 nrec_after = count_of(slot + 2u * stride);   // (a scalar load: two slots ahead)
         if (!nrec && counts[slot] > fit) {   // uniform: an overfull slot
             if (tid0 == 0) {
                 const u32 at = atomicAdd(jb.ctl + 6, 1u);
@@ -587,6 +612,11 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs) 
         SKM_USTAMP(0);
         __syncthreads();
         SKM_USTAMP(1);
+        // the slot after the next one (a claim drawn during the previous slot has arrived in LDS) and its count:
+        // a scalar load, two slots ahead
+        const u32 slot_after = feed.take(scratch + 1);
+        const u32 nrec_after = count_of(slot_after);
+        const bool draw = feed.wants();   // (uniform)
         SKM_MARK("dedup");
         // ---- identical records meet: the first keeps its place, the others add their genome bit to its mask.  A
         // record that stays takes its chunks from a counter (chunks in the low half, k-mers in the high half) and
@@ -650,7 +680,7 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs) 
         }
         // ---- the next slot's record sets out now, into the registers this slot's record has just left: it has the
         // expansion and the read-out to arrive
-        rr = tid < nrec_next ? (jb.reg2 + (u64)(slot + stride) * cap2)[tid] : make_uint4(0, 0, 0, 0);
+        rr = tid < nrec_next ? (jb.reg2 + (u64)slot_next * cap2)[tid] : make_uint4(0, 0, 0, 0);
         clear_keys();
         clear_masks();
         u32 C = sc0 & 0xffffu, N = sc0 >> 16;
@@ -837,6 +867,9 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs) 
             }
             SKM_MARK("insert_done");
             SKM_USTAMP(5);
+            // the next claim: one lane of the last wave, which runs out of chunks first; the barrier below and the
+            // next slot's first one lie between this store and the threads that read it
+            if (draw && q == 0 && tid0 == NT - KH_WAVE) feed.draw(jb.claim, scratch + 1);
             __syncthreads();
             SKM_USTAMP(6);
             // ---- all masks are final: every thread turns the entries it created into histogram bins.
@@ -883,12 +916,16 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs) 
             if (q + 1 < R) __syncthreads();
         }
         SKM_USTAMP(8);
+        if (draw && R == 0 && tid0 == NT - KH_WAVE) feed.draw(jb.claim, scratch + 1);   // (an empty slot: nothing was inserted)
         // ---- on to the next slot: its record has arrived in the meantime.  No barrier here: what the next slot writes
         // before its first barrier (staged records, the set of contents: the KEY plane; this thread's record mask)
         // is read by nobody in the read-out.
         nrec = nrec_next;
         nrec_next = nrec_after;
+        slot = slot_next;
+        slot_next = slot_after;
     }
+    SKM_WGSTAMP(8);
     __syncthreads();
     tid = tid0;
     lane = tid & (KH_WAVE - 1u);
@@ -1371,7 +1408,7 @@ void kh_launch_skm_regroup(const KhSkmJob& job, hipStream_t st) { skm_launch_reg
 void kh_launch_skm_union(const KhSkmJob& job, u32 cs, u32 grid, hipStream_t st) {
     const size_t lds = kh_skm_union_lds_bytes();
     skm_allow_lds(k_skm_union<1024, 4096>, lds);
-    hipLaunchKernelGGL((k_skm_union<1024, 4096>), dim3(grid), dim3(1024), lds, st, job, cs);
+    hipLaunchKernelGGL((k_skm_union<1024, 4096>), dim3(grid), dim3(1024), lds, st, job, cs, skm_first_claimed(job.nslots, grid));
 }
 void kh_launch_skm_pack(const KhSkmPackJob& job, hipStream_t st) {
     if (!job.nslots) return;

@@ -21,6 +21,27 @@
 #include "kh_launch.h"
 
 #define SKM_STAMP(idx) do {} while (0)   // (the phase stamps live in kh_skm.hip's kernels only)
+// (-DKH_STAMPS -DKH_STAMPS_WG: the beginning and the end of every union workgroup's walk, as in kh_skm.hip)
+#if defined(KH_STAMPS) && defined(KH_STAMPS_WG)
+__device__ u64* g_skm2_stamps = nullptr;
+void kh_debug_set_stamps_skm2(u64* p) { (void)hipMemcpyToSymbol(HIP_SYMBOL(g_skm2_stamps), &p, sizeof p); }
+#define SKM2_WGSTAMP(idx)                                                                  \
+    do {                                                                                   \
+        __builtin_amdgcn_sched_barrier(0);                                                 \
+        if (threadIdx.x == 0 && g_skm2_stamps) {                                           \
+            u64* const sp_ = g_skm2_stamps + (u64)blockIdx.x * 16;                         \
+            sp_[(idx)] = __builtin_amdgcn_s_memtime();                                     \
+            sp_[(idx) + 3] = wall_clock64();                                               \
+            if ((idx) == 0) {                                                              \
+                sp_[1] = __builtin_amdgcn_s_getreg(4 | (31 << 11));                        \
+                sp_[2] = __builtin_amdgcn_s_getreg(20 | (31 << 11));                       \
+            }                                                                              \
+        }                                                                                  \
+        __builtin_amdgcn_sched_barrier(0);                                                 \
+    } while (0)
+#else
+#define SKM2_WGSTAMP(idx) do {} while (0)
+#endif
 #include "kh_skm_device.h"
 
 namespace {
@@ -366,7 +387,7 @@ struct SkmClaim2 {
     }
 };
 
-__global__ __launch_bounds__(SKM2_UNT, SKM2_UNT == 1024 ? 8 : 6) void k_skm2_union(const KhSkmJob jb, u32 cs) {
+__global__ __launch_bounds__(SKM2_UNT, SKM2_UNT == 1024 ? 8 : 6) void k_skm2_union(const KhSkmJob jb, u32 cs, u32 first_claimed) {
     extern __shared__ __attribute__((aligned(16))) u8 lds_raw[];
     constexpr u32 NT = SKM2_UNT, T = SKM2_UT, T2 = SKM2_UT2, NW = NT / 64;
     static_assert((T2 & (T2 - 1)) == 0 && T % 4 == 0, "second table: a power of two");
@@ -394,7 +415,7 @@ __global__ __launch_bounds__(SKM2_UNT, SKM2_UNT == 1024 ? 8 : 6) void k_skm2_uni
     constexpr u32 DD = SKM2_DD;
     const u32 tid0 = threadIdx.x, wid = __builtin_amdgcn_readfirstlane(tid0 >> 6);
     u32 tid = tid0, lane = lane_id();
-    const u32 nbins = jb.nbins, cap2 = jb.cap2, nslots = jb.nslots, stride = gridDim.x;
+    const u32 nbins = jb.nbins, cap2 = jb.cap2, nslots = jb.nslots;
     const int k = jb.k;
     // the 2k-bit mask, the shift that right-aligns a reversed 128-bit window, where the last base sits (33 <= k <= 63)
     const Skm2Consts kc(k);
@@ -416,19 +437,20 @@ __global__ __launch_bounds__(SKM2_UNT, SKM2_UNT == 1024 ? 8 : 6) void k_skm2_uni
         return n <= fit ? n : 0u;
     };
     ro.init(jb.ginfo, nbins, jb.abase, tid);
-    if (tid == 0) scratch[0] = 0;
+    if (tid == 0) { scratch[0] = 0; scratch[1] = ~0u; }   // ([1]: the claim that is handed over, SkmSlotFeed)
     u32 st_full = 0, st_exp = 0;
-    u32 slot = blockIdx.x;
+    SkmSlotFeed feed(gridDim.x, nslots, first_claimed);
+    u32 slot = blockIdx.x, slot_next = slot + gridDim.x;
     u32 nrec = count_of(slot);
-    u32 nrec_next = count_of(slot + stride);
+    u32 nrec_next = count_of(slot_next);
     uint4 ra = make_uint4(0, 0, 0, 0), rb = make_uint4(0, 0, 0, 0);
     if (tid < nrec) { const uint4* r = jb.reg2 + ((u64)slot * cap2 + tid) * 2; ra = r[0]; rb = r[1]; }
-    for (; slot < nslots; slot += stride) {
+    SKM2_WGSTAMP(0);
+    while (slot < nslots) {
         tid = tid0;
         asm volatile("" : "+v"(tid));
         lane = tid & (KH_WAVE - 1u);
         const uint4* __restrict__ reg = jb.reg2 + (u64)slot * cap2 * 2;
-        const u32 nrec_after = count_of(slot + 2u * stride);
         if (counts[slot] > fit && tid0 == 0) {   // an overfull slot: listed for k_skm_big
             const u32 at = atomicAdd(jb.ctl + 6, 1u);
             if (at < jb.big_cap) jb.big_list[at] = slot;
@@ -449,6 +471,10 @@ __global__ __launch_bounds__(SKM2_UNT, SKM2_UNT == 1024 ? 8 : 6) void k_skm2_uni
             rmask[tid] = 1u << (tg & 31u);
         }
         __syncthreads();
+        // the slot after the next one (a claim drawn during the previous slot has arrived in LDS) and its count
+        const u32 slot_after = feed.take(scratch + 1);
+        const u32 nrec_after = count_of(slot_after);
+        const bool draw = feed.wants();   // (uniform)
         // ---- identical records meet
         if (__builtin_amdgcn_ballot_w64(nj != 0)) {
             u32 h = a0 * 0x9E3779B1u ^ a1 * 0x85EBCA77u ^ a2 * 0xC2B2AE3Du ^ a3 * 0x27D4EB2Fu ^ b0 * 0x165667B1u ^ b1 * 0xD3A2646Cu ^
@@ -500,7 +526,7 @@ __global__ __launch_bounds__(SKM2_UNT, SKM2_UNT == 1024 ? 8 : 6) void k_skm2_uni
         }
         // ---- the next slot's record sets out; the table is made
         ra = make_uint4(0, 0, 0, 0); rb = make_uint4(0, 0, 0, 0);
-        if (tid < nrec_next) { const uint4* r = jb.reg2 + ((u64)(slot + stride) * cap2 + tid) * 2; ra = r[0]; rb = r[1]; }
+        if (tid < nrec_next) { const uint4* r = jb.reg2 + ((u64)slot_next * cap2 + tid) * 2; ra = r[0]; rb = r[1]; }
         clear_keys();
         clear_masks();
         u32 C = sc0 & 0xffffu, N = sc0 >> 16;
@@ -610,6 +636,9 @@ __global__ __launch_bounds__(SKM2_UNT, SKM2_UNT == 1024 ? 8 : 6) void k_skm2_uni
                     }
                 }
             }
+            // the next claim: one lane of the last wave, which runs out of chunks first; the barrier below and the
+            // next slot's first one lie between this store and the threads that read it
+            if (draw && q == 0 && tid0 == NT - KH_WAVE) feed.draw(jb.claim, scratch + 1);
             __syncthreads();
             // ---- all masks are final: every thread turns the entries it created into histogram bins
 #pragma unroll
@@ -631,9 +660,13 @@ __global__ __launch_bounds__(SKM2_UNT, SKM2_UNT == 1024 ? 8 : 6) void k_skm2_uni
             }
             if (q + 1 < R) __syncthreads();
         }
+        if (draw && R == 0 && tid0 == NT - KH_WAVE) feed.draw(jb.claim, scratch + 1);   // (an empty slot: nothing was inserted)
         nrec = nrec_next;
         nrec_next = nrec_after;
+        slot = slot_next;
+        slot_next = slot_after;
     }
+    SKM2_WGSTAMP(8);
     __syncthreads();
     tid = tid0;
     ro.flush(jb.hist + (u64)(blockIdx.x % jb.reps) * nbins, nbins, jb.dup, tid, NT);
@@ -685,6 +718,6 @@ void kh_launch_skm2_regroup(const KhSkmJob& job, hipStream_t st) { skm_launch_re
 void kh_launch_skm2_union(const KhSkmJob& job, u32 cs, u32 grid, hipStream_t st) {
     const size_t lds = kh_skm2_union_lds_bytes(job.nbins);
     skm_allow_lds(k_skm2_union, lds);
-    hipLaunchKernelGGL(k_skm2_union, dim3(grid), dim3(SKM2_UNT), lds, st, job, cs);
+    hipLaunchKernelGGL(k_skm2_union, dim3(grid), dim3(SKM2_UNT), lds, st, job, cs, skm_first_claimed(job.nslots, grid));
 }
 void kh_launch_skm2_big(const KhSkmJob& job, u32 cs, u32 nbig, hipStream_t st) { skm_launch_big<SkmBig2>(job, cs, nbig, st); }

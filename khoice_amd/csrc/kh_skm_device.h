@@ -5,6 +5,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdlib>
 
 #include "kh_device.h"
@@ -344,6 +345,61 @@ struct SkmReadout {
 };
 
 template <u32 Q> struct SkmRecord { uint4 v[Q]; };   // a record in registers; its header: the last word of v[Q - 1]
+
+// ------------------------------------------------------------------------------------------
+// SLOTS BY CLAIM: which slots a persistent union workgroup works on (k_skm_union, k_skm2_union).
+// The workgroups of a CU do not run at the same speed (the one dispatched first gets the vector issue slots first and
+// walks 154 equal slots in 3/4 of the time of its neighbour, which then finishes alone on a half-empty CU).  So only
+// the first share of the walk is strided as before (slot blockIdx.x + j * grid, the slots below `first_claimed`);
+// behind it a workgroup takes claims of KH_TUNE_SKM_CLAIM consecutive slots from one device counter
+// (KhSkmJob::claim, zeroed with the workspace at every call): the faster workgroup takes more slots.
+// The pipeline keeps its depth: a workgroup holds the current slot and the next one and asks take() for the one after
+// once per slot.  A claim is DRAWN a slot before take() needs it, by one lane of the last wave where that wave has
+// the least to do (the end of the insertions: its chunks of the last pass are the first to run out), and handed over
+// through a word of LDS that everybody reads behind the next slot's first barrier: no barrier of its own, no wait
+// loop, and the round trip of the atomic is not on the path of the other waves.  All state is uniform (scalar
+// registers).  A claim that reaches nslots is the last one drawn; slots at or beyond nslots are empty ones to the
+// caller.  KH_TUNE_SKM_CLAIM 0: the static walk throughout.
+// ------------------------------------------------------------------------------------------
+#ifndef KH_TUNE_SKM_CLAIM
+#define KH_TUNE_SKM_CLAIM 2   // slots per claim (sweep: profiles/README.md, 2026-10-19)
+#endif
+#ifndef KH_TUNE_SKM_CLAIM_STATIC_PCT
+#define KH_TUNE_SKM_CLAIM_STATIC_PCT 50   // share of a workgroup's rounds (nslots / grid) that is walked strided, in per cent
+#endif
+// The first slot that is claimed: behind the strided rounds, of which there are at least three (the pipeline's depth:
+// no atomic at the head of the kernel).  Host side, an argument of the kernels.
+inline u32 skm_first_claimed(const u32 nslots, const u32 grid) {
+    if (!KH_TUNE_SKM_CLAIM) return ~0u;
+    const u64 rounds = std::max<u64>(3, (u64)(nslots / grid) * (u32)KH_TUNE_SKM_CLAIM_STATIC_PCT / 100);
+    return (u32)std::min<u64>(rounds * grid, 0xfffffff0u);
+}
+struct SkmSlotFeed {
+    static constexpr u32 B = KH_TUNE_SKM_CLAIM;
+    u32 grid, nslots, base;   // base: the first claimed slot
+    u32 stat;                 // the next strided slot
+    u32 cnext, cend;          // the claim in hand: slots [cnext, cend)
+    // (the workgroup starts with slots blockIdx.x and blockIdx.x + grid in its pipeline)
+    __device__ __forceinline__ SkmSlotFeed(const u32 grid_, const u32 nslots_, const u32 first_claimed)
+        : grid(grid_), nslots(nslots_), base(first_claimed), stat(blockIdx.x + 2u * grid_), cnext(0), cend(0) {}
+    // true: the next take() opens a new claim, which has to be drawn (draw()) before the barrier in front of it
+    __device__ __forceinline__ bool wants() const { return B && stat >= base && cnext == cend && cend <= nslots; }
+    // one lane draws; `box`: the LDS word that hands the claim over
+    __device__ __forceinline__ void draw(u32* __restrict__ counter, u32* box) const { *box = base + atomicAdd(counter, B); }
+    // the slot two behind the current one; every thread, behind a barrier that follows the draw
+    __device__ __forceinline__ u32 take(const u32* box) {
+        if (!B || stat < base) {
+            const u32 s = stat;
+            stat += grid;
+            return s;
+        }
+        if (cnext == cend && cend <= nslots) {
+            cnext = (u32)__builtin_amdgcn_readfirstlane((int)*box);
+            cend = cnext + B;
+        }
+        return cnext++;
+    }
+};
 
 template <class K> void skm_allow_lds(K kern, size_t bytes) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
