@@ -469,7 +469,21 @@ struct SkmClaim1 {
 // thread's registers and the count of the one after to a scalar register: a workgroup that started with "load the
 // count, then load the records" spent 2.5 of its 6 microseconds waiting for memory with nothing else to do.  The
 // histogram bins and the repeat counters stay in LDS over all slots of the workgroup and are written once.
-template <u32 NT, u32 T>
+//
+// TWO BODIES behind the third barrier (`slot_body`).  A slot whose merged k-mers fit the table (N <= T, what the planner
+// aims at: nearly every slot) takes the LEAN one: no subset loop, no subset filter per key, no clears and barriers
+// between subsets, and none of the scalars those keep alive.  A slot with N > T takes the MULTI one: R = ceil(N / T)
+// subsets of its keys, chosen by hash bits, inserted and read out one after the other on the same planes.  Both are
+// one piece of code with a compile-time flag; the masks-self-clean invariant (at the read-out) holds for either, so
+// lean and multi slots may follow each other in any order in one workgroup's walk.  ctl[7] counts the multi slots.
+// KT: k at compile time (17 .. 32; the masks and shifts of the expansion are immediates), 0: k from the job.
+#ifndef KH_TUNE_SKM_UNION_LEAN
+#define KH_TUNE_SKM_UNION_LEAN 1   // 0: every slot through the multi body (timing study)
+#endif
+#ifndef KH_TUNE_SKM_UNION_KT
+#define KH_TUNE_SKM_UNION_KT 1     // 0: only the runtime-k instantiation (timing study)
+#endif
+template <u32 NT, u32 T, int KT>
 __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs, u32 first_claimed) {
     extern __shared__ __attribute__((aligned(16))) u8 lds_raw[];
     using G = SkmUnionGeo<NT, T>;
@@ -499,7 +513,7 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs, 
     const u32 tid0 = threadIdx.x, wid = __builtin_amdgcn_readfirstlane(tid0 >> 6);
     u32 tid = tid0, lane = lane_id();
     const u32 nbins = jb.nbins, cap2 = jb.cap2, nslots = jb.nslots;
-    const int k = jb.k;
+    const int k = KT ? KT : jb.k;
     const u32 sshift = nbins <= 72u ? 2u : (nbins <= 144u ? 1u : 0u), smask = (1u << sshift) - 1u;
     auto clear_keys = [&]() {
         uint4* k4 = reinterpret_cast<uint4*>(tkey);
@@ -705,218 +719,230 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs, 
         if (tid == 0) scratch[0] = 0;   // (everybody has read it; it is added to again behind the next slot's first barrier)
         SKM_MARK("owner_done");
         SKM_USTAMP(4);
-        const u32 R = (N + T - 1) / T;   // key subsets handled one after the other (1 unless the slot is overfull)
-        const u32 ctid = tid;   // (a rotated numbering of the waves — other SIMDs busy from slot to slot — changed nothing)
-        for (u32 q = 0; q < R; ++q) {
-            if (q) { clear_keys(); clear_masks(); __syncthreads(); }
-            unsigned long long emptyv = EMPTY;   // (opaque: made here, or the compiler keeps the constant in two VGPRs across the loop and spills it)
-            asm volatile("" : "+v"(emptyv));
-            // entries this thread created, per pass: 16-bit fields (bit 15: set = valid, bit 14: second table)
-            u32 made[SKM_PASSES][E / 2];
+        const u32 R0 = (N + T - 1) / T;   // key subsets handled one after the other (1 unless the slot is overfull)
+        // ---- the slot behind the third barrier.  MULTI false: one subset, known at compile time (R is the literal 1:
+        // the subset loop, the filter, the clears and the barrier between subsets fold away); true: R0 subsets.
+        auto slot_body = [&](auto multi_) __attribute__((always_inline)) {
+            constexpr bool MULTI = decltype(multi_)::value;
+            const u32 R = MULTI ? R0 : 1u;
+            const u32 ctid = tid;   // (a rotated numbering of the waves — other SIMDs busy from slot to slot — changed nothing)
+            for (u32 q = 0; q < R; ++q) {
+                if (q) { clear_keys(); clear_masks(); __syncthreads(); }
+                unsigned long long emptyv = EMPTY;   // (opaque: made here, or the compiler keeps the constant in two VGPRs across the loop and spills it)
+                asm volatile("" : "+v"(emptyv));
+                // entries this thread created, per pass: 16-bit fields (bit 15: set = valid, bit 14: second table)
+                u32 made[SKM_PASSES][E / 2];
 #pragma unroll
-            for (u32 ps = 0; ps < SKM_PASSES; ++ps)
+                for (u32 ps = 0; ps < SKM_PASSES; ++ps)
 #pragma unroll
-                for (int e = 0; e < E / 2; ++e) made[ps][e] = 0u;
-            u32 ones = 0;   // keys that sit in exactly one group
+                    for (int e = 0; e < E / 2; ++e) made[ps][e] = 0u;
+                u32 ones = 0;   // keys that sit in exactly one group
 #pragma unroll
-            for (u32 pass = 0; pass < SKM_PASSES; ++pass) {
-                if (pass * NT >= C) break;   // uniform
-                const u32 c = pass * NT + ctid;
-                u64 kreg[E];
-                u32 slot_[E], act = 0, bits = 0, half = 0;
+                for (u32 pass = 0; pass < SKM_PASSES; ++pass) {
+                    if (pass * NT >= C) break;   // uniform
+                    const u32 c = pass * NT + ctid;
+                    u64 kreg[E];
+                    u32 slot_[E], act = 0, bits = 0, half = 0;
 #pragma unroll
-                for (int e = 0; e < E; ++e) { kreg[e] = EMPTY; slot_[e] = 0; }
-                if (c < C) {
-                    const u32 o = owner[c], ri = o >> SKM_OB, first = (o & ((1u << SKM_OB) - 1u)) * (u32)E;
-                    // (an L2 hit: the records were read a moment ago.  Issued before the table clears instead, for the first
-                    // pass, it made the kernel slower: 1.430 -> 1.486 ms, same registers, three alternated runs each)
-                    const uint4 r0 = reg[ri];
-                    bits = rmask[ri];
-                    half = SkmRec1::half(r0.w);
-                    const u32 left = SkmRec1::n(r0.w) - first;
-                    const u32 cnt = left < (u32)E ? left : (u32)E;
-                    // The twin of skm1_expand<E> above, kept in place: through the shared expander (hash, kreg, slot_ and act
-                    // in a callback) registers, scratch and occupancy stay as they are, but the probe rounds behind it are
-                    // structured with 7 % more instructions (s_and_saveexec / s_or / s_cbranch_execz / v_mov).  A change
-                    // of the expansion has to be made in both.
-                    const u64 clo = ((u64)r0.y << 32) | r0.x, chi = ((u64)r0.w << 32) | r0.z;
-                    const u32 sh = 2u * first;   // 0, 2E, .. <= 60
-                    const u64 lo = sh ? (clo >> sh) | (chi << (64u - sh)) : clo, hi = chi >> sh;
-                    const u32 xl = (u32)lo & kml, xh = (u32)(lo >> 32) & kmh;   // the first k-mer, base j at bits 2j
-                    const u64 fw = kh_revpairs64(((u64)xh << 32) | xl) >> fsh;
-                    u32 fl = (u32)fw, fh = (u32)(fw >> 32), rl = ~xl & kml, rh = ~xh & kmh;
-                    const u32 t = (u32)((lo >> tsh) | (hi << (64u - tsh)));   // bits 2e: the last base of the chunk's k-mer e
-                    const u32 tc = ~t;
+                    for (int e = 0; e < E; ++e) { kreg[e] = EMPTY; slot_[e] = 0; }
+                    if (c < C) {
+                        const u32 o = owner[c], ri = o >> SKM_OB, first = (o & ((1u << SKM_OB) - 1u)) * (u32)E;
+                        // (an L2 hit: the records were read a moment ago.  Issued before the table clears instead, for the first
+                        // pass, it made the kernel slower: 1.430 -> 1.486 ms, same registers, three alternated runs each)
+                        const uint4 r0 = reg[ri];
+                        bits = rmask[ri];
+                        half = SkmRec1::half(r0.w);
+                        const u32 left = SkmRec1::n(r0.w) - first;
+                        const u32 cnt = left < (u32)E ? left : (u32)E;
+                        // The twin of skm1_expand<E> above, kept in place: through the shared expander (hash, kreg, slot_ and act
+                        // in a callback) registers, scratch and occupancy stay as they are, but the probe rounds behind it are
+                        // structured with 7 % more instructions (s_and_saveexec / s_or / s_cbranch_execz / v_mov).  A change
+                        // of the expansion has to be made in both.
+                        const u64 clo = ((u64)r0.y << 32) | r0.x, chi = ((u64)r0.w << 32) | r0.z;
+                        const u32 sh = 2u * first;   // 0, 2E, .. <= 60
+                        const u64 lo = sh ? (clo >> sh) | (chi << (64u - sh)) : clo, hi = chi >> sh;
+                        const u32 xl = (u32)lo & kml, xh = (u32)(lo >> 32) & kmh;   // the first k-mer, base j at bits 2j
+                        const u64 fw = kh_revpairs64(((u64)xh << 32) | xl) >> fsh;
+                        u32 fl = (u32)fw, fh = (u32)(fw >> 32), rl = ~xl & kml, rh = ~xh & kmh;
+                        const u32 t = (u32)((lo >> tsh) | (hi << (64u - tsh)));   // bits 2e: the last base of the chunk's k-mer e
+                        const u32 tc = ~t;
 #pragma unroll
-                    for (int e = 0; e < E; ++e) {
-                        if (e) {   // roll both strands by one base
-                            fh = __builtin_amdgcn_alignbit(fh, fl, 30) & kmh;
-                            fl = ((fl << 2) | ((t >> (2 * e)) & 3u)) & kml;
-                            rl = __builtin_amdgcn_alignbit(rh, rl, 2);
-                            rh >>= 2;
-                            if (tsh_high) rh |= ((tc >> (2 * e)) & 3u) << tsh_sub; else rl |= ((tc >> (2 * e)) & 3u) << tsh_sub;
-                        }
-                        const bool fwd = fh < rh || (fh == rh && fl < rl);
-                        const u32 cl = fwd ? fl : rl, ch = fwd ? fh : rh;
-                        const u32 h = key_hash2(cl, ch);
-                        kreg[e] = ((u64)ch << 32) | cl;
-                        slot_[e] = (u32)(((u64)h * T) >> 32);
-                        if (R != 1 && (u32)e < cnt && (((h >> 4) & 0xffffu) * R) >> 16 == q) act |= 1u << e;
-                    }
-                    if (R == 1) act = (1u << cnt) - 1u;
-                }
-#if defined(KH_ABLATE) && KH_ABLATE == 2
-                if (kreg[0] != 0x1234567ull) act = 0;   // timing study: expanded, not inserted
-#endif
-                SKM_MARK("expanded");
-                if (!__builtin_amdgcn_ballot_w64(act != 0)) continue;   // a wave without a chunk
-                u32* const mp = half ? tmhi : tmlo;
-                // ---- probe rounds, all of a thread's keys per round (one dependent LDS round trip per round)
-                u32 was[E];   // the mask half as it was: bits of this record's genomes set already = repeats inside those genomes
-#pragma unroll
-                for (int e = 0; e < E; ++e) was[e] = 0u;
-                u32 mk = 0;   // keys whose compare-and-swap created the entry
-                for (u32 round = 0; round < (u32)KH_TUNE_SKM_FULL_ROUNDS && __builtin_amdgcn_ballot_w64(act != 0); ++round) {
-                    unsigned long long old[E];
-#pragma unroll
-                    for (int e = 0; e < E; ++e)
-                        old[e] = (act & (1u << e)) ? atomicCAS(&tkey[slot_[e]], emptyv, (unsigned long long)kreg[e]) : 0ull;
-#pragma unroll
-                    for (int e = 0; e < E; ++e) {
-                        if (act & (1u << e)) {
-                            const bool fresh = old[e] == emptyv;
-                            if (fresh || old[e] == kreg[e]) {
-                                was[e] = atomicOr(mp + slot_[e], bits);   // looked at after the last round
-                                act &= ~(1u << e);
-                                if (fresh) mk |= 1u << e;
-                            } else {
-                                slot_[e] = (slot_[e] + 1u) & (T - 1u);
+                        for (int e = 0; e < E; ++e) {
+                            if (e) {   // roll both strands by one base
+                                fh = __builtin_amdgcn_alignbit(fh, fl, 30) & kmh;
+                                fl = ((fl << 2) | ((t >> (2 * e)) & 3u)) & kml;
+                                rl = __builtin_amdgcn_alignbit(rh, rl, 2);
+                                rh >>= 2;
+                                if (tsh_high) rh |= ((tc >> (2 * e)) & 3u) << tsh_sub; else rl |= ((tc >> (2 * e)) & 3u) << tsh_sub;
                             }
+                            const bool fwd = fh < rh || (fh == rh && fl < rl);
+                            const u32 cl = fwd ? fl : rl, ch = fwd ? fh : rh;
+                            const u32 h = key_hash2(cl, ch);
+                            kreg[e] = ((u64)ch << 32) | cl;
+                            slot_[e] = (u32)(((u64)h * T) >> 32);
+                            if (R != 1 && (u32)e < cnt && (((h >> 4) & 0xffffu) * R) >> 16 == q) act |= 1u << e;
                         }
+                        if (R == 1) act = (1u << cnt) - 1u;
                     }
-                }
-                SKM_USTAMP(9);
-                SKM_MARK("rounds_done");
-                u32 f16[E];   // where each key's entry is, if this thread created it
+#if defined(KH_ABLATE) && KH_ABLATE == 2
+                    if (kreg[0] != 0x1234567ull) act = 0;   // timing study: expanded, not inserted
+#endif
+                    SKM_MARK("expanded");
+                    if (!__builtin_amdgcn_ballot_w64(act != 0)) continue;   // a wave without a chunk
+                    u32* const mp = half ? tmhi : tmlo;
+                    // ---- probe rounds, all of a thread's keys per round (one dependent LDS round trip per round)
+                    u32 was[E];   // the mask half as it was: bits of this record's genomes set already = repeats inside those genomes
 #pragma unroll
-                for (int e = 0; e < E; ++e) f16[e] = (mk >> e) & 1u ? (0x8000u | slot_[e]) : 0u;
-                // the few keys still homeless: one per lane at a time, second table, then the main one again
-                while (__builtin_amdgcn_ballot_w64(act != 0)) {
-                    const bool have_one = act != 0;
-                    const u32 es = have_one ? (u32)__builtin_ctz(act) : 0u;
-                    u64 K = 0;
+                    for (int e = 0; e < E; ++e) was[e] = 0u;
+                    u32 mk = 0;   // keys whose compare-and-swap created the entry
+                    for (u32 round = 0; round < (u32)KH_TUNE_SKM_FULL_ROUNDS && __builtin_amdgcn_ballot_w64(act != 0); ++round) {
+                        unsigned long long old[E];
 #pragma unroll
-                    for (int e = 0; e < E; ++e)
-                        if (es == (u32)e) K = kreg[e];
-                    const u32 H = key_hash2((u32)K, (u32)(K >> 32));
-                    // level 1: second table, 2: main table, unbounded
-                    u32 S = ((H ^ (H >> 15)) * 0x85EBCA77u) >> T2SH, probes = 0, level = 1;
-                    bool mine = have_one;
-                    u32 where = 0;
-                    while (__builtin_amdgcn_ballot_w64(mine)) {
-                        if (mine) {
-                            unsigned long long* kp = level == 1 ? okey : tkey;
-                            const unsigned long long o2 = atomicCAS(&kp[S], emptyv, (unsigned long long)K);
-                            if (o2 == emptyv || o2 == K) {
-                                u32* mp2 = level == 1 ? (half ? omhi : omlo) : mp;
-                                u32 d = atomicOr(mp2 + S, bits) & bits;
-                                while (d) { atomicAdd(&dupc[half * 32u + (u32)__builtin_ctz(d)], 1u); d &= d - 1u; }
-                                if (o2 == emptyv) where = 0x8000u | (level == 1 ? 0x4000u : 0u) | S;
-                                mine = false;
-                            } else {
-                                ++probes;
-                                if (level == 1 && probes >= 8u) {   // a crowded second table: on in the main one
-                                    level = 2; probes = 0;
-                                    S = (u32)(((u64)H * T) >> 32) + (u32)KH_TUNE_SKM_FULL_ROUNDS;
-                                    S = S & (T - 1u);
-                                } else if (level == 2 && probes >= T) {
-                                    // The main table is full.  With R > 1 the key subsets are picked by hash bits, not by
-                                    // count: a skewed slot (up to SKM_PASSES x NT chunks) can put more than T + T2
-                                    // distinct keys into one subset.  The key is dropped here; the host sees the error,
-                                    // counts a retry and hands the whole call to the key-array form.
-                                    atomicOr(jb.ctl, KH_ERR_CAPACITY);
-                                    mine = false;
+                        for (int e = 0; e < E; ++e)
+                            old[e] = (act & (1u << e)) ? atomicCAS(&tkey[slot_[e]], emptyv, (unsigned long long)kreg[e]) : 0ull;
+#pragma unroll
+                        for (int e = 0; e < E; ++e) {
+                            if (act & (1u << e)) {
+                                const bool fresh = old[e] == emptyv;
+                                if (fresh || old[e] == kreg[e]) {
+                                    was[e] = atomicOr(mp + slot_[e], bits);   // looked at after the last round
+                                    act &= ~(1u << e);
+                                    if (fresh) mk |= 1u << e;
                                 } else {
-                                    S = level == 1 ? ((S + 1u) & (T2 - 1u)) : ((S + 1u) & (T - 1u));
+                                    slot_[e] = (slot_[e] + 1u) & (T - 1u);
                                 }
                             }
                         }
                     }
-                    if (have_one) {
-                        act &= ~(1u << es);
+                    SKM_USTAMP(9);
+                    SKM_MARK("rounds_done");
+                    u32 f16[E];   // where each key's entry is, if this thread created it
+#pragma unroll
+                    for (int e = 0; e < E; ++e) f16[e] = (mk >> e) & 1u ? (0x8000u | slot_[e]) : 0u;
+                    // the few keys still homeless: one per lane at a time, second table, then the main one again
+                    while (__builtin_amdgcn_ballot_w64(act != 0)) {
+                        const bool have_one = act != 0;
+                        const u32 es = have_one ? (u32)__builtin_ctz(act) : 0u;
+                        u64 K = 0;
 #pragma unroll
                         for (int e = 0; e < E; ++e)
-                            if (es == (u32)e) f16[e] = where;
+                            if (es == (u32)e) K = kreg[e];
+                        const u32 H = key_hash2((u32)K, (u32)(K >> 32));
+                        // level 1: second table, 2: main table, unbounded
+                        u32 S = ((H ^ (H >> 15)) * 0x85EBCA77u) >> T2SH, probes = 0, level = 1;
+                        bool mine = have_one;
+                        u32 where = 0;
+                        while (__builtin_amdgcn_ballot_w64(mine)) {
+                            if (mine) {
+                                unsigned long long* kp = level == 1 ? okey : tkey;
+                                const unsigned long long o2 = atomicCAS(&kp[S], emptyv, (unsigned long long)K);
+                                if (o2 == emptyv || o2 == K) {
+                                    u32* mp2 = level == 1 ? (half ? omhi : omlo) : mp;
+                                    u32 d = atomicOr(mp2 + S, bits) & bits;
+                                    while (d) { atomicAdd(&dupc[half * 32u + (u32)__builtin_ctz(d)], 1u); d &= d - 1u; }
+                                    if (o2 == emptyv) where = 0x8000u | (level == 1 ? 0x4000u : 0u) | S;
+                                    mine = false;
+                                } else {
+                                    ++probes;
+                                    if (level == 1 && probes >= 8u) {   // a crowded second table: on in the main one
+                                        level = 2; probes = 0;
+                                        S = (u32)(((u64)H * T) >> 32) + (u32)KH_TUNE_SKM_FULL_ROUNDS;
+                                        S = S & (T - 1u);
+                                    } else if (level == 2 && probes >= T) {
+                                        // The main table is full.  With R > 1 the key subsets are picked by hash bits, not by
+                                        // count: a skewed slot (up to SKM_PASSES x NT chunks) can put more than T + T2
+                                        // distinct keys into one subset.  The key is dropped here; the host sees the error,
+                                        // counts a retry and hands the whole call to the key-array form.
+                                        atomicOr(jb.ctl, KH_ERR_CAPACITY);
+                                        mine = false;
+                                    } else {
+                                        S = level == 1 ? ((S + 1u) & (T2 - 1u)) : ((S + 1u) & (T - 1u));
+                                    }
+                                }
+                            }
+                        }
+                        if (have_one) {
+                            act &= ~(1u << es);
+#pragma unroll
+                            for (int e = 0; e < E; ++e)
+                                if (es == (u32)e) f16[e] = where;
+                        }
                     }
-                }
-                SKM_MARK("serial_done");
+                    SKM_MARK("serial_done");
 #pragma unroll
-                for (int e = 0; e < E / 2; ++e) made[pass][e] = f16[2 * e] | (f16[2 * e + 1] << 16);
-                {   // repeats inside a genome: the bit was set before this instance came
-                    u32 d = 0;
+                    for (int e = 0; e < E / 2; ++e) made[pass][e] = f16[2 * e] | (f16[2 * e + 1] << 16);
+                    {   // repeats inside a genome: the bit was set before this instance came
+                        u32 d = 0;
 #pragma unroll
-                    for (int e = 0; e < E; ++e) d |= was[e] & bits;
-                    if (d) {
+                        for (int e = 0; e < E; ++e) d |= was[e] & bits;
+                        if (d) {
 #pragma unroll
-                        for (int e = 0; e < E; ++e) {
-                            u32 de = was[e] & bits;
-                            while (de) { atomicAdd(&dupc[half * 32u + (u32)__builtin_ctz(de)], 1u); de &= de - 1u; }
+                            for (int e = 0; e < E; ++e) {
+                                u32 de = was[e] & bits;
+                                while (de) { atomicAdd(&dupc[half * 32u + (u32)__builtin_ctz(de)], 1u); de &= de - 1u; }
+                            }
                         }
                     }
                 }
-            }
-            SKM_MARK("insert_done");
-            SKM_USTAMP(5);
-            // the next claim: one lane of the last wave, which runs out of chunks first; the barrier below and the
-            // next slot's first one lie between this store and the threads that read it
-            if (draw && q == 0 && tid0 == NT - KH_WAVE) feed.draw(jb.claim, scratch + 1);
-            __syncthreads();
-            SKM_USTAMP(6);
-            // ---- all masks are final: every thread turns the entries it created into histogram bins.
-            // Invariant (MASKS_SELF_CLEAN): every non-zero mask has exactly one creator; it is read once, here, behind
-            // the barrier after the insertion, and the read stores zero — so both planes of both tables are zero when
-            // the next insertion phase (next subset, next slot) begins.  A mask is only ever ORed into behind a
-            // compare-and-swap that found its key or created it, and whoever created it recorded the place in `made`:
-            // in the probe rounds (`mk`), one key per lane (`where`, either table).  A key dropped under
-            // KH_ERR_CAPACITY touched no mask; a slot handed on inserts nothing (C = 0); with R > 1 each subset's
-            // read-out zeroes what that subset created before the barrier that precedes the next one.
+                SKM_MARK("insert_done");
+                SKM_USTAMP(5);
+                // the next claim: one lane of the last wave, which runs out of chunks first; the barrier below and the
+                // next slot's first one lie between this store and the threads that read it
+                if (draw && q == 0 && tid0 == NT - KH_WAVE) feed.draw(jb.claim, scratch + 1);
+                __syncthreads();
+                SKM_USTAMP(6);
+                // ---- all masks are final: every thread turns the entries it created into histogram bins.
+                // Invariant (MASKS_SELF_CLEAN): every non-zero mask has exactly one creator; it is read once, here, behind
+                // the barrier after the insertion, and the read stores zero — so both planes of both tables are zero when
+                // the next insertion phase (next subset, next slot) begins.  A mask is only ever ORed into behind a
+                // compare-and-swap that found its key or created it, and whoever created it recorded the place in `made`:
+                // in the probe rounds (`mk`), one key per lane (`where`, either table).  A key dropped under
+                // KH_ERR_CAPACITY touched no mask; a slot handed on inserts nothing (C = 0); with R > 1 each subset's
+                // read-out zeroes what that subset created before the barrier that precedes the next one.
 #pragma unroll
-            for (u32 pass = 0; pass < SKM_PASSES; ++pass) {
-                u32 any = 0;
+                for (u32 pass = 0; pass < SKM_PASSES; ++pass) {
+                    u32 any = 0;
 #pragma unroll
-                for (int e = 0; e < E / 2; ++e) any |= made[pass][e];
+                    for (int e = 0; e < E / 2; ++e) any |= made[pass][e];
 #if defined(KH_ABLATE) && KH_ABLATE == 3
-                if (any != 0x7654321u) any = 0;   // timing study: no read-out
+                    if (any != 0x7654321u) any = 0;   // timing study: no read-out
 #endif
-                if (!__builtin_amdgcn_ballot_w64(any != 0)) continue;
+                    if (!__builtin_amdgcn_ballot_w64(any != 0)) continue;
 #pragma unroll
-                for (int e = 0; e < E; ++e) {
-                    const u32 f = (made[pass][e >> 1] >> (16 * (e & 1))) & 0xffffu;
-                    if (f & 0x8000u) {
-                        const u32 at = f & 0x3fffu;
-                        const bool second = f & 0x4000u;
-                        u32 mlo, mhi;
-                        if (MASKS_SELF_CLEAN) {
-                            mlo = atomicExch((second ? omlo : tmlo) + at, 0u);
-                            mhi = atomicExch((second ? omhi : tmhi) + at, 0u);
-                        } else {
-                            mlo = (second ? omlo : tmlo)[at];
-                            mhi = (second ? omhi : tmhi)[at];
+                    for (int e = 0; e < E; ++e) {
+                        const u32 f = (made[pass][e >> 1] >> (16 * (e & 1))) & 0xffffu;
+                        if (f & 0x8000u) {
+                            const u32 at = f & 0x3fffu;
+                            const bool second = f & 0x4000u;
+                            u32 mlo, mhi;
+                            if (MASKS_SELF_CLEAN) {
+                                mlo = atomicExch((second ? omlo : tmlo) + at, 0u);
+                                mhi = atomicExch((second ? omhi : tmhi) + at, 0u);
+                            } else {
+                                mlo = (second ? omlo : tmlo)[at];
+                                mhi = (second ? omhi : tmhi)[at];
+                            }
+                            if (eval_mask(mlo, mhi)) ++ones;
                         }
-                        if (eval_mask(mlo, mhi)) ++ones;
                     }
                 }
+                if (__builtin_amdgcn_ballot_w64(ones != 0)) {
+                    ones = wave_scan_add(ones);
+                    if (lane == KH_WAVE - 1) atomicAdd(&hstripe[(jb.abase + 1u) << sshift], ones);
+                }
+                SKM_MARK("readout_done");
+                SKM_USTAMP(7);
+                if (q + 1 < R) __syncthreads();
             }
-            if (__builtin_amdgcn_ballot_w64(ones != 0)) {
-                ones = wave_scan_add(ones);
-                if (lane == KH_WAVE - 1) atomicAdd(&hstripe[(jb.abase + 1u) << sshift], ones);
-            }
-            SKM_MARK("readout_done");
-            SKM_USTAMP(7);
-            if (q + 1 < R) __syncthreads();
+        };
+        if (KH_TUNE_SKM_UNION_LEAN && R0 == 1u) {
+            slot_body(std::false_type{});
+        } else if (__builtin_expect(R0 != 0u, 0)) {   // (uniform, cold)
+            if (R0 > 1u && tid0 == 0) atomicAdd(jb.ctl + 7, 1u);   // slots taken in more than one subset
+            slot_body(std::true_type{});
         }
         SKM_USTAMP(8);
-        if (draw && R == 0 && tid0 == NT - KH_WAVE) feed.draw(jb.claim, scratch + 1);   // (an empty slot: nothing was inserted)
+        if (draw && R0 == 0 && tid0 == NT - KH_WAVE) feed.draw(jb.claim, scratch + 1);   // (an empty slot: nothing was inserted)
         // ---- on to the next slot: its record has arrived in the meantime.  No barrier here: what the next slot writes
         // before its first barrier (staged records, the set of contents: the KEY plane; this thread's record mask)
         // is read by nobody in the read-out.
@@ -1405,10 +1431,21 @@ void kh_launch_skm_scatter(const KhSkmJob& job, u32 ntiles, hipStream_t st) {
     }
 }
 void kh_launch_skm_regroup(const KhSkmJob& job, hipStream_t st) { skm_launch_regroup<SkmRec1>(job, st); }
-void kh_launch_skm_union(const KhSkmJob& job, u32 cs, u32 grid, hipStream_t st) {
+template <int KT> static void launch_union_k(const KhSkmJob& job, u32 cs, u32 grid, hipStream_t st) {
     const size_t lds = kh_skm_union_lds_bytes();
-    skm_allow_lds(k_skm_union<1024, 4096>, lds);
-    hipLaunchKernelGGL((k_skm_union<1024, 4096>), dim3(grid), dim3(1024), lds, st, job, cs, skm_first_claimed(job.nslots, grid));
+    skm_allow_lds(k_skm_union<1024, 4096, KT>, lds);
+    hipLaunchKernelGGL((k_skm_union<1024, 4096, KT>), dim3(grid), dim3(1024), lds, st, job, cs, skm_first_claimed(job.nslots, grid));
+}
+void kh_launch_skm_union(const KhSkmJob& job, u32 cs, u32 grid, hipStream_t st) {
+    switch (job.k) {
+#if KH_TUNE_SKM_UNION_KT
+#define SKM_K(KK) case KK: launch_union_k<KK>(job, cs, grid, st); break;
+        SKM_K(17) SKM_K(18) SKM_K(19) SKM_K(20) SKM_K(21) SKM_K(22) SKM_K(23) SKM_K(24)
+        SKM_K(25) SKM_K(26) SKM_K(27) SKM_K(28) SKM_K(29) SKM_K(30) SKM_K(31) SKM_K(32)
+#undef SKM_K
+#endif
+        default: launch_union_k<0>(job, cs, grid, st); break;   // any other k that reaches here: k from the job
+    }
 }
 void kh_launch_skm_pack(const KhSkmPackJob& job, hipStream_t st) {
     if (!job.nslots) return;
