@@ -295,7 +295,15 @@ int kh_exp2_run(kh_ctx *ctx, int nseq, const uint8_t *const *seqs, const uint64_
  * group with them); otherwise, and whenever the bitmaps do not fit (1023 genomes per group, a pivot whose bins and the
  * operand counters exceed 4096, the memory budget), one batched build, the unions and intersect + histogram on sets in
  * device memory.  Switches as for kh_exp1_run: KHOICE_NO_BMP, KHOICE_NO_SKM, KHOICE_BMP_MAX_K, KHOICE_BMP_MAX_BYTES;
- * KHOICE_BMP_MAX_BINS lowers the 4096 (more, smaller batches of pivots). */
+ * KHOICE_BMP_MAX_BINS lowers the 4096 (more, smaller batches of pivots).
+ *
+ * KHOICE_EXP3_SKM=1 (read at the call; any other value or unset: as above) adds a third form for 17 <= k <= 63, pivots
+ * and at most 63 genomes: genomes and read sets go through the super-k-mer scatter and regroup of kh_exp1_run as one
+ * list of operands and one kernel (k_skm_cross) reads, per slot, every k-mer's mask of operands out into the same bins
+ * as the bitmap form; pivots beyond 64 - nseq go in further passes.  It declines (the set form answers, nothing
+ * counted) where the slot geometry or the memory does not fit, under KHOICE_NO_SKM, and for k > 32 under
+ * KHOICE_NO_SKM2; an overflow on the way counts one retry in kh_stats and the set form answers.  The default above
+ * k = 12 stays the set form until the measured table says otherwise. */
 int kh_exp3_run(kh_ctx *ctx, int nseq, const uint8_t *const *seqs, const uint64_t *lens, int on_device,
                 const int *group_of, int ngroups,
                 int npivots, const uint8_t *const *pivot_seqs, const uint64_t *pivot_lens,

@@ -231,7 +231,7 @@ static const char* kClsNames[KC_COUNT] = {"extract_hist", "bucket_plan", "extrac
                                           "bucket_sort_rle", "range_bounds", "setop", "histogram",
                                           "remix", "copy_in", "union_tagged", "skm_scatter",
                                           "skm_regroup", "skm_union", "skm_big", "skm_pack", "skm_phased", "bmp_build",
-                                          "bmp_readout", "bmp_pivot", "bmp_cross", "bmp_count", "bmp_present", "bmp_member"};
+                                          "bmp_readout", "bmp_pivot", "bmp_cross", "bmp_count", "bmp_present", "bmp_member", "skm_cross"};
 
 // ------------------------------------------------------------------------------ ctx API
 extern "C" int kh_device_count(void) {
@@ -313,14 +313,15 @@ extern "C" int kh_stats(kh_ctx* c, char* buf, size_t buflen) {
     s += t;
     snprintf(t, sizeof t,
              "\"builds\":%llu,\"bases\":%llu,\"text_packed\":%llu,\"kmers\":%llu,\"distinct\":%llu,\"setops\":%llu,"
-             "\"setop_in\":%llu,\"setop_out\":%llu,\"retries\":%llu,\"order_fallbacks\":%llu,\"skm_records\":%llu,\"big_slots\":%llu,\"poisoned_bytes\":%llu,\"pool_bytes\":%zu,",
+             "\"setop_in\":%llu,\"setop_out\":%llu,\"retries\":%llu,\"order_fallbacks\":%llu,\"skm_records\":%llu,\"big_slots\":%llu,\"cross_multi_slots\":%llu,\"poisoned_bytes\":%llu,\"pool_bytes\":%zu,",
              (unsigned long long)c->stat.builds, (unsigned long long)c->stat.bases,
              (unsigned long long)c->stat.text_packed,
              (unsigned long long)c->stat.kmers, (unsigned long long)c->stat.distinct,
              (unsigned long long)c->stat.setops, (unsigned long long)c->stat.setop_in,
              (unsigned long long)c->stat.setop_out, (unsigned long long)c->stat.retries,
              (unsigned long long)c->stat.order_fallbacks, (unsigned long long)c->stat.skm_records,
-             (unsigned long long)c->stat.big_slots, (unsigned long long)c->stat.poisoned_bytes,
+             (unsigned long long)c->stat.big_slots, (unsigned long long)c->stat.cross_multi_slots,
+             (unsigned long long)c->stat.poisoned_bytes,
              c->pool.total_bytes);
     s += t;
     s += "\"kernels\":{";
@@ -1737,7 +1738,8 @@ struct SkmGeometry {
 };
 // The slot geometry for `positions` k-mer positions whose largest group has `fan` genomes; force_slots: the number of
 // slots all ranks agreed on (slots are a global function of the minimizer).  false: the form does not apply.
-static bool skm_plan(int k, u64 positions, u32 fan, u32 force_slots, int cus, SkmGeometry* out) {
+// table: the instances "mean + 2.5 sigma" aims at; 0: the table of the union of the key width.
+static bool skm_plan(int k, u64 positions, u32 fan, u32 force_slots, int cus, SkmGeometry* out, u32 table = 0) {
     if (!skm_form_k(k)) return false;
     SkmGeometry g;
     g.two = k > KH_SKM_MAX_K;
@@ -1762,7 +1764,7 @@ static bool skm_plan(int k, u64 positions, u32 fan, u32 force_slots, int cus, Sk
     // (largest group) instances, so sigma = sqrt(mean x c); mean + 2.5 sigma = T  (measured: 2500 / 2900 / 3200 /
     // 3500 / 3800 at k = 31 with groups of five: union 1.96 / 1.81 / 1.75 / 1.80 / 1.94 ms; the rule gives 3180)
     const double clump = skm_clump(g.w, fan);
-    const double T = g.two ? (double)kh_skm2_table() : 4096.0;   // (one-word keys: k_skm_union's 4096 entries)
+    const double T = table ? (double)table : g.two ? (double)kh_skm2_table() : 4096.0;   // (one-word keys: k_skm_union's 4096 entries)
     const double r = 0.5 * (-2.5 * std::sqrt(clump) + std::sqrt(6.25 * clump + 4.0 * T));
     u32 mean = (u32)std::max(256.0, r * r);
     if (const char* e = getenv("KHOICE_SKM_MEAN")) mean = std::max<u32>(64, (u32)strtoul(e, nullptr, 10));
@@ -1776,6 +1778,7 @@ static bool skm_plan(int k, u64 positions, u32 fan, u32 force_slots, int cus, Sk
         mean = std::max<u32>(256, (u32)((double)mean * (double)max_cap2 / c2 * 0.98));
     }
     u64 nslots64 = force_slots ? force_slots : std::max<u64>(1, (positions + mean - 1) / mean);
+    bool fuller = false;   // the slots hold more than `mean` (callers with a `table` only)
     // One-word keys a little above 256 x 512 slots (short windows on the headline shape: k = 20): 512 coarse buckets
     // double the scatter's cursors and LDS (k = 20: scatter 2.3 ms against 1.0 at k = 21).  Since a slot's region may
     // overflow (side list, k_skm_big) its slack can be cut instead: stay at 256 x 512 slots with slack down to 1.4.
@@ -1792,7 +1795,15 @@ static bool skm_plan(int k, u64 positions, u32 fan, u32 force_slots, int cus, Sk
     }
     // coarse buckets: 256 keep the scatter's runs long; inputs past 256 x 512 slots (> 400 M k-mers) take 512
     const u32 max_coarse = (g.two || nslots64 > (u64)KH_SKM_MAX_COARSE * KH_SKM_MAX_FINE) ? KH_SKM2_MAX_COARSE : KH_SKM_MAX_COARSE;
-    if (nslots64 > (u64)max_coarse * (g.two ? KH_SKM2_MAX_FINE : KH_SKM_MAX_FINE)) return false;
+    if (nslots64 > (u64)max_coarse * (g.two ? KH_SKM2_MAX_FINE : KH_SKM_MAX_FINE)) {
+        // more slots than the two levels number.  A caller whose kernel takes a slot in rounds (`table`: k_skm_cross)
+        // gets all of them, fuller than the rule wants — as long as a region with its whole slack holds their records
+        // (below; measured without that condition at k = 17 on 625 Mbp: regions cut to 1.4 x the mean, more records
+        // spilled than the side list keeps, the call paid 15 ms for the attempt before the set form answered)
+        if (!table || force_slots) return false;
+        nslots64 = (u64)max_coarse * (g.two ? KH_SKM2_MAX_FINE : KH_SKM_MAX_FINE);
+        fuller = true;
+    }
     g.nslots = (u32)nslots64;
     g.S = std::max<u32>(1, (g.nslots + max_coarse - 1) / max_coarse);
     g.nb1 = (g.nslots + g.S - 1) / g.S;
@@ -1800,7 +1811,7 @@ static bool skm_plan(int k, u64 positions, u32 fan, u32 force_slots, int cus, Sk
     if (const char* e = getenv("KHOICE_SKM_SLACK")) slack1 = slack2 = std::max(0.01, atof(e));   // below 1: tests of the overflow fall-back
     const u64 cap1_64 = ((u64)(recs / g.nb1 * slack1) + 2048 + 63) & ~63ull;
     u64 cap2_64 = ((u64)(recs / g.nslots * slack2) + 96 + 15) & ~15ull;
-    if (cap2_64 > max_cap2 && !force_slots) {
+    if (cap2_64 > max_cap2 && !force_slots && !fuller) {
         // Large groups: the copies of a locus (one record per genome of the group) arrive in a slot together, so the
         // five-sigma region is larger than the union takes.  The region is cut to what it takes and the slots with a
         // locus too many go the side-list way (k_skm_big); only when there are more of those than the side list
@@ -1836,7 +1847,8 @@ struct SkmStage {
 };
 // (a) + (b): the geometry, then the input staged, scattered and regrouped by slot
 static int skm_prepare(kh_ctx* c, int nseq, const uint8_t* const* seqs, const uint64_t* lens, int on_device,
-                       const int* group_of, int ngroups, int k, bool by_group, u32 force_slots, u32 fan_hint, SkmStage* s) {
+                       const int* group_of, int ngroups, int k, bool by_group, u32 force_slots, u32 fan_hint, SkmStage* s,
+                       u32 table = 0 /* skm_plan's: 0 for the unions */) {
     TagLayout* L = &s->L;
     if (!skm_form_k(k)) return KH_OK;
     if ((!by_group && nseq > KH_TAG_MAX_OPS) || ngroups > KH_TAG_MAX_OPS) return KH_OK;
@@ -1844,7 +1856,7 @@ static int skm_prepare(kh_ctx* c, int nseq, const uint8_t* const* seqs, const ui
     if (L->nbins > (u32)KH_TAG_MAX_BINS) return KH_OK;
     const u64 positions = kmer_positions(nseq, lens, k, &s->bases);
     // (fan_hint: genomes whose copies of a locus arrive together although they are tags of ONE group)
-    if (!skm_plan(k, positions, std::max(L->fan, fan_hint), force_slots, c->cus, &s->g)) return KH_OK;
+    if (!skm_plan(k, positions, std::max(L->fan, fan_hint), force_slots, c->cus, &s->g, table)) return KH_OK;
     const SkmGeometry& g = s->g;
     const size_t rec_bytes = g.two ? 32 : 16;
     const size_t reg1_bytes = rec_bytes * (size_t)g.nb1 * g.cap1, reg2_bytes = rec_bytes * (size_t)g.nslots * g.cap2;
@@ -3436,6 +3448,144 @@ static int exp3_bmp(kh_ctx* c, const Exp3In& in, const Exp3Out& out, bool* done)
     *done = true;
     return KH_OK;
 }
+// The super-k-mer form (k_skm_cross, kh_skm_device.h; k = 17 .. 63, taken only with KHOICE_EXP3_SKM=1 — the set form
+// stays the default until the form has been measured): genomes and pivots go through the unchanged scatter and regroup
+// as ONE list of texts, the pivots behind the genomes and every pivot a group of its own (TagLayout: its tag is then
+// nseq + q; a read set's line feeds are non-bases to the scatter).  One direct launch walks all slots, a listed one
+// the slots whose region overflowed.  At most 64 operands a pass: more pivots than 64 - nseq go in batches, every
+// batch with the genomes staged, scattered and walked AGAIN (wasteful, known: a pass that keeps the genomes' records
+// is what would mend it); the genomes' distinct counts are the first pass's.  *done == false and no retry counted: the
+// form does not apply (switch, k, KHOICE_NO_SKM / KHOICE_NO_SKM2, no pivot — the set form builds the genomes only —,
+// more than 63 genomes, no k-mer position, geometry, memory), nothing of the outputs was written.  A capacity or order
+// error of a kernel, or more spilled records or listed slots than are kept: retries++, and the set form answers.
+static int exp3_skm(kh_ctx* c, const Exp3In& in, const Exp3Out& out, bool* done) {
+    *done = false;
+    const int k = in.k, nseq = in.nseq, ngroups = in.ngroups, npiv = in.npivots;
+    const char* sw = getenv("KHOICE_EXP3_SKM");
+    if (!sw || atoi(sw) != 1 || !skm_form_k(k)) return KH_OK;
+    if (!npiv || nseq >= KH_TAG_MAX_OPS) return KH_OK;
+    const int batch = std::min(npiv, KH_TAG_MAX_OPS - nseq), nbatches = (npiv + batch - 1) / batch;
+    u64 gbases = 0, pbases = 0;
+    const u64 gpos = kmer_positions(nseq, in.lens, k, &gbases);
+    for (int b = 0; b < nbatches; ++b)   // (a pass without a k-mer position has no geometry)
+        if (!(gpos + kmer_positions(std::min(batch, npiv - b * batch), in.pivot_lens + (size_t)b * batch, k))) return KH_OK;
+    kmer_positions(npiv, in.pivot_lens, k, &pbases);
+    const bool two = k > KH_SKM_MAX_K;
+    const u32 round = two ? kh_skm2_cross_round() : kh_skm_cross_round();
+    u32 fan = 1;
+    {
+        std::vector<u32> gs(ngroups, 0);
+        for (int i = 0; i < nseq; ++i) fan = std::max(fan, ++gs[in.group_of[i]]);
+    }
+    std::vector<u64> dseq(nseq, 0), dpiv(npiv, 0), occ((size_t)npiv * nseq, 0);   // occ[p][first genome of g + v - 1]
+    std::vector<int> gstart, gsize;
+    u64 kmers = 0, records = 0, multi = 0, big = 0;
+    for (int b = 0; b < nbatches; ++b) {
+        const int p0 = b * batch, np = std::min(batch, npiv - p0), nops = nseq + np;
+        std::vector<const uint8_t*> seqs(in.seqs, in.seqs + nseq);
+        std::vector<uint64_t> lens(in.lens, in.lens + nseq);
+        std::vector<int> group_of(in.group_of, in.group_of + nseq);
+        for (int q = 0; q < np; ++q) {
+            seqs.push_back(in.pivot_seqs[p0 + q]);
+            lens.push_back(in.pivot_lens[p0 + q]);
+            group_of.push_back(ngroups + q);
+        }
+        SkmStage s(c);
+        // fan hint: a pivot's reads bring copies of their locus into the slot of the group they were drawn from — one
+        // more than the largest group.  A guess (reads may cover a locus many times); the side list takes what it misses.
+        KHCHK(skm_prepare(c, nops, seqs.data(), lens.data(), in.on_device, group_of.data(), ngroups + np, k, false, 0, fan + 1, &s, round));
+        if (!s.staged) {
+            if (b) c->stat.retries++;   // (a later pass whose geometry or memory does not fit: work was done for nothing)
+            return KH_OK;
+        }
+        const TagLayout& L = s.L;
+        const KhSkmJob& job = s.job;
+        hipStream_t st = c->st;
+        KhSkmCrossJob cj{};
+        cj.ngenomes = (u32)nseq;
+        cj.nbins = (u32)np * (u32)nseq;
+        const u64 pm = (np >= 64 ? ~0ull : (1ull << np) - 1ull) << nseq;
+        cj.pmlo = (u32)pm; cj.pmhi = (u32)(pm >> 32);
+        const u32 grid = std::min<u32>(s.g.nslots, (two ? kh_skm2_cross_per_cu() : kh_skm_cross_per_cu()) * (u32)std::max(1, c->cus));
+        cj.reps = std::min<u32>(grid, 64);
+        const size_t bins_bytes = 8 * (size_t)cj.reps * cj.nbins;
+        Tmp d_bins;
+        TMP_ALLOC(d_bins, c, bins_bytes);
+        Pinned pin{c};
+        PIN_ALLOC(pin, bins_bytes);
+        cj.bins = d_bins.as<unsigned long long>();
+        HIPCHK(hipMemsetAsync(cj.bins, 0, bins_bytes, st));
+        auto launch = [&](u32 g) { if (two) kh_launch_skm2_cross(job, cj, g, st); else kh_launch_skm_cross(job, cj, g, st); };
+        KHCHK(timed_launch(c, KC_SKM_CROSS, [&] { launch(grid); }));
+        // [ctl .. dup] of the workspace, laid out in h_down as on the device
+        u8* wsp = s.d_ws.as<u8>();
+        auto down = [&](const void* d) { return s.h_down + (static_cast<const u8*>(d) - wsp); };
+        const size_t ctl_bytes = reinterpret_cast<const u8*>(job.cur1) - reinterpret_cast<const u8*>(job.ctl);
+        const u32* h_ctl = reinterpret_cast<const u32*>(down(job.ctl));
+        HIPCHK(hipMemcpyAsync(down(job.ctl), job.ctl, ctl_bytes, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (h_ctl[6] && !(h_ctl[0] & (KH_ERR_CAPACITY | KH_ERR_ORDER))) {   // overfull slots: the listed launch, and the read-back again
+            if (h_ctl[5] > SkmStage::spill_cap || h_ctl[6] > SkmStage::big_cap) { c->stat.retries++; return KH_OK; }
+            big += h_ctl[6];
+            cj.nlisted = h_ctl[6];
+            KHCHK(timed_launch(c, KC_SKM_CROSS, [&] { launch(cj.nlisted); }));
+            HIPCHK(hipMemcpyAsync(down(job.ctl), job.ctl, ctl_bytes, hipMemcpyDeviceToHost, st));
+        }
+        HIPCHK(hipMemcpyAsync(pin.p, cj.bins, bins_bytes, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (h_ctl[0] & (KH_ERR_CAPACITY | KH_ERR_ORDER)) {
+            c->stat.retries++;
+            return KH_OK;   // a region, the side list or a table overflowed: the set form takes over
+        }
+        records += h_ctl[2];
+        multi += h_ctl[7];
+        const u64* h_inst = reinterpret_cast<const u64*>(down(job.inst));
+        const u64* h_dup = reinterpret_cast<const u64*>(down(job.dup));
+        for (int i = 0; i < nops; ++i) {   // operand i is text perm[i] of this pass: genomes in group-major order, then its pivots
+            const int t = L.perm[i];
+            const u64 d = h_inst[i] - h_dup[i];
+            if (t >= nseq) { dpiv[p0 + t - nseq] = d; kmers += h_inst[i]; }
+            else if (b == 0) { dseq[t] = d; kmers += h_inst[i]; }
+        }
+        const u64* h_bins = static_cast<const u64*>(pin.p);
+        for (u32 r = 0; r < cj.reps; ++r)
+            for (int q = 0; q < np; ++q)
+                for (int j = 0; j < nseq; ++j) occ[(size_t)(p0 + q) * nseq + j] += h_bins[(size_t)r * cj.nbins + (size_t)q * nseq + j];
+        if (b == 0) {
+            gstart.assign(L.gstart.begin(), L.gstart.begin() + ngroups);
+            gsize.assign(L.gsize.begin(), L.gsize.begin() + ngroups);
+        }
+    }
+    // ---- every pass went through: the outputs, and the accounting of exp3_bmp
+    out.clear(in);
+    u64 dsum = 0, met = 0;
+    for (int i = 0; i < nseq; ++i) {
+        dsum += dseq[i];
+        if (out.distinct_per_seq) out.distinct_per_seq[i] = dseq[i];
+    }
+    for (int p = 0; p < npiv; ++p) {
+        dsum += dpiv[p];
+        if (out.distinct_per_pivot) out.distinct_per_pivot[p] = dpiv[p];
+        for (int g = 0; g < ngroups; ++g)
+            for (int v = 1; v <= gsize[g]; ++v) {
+                const u64 n = occ[(size_t)p * nseq + gstart[g] + v - 1];
+                met += n;
+                out.add(in, p, g, (u32)v, n);
+            }
+    }
+    c->stat.skm_records += records;
+    c->stat.cross_multi_slots += multi;
+    c->stat.big_slots += big;
+    c->stat.bases += gbases + pbases;
+    c->stat.builds += (u64)nseq + (u64)npiv;
+    c->stat.kmers += kmers;
+    c->stat.distinct += dsum;
+    c->stat.setop_in += dsum;
+    c->stat.setop_out += met;   // pivot k-mers met in a group, summed over the groups
+    c->stat.setops++;
+    *done = true;
+    return KH_OK;
+}
 // The set form: the calls of workflow/exp_type_3.py::run_batched on sets that stay in device memory — one batched plain
 // build of genomes and pivots, the -cs{cs} union of every group, and intersect -ocsum + histogram of every pivot with
 // every union.  No kernel of its own.
@@ -3469,6 +3619,8 @@ extern "C" int kh_exp3_run(kh_ctx* c, int nseq, const uint8_t* const* seqs, cons
     HIPCHK(hipSetDevice(c->dev));
     bool done = false;
     KHCHK(exp3_bmp(c, in, out, &done));
+    if (done) return KH_OK;
+    KHCHK(exp3_skm(c, in, out, &done));   // (KHOICE_EXP3_SKM=1 only)
     if (done) return KH_OK;
     return exp3_sets(c, in, out);
 }

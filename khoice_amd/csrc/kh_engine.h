@@ -32,12 +32,13 @@ enum KernelClass {
     KC_EXTRACT_HIST = 0, KC_BUCKET_PLAN, KC_EXTRACT_SCATTER, KC_BUCKET_SORT, KC_RANGE_BOUNDS,
     KC_SETOP, KC_HISTOGRAM, KC_REMIX, KC_COPY_IN, KC_UNION_TAGGED, KC_SKM_SCATTER, KC_SKM_REGROUP, KC_SKM_UNION,
     KC_SKM_BIG, KC_SKM_PACK, KC_SKM_PHASED, KC_BMP_BUILD, KC_BMP_READOUT, KC_BMP_PIVOT, KC_BMP_CROSS, KC_BMP_COUNT,
-    KC_BMP_PRESENT, KC_BMP_MEMBER, KC_COUNT
+    KC_BMP_PRESENT, KC_BMP_MEMBER, KC_SKM_CROSS, KC_COUNT
 };
 struct ProfEvt { int cls; hipEvent_t a, b; };
 struct Stats {
     u64 builds = 0, bases = 0, kmers = 0, distinct = 0, setops = 0, setop_in = 0, setop_out = 0,
         retries = 0, order_fallbacks = 0, skm_records = 0, big_slots = 0,
+        cross_multi_slots = 0,   // slots k_skm_cross took in more than one round of key subsets
         text_packed = 0,   // bytes of sequence text copied into a batch buffer (0 for a text read in place)
         poisoned_bytes = 0;   // device and pinned bytes filled under KHOICE_DEBUG_POISON (0 when unset)
 };

@@ -170,6 +170,19 @@ void kh_launch_skm_regroup(const KhSkmJob& job, hipStream_t st);
 void kh_launch_skm_union(const KhSkmJob& job, u32 cs, u32 grid, hipStream_t st);   // persistent: grid workgroups walk the slots
 u32 kh_skm_union_per_cu();   // workgroups of the union that fit a CU
 void kh_launch_skm_big(const KhSkmJob& job, u32 cs, u32 nbig, hipStream_t st);   // the slots of big_list, one workgroup each
+// ---- experiment type 3 from the same records (k_skm_cross, kh_skm_device.h): the operands of the scatter are the
+// genomes in group-major order, then the pivots of the pass, every pivot a group of its own in `ginfo`.  What the
+// kernel needs beyond KhSkmJob, which stays as the other kernels know it:
+struct KhSkmCrossJob {
+    unsigned long long* bins;       // [reps][nbins] zeroed: pivot q, c >= 1 genomes of the group whose first genome is g0: q * ngenomes + g0 + c - 1
+    u32 pmlo, pmhi;                 // the pivots' bits of the operand mask
+    u32 ngenomes;                   // operands [0, ngenomes) are genomes, the rest pivots
+    u32 nbins, reps;                // nbins = pivots * ngenomes <= 1024
+    u32 nlisted;                    // 0: the direct launch over all slots; else the listed launch over big_list[0 .. nlisted)
+};
+u32 kh_skm_cross_round();           // k-mer instances of a slot the kernel takes in one round
+u32 kh_skm_cross_per_cu();          // workgroups of the direct launch that fit a CU
+void kh_launch_skm_cross(const KhSkmJob& job, const KhSkmCrossJob& cj, u32 grid, hipStream_t st);
 // ---- the exchange form of the across-group step (multi-GPU; kh_skm.hip k_skm_pack / k_skm_phased)
 struct KhSkmPackJob {
     const uint4* reg2;              // [nslots][cap2] this rank's records by slot (tag = local group, < 32)
@@ -229,6 +242,9 @@ u32 kh_skm2_max_cap2();
 u32 kh_skm2_table();
 u32 kh_skm2_union_per_cu();   // workgroups of the two-word union that fit a CU
 void kh_launch_skm2_big(const KhSkmJob& job, u32 cs, u32 nbig, hipStream_t st);
+u32 kh_skm2_cross_round();
+u32 kh_skm2_cross_per_cu();
+void kh_launch_skm2_cross(const KhSkmJob& job, const KhSkmCrossJob& cj, u32 grid, hipStream_t st);
 size_t kh_skm2_scatter_lds_bytes(u32 nb1);
 size_t kh_skm2_union_lds_bytes(u32 nbins);
 void kh_launch_skm2_scatter(const KhSkmJob& job, u32 ntiles, hipStream_t st);

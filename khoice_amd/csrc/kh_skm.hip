@@ -1471,3 +1471,8 @@ void kh_launch_skm_phased(const KhSkmPhasedJob& job, u32 grid, hipStream_t st) {
     hipLaunchKernelGGL(k_skm_phased, dim3(grid), dim3(SKM_PH_NT), lds, st, job);
 }
 void kh_launch_skm_big(const KhSkmJob& job, u32 cs, u32 nbig, hipStream_t st) { skm_launch_big<SkmBig1>(job, cs, nbig, st); }
+// k_skm_cross (kh_skm_device.h) with one-word keys
+constexpr bool SKM_CROSS1_VGPRS64 = true;   // resource report: 59 VGPRs, 78 SGPRs (53 more kept in VGPR lanes), no scratch, 8 waves per SIMD; 81280 bytes of LDS
+u32 kh_skm_cross_round() { return skm_cross_round<SkmBig1>(); }
+u32 kh_skm_cross_per_cu() { return skm_cross_per_cu<SkmBig1>(SKM_CROSS1_VGPRS64); }
+void kh_launch_skm_cross(const KhSkmJob& job, const KhSkmCrossJob& cj, u32 grid, hipStream_t st) { skm_launch_cross<SkmBig1>(job, cj, grid, st); }

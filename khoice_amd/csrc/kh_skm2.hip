@@ -721,3 +721,8 @@ void kh_launch_skm2_union(const KhSkmJob& job, u32 cs, u32 grid, hipStream_t st)
     hipLaunchKernelGGL(k_skm2_union, dim3(grid), dim3(SKM2_UNT), lds, st, job, cs, skm_first_claimed(job.nslots, grid));
 }
 void kh_launch_skm2_big(const KhSkmJob& job, u32 cs, u32 nbig, hipStream_t st) { skm_launch_big<SkmBig2>(job, cs, nbig, st); }
+// k_skm_cross (kh_skm_device.h) with two-word keys
+constexpr bool SKM_CROSS2_VGPRS64 = true;   // resource report: 58 VGPRs, 78 SGPRs (66 more kept in VGPR lanes), no scratch, 8 waves per SIMD; 64384 bytes of LDS
+u32 kh_skm2_cross_round() { return skm_cross_round<SkmBig2>(); }
+u32 kh_skm2_cross_per_cu() { return skm_cross_per_cu<SkmBig2>(SKM_CROSS2_VGPRS64); }
+void kh_launch_skm2_cross(const KhSkmJob& job, const KhSkmCrossJob& cj, u32 grid, hipStream_t st) { skm_launch_cross<SkmBig2>(job, cj, grid, st); }

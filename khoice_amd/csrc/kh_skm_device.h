@@ -630,3 +630,225 @@ template <class Tr> void skm_launch_big(const KhSkmJob& job, u32 cs, u32 nbig, h
     skm_allow_lds(k_skm_big<Tr>, lds);
     hipLaunchKernelGGL(k_skm_big<Tr>, dim3(nbig, nbig < 2048u ? (u32)(y < 1 ? 1 : (y > 16 ? 16 : y)) : 1u), dim3(SKM_BIG_NT), lds, st, job, cs);
 }
+
+// ------------------------------------------------------------------------------------------
+// Experiment type 3 (kh_exp3_run above the bitmaps): pivots against groups from the same records.  The operands are
+// the genomes in group-major order, then the pivots (read sets) of the pass as further tags: bit t of a key's 64-bit
+// mask says that operand t holds it.  k_skm_big's walk of one slot — count the instances, rounds of key subsets,
+// chunks numbered in batches, every k-mer into the table by the probe walk, the operand's bit into the mask plane of
+// its half — and a read-out that knows the pivots: an entry whose mask holds pivots P and, of group g, c >= 1
+// genomes adds one to bin q * ngenomes + (first genome of g) + c - 1 for every q in P (k_bmp_cross's bins; the host
+// clamps the counts).  An entry no pivot holds counts nowhere.  No counter across groups, no own-group exception:
+// the two things types 2 and 4 will have to add to this read-out.
+//
+// Two launches of one body.  DIRECT (cj.nlisted == 0): persistent workgroups walk all slots grid-strided; a slot with
+// more records than its region holds is listed (big_list, ctl[6]) as the unions list it, and skipped.  LISTED: work
+// item i is slot big_list[i], its region plus its records on the side list.  The bins stay in LDS over the whole walk
+// and go to one replica of the device block at the end.  ctl[7]: slots taken in more than one round.
+// Nothing is tuned: no merge of identical records, read-out by a scan of the table, one slot at a time.
+// ------------------------------------------------------------------------------------------
+constexpr u32 SKM_CROSS_BINS = 1024;   // pivots x genomes of a pass at most: 32 x 32 of 64 operands
+template <class Tr> constexpr u32 skm_cross_round() { return Tr::T - Tr::T / 4; }   // k-mer instances a round takes (k_skm_big's ROUND)
+// the round (of R < 65536) a key belongs to: k_skm_big's rule, sixteen hash bits scaled to [0, R)
+__device__ __forceinline__ u32 skm_cross_round_of(const u32 H, const u32 R) {
+    const u32 part = (H >> 4) & 0xffffu;
+    return (part * R) >> 16;
+}
+template <class Tr> constexpr size_t skm_cross_lds_bytes(bool listed) {
+    return (size_t)(Tr::T + Tr::T2) * (Tr::KEY_BYTES + 8) + 1024 + 128 + 256 + (size_t)SKM_CROSS_BINS * 4 +
+           (size_t)(Tr::BATCH << Tr::OB) * 2 + (listed ? (size_t)SKM_BIG_IDX * 4 : 0);
+}
+template <class Tr>
+__global__ __launch_bounds__(SKM_BIG_NT, 8) void k_skm_cross(const KhSkmJob jb, const KhSkmCrossJob cj) {
+    extern __shared__ __attribute__((aligned(16))) u8 lds_raw[];
+    using Rec = typename Tr::Rec;
+    constexpr u32 NT = SKM_BIG_NT, T = Tr::T, T2 = Tr::T2, Q = Rec::Q, MAXCH = Tr::BATCH << Tr::OB;
+    constexpr u32 ROUND = skm_cross_round<Tr>();
+    constexpr u32 E = (u32)Tr::E;
+    constexpr u64 EMPTY = ~0ull;
+    u8* p = lds_raw;
+    u8* kmain = p;                                                         p += (size_t)T * Tr::KEY_BYTES;
+    u32* tmlo = reinterpret_cast<u32*>(p);                                 p += (size_t)T * 4;
+    u32* tmhi = reinterpret_cast<u32*>(p);                                 p += (size_t)T * 4;
+    u8* ksecond = p;                                                       p += (size_t)T2 * Tr::KEY_BYTES;
+    u32* omlo = reinterpret_cast<u32*>(p);                                 p += (size_t)T2 * 4;
+    u32* omhi = reinterpret_cast<u32*>(p);                                 p += (size_t)T2 * 4;
+    constexpr u32 omask_off = (T * 8 + T2 * Tr::KEY_BYTES) / 4;            // omlo - tmlo
+    constexpr u32 okey_off = T * (Tr::KEY_BYTES + 8) / 8;                  // the second table's key planes behind the main one's, in u64
+    uint4* gtab = reinterpret_cast<uint4*>(p);                             p += 1024;   // [KH_TAG_MAX_OPS] per operand: its group's mask (two halves), the group's first genome
+    u32* scratch = reinterpret_cast<u32*>(p);                              p += 128;    // [0] chunks, [2] k-mers, [3] side-list records
+    u32* dupc = reinterpret_cast<u32*>(p);                                 p += 256;    // [KH_TAG_MAX_OPS] per operand: instances whose (k-mer, operand) pair was seen before
+    u32* bins = reinterpret_cast<u32*>(p);                                 p += (size_t)SKM_CROSS_BINS * 4;
+    u16* owner = reinterpret_cast<u16*>(p);                                p += (size_t)MAXCH * 2;
+    u32* sidx = reinterpret_cast<u32*>(p);                                 // [SKM_BIG_IDX] listed launch only: this slot's records on the side list
+    const u32 tid = threadIdx.x, lane = lane_id();
+    const u32 cap2 = jb.cap2;
+    const bool listed = cj.nlisted != 0u;
+    const u32 nwork = listed ? (cj.nlisted < jb.big_cap ? cj.nlisted : jb.big_cap) : jb.nslots;
+    const u32 nbins = cj.nbins < SKM_CROSS_BINS ? cj.nbins : SKM_CROSS_BINS;
+    const u32 ngen = cj.ngenomes, pmlo = cj.pmlo, pmhi = cj.pmhi;
+    const typename Tr::Consts kc(jb.k);
+    if (tid < (u32)KH_TAG_MAX_OPS) {
+        const u32 g = jb.ginfo[tid], g0 = g & 0xffu, gn = (g >> 8) & 0xffu;
+        const u64 gm = gn ? (gn >= 64u ? ~0ull : ((1ull << gn) - 1ull)) << g0 : 0ull;
+        gtab[tid] = make_uint4((u32)gm, (u32)(gm >> 32), g0, 0u);
+        dupc[tid] = 0;
+    }
+    for (u32 i = tid; i < SKM_CROSS_BINS; i += NT) bins[i] = 0;
+    u32 nspill_all = 0;
+    if (listed) {
+        nspill_all = jb.ctl[5];
+        nspill_all = nspill_all < jb.spill_cap ? nspill_all : jb.spill_cap;
+    }
+    // one occupied entry: the pivots of its mask against every group of its genomes
+    auto count_entry = [&](u32 mlo, u32 mhi) __attribute__((always_inline)) {
+        const u32 plo = mlo & pmlo, phi = mhi & pmhi;
+        if (!(plo | phi)) return;
+        mlo &= ~pmlo;
+        mhi &= ~pmhi;
+        while (mlo | mhi) {
+            const u32 first = mlo ? (u32)__builtin_ctz(mlo) : 32u + (u32)__builtin_ctz(mhi);
+            const uint4 g = gtab[first];
+            const u32 c = (u32)__popc(mlo & g.x) + (u32)__popc(mhi & g.y);
+            const u32 bin = g.z + c - 1u;   // (c >= 1: the group's mask holds `first`; a tag outside every group counts as a group of one)
+            u32 ql = plo, qh = phi;
+            while (ql | qh) {
+                const u32 op = ql ? (u32)__builtin_ctz(ql) : 32u + (u32)__builtin_ctz(qh);
+                const u32 at = (op - ngen) * ngen + bin;
+                if (op >= ngen && bin < ngen && at < nbins) atomicAdd(&bins[at], 1u);
+                if (ql) ql &= ql - 1u; else qh &= qh - 1u;
+            }
+            const u32 keep_hi = mlo ? ~0u : mhi - 1u;   // (the lowest bit goes in any case: the loop ends)
+            mlo &= ~g.x & (mlo - 1u);
+            mhi &= ~g.y & keep_hi;
+        }
+    };
+    u32 st_full = 0, st_exp = 0, st_multi = 0;   // fullest slot seen, k-mer instances expanded, slots of several rounds (uniform)
+    __syncthreads();
+    for (u32 it = blockIdx.x; it < nwork; it += gridDim.x) {
+        const u32 slot = listed ? jb.big_list[it] : it;
+        if (slot >= jb.nslots) continue;   // (uniform; a listed slot is one the direct launch wrote)
+        const u32 have = jb.cur2[slot];
+        if (!listed) {   // uniform
+            if (!have) continue;
+            if (have > cap2) {   // an overfull slot: listed for the second launch, as the unions list theirs
+                if (tid == 0) {
+                    const u32 at = atomicAdd(jb.ctl + 6, 1u);
+                    if (at < jb.big_cap) jb.big_list[at] = slot;
+                }
+                continue;
+            }
+        }
+        if (tid < 8) scratch[tid] = 0;
+        __syncthreads();
+        // ---- this slot's records on the side list
+        u32 nside = 0;
+        if (listed) {
+            for (u32 i = tid; i < nspill_all; i += NT) {
+                if (jb.spill_slot[i] == slot) {
+                    const u32 at = atomicAdd(&scratch[3], 1u);
+                    if (at < SKM_BIG_IDX) sidx[at] = i;
+                }
+            }
+            __syncthreads();
+            nside = scratch[3];
+            if (nside > SKM_BIG_IDX) {   // (more than this kernel indexes: the host falls back)
+                if (tid == 0) atomicOr(jb.ctl, KH_ERR_CAPACITY);
+                nside = SKM_BIG_IDX;
+            }
+        }
+        const u32 nreg = have < cap2 ? have : cap2;
+        const uint4* __restrict__ reg = jb.reg2 + (u64)slot * cap2 * Q;
+        const u32 nall = nreg + nside;
+        // uint4 q of record i; the header sits in the last word of uint4 Q - 1
+        auto rec_q = [&](u32 i, u32 q) __attribute__((always_inline)) -> uint4 { return i < nreg ? reg[(u64)Q * i + q] : jb.spill_rec[(u64)Q * sidx[i - nreg] + q]; };
+        // ---- k-mer instances of the slot -> rounds
+        {
+            u32 mine = 0;
+            for (u32 i = tid; i < nall; i += NT) mine += Rec::n(rec_q(i, Q - 1).w);
+            const u32 tot = wave_scan_add(mine);
+            if (lane == KH_WAVE - 1 && tot) atomicAdd(&scratch[2], tot);
+        }
+        __syncthreads();
+        const u32 N = scratch[2];
+        const u32 R = (N + ROUND - 1u) / ROUND;
+        st_full = N > st_full ? N : st_full;
+        st_exp += N;
+        st_multi += R > 1u ? 1u : 0u;
+        for (u32 q = 0; q < R; ++q) {
+            // a fresh table: key planes all ones, both mask planes zero
+            for (u32 i = tid; i < T * Tr::KEY_BYTES / 16; i += NT) reinterpret_cast<uint4*>(kmain)[i] = make_uint4(0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu);
+            for (u32 i = tid; i < T2 * Tr::KEY_BYTES / 16; i += NT) reinterpret_cast<uint4*>(ksecond)[i] = make_uint4(0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu);
+            for (u32 i = tid; i < T / 2; i += NT) reinterpret_cast<uint4*>(tmlo)[i] = make_uint4(0u, 0u, 0u, 0u);
+            if (tid < T2) { omlo[tid] = 0u; omhi[tid] = 0u; }
+            __syncthreads();
+            for (u32 b0 = 0; b0 < nall; b0 += Tr::BATCH) {   // batches of records, one per thread of the first waves
+                const u32 mine_i = b0 + tid;
+                const u32 nj = tid < Tr::BATCH && mine_i < nall ? Rec::n(rec_q(mine_i, Q - 1).w) : 0u;
+                const u32 nch = (nj + E - 1u) / E;
+                {
+                    const u32 incl = wave_scan_add(nch);
+                    u32 wbase = 0;
+                    if (lane == KH_WAVE - 1 && incl) wbase = atomicAdd(&scratch[0], incl);
+                    wbase = (u32)__builtin_amdgcn_readlane((int)wbase, KH_WAVE - 1);
+                    const u32 cstart = wbase + incl - nch;
+                    if (cstart + nch <= MAXCH)
+                        for (u32 cc = 0; cc < nch; ++cc) owner[cstart + cc] = (u16)((tid << Tr::OB) | cc);
+                }
+                __syncthreads();
+                u32 C = scratch[0];
+                if (C > MAXCH) {   // (cannot happen: a record has at most 1 << OB chunks)
+                    if (tid == 0) atomicOr(jb.ctl, KH_ERR_CAPACITY);
+                    C = 0;
+                }
+                for (u32 c = tid; c < C; c += NT) {
+                    const u32 o = owner[c], ri = b0 + (o >> Tr::OB), first = (o & ((1u << Tr::OB) - 1u)) * E;
+                    SkmRecord<Q> r0;
+#pragma unroll
+                    for (u32 qq = 0; qq < Q; ++qq) r0.v[qq] = rec_q(ri, qq);
+                    const u32 hw = r0.v[Q - 1].w;
+                    const u32 tg = Rec::tag(hw), bit = 1u << (tg & 31u), half = Rec::half(hw);
+                    const u32 cnt = Rec::n(hw) - first;   // k-mers of the record from `first` on: the chunk holds min(cnt, E)
+                    Tr::expand(r0, first, kc, [&](const u32 e, const typename Tr::Key& K) __attribute__((always_inline)) {
+                        if (e >= cnt) return;
+                        const u32 H = Tr::hash(K);
+                        if (R != 1 && skm_cross_round_of(H, R) != q) return;   // another round's key
+                        skm_probe_walk<T, T2>(H, jb.ctl, Tr::claim(kmain, okey_off, K), [&](const bool second, const u32 S, bool) __attribute__((always_inline)) {
+                            u32* const mp = tmlo + (second ? omask_off + half * T2 : half * T) + S;
+                            if (atomicOr(mp, bit) & bit) atomicAdd(&dupc[tg], 1u);   // this operand had the k-mer already
+                        });
+                    });
+                }
+                __syncthreads();
+                if (tid == 0) scratch[0] = 0;
+                __syncthreads();
+            }
+            // ---- read-out: every occupied entry
+            for (u32 i = tid; i < T; i += NT)
+                if (reinterpret_cast<const u64*>(kmain)[i] != EMPTY) count_entry(tmlo[i], tmhi[i]);
+            if (tid < T2 && reinterpret_cast<const u64*>(ksecond)[tid] != EMPTY) count_entry(omlo[tid], omhi[tid]);
+            __syncthreads();
+        }
+        __syncthreads();   // (a slot without a round: scratch is written again only behind this)
+    }
+    __syncthreads();
+    unsigned long long* __restrict__ rep = cj.bins + (u64)(blockIdx.x % cj.reps) * cj.nbins;
+    for (u32 i = tid; i < nbins; i += NT)
+        if (bins[i]) atomicAdd(&rep[i], (unsigned long long)bins[i]);
+    if (tid < (u32)KH_TAG_MAX_OPS && dupc[tid]) atomicAdd(&jb.dup[tid], (unsigned long long)dupc[tid]);
+    if (tid == 0) {
+        if (st_full > T) atomicMax(jb.ctl + 1, st_full);
+        if (st_exp) atomicAdd(jb.ctl + 3, st_exp);
+        if (st_multi) atomicAdd(jb.ctl + 7, st_multi);
+    }
+}
+// workgroups of k_skm_cross<Tr> a CU holds in the direct launch: by its LDS (160 KB a CU) and by its 1024 threads
+// (sixteen waves: two workgroups when the kernel keeps to 64 VGPRs, which `vgprs64` says it does)
+template <class Tr> constexpr u32 skm_cross_per_cu(bool vgprs64) {
+    return vgprs64 && 2 * skm_cross_lds_bytes<Tr>(false) <= 160 * 1024 ? 2u : 1u;
+}
+template <class Tr> void skm_launch_cross(const KhSkmJob& job, const KhSkmCrossJob& cj, u32 grid, hipStream_t st) {
+    if (!grid) return;
+    skm_allow_lds(k_skm_cross<Tr>, skm_cross_lds_bytes<Tr>(true));
+    hipLaunchKernelGGL(k_skm_cross<Tr>, dim3(grid), dim3(SKM_BIG_NT), skm_cross_lds_bytes<Tr>(cj.nlisted != 0u), st, job, cj);
+}

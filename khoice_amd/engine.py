@@ -588,7 +588,10 @@ class Engine:
                  hist_len: int = 5001):
         """Device side of exp_type_3.smk:176-277 for one k: the read set of every pivot against the rest-of-set union of
         every group.  Returns a dict with inter_hist[npivots, ngroups, hist_len] (the `intersect -ocsum` histograms),
-        distinct_per_seq[nseq] and distinct_per_pivot[npivots].  seqs and pivots: host bytes or device-resident texts."""
+        distinct_per_seq[nseq] and distinct_per_pivot[npivots].  seqs and pivots: host bytes or device-resident texts.
+        Forms: presence bitmaps for k <= 12, the set operations inside the library above; with KHOICE_EXP3_SKM=1 in the
+        environment at the call (os.environ; read every time) k = 17 .. 63 is answered from super-k-mer records by one
+        kernel (k_skm_cross) when there are pivots and at most 63 genomes — the same numbers, `skm_cross` in stats()."""
         ptrs, lens, on_dev, keep = self._seq_args(seqs)
         n, npv = len(seqs), len(pivots)
         pptrs, plens, p_on_dev, pkeep = self._seq_args(pivots) if npv else (None, np.zeros(1, dtype=np.uint64), on_dev, [])

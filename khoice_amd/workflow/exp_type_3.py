@@ -191,7 +191,9 @@ def run_batched(work_root: str, k_values: Sequence, num_datasets: int, device: i
 def run_fused(work_root: str, k_values: Sequence, num_datasets: int, device: int = 0):
     """The files and CSV of run_batched from one Engine.exp3_run per k (kh_exp3_run: presence bitmaps for k <= 12, the
     set operations inside the library above): the texts are read once, the intersect histograms are the call's
-    inter_hist, a pivot's own histogram its distinct count in line 1."""
+    inter_hist, a pivot's own histogram its distinct count in line 1.  With KHOICE_EXP3_SKM=1 in the environment the
+    library answers k = 17 .. 63 from super-k-mer records (k_skm_cross) instead — the switch is read inside
+    kh_exp3_run at every call, so this runner gets the form without a change; the files are the same."""
     import numpy as np
     from .. import engine as E
     k_values = [str(k) for k in k_values]
