@@ -462,6 +462,40 @@ static void dump_wg_ends(kh_ctx* c, DevBuf* sb, u32 grid) {
 #endif
 #endif
 
+// The texts of a run on the device (build_once, skm_prepare, BmpRun): a text that is resident and 16-byte aligned is
+// read in place, every other one is packed into d_seq at a multiple of 16 bytes, with 256 bytes behind the last (16-byte
+// loads may run past the last base).
+struct TextStage {
+    Tmp d_seq;                      // the packed copy (256 bytes when every text is read in place)
+    std::vector<const u8*> dev;     // text i on the device
+    // text i is seqs[perm ? perm[i] : i].  The copies are queued on the context's stream (inside the caller's KC_COPY_IN)
+    // and counted in text_packed.
+    int copy_in(kh_ctx* c, int n, const uint8_t* const* seqs, const uint64_t* lens, int on_device, const int* perm = nullptr) {
+        auto in_place = [&](const uint8_t* p) { return on_device && (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+        std::vector<u64> pack_off(n);
+        u64 seq_bytes = 0;
+        bool need_pack = false;
+        for (int i = 0; i < n; ++i) {
+            const int t = perm ? perm[i] : i;
+            pack_off[i] = seq_bytes;
+            seq_bytes += (lens[t] + 15) & ~15ull;
+            if (!in_place(seqs[t])) need_pack = true;
+        }
+        TMP_ALLOC(d_seq, c, need_pack ? seq_bytes + 256 : 256);
+        dev.resize(n);
+        for (int i = 0; i < n; ++i) {
+            const int t = perm ? perm[i] : i;
+            if (in_place(seqs[t])) { dev[i] = seqs[t]; continue; }
+            dev[i] = d_seq.as<u8>() + pack_off[i];
+            if (!lens[t]) continue;
+            HIPCHK(hipMemcpyAsync(d_seq.as<u8>() + pack_off[i], seqs[t], lens[t],
+                                  on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->st));
+            c->stat.text_packed += lens[t];
+        }
+        return KH_OK;
+    }
+};
+
 // ------------------------------------------------------------------------------ K1 build
 // What a grid-mode build (KhGrid, kh_launch.h) leaves behind: nothing has been synchronised when
 // build_once returns, the caller queues the tagged union behind it and waits once.
@@ -493,9 +527,8 @@ static int build_once(kh_ctx* c, int nseq, const uint8_t* const* seqs, const uin
 
     // ---- segment layout
     std::vector<KhSeg> segs(nseq);
-    std::vector<u64> pack_off(nseq);
     std::vector<KhTile> tiles;
-    u64 seq_bytes = 0, total_pos = 0, thist_n = 0, bases = 0;
+    u64 total_pos = 0, thist_n = 0, bases = 0;
     u32 nb_total = 0, max_nb = 1;
     // Positions per extraction workgroup (tile): 65536 amortises the cursor rows best, but a small
     // batch (the per-call path: one 5 Mbp genome is 77 such tiles on 256 CUs) is cut finer so that
@@ -518,7 +551,6 @@ static int build_once(kh_ctx* c, int nseq, const uint8_t* const* seqs, const uin
     for (int i = 0; i < nseq; ++i) {
         KhSeg& s = segs[i];
         s.seq = nullptr;
-        pack_off[i] = seq_bytes;
         s.len = lens[i];
         s.npos = lens[i] >= (u64)k ? lens[i] - k + 1 : 0;
         const u64 want_b = grid ? grid_nb : std::max<u64>(1, (s.npos + mean - 1) / mean);
@@ -540,16 +572,13 @@ static int build_once(kh_ctx* c, int nseq, const uint8_t* const* seqs, const uin
         nb_total += s.nbuckets;
         max_nb = std::max(max_nb, s.nbuckets);
         total_pos += s.npos;
-        seq_bytes += (lens[i] + 15) & ~15ull;
         bases += lens[i];
     }
-    seq_bytes += 256;   // tail padding: 16-byte loads may run past the last base
     const u32 ntiles = (u32)tiles.size();
     const u32 nb_alloc = (max_nb + 3) & ~3u;
 
     // ---- device buffers
-    Tmp d_seq, d_thist, d_tot, d_bstart, d_part, d_lb;
-    TMP_ALLOC(d_seq, c, seq_bytes);
+    Tmp d_thist, d_tot, d_bstart, d_part, d_lb;
     TMP_ALLOC(d_thist, c, 4 * std::max<u64>(1, thist_n));
     TMP_ALLOC(d_tot, c, 8 * (u64)nb_total);
     TMP_ALLOC(d_bstart, c, 8 * ((u64)nb_total + 1));
@@ -594,20 +623,10 @@ static int build_once(kh_ctx* c, int nseq, const uint8_t* const* seqs, const uin
     }
     struct Guard { DevBuf *&a, *&b; ~Guard() { buf_unref(a); buf_unref(b); } } guard{okeys, ocnt};
 
-    // device-resident, 16-byte aligned inputs are read in place; anything else is packed into
-    // the aligned batch buffer first
+    TextStage texts;
     c->prof_begin(KC_COPY_IN);
-    for (int i = 0; i < nseq; ++i) {
-        if (on_device && (reinterpret_cast<uintptr_t>(seqs[i]) & 15) == 0) {
-            segs[i].seq = seqs[i];
-            continue;
-        }
-        segs[i].seq = d_seq.as<u8>() + pack_off[i];
-        if (!lens[i]) continue;
-        HIPCHK(hipMemcpyAsync(d_seq.as<u8>() + pack_off[i], seqs[i], lens[i],
-                              on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
-        c->stat.text_packed += lens[i];
-    }
+    KHCHK(texts.copy_in(c, nseq, seqs, lens, on_device));
+    for (int i = 0; i < nseq; ++i) segs[i].seq = texts.dev[i];
     // Start order of pass C (KhBucketWork): buckets of up to 64 consecutive segments are
     // interleaved (bucket 0 of each, bucket 1 of each, ...), every segment writes into its own
     // output region [out_base, out_base + npos) and runs its own look-back chain.
@@ -647,7 +666,7 @@ static int build_once(kh_ctx* c, int nseq, const uint8_t* const* seqs, const uin
 
     // ---- pass A, bucket plan, pass B
     c->prof_begin(KC_EXTRACT_HIST);
-    kh_launch_extract(W, false, d_seq.as<u8>(), d_segs_p, d_tiles_p, ntiles,
+    kh_launch_extract(W, false, texts.d_seq.as<u8>(), d_segs_p, d_tiles_p, ntiles,
                       nb_alloc, k, d_thist.as<u32>(), nullptr, nullptr, tile_pos, st);
     c->prof_end();
     c->prof_begin(KC_BUCKET_PLAN);
@@ -678,7 +697,7 @@ static int build_once(kh_ctx* c, int nseq, const uint8_t* const* seqs, const uin
     kh_debug_set_stamps(d_stamps_b.as<u64>());
 #endif
     c->prof_begin(KC_EXTRACT_SCATTER);
-    kh_launch_extract(W, true, d_seq.as<u8>(), d_segs_p, d_tiles_p, ntiles,
+    kh_launch_extract(W, true, texts.d_seq.as<u8>(), d_segs_p, d_tiles_p, ntiles,
                       nb_alloc, k, d_thist.as<u32>(), d_bstart.as<u64>(), d_part.b->p, tile_pos, st);
     c->prof_end();
 #ifdef KH_STAMPS
@@ -1728,6 +1747,7 @@ static u64 skm_part_cap(u64 positions, double per_kmer, int nparts) {
     return ((u64)((double)positions * per_kmer * 1.3 / nparts) + 8192 + 63) & ~63ull;
 }
 struct SkmGeometry {
+    const KhSkmWidth* wd = nullptr; // the key width's constants and launchers (kh_skm_width)
     bool two = false;               // two-word keys
     int m = 0;                      // minimizer length
     u32 w = 0, nmax = 0;            // m-mers per k-mer, k-mers per record at most
@@ -1743,16 +1763,18 @@ static bool skm_plan(int k, u64 positions, u32 fan, u32 force_slots, int cus, Sk
     if (!skm_form_k(k)) return false;
     SkmGeometry g;
     g.two = k > KH_SKM_MAX_K;
+    const KhSkmWidth& wd = kh_skm_width(g.two);
+    g.wd = &wd;
     if (!g.two) {
         g.m = skm_minimizer_len(k);
         if (const char* e = getenv("KHOICE_SKM_M")) g.m = std::min(16, std::max(2, atoi(e)));   // experiments
         if (g.m >= k) return false;
         g.w = (u32)(k - g.m + 1);
         g.nmax = (u32)std::min(31, 55 - k);
-        if (!kh_skm_supports_w(g.w)) return false;
+        if (!wd.supports_w(g.w)) return false;
     } else {   // the scatter exists for every third window width: one of m = 16, 15, 14 fits
         g.m = 16;
-        while (g.m >= 14 && !kh_skm2_supports_w((u32)(k - g.m + 1))) --g.m;
+        while (g.m >= 14 && !wd.supports_w((u32)(k - g.m + 1))) --g.m;
         if (g.m < 14) return false;
         g.w = (u32)(k - g.m + 1);
         g.nmax = (u32)std::min(63, 118 - k);
@@ -1764,13 +1786,13 @@ static bool skm_plan(int k, u64 positions, u32 fan, u32 force_slots, int cus, Sk
     // (largest group) instances, so sigma = sqrt(mean x c); mean + 2.5 sigma = T  (measured: 2500 / 2900 / 3200 /
     // 3500 / 3800 at k = 31 with groups of five: union 1.96 / 1.81 / 1.75 / 1.80 / 1.94 ms; the rule gives 3180)
     const double clump = skm_clump(g.w, fan);
-    const double T = table ? (double)table : g.two ? (double)kh_skm2_table() : 4096.0;   // (one-word keys: k_skm_union's 4096 entries)
+    const double T = table ? (double)table : (double)wd.table;
     const double r = 0.5 * (-2.5 * std::sqrt(clump) + std::sqrt(6.25 * clump + 4.0 * T));
     u32 mean = (u32)std::max(256.0, r * r);
     if (const char* e = getenv("KHOICE_SKM_MEAN")) mean = std::max<u32>(64, (u32)strtoul(e, nullptr, 10));
     const double per_kmer = skm_per_kmer(g.w);
     double slack1 = 1.25, slack2 = 1.7;
-    const u32 max_cap2 = g.two ? kh_skm2_max_cap2() : kh_skm_union_max_cap2();
+    const u32 max_cap2 = wd.max_cap2;
     for (int it = 0; it < 8; ++it) {   // short windows (k = 20 .. 22: 3.5 k-mers per record): fewer instances per slot so that its records fit
         slack2 = skm_region_slack(clump, (double)mean);
         const double c2 = (double)mean * per_kmer * slack2 + 96 + 16;
@@ -1784,24 +1806,24 @@ static bool skm_plan(int k, u64 positions, u32 fan, u32 force_slots, int cus, Sk
     // overflow (side list, k_skm_big) its slack can be cut instead: stay at 256 x 512 slots with slack down to 1.4.
     // Two-word keys a little above 512 x 1024 slots (configs[2] at k = 41, the pass by group over 500 M positions):
     // the same cut, up to what the union's table takes in one go on average.
-    const u64 lim = g.two ? (u64)KH_SKM2_MAX_COARSE * KH_SKM2_MAX_FINE : (u64)KH_SKM_MAX_COARSE * KH_SKM_MAX_FINE;
+    const u64 lim = (u64)wd.max_coarse * wd.max_fine;
     if (!force_slots && nslots64 > lim) {
         const double per_slot = (double)positions * per_kmer / (double)lim;
         const double s2 = ((double)max_cap2 - 112.0) / per_slot;
-        if (s2 >= 1.4 && (!g.two || (double)positions / (double)lim <= 0.75 * (double)kh_skm2_table())) {
+        if (s2 >= 1.4 && (!g.two || (double)positions / (double)lim <= 0.75 * (double)wd.table)) {
             nslots64 = lim;
             slack2 = std::min(slack2, s2);
         }
     }
     // coarse buckets: 256 keep the scatter's runs long; inputs past 256 x 512 slots (> 400 M k-mers) take 512
-    const u32 max_coarse = (g.two || nslots64 > (u64)KH_SKM_MAX_COARSE * KH_SKM_MAX_FINE) ? KH_SKM2_MAX_COARSE : KH_SKM_MAX_COARSE;
-    if (nslots64 > (u64)max_coarse * (g.two ? KH_SKM2_MAX_FINE : KH_SKM_MAX_FINE)) {
+    const u32 max_coarse = nslots64 > lim ? kh_skm_width(true).max_coarse : wd.max_coarse;   // (one-word keys past their own limit: the two-word scatter's 512)
+    if (nslots64 > (u64)max_coarse * wd.max_fine) {
         // more slots than the two levels number.  A caller whose kernel takes a slot in rounds (`table`: k_skm_cross)
         // gets all of them, fuller than the rule wants — as long as a region with its whole slack holds their records
         // (below; measured without that condition at k = 17 on 625 Mbp: regions cut to 1.4 x the mean, more records
         // spilled than the side list keeps, the call paid 15 ms for the attempt before the set form answered)
         if (!table || force_slots) return false;
-        nslots64 = (u64)max_coarse * (g.two ? KH_SKM2_MAX_FINE : KH_SKM_MAX_FINE);
+        nslots64 = (u64)max_coarse * wd.max_fine;
         fuller = true;
     }
     g.nslots = (u32)nslots64;
@@ -1823,31 +1845,96 @@ static bool skm_plan(int k, u64 positions, u32 fan, u32 force_slots, int cus, Sk
     g.cap1 = (u32)cap1_64;
     g.cap2 = (u32)cap2_64;
     // the union is persistent (as many workgroups as fit the chip, each with a histogram of its own)
-    g.ugrid = std::min<u32>(g.nslots, (g.two ? kh_skm2_union_per_cu() : kh_skm_union_per_cu()) * (u32)std::max(1, cus));
+    g.ugrid = std::min<u32>(g.nslots, wd.union_per_cu * (u32)std::max(1, cus));
     *out = g;
     return true;
 }
-// A pass of the super-k-mer form between the regroup and the union: its device buffers and pinned staging.
-struct SkmStage {
+// a launch under its profiling class, and the error it may have left
+template <class F> static int timed_launch(kh_ctx* c, int cls, F launch) {
+    c->prof_begin(cls);
+    launch();
+    c->prof_end();
+    HIPCHK(hipGetLastError());
+    return KH_OK;
+}
+// One run of a super-k-mer form, what exp1_skm, exp3_skm and skm_pack_impl do alike.  In this order: skm_prepare() (the
+// geometry, the texts, scatter and regroup; !staged: the form does not apply); the form's own launch over the records
+// by slot; settle() (exp1_skm, exp3_skm) or read_back() (skm_pack_impl); then h_ctl(), h_hist() and per_text().
+// Workspace: [hist: reps x nbins u64][ctl: KH_SKM_CTL_WORDS u32][inst: nseq u64][dup: 64 u64] (zeroed, read back)
+// [cur1: nb1 x KH_SKM_CUR1_STRIDE u32][cur2: nslots u32][claim: a 128-byte line of its own] (zeroed) [ginfo: 64 u32]
+// [tags: nseq u8][segs][tiles] (one upload)
+struct SkmRun {
+    kh_ctx* c;
     TagLayout L;
     SkmGeometry g;
     KhSkmJob job;
-    Tmp d_seq, d_ws, d_reg1, d_reg2, d_spill;
+    struct Layout { size_t ctl, inst, dup, cur1, cur2, claim, ginfo, tags, segs, tiles, bytes; } off{};   // (hist at 0)
+    TextStage texts;
+    Tmp d_ws, d_reg1, d_reg2, d_spill;
     Pinned pin;
     u8* h_down = nullptr;           // pinned read-back of the workspace's [hist .. dup], laid out as on the device
     u32 ntiles = 0;
     u64 bases = 0;
     bool staged = false;            // false: the form does not apply (k, operands, geometry, memory)
-    // one-word keys: what a slot's region cannot hold goes to a side list, the slot to a kernel of its own
+    // what a slot's region cannot hold goes to a side list (d_spill: [spill_cap] records, [spill_cap] u32 slots, [big_cap]
+    // u32 listed slots), the slot to a launch of its own
     static constexpr u32 spill_cap = 1u << 20, big_cap = 16384u;
 #ifdef KH_STAMPS
     Tmp d_stamps;
 #endif
-    explicit SkmStage(kh_ctx* c) : pin{c} {}
+    explicit SkmRun(kh_ctx* ctx) : c(ctx), pin{ctx} {}
+
+    void layout(size_t hist_words, int nseq) {
+        off.ctl = 8 * hist_words;
+        off.inst = off.ctl + 4 * (size_t)KH_SKM_CTL_WORDS;
+        off.dup = off.inst + 8 * (size_t)nseq;
+        off.cur1 = off.dup + 8 * 64;
+        off.cur2 = off.cur1 + 4 * (size_t)KH_SKM_CUR1_STRIDE * g.nb1;
+        off.claim = (off.cur2 + 4 * (size_t)g.nslots + 127) & ~(size_t)127;
+        off.ginfo = off.claim + 128;
+        off.tags = off.ginfo + 256;
+        off.segs = off.tags + (((size_t)nseq + 15) & ~(size_t)15);
+        off.tiles = off.segs + sizeof(KhSeg) * nseq;
+        off.bytes = off.tiles + sizeof(KhTile) * (size_t)std::max<u32>(1, ntiles);
+    }
+    template <class T> T* dev(size_t o) const { return reinterpret_cast<T*>(d_ws.as<u8>() + o); }
+    // [from, dup's end) of the workspace into h_down, and the wait for it
+    int read_back(size_t from) {
+        HIPCHK(hipMemcpyAsync(h_down + from, d_ws.as<u8>() + from, off.cur1 - from, hipMemcpyDeviceToHost, c->st));
+        HIPCHK(hipStreamSynchronize(c->st));
+        return KH_OK;
+    }
+    const u64* h_hist() const { return reinterpret_cast<const u64*>(h_down); }             // [reps][nbins]
+    const u32* h_ctl() const { return reinterpret_cast<const u32*>(h_down + off.ctl); }    // [KH_SKM_CTL_WORDS]
+    const u64* h_inst() const { return reinterpret_cast<const u64*>(h_down + off.inst); }  // [nseq]
+    const u64* h_dup() const { return reinterpret_cast<const u64*>(h_down + off.dup); }    // [64]
+    bool failed() const { return (h_ctl()[KH_SKM_CTL_ERR] & (KH_ERR_CAPACITY | KH_ERR_ORDER)) != 0; }
+    // After the form's first launch: [from, dup's end) read back; overfull slots (skewed input: a minimizer shared by far
+    // more k-mers than a hash predicts) were listed and left out — listed(n) launches the kernel that takes the n of them
+    // (only these slots are done twice, not the call), and the read-back again.  *declines (retries counted): more
+    // spilled records or listed slots than are kept, or a region, a slot or a table overflowed; another form answers.
+    template <class F> int settle(size_t from, F listed, bool* declines) {
+        *declines = true;
+        KHCHK(read_back(from));
+        const u32* hc = h_ctl();
+        if (hc[KH_SKM_CTL_LISTED] && !failed()) {
+            if (hc[KH_SKM_CTL_SPILLED] > spill_cap || hc[KH_SKM_CTL_LISTED] > big_cap) { c->stat.retries++; return KH_OK; }
+            KHCHK(listed(hc[KH_SKM_CTL_LISTED]));
+            KHCHK(read_back(from));
+        }
+        if (failed()) { c->stat.retries++; return KH_OK; }
+        *declines = false;
+        return KH_OK;
+    }
+    // f(t, instances, distinct) for every operand: the caller's text t, its valid k-mer instances, and (after the union
+    // or the cross kernel) its distinct k-mers = instances minus those whose (k-mer, operand) pair was seen before
+    template <class F> void per_text(F f) const {
+        for (int i = 0; i < L.nseq; ++i) f(L.perm[i], h_inst()[i], h_inst()[i] - h_dup()[i]);
+    }
 };
 // (a) + (b): the geometry, then the input staged, scattered and regrouped by slot
 static int skm_prepare(kh_ctx* c, int nseq, const uint8_t* const* seqs, const uint64_t* lens, int on_device,
-                       const int* group_of, int ngroups, int k, bool by_group, u32 force_slots, u32 fan_hint, SkmStage* s,
+                       const int* group_of, int ngroups, int k, bool by_group, u32 force_slots, u32 fan_hint, SkmRun* s,
                        u32 table = 0 /* skm_plan's: 0 for the unions */) {
     TagLayout* L = &s->L;
     if (!skm_form_k(k)) return KH_OK;
@@ -1858,7 +1945,8 @@ static int skm_prepare(kh_ctx* c, int nseq, const uint8_t* const* seqs, const ui
     // (fan_hint: genomes whose copies of a locus arrive together although they are tags of ONE group)
     if (!skm_plan(k, positions, std::max(L->fan, fan_hint), force_slots, c->cus, &s->g, table)) return KH_OK;
     const SkmGeometry& g = s->g;
-    const size_t rec_bytes = g.two ? 32 : 16;
+    const KhSkmWidth& wd = *g.wd;
+    const size_t rec_bytes = wd.rec_bytes;
     const size_t reg1_bytes = rec_bytes * (size_t)g.nb1 * g.cap1, reg2_bytes = rec_bytes * (size_t)g.nslots * g.cap2;
     HIPCHK(hipSetDevice(c->dev));
     {
@@ -1876,80 +1964,55 @@ static int skm_prepare(kh_ctx* c, int nseq, const uint8_t* const* seqs, const ui
         while (tile_pos > (u32)KH_SUBTILE && (positions + tile_pos - 1) / tile_pos < want_tiles) tile_pos >>= 1;
     }
     std::vector<KhSeg> segs(nseq);
-    std::vector<u64> pack_off(nseq);
     std::vector<KhTile> tiles;
-    u64 seq_bytes = 0;
     for (int i = 0; i < nseq; ++i) {
         KhSeg& sg = segs[i];
         memset(&sg, 0, sizeof sg);
         const u64 len = lens[L->perm[i]];
-        pack_off[i] = seq_bytes;
         sg.len = len;
         sg.npos = len >= (u64)k ? len - k + 1 : 0;
         sg.ntiles = (u32)((sg.npos + tile_pos - 1) / tile_pos);
         sg.tile_base = (u32)tiles.size();
         for (u32 t = 0; t < sg.ntiles; ++t) tiles.push_back(KhTile{(u32)i, t});
-        seq_bytes += (len + 15) & ~15ull;
     }
-    seq_bytes += 256;
-    const u32 ntiles = (u32)tiles.size();
+    const u32 ntiles = s->ntiles = (u32)tiles.size();
     const u32 reps = g.ugrid;
-    const size_t hist_words = (size_t)reps * L->nbins;
-    // workspace: [hist][ctl: 8 u32][inst: nseq u64][dup: 64 u64][cur1: nb1 u32][cur2: nslots u32][claim: a 128-byte
-    // line of its own] (zeroed) [ginfo: 64 u32]
-    const size_t off_ctl = 8 * hist_words, off_inst = off_ctl + 32, off_dup = off_inst + 8 * (size_t)nseq,
-                 off_cur1 = off_dup + 8 * 64, off_cur2 = off_cur1 + 4 * (size_t)KH_SKM_CUR1_STRIDE * g.nb1,
-                 off_claim = (off_cur2 + 4 * (size_t)g.nslots + 127) & ~(size_t)127,
-                 off_ginfo = off_claim + 128, off_tags = off_ginfo + 256,
-                 off_segs = off_tags + (((size_t)nseq + 15) & ~(size_t)15), off_tiles = off_segs + sizeof(KhSeg) * nseq,
-                 ws_bytes = off_tiles + sizeof(KhTile) * (size_t)std::max<u32>(1, ntiles);   // [ginfo .. tiles]: one upload
-    const u32 spill_cap = SkmStage::spill_cap;
-    bool need_pack = false;
-    for (int i = 0; i < nseq; ++i)
-        if (!(on_device && (reinterpret_cast<uintptr_t>(seqs[L->perm[i]]) & 15) == 0)) need_pack = true;
-    TMP_ALLOC(s->d_seq, c, need_pack ? seq_bytes : 256);
-    TMP_ALLOC(s->d_ws, c, ws_bytes);
+    s->layout((size_t)reps * L->nbins, nseq);
+    const SkmRun::Layout& off = s->off;
+    const u32 spill_cap = SkmRun::spill_cap;
+    TMP_ALLOC(s->d_ws, c, off.bytes);
     TMP_ALLOC(s->d_reg1, c, reg1_bytes);
     TMP_ALLOC(s->d_reg2, c, reg2_bytes);
-    TMP_ALLOC(s->d_spill, c, (size_t)spill_cap * (rec_bytes + 4) + (size_t)SkmStage::big_cap * 4);
-    // pinned staging: [segs][tiles][ginfo] up, [hist .. dup] down
-    const size_t up_bytes = ws_bytes - off_ginfo;   // the upload, laid out as on the device
-    const size_t down_bytes = off_cur1;
-    PIN_ALLOC(s->pin, up_bytes + down_bytes + 64);
+    TMP_ALLOC(s->d_spill, c, (size_t)spill_cap * (rec_bytes + 4) + (size_t)SkmRun::big_cap * 4);
+    // pinned staging: [ginfo][tags][segs][tiles] up, [hist .. dup] down
+    const size_t up_bytes = off.bytes - off.ginfo;   // the upload, laid out as on the device
+    PIN_ALLOC(s->pin, up_bytes + off.cur1 + 64);
     u8* h_up = static_cast<u8*>(s->pin.p);
     s->h_down = h_up + ((up_bytes + 63) & ~(size_t)63);
     c->prof_begin(KC_COPY_IN);
-    for (int i = 0; i < nseq; ++i) {
-        const uint8_t* src = seqs[L->perm[i]];
-        if (on_device && (reinterpret_cast<uintptr_t>(src) & 15) == 0) { segs[i].seq = src; continue; }
-        segs[i].seq = s->d_seq.as<u8>() + pack_off[i];
-        if (!segs[i].len) continue;
-        HIPCHK(hipMemcpyAsync(s->d_seq.as<u8>() + pack_off[i], src, segs[i].len,
-                              on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
-        c->stat.text_packed += segs[i].len;
-    }
-    memcpy(h_up + (off_segs - off_ginfo), segs.data(), sizeof(KhSeg) * nseq);
-    if (ntiles) memcpy(h_up + (off_tiles - off_ginfo), tiles.data(), sizeof(KhTile) * (size_t)ntiles);
-    L->words(reinterpret_cast<u32*>(h_up), h_up + (off_tags - off_ginfo), group_of);
-    u8* wsp = s->d_ws.as<u8>();
-    HIPCHK(hipMemsetAsync(wsp, 0, off_ginfo, st));
-    HIPCHK(hipMemcpyAsync(wsp + off_ginfo, h_up, up_bytes, hipMemcpyHostToDevice, st));
+    KHCHK(s->texts.copy_in(c, nseq, seqs, lens, on_device, L->perm.data()));
+    for (int i = 0; i < nseq; ++i) segs[i].seq = s->texts.dev[i];
+    memcpy(h_up + (off.segs - off.ginfo), segs.data(), sizeof(KhSeg) * nseq);
+    if (ntiles) memcpy(h_up + (off.tiles - off.ginfo), tiles.data(), sizeof(KhTile) * (size_t)ntiles);
+    L->words(reinterpret_cast<u32*>(h_up), h_up + (off.tags - off.ginfo), group_of);
+    HIPCHK(hipMemsetAsync(s->d_ws.b->p, 0, off.ginfo, st));
+    HIPCHK(hipMemcpyAsync(s->dev<u8>(off.ginfo), h_up, up_bytes, hipMemcpyHostToDevice, st));
     c->prof_end();
 
     KhSkmJob& job = s->job;
-    job.seg_tag = by_group ? wsp + off_tags : nullptr;
-    job.segs = reinterpret_cast<const KhSeg*>(wsp + off_segs);
-    job.tiles = reinterpret_cast<const KhTile*>(wsp + off_tiles);
+    job.seg_tag = by_group ? s->dev<const u8>(off.tags) : nullptr;
+    job.segs = s->dev<const KhSeg>(off.segs);
+    job.tiles = s->dev<const KhTile>(off.tiles);
     job.reg1 = s->d_reg1.as<uint4>();
     job.reg2 = s->d_reg2.as<uint4>();
-    job.cur1 = reinterpret_cast<u32*>(wsp + off_cur1);
-    job.cur2 = reinterpret_cast<u32*>(wsp + off_cur2);
-    job.inst = reinterpret_cast<unsigned long long*>(wsp + off_inst);
-    job.dup = reinterpret_cast<unsigned long long*>(wsp + off_dup);
-    job.ginfo = reinterpret_cast<const u32*>(wsp + off_ginfo);
-    job.hist = reinterpret_cast<unsigned long long*>(wsp);
-    job.ctl = reinterpret_cast<u32*>(wsp + off_ctl);
-    job.claim = reinterpret_cast<u32*>(wsp + off_claim);
+    job.cur1 = s->dev<u32>(off.cur1);
+    job.cur2 = s->dev<u32>(off.cur2);
+    job.inst = s->dev<unsigned long long>(off.inst);
+    job.dup = s->dev<unsigned long long>(off.dup);
+    job.ginfo = s->dev<const u32>(off.ginfo);
+    job.hist = s->dev<unsigned long long>(0);
+    job.ctl = s->dev<u32>(off.ctl);
+    job.claim = s->dev<u32>(off.claim);
     job.tile_pos = tile_pos;
     job.k = k; job.m = g.m; job.w = g.w; job.nmax = g.nmax;
     job.nslots = g.nslots; job.S = g.S; job.nb1 = g.nb1; job.cap1 = g.cap1; job.cap2 = g.cap2;
@@ -1958,8 +2021,7 @@ static int skm_prepare(kh_ctx* c, int nseq, const uint8_t* const* seqs, const ui
     job.spill_slot = reinterpret_cast<u32*>(s->d_spill.as<u8>() + (size_t)spill_cap * rec_bytes);
     job.big_list = reinterpret_cast<u32*>(s->d_spill.as<u8>() + (size_t)spill_cap * (rec_bytes + 4));
     job.spill_cap = spill_cap;
-    job.big_cap = SkmStage::big_cap;
-    s->ntiles = ntiles;
+    job.big_cap = SkmRun::big_cap;
 #ifdef KH_STAMPS
     const u64 nst = std::max<u64>(ntiles, g.nslots);
     TMP_ALLOC(s->d_stamps, c, 128 * nst);
@@ -1967,8 +2029,7 @@ static int skm_prepare(kh_ctx* c, int nseq, const uint8_t* const* seqs, const ui
     kh_debug_set_stamps_skm(s->d_stamps.as<u64>());
 #endif
     c->prof_begin(KC_SKM_SCATTER);
-    if (g.two) kh_launch_skm2_scatter(job, ntiles, st);
-    else kh_launch_skm_scatter(job, ntiles, st);
+    wd.scatter(job, ntiles, st);
     c->prof_end();
 #ifdef KH_STAMPS
     report_stamps(c, "skm_scatter (second sub-tile: codes / hashes / minima / slots+count / - / append / barrier / -)", s->d_stamps.b, ntiles);
@@ -1976,8 +2037,7 @@ static int skm_prepare(kh_ctx* c, int nseq, const uint8_t* const* seqs, const ui
     kh_debug_set_stamps_skm(nullptr);
 #endif
     c->prof_begin(KC_SKM_REGROUP);
-    if (g.two) kh_launch_skm2_regroup(job, st);
-    else kh_launch_skm_regroup(job, st);
+    wd.regroup(job, st);
     c->prof_end();
 #ifdef KH_STAMPS
     kh_debug_set_stamps_skm(s->d_stamps.as<u64>());
@@ -1992,18 +2052,14 @@ static int skm_prepare(kh_ctx* c, int nseq, const uint8_t* const* seqs, const ui
 static int exp1_skm(kh_ctx* c, const Exp1In& in, uint64_t* within_hist, uint64_t* across_hist, uint64_t* distinct_per_seq,
                     bool* done, bool by_group = false) {
     *done = false;
-    SkmStage s(c);
+    SkmRun s(c);
     KHCHK(skm_prepare(c, in.nseq, in.seqs, in.lens, in.on_device, in.group_of, in.ngroups, in.k, by_group, 0, 0, &s));
     if (!s.staged) return KH_OK;
     const TagLayout& L = s.L;
     const SkmGeometry& g = s.g;
     const KhSkmJob& job = s.job;
     hipStream_t st = c->st;
-    c->prof_begin(KC_SKM_UNION);
-    if (g.two) kh_launch_skm2_union(job, in.cs, g.ugrid, st);
-    else kh_launch_skm_union(job, in.cs, g.ugrid, st);
-    c->prof_end();
-    HIPCHK(hipGetLastError());
+    KHCHK(timed_launch(c, KC_SKM_UNION, [&] { g.wd->unite(job, in.cs, g.ugrid, st); }));
 #if defined(KH_STAMPS) && defined(KH_STAMPS_WG)
     dump_wg_ends(c, s.d_stamps.b, g.ugrid);
     kh_debug_set_stamps_skm(nullptr);
@@ -2016,8 +2072,8 @@ static int exp1_skm(kh_ctx* c, const Exp1In& in, uint64_t* within_hist, uint64_t
         std::vector<u32> h1(g.nb1), h2(g.nslots);
         HIPCHK(hipMemcpy2DAsync(h1.data(), 4, job.cur1, 4 * (size_t)KH_SKM_CUR1_STRIDE, 4, g.nb1, hipMemcpyDeviceToHost, st));
         HIPCHK(hipMemcpyAsync(h2.data(), job.cur2, 4 * (size_t)g.nslots, hipMemcpyDeviceToHost, st));
-        u32 hc[8];
-        HIPCHK(hipMemcpyAsync(hc, job.ctl, 32, hipMemcpyDeviceToHost, st));
+        u32 hc[KH_SKM_CTL_WORDS];
+        HIPCHK(hipMemcpyAsync(hc, job.ctl, sizeof hc, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
         u64 t1 = 0, t2 = 0;
         u32 m1 = 0, m2 = 0;
@@ -2026,57 +2082,463 @@ static int exp1_skm(kh_ctx* c, const Exp1In& in, uint64_t* within_hist, uint64_t
         fprintf(stderr, "[skm] k=%d m=%d w=%u nmax=%u positions=%llu records=%llu (%.2f k-mers each) nb1=%u S=%u nslots=%u | "
                         "coarse: mean %.0f max %u cap %u | slot: mean %.1f max %u cap %u | tiles %u x %u | expanded: %u k-mers | errors %u spilled %u overfull slots %u multi-subset slots %u\n",
                 in.k, g.m, g.w, g.nmax, (unsigned long long)g.positions, (unsigned long long)t1, (double)g.positions / std::max<u64>(1, t1),
-                g.nb1, g.S, g.nslots, (double)t1 / g.nb1, m1, g.cap1, (double)t2 / g.nslots, m2, g.cap2, s.ntiles, job.tile_pos, hc[3], hc[0], hc[5], hc[6], g.two ? 0u : hc[7]);
+                g.nb1, g.S, g.nslots, (double)t1 / g.nb1, m1, g.cap1, (double)t2 / g.nslots, m2, g.cap2, s.ntiles, job.tile_pos,
+                hc[KH_SKM_CTL_EXPANDED], hc[KH_SKM_CTL_ERR], hc[KH_SKM_CTL_SPILLED], hc[KH_SKM_CTL_LISTED], g.two ? 0u : hc[KH_SKM_CTL_MULTI]);
     }
-    u8* h_down = s.h_down;
-    u8* wsp = s.d_ws.as<u8>();
-    auto down = [&](const void* d) { return h_down + (static_cast<const u8*>(d) - wsp); };   // the host copy of a workspace field
-    const size_t down_bytes = down(job.cur1) - h_down;
-    HIPCHK(hipMemcpyAsync(h_down, wsp, down_bytes, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    const u64* h_hist = reinterpret_cast<const u64*>(h_down);
-    const u32* h_ctl = reinterpret_cast<const u32*>(down(job.ctl));
-    if (h_ctl[6] && !(h_ctl[0] & (KH_ERR_CAPACITY | KH_ERR_ORDER))) {
-        // overfull slots (skewed input: a minimizer shared by far more k-mers than a hash predicts): the union left
-        // them out; one workgroup each now, and the read-back again — only these slots are done twice, not the call
-        if (h_ctl[5] > SkmStage::spill_cap || h_ctl[6] > SkmStage::big_cap) { c->stat.retries++; return KH_OK; }   // too many: the key-array form
-        c->stat.big_slots += h_ctl[6];
-        c->prof_begin(KC_SKM_BIG);
-        if (g.two) kh_launch_skm2_big(job, in.cs, h_ctl[6], st);
-        else kh_launch_skm_big(job, in.cs, h_ctl[6], st);
-        c->prof_end();
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(h_down, wsp, down_bytes, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-    }
-    const u64* h_inst = reinterpret_cast<const u64*>(down(job.inst));
-    const u64* h_dup = reinterpret_cast<const u64*>(down(job.dup));
-    if (h_ctl[0] & (KH_ERR_CAPACITY | KH_ERR_ORDER)) {
-        c->stat.retries++;
-        return KH_OK;   // a region or a slot overflowed: the key-array form takes over
-    }
-    c->stat.skm_records += h_ctl[2];
+    bool declines = false;
+    KHCHK(s.settle(0, [&](u32 nbig) {
+        c->stat.big_slots += nbig;
+        return timed_launch(c, KC_SKM_BIG, [&] { g.wd->big(job, in.cs, nbig, st); });
+    }, &declines));
+    if (declines) return KH_OK;   // the key-array form takes over
+    c->stat.skm_records += s.h_ctl()[KH_SKM_CTL_RECORDS];
     if (!L.by_group) {
         c->stat.bases += s.bases;
         c->stat.builds += L.nseq;
-        u64 inst = 0, dsum = 0;
-        for (int i = 0; i < L.nseq; ++i) {
-            const u64 d = h_inst[i] - h_dup[i];
-            inst += h_inst[i];
+        u64 isum = 0, dsum = 0;
+        s.per_text([&](int t, u64 inst, u64 d) {
+            isum += inst;
             dsum += d;
-            if (distinct_per_seq) distinct_per_seq[L.perm[i]] = d;
-        }
-        c->stat.kmers += inst;
+            if (distinct_per_seq) distinct_per_seq[t] = d;
+        });
+        c->stat.kmers += isum;
         c->stat.distinct += dsum;
         c->stat.setop_in += dsum;
     }
     c->stat.setops++;
     std::vector<u64> bins(L.nbins, 0);
-    L.add_bins(bins, h_hist, job.reps);
+    L.add_bins(bins, s.h_hist(), job.reps);
     L.fold(c, bins, within_hist, across_hist, in.hist_len);
     *done = true;
     return KH_OK;
 }
+// ------------------------------------------------------------------------------ exchange form of steps 7-8
+// Multi-GPU (khoice_amd/dist.py): every rank turns its genomes into records tagged with the LOCAL group number,
+// merges identical ones and packs them by the rank that owns their slot (kh_skm_pack); the packed arrays travel
+// (all-to-all); the owner runs ONE phased union over the pieces it received (kh_skm_phased_histogram) and the small
+// histograms are all-reduced.  Slot geometry must be the same on all ranks: kh_skm_exchange_plan works it out from
+// numbers the ranks have agreed on (the largest rank's k-mer positions, the largest group).
+static bool skm_exchange_k(int k) { return k >= KH_SKM_MIN_K && k <= KH_SKM_MAX_K; }
+
+// slots for `nparts` pieces of at most positions_max k-mer positions each; false: too many k-mers per piece
+static bool skm_exchange_geometry(int k, uint64_t positions_max, int nparts, u32 fan, u64* nslots, double* per_kmer_out,
+                                  double eff_parts = 0.0 /* pieces that share most k-mers count as fewer; 0: nparts */) {
+    const int m = skm_minimizer_len(k);
+    const u32 w = (u32)(k - m + 1);
+    const double per_kmer = skm_per_kmer(w);
+    // k-mer instances per slot and rank.  The owner's table (4096 entries) takes ~3000 instances per round: with
+    // groups of related genomes about 0.55 of a rank's instances survive the merge of identical records, so
+    // 2600 / (0.55 x nparts) per rank keeps the owner at one round (unrelated genomes: two).  A rank's slot must also
+    // fit the pack kernel's 1024 records, and the two partition levels give 512 x 512 slots at most (beyond: the
+    // slots grow and the owner takes more rounds).
+    // The regions of a rank's slots are sized as exp1_skm sizes them (skm_region_slack): they must stay below the pack
+    // kernel's 1024 records.
+    const double clump = skm_clump(w, std::max<u32>(1, fan));
+    auto region = [&](double mean) { return mean * per_kmer * skm_region_slack(clump, mean) + 128.0; };
+    if (eff_parts <= 0.0) eff_parts = (double)nparts;
+    double mean = std::min(2600.0 / (0.55 * eff_parts), (1024.0 - 128.0) / (1.7 * per_kmer));
+    while (mean > 64.0 && region(mean) > 1008.0) mean *= 0.95;
+    if (const char* e = getenv("KHOICE_SKM_EXCHANGE_MEAN")) mean = std::max(16.0, atof(e));   // tests: rounds on the owner
+    u64 ns = std::max<u64>((u64)nparts, (u64)((double)std::max<u64>(1, positions_max) / mean) + 1);
+    ns = std::min<u64>(ns, (u64)KH_SKM2_MAX_COARSE * KH_SKM_MAX_FINE);
+    if (region((double)positions_max / (double)ns) > 1024.0) return false;
+    *nslots = ns;
+    *per_kmer_out = per_kmer;
+    return true;
+}
+extern "C" int kh_skm_exchange_plan(kh_ctx* c, int k, uint64_t positions_max, uint32_t fan_max, int nparts, uint32_t* nslots,
+                                    uint32_t* slots_per_part, uint64_t* part_cap) {
+    if (!c || !nslots || !slots_per_part || !part_cap || nparts < 1) return kh_fail(KH_E_ARG, "kh_skm_exchange_plan: bad argument");
+    if (!skm_exchange_k(k)) return kh_fail(KH_E_ARG, "the exchange form takes k = %d .. %d", KH_SKM_MIN_K, KH_SKM_MAX_K);
+    u64 ns = 0;
+    double per_kmer = 0;
+    if (!skm_exchange_geometry(k, positions_max, nparts, fan_max, &ns, &per_kmer))
+        return kh_fail(KH_E_CAPACITY, "too many k-mers per rank for the exchange form (%llu positions)", (unsigned long long)positions_max);
+    *nslots = (u32)ns;
+    *slots_per_part = (u32)((ns + nparts - 1) / nparts);
+    *part_cap = skm_part_cap(positions_max, per_kmer, nparts);
+    return KH_OK;
+}
+
+// The one-GPU use of kh_skm_pack (a group of more than 64 genomes in sub-batches, exp1_big_group_skm): the tags are
+// genomes of ONE group, whose copies of a locus arrive together.
+struct SkmPackLocal {
+    std::vector<u64> inst;   // out: k-mer instances per sequence, in the caller's order
+    u64 dup[32] = {};        // out: instances whose (k-mer, tag) pair was seen before
+    Tmp spill;               // out: records that did not fit their slot's region: [SkmRun::spill_cap] records, then as many u32 slots
+    u32 spill_n = 0;
+    bool done = false;       // what does not fit: false instead of an error
+};
+// The records by slot, (a) + (b) with the slots all ranks agreed on, packed by the part that owns their slot
+static int skm_pack_impl(kh_ctx* c, int nseq, const uint8_t* const* seqs, const uint64_t* lens, int on_device,
+                         const int* tag_of, int k, uint32_t nslots, int nparts, uint64_t part_cap, void* rec_out,
+                         uint32_t* mask_out, uint32_t* count_out, uint32_t* off_out, uint64_t* part_n, SkmPackLocal* loc) {
+    if (loc) loc->done = false;
+    if (!c || nseq < 0 || (nseq && (!seqs || !lens || !tag_of)) || nparts < 1 || !nslots || !rec_out || !mask_out || !count_out ||
+        !off_out || !part_n)
+        return kh_fail(KH_E_ARG, "kh_skm_pack: bad argument");
+    if (!skm_exchange_k(k)) return kh_fail(KH_E_ARG, "the exchange form takes k = %d .. %d", KH_SKM_MIN_K, KH_SKM_MAX_K);
+    int ntags = 0;
+    for (int i = 0; i < nseq; ++i) {
+        if (tag_of[i] < 0 || tag_of[i] >= 32) return kh_fail(KH_E_ARG, "kh_skm_pack: tag %d outside 0..31", tag_of[i]);
+        ntags = std::max(ntags, tag_of[i] + 1);
+    }
+    HIPCHK(hipSetDevice(c->dev));
+    hipStream_t st = c->st;
+    {   // every tag needs a sequence for the geometry code (groups without genomes are refused there): tags are dense here
+        std::vector<int> seen(ntags, 0);
+        for (int i = 0; i < nseq; ++i) seen[tag_of[i]] = 1;
+        for (int t = 0; t < ntags; ++t)
+            if (!seen[t]) return kh_fail(KH_E_ARG, "kh_skm_pack: tag %d has no sequence", t);
+    }
+    const u32 spp = (nslots + (u32)nparts - 1) / (u32)nparts;
+    if (!loc && !kmer_positions(nseq, lens, k)) {
+        // a rank without k-mers (no sequences, or all shorter than k) still sends its parts: all empty
+        HIPCHK(hipMemsetAsync(count_out, 0, 4 * (size_t)spp * nparts, st));
+        HIPCHK(hipMemsetAsync(off_out, 0, 4 * (size_t)spp * nparts, st));
+        HIPCHK(hipStreamSynchronize(st));
+        for (int p = 0; p < nparts; ++p) part_n[p] = 0;
+        return KH_OK;
+    }
+    SkmRun s(c);
+    KHCHK(skm_prepare(c, nseq, seqs, lens, on_device, tag_of, ntags, k, /*by_group=*/true, nslots, loc ? (u32)nseq : 0u, &s));
+    u32 spilled = 0;
+    if (s.staged) {
+        HIPCHK(hipGetLastError());
+        KHCHK(s.read_back(s.off.ctl));   // the control words and the instances per sequence
+        const u32* h_ctl = s.h_ctl();
+        spilled = h_ctl[KH_SKM_CTL_SPILLED];
+        if (getenv("KHOICE_SKM_DEBUG"))
+            fprintf(stderr, "[skm records] k=%d positions=%llu nb1=%u S=%u nslots=%u cap1 %u cap2 %u | records %u errors %u spilled %u\n", k,
+                    (unsigned long long)s.g.positions, s.g.nb1, s.g.S, s.g.nslots, s.g.cap1, s.g.cap2, h_ctl[KH_SKM_CTL_RECORDS],
+                    h_ctl[KH_SKM_CTL_ERR], spilled);
+        // (records on the side list: handed out to a caller that asked for them, a failure otherwise)
+        if (s.failed() || (spilled && (!loc || s.g.two || spilled > SkmRun::spill_cap))) {
+            c->stat.retries++;
+            s.staged = false;
+        }
+    }
+    if (!s.staged) {
+        if (loc) return KH_OK;
+        return kh_fail(KH_E_CAPACITY, "kh_skm_pack: the records did not fit their regions (low-complexity input?)");
+    }
+    if (spilled) {
+        loc->spill.b = s.d_spill.b; s.d_spill.b = nullptr;
+        loc->spill_n = spilled;
+    }
+    c->stat.skm_records += s.h_ctl()[KH_SKM_CTL_RECORDS];
+    if (loc) {
+        loc->inst.assign(nseq, 0);
+        s.per_text([&](int t, u64 inst, u64) { loc->inst[t] = inst; });
+    }
+    for (Tmp* t : {&s.texts.d_seq, &s.d_reg1, &s.d_spill}) { buf_unref(t->b); t->b = nullptr; }   // from here on: the records by slot
+    Tmp d_ctl;
+    u32 nsub = loc ? 64u : 1u;   // (the one-GPU use: 64 cursors into its one part, which does not travel)
+    // The caller wants every part without gaps (it travels): packed through 64 cursors into a buffer of our own and
+    // moved together afterwards — one cursor per part is a queue of returning atomics (78 K slots: 0.8 ms).
+    const bool compact = nsub == 1 && spp >= 2048;
+    if (compact) nsub = 64;
+    // the pack's control block: [KH_SKM_XCTL_CURSORS u32][cursors: nparts x nsub u32][part_n: nparts u32][dup: 32 u64]
+    const size_t off_cursors = 4 * (size_t)KH_SKM_XCTL_CURSORS, off_part_n = (off_cursors + 4 * (size_t)nparts * nsub + 7) & ~(size_t)7,
+                 off_dup = off_part_n + ((4 * (size_t)nparts + 7) & ~(size_t)7), ctl_bytes = off_dup + 8 * 32;
+    Tmp d_tmp;
+    if (compact) TMP_ALLOC(d_tmp, c, (size_t)nparts * part_cap * 20);
+    TMP_ALLOC(d_ctl, c, ctl_bytes);
+    HIPCHK(hipMemsetAsync(d_ctl.b->p, 0, ctl_bytes, st));
+    HIPCHK(hipMemsetAsync(count_out, 0, 4 * (size_t)spp * nparts, st));   // (slots past the last one: nothing)
+    HIPCHK(hipMemsetAsync(off_out, 0, 4 * (size_t)spp * nparts, st));
+    KhSkmPackJob job;
+    job.reg2 = s.d_reg2.as<uint4>();
+    job.cur2 = s.job.cur2;
+    job.out_rec = compact ? d_tmp.as<uint4>() : static_cast<uint4*>(rec_out);
+    job.out_mask = compact ? reinterpret_cast<u32*>(d_tmp.as<u8>() + 16 * (size_t)nparts * part_cap) : mask_out;
+    job.part_cursor = d_ctl.as<u32>() + KH_SKM_XCTL_CURSORS;
+    job.slot_count = count_out;
+    job.slot_off = off_out;
+    job.ctl = d_ctl.as<u32>();
+    job.dup = loc ? reinterpret_cast<unsigned long long*>(d_ctl.as<u8>() + off_dup) : nullptr;
+    job.part_cap = part_cap;
+    job.cap2 = s.g.cap2;
+    job.nslots = s.g.nslots;
+    job.spp = spp;
+    job.nsub = nsub;
+    c->prof_begin(KC_SKM_PACK);
+    kh_launch_skm_pack(job, st);
+    if (compact) {
+        KhSkmCompactJob cj;
+        cj.tmp_rec = job.out_rec;
+        cj.tmp_mask = job.out_mask;
+        cj.out_rec = static_cast<uint4*>(rec_out);
+        cj.out_mask = mask_out;
+        cj.cursors = job.part_cursor;
+        cj.slot_off = off_out;
+        cj.part_n = reinterpret_cast<u32*>(d_ctl.as<u8>() + off_part_n);
+        cj.part_cap = part_cap;
+        cj.nslots = s.g.nslots;
+        cj.spp = spp;
+        cj.nsub = nsub;
+        cj.nparts = (u32)nparts;
+        kh_launch_skm_pack_compact(cj, st);
+    }
+    c->prof_end();
+    HIPCHK(hipGetLastError());
+    std::vector<u32> h(ctl_bytes / 4);
+    HIPCHK(hipMemcpyAsync(h.data(), d_ctl.b->p, ctl_bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (h[KH_SKM_XCTL_ERR] & KH_ERR_ORDER) return kh_fail(KH_E_INTERNAL, "kh_skm_pack: a record carried a tag above 31");
+    if (h[KH_SKM_XCTL_ERR] & KH_ERR_CAPACITY) {
+        if (loc) return KH_OK;
+        return kh_fail(KH_E_CAPACITY, "kh_skm_pack: a slot or a part overflowed");
+    }
+    for (int p = 0; p < nparts; ++p) {   // (with several cursors per part: the records, which then lie with gaps)
+        part_n[p] = 0;
+        for (u32 q = 0; q < nsub; ++q) part_n[p] += h[KH_SKM_XCTL_CURSORS + (size_t)p * nsub + q];
+    }
+    if (loc) {
+        memcpy(loc->dup, reinterpret_cast<const u8*>(h.data()) + off_dup, 8 * 32);
+        loc->done = true;
+    }
+    return KH_OK;
+}
+extern "C" int kh_skm_pack(kh_ctx* c, int nseq, const uint8_t* const* seqs, const uint64_t* lens, int on_device,
+                           const int* tag_of, int k, uint32_t nslots, int nparts, uint64_t part_cap, void* rec_out,
+                           uint32_t* mask_out, uint32_t* count_out, uint32_t* off_out, uint64_t* part_n) {
+    return skm_pack_impl(c, nseq, seqs, lens, on_device, tag_of, k, nslots, nparts, part_cap, rec_out, mask_out, count_out, off_out,
+                         part_n, nullptr);
+}
+
+// The one-GPU use of kh_skm_phased_histogram (exp1_big_group_skm): the pieces are the phases of one group.
+struct SkmPhases {
+    std::vector<u32> row, join;   // per piece: its phase (the row of `dup` it counts into), "the next piece goes on in the same phase"
+    u32 share_q8 = 256;           // share of a piece's instances that are new to its phase, x 256
+    std::vector<u64> dup;         // out [pieces][32]: repeats under one tag
+    bool done = false;            // an overfilled table: false instead of an error
+};
+static int skm_phased_impl(kh_ctx* c, int k, int npieces, const void* const* recs, const uint32_t* const* masks,
+                           const uint32_t* const* counts, const uint32_t* const* offs, uint32_t nslots, uint32_t cs,
+                           uint64_t* hist, uint32_t hist_len, SkmPhases* ph) {
+    if (ph) ph->done = false;
+    if (!c || npieces < 1 || !recs || !masks || !counts || !offs || !hist || hist_len < 2 || cs < 1)
+        return kh_fail(KH_E_ARG, "kh_skm_phased_histogram: bad argument");
+    if (!skm_exchange_k(k)) return kh_fail(KH_E_ARG, "the exchange form takes k = %d .. %d", KH_SKM_MIN_K, KH_SKM_MAX_K);
+    HIPCHK(hipSetDevice(c->dev));
+    hipStream_t st = c->st;
+    const size_t off_pieces = 64, off_hist = (off_pieces + sizeof(KhSkmPiece) * (size_t)npieces + 63) & ~(size_t)63;
+    const size_t off_pdup = off_hist + 8 * (size_t)hist_len, ws_bytes = off_pdup + (ph ? 8 * 32 * (size_t)npieces : 0);
+    Tmp d_ws;
+    TMP_ALLOC(d_ws, c, ws_bytes);
+    std::vector<u8> up(off_hist, 0);
+    KhSkmPiece* hp = reinterpret_cast<KhSkmPiece*>(up.data() + off_pieces);
+    for (int i = 0; i < npieces; ++i) {
+        hp[i].rec = static_cast<const uint4*>(recs[i]);
+        hp[i].mask = masks[i];
+        hp[i].count = counts[i];
+        hp[i].off = offs[i];
+        hp[i].dup_row = ph ? ph->row[i] : (u32)i;
+        hp[i].join_next = ph ? ph->join[i] : 0u;
+    }
+    HIPCHK(hipMemsetAsync(d_ws.b->p, 0, ws_bytes, st));
+    HIPCHK(hipMemcpyAsync(d_ws.b->p, up.data(), off_hist, hipMemcpyHostToDevice, st));
+    KhSkmPhasedJob job;
+    job.pieces = reinterpret_cast<const KhSkmPiece*>(d_ws.as<u8>() + off_pieces);
+    job.hist = reinterpret_cast<unsigned long long*>(d_ws.as<u8>() + off_hist);
+    job.ctl = d_ws.as<u32>();
+    job.dup = ph ? reinterpret_cast<unsigned long long*>(d_ws.as<u8>() + off_pdup) : nullptr;
+    job.npieces = (u32)npieces;
+    job.share_q8 = std::min<u32>(256, std::max<u32>(1, ph ? ph->share_q8 : 256u));
+    job.nslots = nslots;
+    job.hist_len = hist_len;
+    job.cs = cs;
+    job.k = k;
+    c->prof_begin(KC_SKM_PHASED);
+    kh_launch_skm_phased(job, std::min<u32>(std::max<u32>(1, nslots), 2u * (u32)std::max(1, c->cus)), st);
+    c->prof_end();
+    HIPCHK(hipGetLastError());
+    u32 h_ctl[4];
+    HIPCHK(hipMemcpyAsync(h_ctl, d_ws.b->p, 16, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(hist, d_ws.as<u8>() + off_hist, 8 * (size_t)hist_len, hipMemcpyDeviceToHost, st));
+    if (ph) {
+        ph->dup.assign(32 * (size_t)npieces, 0);
+        HIPCHK(hipMemcpyAsync(ph->dup.data(), d_ws.as<u8>() + off_pdup, 8 * 32 * (size_t)npieces, hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    if (h_ctl[KH_SKM_XCTL_ERR] & KH_ERR_CAPACITY) {
+        if (ph) return KH_OK;
+        return kh_fail(KH_E_CAPACITY, "kh_skm_phased_histogram: a slot held more k-mers than its table");
+    }
+    c->stat.setops++;
+    if (ph) ph->done = true;
+    return KH_OK;
+}
+extern "C" int kh_skm_phased_histogram(kh_ctx* c, int k, int npieces, const void* const* recs, const uint32_t* const* masks,
+                                       const uint32_t* const* counts, const uint32_t* const* offs, uint32_t nslots, uint32_t cs,
+                                       uint64_t* hist, uint32_t hist_len) {
+    return skm_phased_impl(c, k, npieces, recs, masks, counts, offs, nslots, cs, hist, hist_len, nullptr);
+}
+
+// One group of more than 64 genomes in the super-k-mer form (one-word keys): sub-batches of up to 32 genomes, each
+// turned into records tagged with the genome's number in the sub-batch, identical records merged (k_skm_pack, one
+// part); the sub-batches are the PHASES of one phased union (k_skm_phased): the counter of an entry ends as "in how
+// many genomes of the group", which is the group's step_4 histogram.  Distinct k-mers of a genome: its instances minus
+// the repeats under its tag (whole records at the merge, single k-mers at the insertion).  *done == false: the
+// caller takes the key-array sub-batches.
+static int exp1_big_group_skm(kh_ctx* c, int n, const uint8_t* const* seqs, const uint64_t* lens, int on_device, int k, u32 cs,
+                              uint64_t* whist, u32 hist_len, uint64_t* dist /* [n] or null */, bool* done) {
+    *done = false;
+    if (!skm_exchange_k(k) || getenv("KHOICE_NO_SKM") || getenv("KHOICE_NO_SKM_PHASED") || !whist) return KH_OK;
+    constexpr int SUB = 32;
+    const int P = (n + SUB - 1) / SUB;
+    if (P > (int)KH_SKM_PHASED_MAX_DUP_PIECES) return KH_OK;
+    std::vector<int> first(P + 1, 0);
+    for (int p = 0; p < P; ++p) first[p + 1] = first[p] + (n - first[p] + (P - p) - 1) / (P - p);   // balanced sizes
+    u64 pos_max = 0;
+    std::vector<u64> pos(P, 0);
+    for (int p = 0; p < P; ++p) {
+        pos[p] = kmer_positions(first[p + 1] - first[p], lens + first[p], k);
+        pos_max = std::max(pos_max, pos[p]);
+    }
+    if (!pos_max) return KH_OK;
+    u64 ns = 0;
+    double per_kmer = 0;
+    const bool dbg = getenv("KHOICE_SKM_DEBUG") != nullptr;
+    // How much the sub-batches of a group share decides how large a slot may be: its table holds one sub-batch's k-mers
+    // plus what each further one adds (`novelty` of its own).  Measured: the synthetic genomes (1 % divergence from one
+    // ancestor, independent per genome) add 0.7 — with 0.3 assumed a table overfilled and the repeated launch cost more
+    // than the 2.5 x larger slots saved (12.1 -> 14.0 ms) — so the default assumes unrelated sub-batches (1.0); real
+    // collections with a tree-like history share more: KHOICE_SKM_PHASED_NOVELTY (an overfilled table is caught and the
+    // launch repeated with rounds sized for unrelated pieces).
+    double novelty = 1.0;
+    if (const char* e = getenv("KHOICE_SKM_PHASED_NOVELTY")) novelty = std::min(1.0, std::max(0.05, atof(e)));
+    const double eff_parts = 1.0 + novelty * (double)(P - 1);
+    const u32 share_q8 = (u32)std::min(256.0, std::ceil(256.0 * eff_parts / (double)P));
+    if (!skm_exchange_geometry(k, pos_max, P, (u32)SUB, &ns, &per_kmer, eff_parts)) {
+        if (dbg) fprintf(stderr, "[skm phased] %d genomes in %d phases: no geometry for %llu positions per phase\n", n, P, (unsigned long long)pos_max);
+        return KH_OK;
+    }
+    const u32 nslots = (u32)ns;
+    if (dbg) fprintf(stderr, "[skm phased] %d genomes in %d phases, %u slots, %.0f positions per slot and phase\n", n, P, nslots, (double)pos_max / nslots);
+    HIPCHK(hipSetDevice(c->dev));
+    std::vector<std::unique_ptr<Tmp>> bufs;
+    std::vector<const void*> recs;
+    std::vector<const uint32_t*> masks, counts, offs;
+    SkmPhases ph;
+    auto add_piece = [&](const u8* b, size_t off_mask, size_t off_count, size_t off_off, u32 row, u32 join) {
+        recs.push_back(b);
+        masks.push_back(reinterpret_cast<const u32*>(b + off_mask));
+        counts.push_back(reinterpret_cast<const u32*>(b + off_count));
+        offs.push_back(reinterpret_cast<const u32*>(b + off_off));
+        ph.row.push_back(row);
+        ph.join.push_back(join);
+    };
+    std::vector<u64> inst_all(n, 0), dup_all(n, 0);
+    hipStream_t st = c->st;
+    for (int p = 0; p < P; ++p) {
+        const int m = first[p + 1] - first[p];
+        const u64 cap = skm_part_cap(pos[p], per_kmer, 1);
+        const size_t off_mask = 16 * (size_t)cap, off_count = off_mask + 4 * (size_t)cap, off_off = off_count + 4 * (size_t)((nslots + 3) & ~3u),
+                     bytes = off_off + 4 * (size_t)((nslots + 3) & ~3u);
+        bufs.emplace_back(new Tmp);
+        TMP_ALLOC(*bufs.back(), c, bytes);
+        u8* base = bufs.back()->as<u8>();
+        std::vector<int> tag(m);
+        for (int j = 0; j < m; ++j) tag[j] = j;
+        u64 part_n = 0;
+        SkmPackLocal loc;
+        KHCHK(skm_pack_impl(c, m, seqs + first[p], lens + first[p], on_device, tag.data(), k, nslots, 1, cap, base,
+                            reinterpret_cast<u32*>(base + off_mask), reinterpret_cast<u32*>(base + off_count),
+                            reinterpret_cast<u32*>(base + off_off), &part_n, &loc));
+        if (!loc.done) {
+            if (dbg) fprintf(stderr, "[skm phased] phase %d: the records did not fit\n", p);
+            return KH_OK;
+        }
+        if (dbg) fprintf(stderr, "[skm phased] phase %d: %llu records travel (cap %llu), %u on the side list\n", p, (unsigned long long)part_n,
+                         (unsigned long long)cap, loc.spill_n);
+        add_piece(base, off_mask, off_count, off_off, (u32)p, 0);
+        for (int j = 0; j < m; ++j) { inst_all[first[p] + j] = loc.inst[j]; dup_all[first[p] + j] = loc.dup[j]; }
+        if (loc.spill_n) {
+            // Overfull slots (low-complexity sequence): what the regions could not hold is on the side list, unmerged and
+            // in no order.  It joins the sub-batch's phase as extra pieces — sorted by slot on the host (rare, small),
+            // at most 1024 records of a slot per piece.
+            const u32 ns = loc.spill_n;
+            std::vector<uint4> hrec(ns);
+            std::vector<u32> hslot(ns), order(ns);
+            HIPCHK(hipMemcpyAsync(hrec.data(), loc.spill.b->p, 16 * (size_t)ns, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpyAsync(hslot.data(), static_cast<const u8*>(loc.spill.b->p) + 16 * (size_t)SkmRun::spill_cap, 4 * (size_t)ns,
+                                  hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            for (u32 i = 0; i < ns; ++i) {
+                order[i] = i;
+                if (hslot[i] >= nslots) return kh_fail(KH_E_INTERNAL, "side list: slot %u of %u", hslot[i], nslots);
+            }
+            std::stable_sort(order.begin(), order.end(), [&](u32 a, u32 b) { return hslot[a] < hslot[b]; });
+            std::vector<u32> run(nslots, 0);
+            u32 longest = 0;
+            for (u32 i = 0; i < ns; ++i) longest = std::max(longest, ++run[hslot[i]]);
+            const u32 extra = (longest + 1023u) / 1024u;
+            ph.join.back() = 1;
+            for (u32 e = 0; e < extra; ++e) {
+                std::vector<uint4> prec;
+                std::vector<u32> pmask, pcount(nslots, 0), poff(nslots, 0);
+                for (u32 i = 0; i < ns;) {   // the sorted list, a slot's run at a time
+                    const u32 sl = hslot[order[i]], len = run[sl];
+                    const u32 lo = std::min(len, e * 1024u), hi = std::min(len, (e + 1) * 1024u);
+                    poff[sl] = (u32)prec.size();
+                    pcount[sl] = hi - lo;
+                    for (u32 j = lo; j < hi; ++j) {
+                        const uint4 r = hrec[order[i + j]];
+                        prec.push_back(r);
+                        pmask.push_back(1u << (SkmRec1::tag(r.w) & 31u));   // (tags of the exchange form are below 32)
+                    }
+                    i += len;
+                }
+                const size_t nrec_e = std::max<size_t>(1, prec.size());
+                const size_t e_mask = 16 * nrec_e, e_count = e_mask + ((4 * nrec_e + 15) & ~(size_t)15), e_off = e_count + 4 * (size_t)((nslots + 3) & ~3u),
+                             e_bytes = e_off + 4 * (size_t)((nslots + 3) & ~3u);
+                bufs.emplace_back(new Tmp);
+                TMP_ALLOC(*bufs.back(), c, e_bytes);
+                u8* eb = bufs.back()->as<u8>();
+                if (!prec.empty()) {
+                    HIPCHK(hipMemcpyAsync(eb, prec.data(), 16 * prec.size(), hipMemcpyHostToDevice, st));
+                    HIPCHK(hipMemcpyAsync(eb + e_mask, pmask.data(), 4 * pmask.size(), hipMemcpyHostToDevice, st));
+                }
+                HIPCHK(hipMemcpyAsync(eb + e_count, pcount.data(), 4 * (size_t)nslots, hipMemcpyHostToDevice, st));
+                HIPCHK(hipMemcpyAsync(eb + e_off, poff.data(), 4 * (size_t)nslots, hipMemcpyHostToDevice, st));
+                HIPCHK(hipStreamSynchronize(st));   // (the host vectors go out of scope)
+                add_piece(eb, e_mask, e_count, e_off, (u32)p, e + 1 < extra ? 1u : 0u);
+            }
+            c->stat.big_slots += (u64)std::count_if(run.begin(), run.end(), [](u32 v) { return v != 0; });
+        }
+    }
+    std::vector<u64> hist(hist_len, 0);
+    ph.share_q8 = share_q8;
+    KHCHK(skm_phased_impl(c, k, (int)recs.size(), recs.data(), masks.data(), counts.data(), offs.data(), nslots, cs, hist.data(), hist_len, &ph));
+    if (!ph.done && share_q8 < 256) {   // a table overfilled: the genomes share less than assumed — rounds for unrelated pieces
+        if (dbg) fprintf(stderr, "[skm phased] a table overfilled with rounds sized for shared k-mers: once more\n");
+        c->stat.retries++;
+        ph.share_q8 = 256;
+        KHCHK(skm_phased_impl(c, k, (int)recs.size(), recs.data(), masks.data(), counts.data(), offs.data(), nslots, cs, hist.data(), hist_len, &ph));
+    }
+    if (!ph.done) {
+        if (dbg) fprintf(stderr, "[skm phased] the phased union overflowed\n");
+        return KH_OK;
+    }
+    memcpy(whist, hist.data(), 8 * (size_t)hist_len);
+    u64 bases = 0, isum = 0, dsum = 0;
+    for (int p = 0; p < P; ++p)
+        for (int i = first[p]; i < first[p + 1]; ++i) {
+            const u64 d = inst_all[i] - dup_all[i] - ph.dup[(size_t)p * 32 + (i - first[p])];
+            if (dist) dist[i] = d;
+            bases += lens[i]; isum += inst_all[i]; dsum += d;
+        }
+    c->stat.bases += bases;
+    c->stat.builds += n;
+    c->stat.kmers += isum;
+    c->stat.distinct += dsum;
+    c->stat.setop_in += dsum;
+    *done = true;
+    return KH_OK;
+}
+
 // What the presence-bitmap forms (exp1_bmp .. exp4_bmp) share: the switches, the geometry of the build, the tables of
 // splits and operands, the copy-in of the texts, and the run that strings them together (BmpRun).
 static bool bmp_form_k(int k) {
@@ -2089,16 +2551,12 @@ struct BmpStage {
     u64 nwords = 0, nsplits = 0, bases = 0;
     u32 range_bits = 0, nranges = 0, tile_pos = 0;
     u32 rwaves = 0, rgrid = 0;            // launch shape of the read-out
-    std::vector<KhBmpSplit> splits;       // (seq: filled in by bmp_copy_in)
+    std::vector<KhBmpSplit> splits;       // (seq: filled in by BmpRun::upload)
     std::vector<KhBmpOp> ops;
-    std::vector<u64> pack_off;            // where an operand's text goes in the packed copy
-    u64 seq_bytes = 0;
-    bool need_pack = false;
 };
 // nops operands (seqs / lens in operand order).  extra_rows: further bitmaps of nwords words the caller keeps beside
 // the partial ones, under the same budget.  *fits == false: the form declines.
-static int bmp_plan(kh_ctx* c, int k, int nops, const uint8_t* const* seqs, const uint64_t* lens, int on_device,
-                    u64 extra_rows, BmpStage* s, bool* fits) {
+static int bmp_plan(kh_ctx* c, int k, int nops, const uint64_t* lens, u64 extra_rows, BmpStage* s, bool* fits) {
     *fits = false;
     // ---- geometry: ranges of the code space, tiles, splits
     const u64 nwords = k >= 3 ? 1ull << (2 * k - 6) : 1;
@@ -2151,13 +2609,9 @@ static int bmp_plan(kh_ctx* c, int k, int nops, const uint8_t* const* seqs, cons
     s->nwords = nwords; s->nsplits = nsplits; s->bases = bases;
     s->range_bits = range_bits; s->nranges = nranges; s->tile_pos = tile_pos;
     s->ops.resize(nops);
-    s->pack_off.resize(nops);
     s->splits.reserve(nsplits);
     for (int i = 0; i < nops; ++i) {
         const u64 len = lens[i], npos = len >= (u64)k ? len - k + 1 : 0;
-        s->pack_off[i] = s->seq_bytes;
-        s->seq_bytes += (len + 15) & ~15ull;
-        if (!(on_device && (reinterpret_cast<uintptr_t>(seqs[i]) & 15) == 0)) s->need_pack = true;
         s->ops[i].split0 = (u32)s->splits.size();
         u64 p0 = 0;
         do {
@@ -2167,37 +2621,12 @@ static int bmp_plan(kh_ctx* c, int k, int nops, const uint8_t* const* seqs, cons
         } while (p0 < npos);
         s->ops[i].nsplits = (u32)s->splits.size() - s->ops[i].split0;
     }
-    s->seq_bytes += 256;
     // the read-out: a wave per 64 words and genome; where the words alone leave most of the chip idle (k <= 10: at
     // most 256 blocks of 64 words) sixteen genomes are in flight per block, else four
     const u64 rblocks = (nwords + 63) / 64;
     s->rwaves = rblocks <= 256 ? 16u : 4u;
     s->rgrid = (u32)std::min<u64>(rblocks, 8ull * (u64)std::max(1, c->cus));
     *fits = true;
-    return KH_OK;
-}
-// the texts that are not resident and aligned go into d_seq (s->seq_bytes, where s->need_pack); every split learns its text
-static int bmp_copy_in(kh_ctx* c, BmpStage* s, const uint8_t* const* seqs, const uint64_t* lens, int on_device, u8* d_seq) {
-    for (size_t i = 0; i < s->ops.size(); ++i) {
-        const uint8_t* src = seqs[i];
-        const u8* dev = src;
-        if (!(on_device && (reinterpret_cast<uintptr_t>(src) & 15) == 0)) {
-            dev = d_seq + s->pack_off[i];
-            if (lens[i]) {
-                HIPCHK(hipMemcpyAsync(d_seq + s->pack_off[i], src, lens[i], on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->st));
-                c->stat.text_packed += lens[i];
-            }
-        }
-        for (u32 j = 0; j < s->ops[i].nsplits; ++j) s->splits[s->ops[i].split0 + j].seq = dev;
-    }
-    return KH_OK;
-}
-// a launch under its profiling class, and the error it may have left
-template <class F> static int timed_launch(kh_ctx* c, int cls, F launch) {
-    c->prof_begin(cls);
-    launch();
-    c->prof_end();
-    HIPCHK(hipGetLastError());
     return KH_OK;
 }
 // The operands of a bitmap run: the genomes in group-major order (within a group in the caller's order), then the
@@ -2261,7 +2690,8 @@ struct BmpRun {
     size_t hist_stride = 0, off_inst = 0, off_splits = 0, off_ops = 0, ws_bytes = 0;
     struct Table { size_t off; const void* src; size_t bytes; };
     std::vector<Table> tables;
-    Tmp d_seq, d_ws, d_partial;
+    TextStage texts;
+    Tmp d_ws, d_partial;
     Pinned pin;
     u8 *h_up = nullptr, *h_down = nullptr;
 
@@ -2269,7 +2699,7 @@ struct BmpRun {
     int nops() const { return (int)o.seq.size(); }
     static u32 reps_max(u32 nb) { return std::max<u32>(1, std::min<u32>(64, 65536u / nb)); }
     // *fits == false: the form declines
-    int plan(u64 extra_rows, bool* fits) { return bmp_plan(c, k, nops(), o.seq.data(), o.len.data(), on_device, extra_rows, &s, fits); }
+    int plan(u64 extra_rows, bool* fits) { return bmp_plan(c, k, nops(), o.len.data(), extra_rows, &s, fits); }
     void layout(u32 blocks, u32 nb_of_block) {
         nb = nb_of_block;
         reps = std::min(s.rgrid, reps_max(nb));
@@ -2288,7 +2718,6 @@ struct BmpRun {
     }
     // the device memory, the texts copied in, the zeroed region zeroed and the tables uploaded; `also` runs among the copies
     template <class F> int upload(F also) {
-        TMP_ALLOC(d_seq, c, s.need_pack ? s.seq_bytes : 256);
         TMP_ALLOC(d_ws, c, ws_bytes);
         TMP_ALLOC(d_partial, c, (size_t)(s.nsplits * s.nwords * 8));
         const size_t up_bytes = ws_bytes - off_splits;
@@ -2296,7 +2725,8 @@ struct BmpRun {
         h_up = static_cast<u8*>(pin.p);
         h_down = h_up + ((up_bytes + 63) & ~(size_t)63);
         c->prof_begin(KC_COPY_IN);
-        KHCHK(bmp_copy_in(c, &s, o.seq.data(), o.len.data(), on_device, d_seq.as<u8>()));
+        KHCHK(texts.copy_in(c, nops(), o.seq.data(), o.len.data(), on_device));
+        for (KhBmpSplit& sp : s.splits) sp.seq = texts.dev[sp.op];   // every split learns its text
         memset(h_up, 0, up_bytes);
         for (const Table& t : tables)
             if (t.bytes) memcpy(h_up + (t.off - off_splits), t.src, t.bytes);
@@ -2708,8 +3138,6 @@ static int exp1_fused_rescaled(kh_ctx* c, const Exp1In& in, SubBatch& b, u32 cs,
     }
     return KH_OK;
 }
-static int exp1_big_group_skm(kh_ctx* c, int n, const uint8_t* const* seqs, const uint64_t* lens, int on_device, int k, u32 cs,
-                              uint64_t* whist, u32 hist_len, uint64_t* dist, bool* done);
 // One group of more than 64 genomes (exp_type_1.smk:36-61 lists whatever data/dataset_N holds): sub-batches of
 // up to 64 genomes, each a fused build + tagged union in which every genome is a group of its own, so that the
 // set a sub-batch emits carries "in how many of its genomes"; one counter-summing union of those sets is the
@@ -3470,8 +3898,7 @@ static int exp3_skm(kh_ctx* c, const Exp3In& in, const Exp3Out& out, bool* done)
     for (int b = 0; b < nbatches; ++b)   // (a pass without a k-mer position has no geometry)
         if (!(gpos + kmer_positions(std::min(batch, npiv - b * batch), in.pivot_lens + (size_t)b * batch, k))) return KH_OK;
     kmer_positions(npiv, in.pivot_lens, k, &pbases);
-    const bool two = k > KH_SKM_MAX_K;
-    const u32 round = two ? kh_skm2_cross_round() : kh_skm_cross_round();
+    const KhSkmWidth& wd = kh_skm_width(k > KH_SKM_MAX_K);
     u32 fan = 1;
     {
         std::vector<u32> gs(ngroups, 0);
@@ -3490,10 +3917,10 @@ static int exp3_skm(kh_ctx* c, const Exp3In& in, const Exp3Out& out, bool* done)
             lens.push_back(in.pivot_lens[p0 + q]);
             group_of.push_back(ngroups + q);
         }
-        SkmStage s(c);
+        SkmRun s(c);
         // fan hint: a pivot's reads bring copies of their locus into the slot of the group they were drawn from — one
         // more than the largest group.  A guess (reads may cover a locus many times); the side list takes what it misses.
-        KHCHK(skm_prepare(c, nops, seqs.data(), lens.data(), in.on_device, group_of.data(), ngroups + np, k, false, 0, fan + 1, &s, round));
+        KHCHK(skm_prepare(c, nops, seqs.data(), lens.data(), in.on_device, group_of.data(), ngroups + np, k, false, 0, fan + 1, &s, wd.cross_round));
         if (!s.staged) {
             if (b) c->stat.retries++;   // (a later pass whose geometry or memory does not fit: work was done for nothing)
             return KH_OK;
@@ -3506,7 +3933,7 @@ static int exp3_skm(kh_ctx* c, const Exp3In& in, const Exp3Out& out, bool* done)
         cj.nbins = (u32)np * (u32)nseq;
         const u64 pm = (np >= 64 ? ~0ull : (1ull << np) - 1ull) << nseq;
         cj.pmlo = (u32)pm; cj.pmhi = (u32)(pm >> 32);
-        const u32 grid = std::min<u32>(s.g.nslots, (two ? kh_skm2_cross_per_cu() : kh_skm_cross_per_cu()) * (u32)std::max(1, c->cus));
+        const u32 grid = std::min<u32>(s.g.nslots, wd.cross_per_cu * (u32)std::max(1, c->cus));
         cj.reps = std::min<u32>(grid, 64);
         const size_t bins_bytes = 8 * (size_t)cj.reps * cj.nbins;
         Tmp d_bins;
@@ -3515,38 +3942,22 @@ static int exp3_skm(kh_ctx* c, const Exp3In& in, const Exp3Out& out, bool* done)
         PIN_ALLOC(pin, bins_bytes);
         cj.bins = d_bins.as<unsigned long long>();
         HIPCHK(hipMemsetAsync(cj.bins, 0, bins_bytes, st));
-        auto launch = [&](u32 g) { if (two) kh_launch_skm2_cross(job, cj, g, st); else kh_launch_skm_cross(job, cj, g, st); };
-        KHCHK(timed_launch(c, KC_SKM_CROSS, [&] { launch(grid); }));
-        // [ctl .. dup] of the workspace, laid out in h_down as on the device
-        u8* wsp = s.d_ws.as<u8>();
-        auto down = [&](const void* d) { return s.h_down + (static_cast<const u8*>(d) - wsp); };
-        const size_t ctl_bytes = reinterpret_cast<const u8*>(job.cur1) - reinterpret_cast<const u8*>(job.ctl);
-        const u32* h_ctl = reinterpret_cast<const u32*>(down(job.ctl));
-        HIPCHK(hipMemcpyAsync(down(job.ctl), job.ctl, ctl_bytes, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        if (h_ctl[6] && !(h_ctl[0] & (KH_ERR_CAPACITY | KH_ERR_ORDER))) {   // overfull slots: the listed launch, and the read-back again
-            if (h_ctl[5] > SkmStage::spill_cap || h_ctl[6] > SkmStage::big_cap) { c->stat.retries++; return KH_OK; }
-            big += h_ctl[6];
-            cj.nlisted = h_ctl[6];
-            KHCHK(timed_launch(c, KC_SKM_CROSS, [&] { launch(cj.nlisted); }));
-            HIPCHK(hipMemcpyAsync(down(job.ctl), job.ctl, ctl_bytes, hipMemcpyDeviceToHost, st));
-        }
+        KHCHK(timed_launch(c, KC_SKM_CROSS, [&] { wd.cross(job, cj, grid, st); }));
+        bool declines = false;
+        KHCHK(s.settle(s.off.ctl, [&](u32 nlisted) {   // ([ctl .. dup] of the workspace; the bins are read back below)
+            big += nlisted;
+            cj.nlisted = nlisted;
+            return timed_launch(c, KC_SKM_CROSS, [&] { wd.cross(job, cj, nlisted, st); });
+        }, &declines));
+        if (declines) return KH_OK;   // the set form takes over
         HIPCHK(hipMemcpyAsync(pin.p, cj.bins, bins_bytes, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
-        if (h_ctl[0] & (KH_ERR_CAPACITY | KH_ERR_ORDER)) {
-            c->stat.retries++;
-            return KH_OK;   // a region, the side list or a table overflowed: the set form takes over
-        }
-        records += h_ctl[2];
-        multi += h_ctl[7];
-        const u64* h_inst = reinterpret_cast<const u64*>(down(job.inst));
-        const u64* h_dup = reinterpret_cast<const u64*>(down(job.dup));
-        for (int i = 0; i < nops; ++i) {   // operand i is text perm[i] of this pass: genomes in group-major order, then its pivots
-            const int t = L.perm[i];
-            const u64 d = h_inst[i] - h_dup[i];
-            if (t >= nseq) { dpiv[p0 + t - nseq] = d; kmers += h_inst[i]; }
-            else if (b == 0) { dseq[t] = d; kmers += h_inst[i]; }
-        }
+        records += s.h_ctl()[KH_SKM_CTL_RECORDS];
+        multi += s.h_ctl()[KH_SKM_CTL_MULTI];
+        s.per_text([&](int t, u64 inst, u64 d) {   // text t of this pass: the genomes, then its pivots
+            if (t >= nseq) { dpiv[p0 + t - nseq] = d; kmers += inst; }
+            else if (b == 0) { dseq[t] = d; kmers += inst; }
+        });
         const u64* h_bins = static_cast<const u64*>(pin.p);
         for (u32 r = 0; r < cj.reps; ++r)
             for (int q = 0; q < np; ++q)
@@ -3623,433 +4034,6 @@ extern "C" int kh_exp3_run(kh_ctx* c, int nseq, const uint8_t* const* seqs, cons
     KHCHK(exp3_skm(c, in, out, &done));   // (KHOICE_EXP3_SKM=1 only)
     if (done) return KH_OK;
     return exp3_sets(c, in, out);
-}
-
-// ------------------------------------------------------------------------------ exchange form of steps 7-8
-// Multi-GPU (khoice_amd/dist.py): every rank turns its genomes into records tagged with the LOCAL group number,
-// merges identical ones and packs them by the rank that owns their slot (kh_skm_pack); the packed arrays travel
-// (all-to-all); the owner runs ONE phased union over the pieces it received (kh_skm_phased_histogram) and the small
-// histograms are all-reduced.  Slot geometry must be the same on all ranks: kh_skm_exchange_plan works it out from
-// numbers the ranks have agreed on (the largest rank's k-mer positions, the largest group).
-static bool skm_exchange_k(int k) { return k >= KH_SKM_MIN_K && k <= KH_SKM_MAX_K; }
-
-// slots for `nparts` pieces of at most positions_max k-mer positions each; false: too many k-mers per piece
-static bool skm_exchange_geometry(int k, uint64_t positions_max, int nparts, u32 fan, u64* nslots, double* per_kmer_out,
-                                  double eff_parts = 0.0 /* pieces that share most k-mers count as fewer; 0: nparts */) {
-    const int m = skm_minimizer_len(k);
-    const u32 w = (u32)(k - m + 1);
-    const double per_kmer = skm_per_kmer(w);
-    // k-mer instances per slot and rank.  The owner's table (4096 entries) takes ~3000 instances per round: with
-    // groups of related genomes about 0.55 of a rank's instances survive the merge of identical records, so
-    // 2600 / (0.55 x nparts) per rank keeps the owner at one round (unrelated genomes: two).  A rank's slot must also
-    // fit the pack kernel's 1024 records, and the two partition levels give 512 x 512 slots at most (beyond: the
-    // slots grow and the owner takes more rounds).
-    // The regions of a rank's slots are sized as exp1_skm sizes them (skm_region_slack): they must stay below the pack
-    // kernel's 1024 records.
-    const double clump = skm_clump(w, std::max<u32>(1, fan));
-    auto region = [&](double mean) { return mean * per_kmer * skm_region_slack(clump, mean) + 128.0; };
-    if (eff_parts <= 0.0) eff_parts = (double)nparts;
-    double mean = std::min(2600.0 / (0.55 * eff_parts), (1024.0 - 128.0) / (1.7 * per_kmer));
-    while (mean > 64.0 && region(mean) > 1008.0) mean *= 0.95;
-    if (const char* e = getenv("KHOICE_SKM_EXCHANGE_MEAN")) mean = std::max(16.0, atof(e));   // tests: rounds on the owner
-    u64 ns = std::max<u64>((u64)nparts, (u64)((double)std::max<u64>(1, positions_max) / mean) + 1);
-    ns = std::min<u64>(ns, (u64)KH_SKM2_MAX_COARSE * KH_SKM_MAX_FINE);
-    if (region((double)positions_max / (double)ns) > 1024.0) return false;
-    *nslots = ns;
-    *per_kmer_out = per_kmer;
-    return true;
-}
-extern "C" int kh_skm_exchange_plan(kh_ctx* c, int k, uint64_t positions_max, uint32_t fan_max, int nparts, uint32_t* nslots,
-                                    uint32_t* slots_per_part, uint64_t* part_cap) {
-    if (!c || !nslots || !slots_per_part || !part_cap || nparts < 1) return kh_fail(KH_E_ARG, "kh_skm_exchange_plan: bad argument");
-    if (!skm_exchange_k(k)) return kh_fail(KH_E_ARG, "the exchange form takes k = %d .. %d", KH_SKM_MIN_K, KH_SKM_MAX_K);
-    u64 ns = 0;
-    double per_kmer = 0;
-    if (!skm_exchange_geometry(k, positions_max, nparts, fan_max, &ns, &per_kmer))
-        return kh_fail(KH_E_CAPACITY, "too many k-mers per rank for the exchange form (%llu positions)", (unsigned long long)positions_max);
-    *nslots = (u32)ns;
-    *slots_per_part = (u32)((ns + nparts - 1) / nparts);
-    *part_cap = skm_part_cap(positions_max, per_kmer, nparts);
-    return KH_OK;
-}
-
-// The one-GPU use of kh_skm_pack (a group of more than 64 genomes in sub-batches, exp1_big_group_skm): the tags are
-// genomes of ONE group, whose copies of a locus arrive together.
-struct SkmPackLocal {
-    std::vector<u64> inst;   // out: k-mer instances per sequence, in the caller's order
-    u64 dup[32] = {};        // out: instances whose (k-mer, tag) pair was seen before
-    Tmp spill;               // out: records that did not fit their slot's region: [SkmStage::spill_cap] records, then as many u32 slots
-    u32 spill_n = 0;
-    bool done = false;       // what does not fit: false instead of an error
-};
-// The records by slot, (a) + (b) with the slots all ranks agreed on, packed by the part that owns their slot
-static int skm_pack_impl(kh_ctx* c, int nseq, const uint8_t* const* seqs, const uint64_t* lens, int on_device,
-                         const int* tag_of, int k, uint32_t nslots, int nparts, uint64_t part_cap, void* rec_out,
-                         uint32_t* mask_out, uint32_t* count_out, uint32_t* off_out, uint64_t* part_n, SkmPackLocal* loc) {
-    if (loc) loc->done = false;
-    if (!c || nseq < 0 || (nseq && (!seqs || !lens || !tag_of)) || nparts < 1 || !nslots || !rec_out || !mask_out || !count_out ||
-        !off_out || !part_n)
-        return kh_fail(KH_E_ARG, "kh_skm_pack: bad argument");
-    if (!skm_exchange_k(k)) return kh_fail(KH_E_ARG, "the exchange form takes k = %d .. %d", KH_SKM_MIN_K, KH_SKM_MAX_K);
-    int ntags = 0;
-    for (int i = 0; i < nseq; ++i) {
-        if (tag_of[i] < 0 || tag_of[i] >= 32) return kh_fail(KH_E_ARG, "kh_skm_pack: tag %d outside 0..31", tag_of[i]);
-        ntags = std::max(ntags, tag_of[i] + 1);
-    }
-    HIPCHK(hipSetDevice(c->dev));
-    hipStream_t st = c->st;
-    {   // every tag needs a sequence for the geometry code (groups without genomes are refused there): tags are dense here
-        std::vector<int> seen(ntags, 0);
-        for (int i = 0; i < nseq; ++i) seen[tag_of[i]] = 1;
-        for (int t = 0; t < ntags; ++t)
-            if (!seen[t]) return kh_fail(KH_E_ARG, "kh_skm_pack: tag %d has no sequence", t);
-    }
-    const u32 spp = (nslots + (u32)nparts - 1) / (u32)nparts;
-    if (!loc && !kmer_positions(nseq, lens, k)) {
-        // a rank without k-mers (no sequences, or all shorter than k) still sends its parts: all empty
-        HIPCHK(hipMemsetAsync(count_out, 0, 4 * (size_t)spp * nparts, st));
-        HIPCHK(hipMemsetAsync(off_out, 0, 4 * (size_t)spp * nparts, st));
-        HIPCHK(hipStreamSynchronize(st));
-        for (int p = 0; p < nparts; ++p) part_n[p] = 0;
-        return KH_OK;
-    }
-    SkmStage s(c);
-    KHCHK(skm_prepare(c, nseq, seqs, lens, on_device, tag_of, ntags, k, /*by_group=*/true, nslots, loc ? (u32)nseq : 0u, &s));
-    u32 h_ctl[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (s.staged) {
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(h_ctl, s.job.ctl, 32, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        if (getenv("KHOICE_SKM_DEBUG"))
-            fprintf(stderr, "[skm records] k=%d positions=%llu nb1=%u S=%u nslots=%u cap1 %u cap2 %u | records %u errors %u spilled %u\n", k,
-                    (unsigned long long)s.g.positions, s.g.nb1, s.g.S, s.g.nslots, s.g.cap1, s.g.cap2, h_ctl[2], h_ctl[0], h_ctl[5]);
-        // (records on the side list: handed out to a caller that asked for them, a failure otherwise)
-        if ((h_ctl[0] & (KH_ERR_CAPACITY | KH_ERR_ORDER)) || (h_ctl[5] && (!loc || s.g.two || h_ctl[5] > SkmStage::spill_cap))) {
-            c->stat.retries++;
-            s.staged = false;
-        }
-    }
-    if (!s.staged) {
-        if (loc) return KH_OK;
-        return kh_fail(KH_E_CAPACITY, "kh_skm_pack: the records did not fit their regions (low-complexity input?)");
-    }
-    if (h_ctl[5]) {
-        loc->spill.b = s.d_spill.b; s.d_spill.b = nullptr;
-        loc->spill_n = h_ctl[5];
-    }
-    c->stat.skm_records += h_ctl[2];
-    if (loc) {
-        std::vector<u64> hi(nseq);
-        HIPCHK(hipMemcpyAsync(hi.data(), s.job.inst, 8 * (size_t)nseq, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        loc->inst.assign(nseq, 0);
-        for (int i = 0; i < nseq; ++i) loc->inst[s.L.perm[i]] = hi[i];
-    }
-    for (Tmp* t : {&s.d_seq, &s.d_reg1, &s.d_spill}) { buf_unref(t->b); t->b = nullptr; }   // from here on: the records by slot
-    Tmp d_ctl;
-    u32 nsub = loc ? 64u : 1u;   // (the one-GPU use: 64 cursors into its one part, which does not travel)
-    // The caller wants every part without gaps (it travels): packed through 64 cursors into a buffer of our own and
-    // moved together afterwards — one cursor per part is a queue of returning atomics (78 K slots: 0.8 ms).
-    const bool compact = nsub == 1 && spp >= 2048;
-    if (compact) nsub = 64;
-    const size_t off_pn = (64 + 4 * (size_t)nparts * nsub + 7) & ~(size_t)7, off_dup = off_pn + ((4 * (size_t)nparts + 7) & ~(size_t)7),
-                 ctl_bytes = off_dup + 8 * 32;
-    Tmp d_tmp;
-    if (compact) TMP_ALLOC(d_tmp, c, (size_t)nparts * part_cap * 20);
-    TMP_ALLOC(d_ctl, c, ctl_bytes);
-    HIPCHK(hipMemsetAsync(d_ctl.b->p, 0, ctl_bytes, st));
-    HIPCHK(hipMemsetAsync(count_out, 0, 4 * (size_t)spp * nparts, st));   // (slots past the last one: nothing)
-    HIPCHK(hipMemsetAsync(off_out, 0, 4 * (size_t)spp * nparts, st));
-    KhSkmPackJob job;
-    job.reg2 = s.d_reg2.as<uint4>();
-    job.cur2 = s.job.cur2;
-    job.out_rec = compact ? d_tmp.as<uint4>() : static_cast<uint4*>(rec_out);
-    job.out_mask = compact ? reinterpret_cast<u32*>(d_tmp.as<u8>() + 16 * (size_t)nparts * part_cap) : mask_out;
-    job.part_cursor = reinterpret_cast<u32*>(d_ctl.as<u8>() + 64);
-    job.slot_count = count_out;
-    job.slot_off = off_out;
-    job.ctl = d_ctl.as<u32>();
-    job.dup = loc ? reinterpret_cast<unsigned long long*>(d_ctl.as<u8>() + off_dup) : nullptr;
-    job.part_cap = part_cap;
-    job.cap2 = s.g.cap2;
-    job.nslots = s.g.nslots;
-    job.spp = spp;
-    job.nsub = nsub;
-    c->prof_begin(KC_SKM_PACK);
-    kh_launch_skm_pack(job, st);
-    if (compact) {
-        KhSkmCompactJob cj;
-        cj.tmp_rec = job.out_rec;
-        cj.tmp_mask = job.out_mask;
-        cj.out_rec = static_cast<uint4*>(rec_out);
-        cj.out_mask = mask_out;
-        cj.cursors = job.part_cursor;
-        cj.slot_off = off_out;
-        cj.part_n = reinterpret_cast<u32*>(d_ctl.as<u8>() + off_pn);
-        cj.part_cap = part_cap;
-        cj.nslots = s.g.nslots;
-        cj.spp = spp;
-        cj.nsub = nsub;
-        cj.nparts = (u32)nparts;
-        kh_launch_skm_pack_compact(cj, st);
-    }
-    c->prof_end();
-    HIPCHK(hipGetLastError());
-    std::vector<u32> h(ctl_bytes / 4);
-    HIPCHK(hipMemcpyAsync(h.data(), d_ctl.b->p, ctl_bytes, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (h[0] & KH_ERR_ORDER) return kh_fail(KH_E_INTERNAL, "kh_skm_pack: a record carried a tag above 31");
-    if (h[0] & KH_ERR_CAPACITY) {
-        if (loc) return KH_OK;
-        return kh_fail(KH_E_CAPACITY, "kh_skm_pack: a slot or a part overflowed");
-    }
-    for (int p = 0; p < nparts; ++p) {   // (with several cursors per part: the records, which then lie with gaps)
-        part_n[p] = 0;
-        for (u32 q = 0; q < nsub; ++q) part_n[p] += h[16 + (size_t)p * nsub + q];
-    }
-    if (loc) {
-        memcpy(loc->dup, reinterpret_cast<const u8*>(h.data()) + off_dup, 8 * 32);
-        loc->done = true;
-    }
-    return KH_OK;
-}
-extern "C" int kh_skm_pack(kh_ctx* c, int nseq, const uint8_t* const* seqs, const uint64_t* lens, int on_device,
-                           const int* tag_of, int k, uint32_t nslots, int nparts, uint64_t part_cap, void* rec_out,
-                           uint32_t* mask_out, uint32_t* count_out, uint32_t* off_out, uint64_t* part_n) {
-    return skm_pack_impl(c, nseq, seqs, lens, on_device, tag_of, k, nslots, nparts, part_cap, rec_out, mask_out, count_out, off_out,
-                         part_n, nullptr);
-}
-
-// The one-GPU use of kh_skm_phased_histogram (exp1_big_group_skm): the pieces are the phases of one group.
-struct SkmPhases {
-    std::vector<u32> row, join;   // per piece: its phase (the row of `dup` it counts into), "the next piece goes on in the same phase"
-    u32 share_q8 = 256;           // share of a piece's instances that are new to its phase, x 256
-    std::vector<u64> dup;         // out [pieces][32]: repeats under one tag
-    bool done = false;            // an overfilled table: false instead of an error
-};
-static int skm_phased_impl(kh_ctx* c, int k, int npieces, const void* const* recs, const uint32_t* const* masks,
-                           const uint32_t* const* counts, const uint32_t* const* offs, uint32_t nslots, uint32_t cs,
-                           uint64_t* hist, uint32_t hist_len, SkmPhases* ph) {
-    if (ph) ph->done = false;
-    if (!c || npieces < 1 || !recs || !masks || !counts || !offs || !hist || hist_len < 2 || cs < 1)
-        return kh_fail(KH_E_ARG, "kh_skm_phased_histogram: bad argument");
-    if (!skm_exchange_k(k)) return kh_fail(KH_E_ARG, "the exchange form takes k = %d .. %d", KH_SKM_MIN_K, KH_SKM_MAX_K);
-    HIPCHK(hipSetDevice(c->dev));
-    hipStream_t st = c->st;
-    const size_t off_pieces = 64, off_hist = (off_pieces + sizeof(KhSkmPiece) * (size_t)npieces + 63) & ~(size_t)63;
-    const size_t off_pdup = off_hist + 8 * (size_t)hist_len, ws_bytes = off_pdup + (ph ? 8 * 32 * (size_t)npieces : 0);
-    Tmp d_ws;
-    TMP_ALLOC(d_ws, c, ws_bytes);
-    std::vector<u8> up(off_hist, 0);
-    KhSkmPiece* hp = reinterpret_cast<KhSkmPiece*>(up.data() + off_pieces);
-    for (int i = 0; i < npieces; ++i) {
-        hp[i].rec = static_cast<const uint4*>(recs[i]);
-        hp[i].mask = masks[i];
-        hp[i].count = counts[i];
-        hp[i].off = offs[i];
-        hp[i].dup_row = ph ? ph->row[i] : (u32)i;
-        hp[i].join_next = ph ? ph->join[i] : 0u;
-    }
-    HIPCHK(hipMemsetAsync(d_ws.b->p, 0, ws_bytes, st));
-    HIPCHK(hipMemcpyAsync(d_ws.b->p, up.data(), off_hist, hipMemcpyHostToDevice, st));
-    KhSkmPhasedJob job;
-    job.pieces = reinterpret_cast<const KhSkmPiece*>(d_ws.as<u8>() + off_pieces);
-    job.hist = reinterpret_cast<unsigned long long*>(d_ws.as<u8>() + off_hist);
-    job.ctl = d_ws.as<u32>();
-    job.dup = ph ? reinterpret_cast<unsigned long long*>(d_ws.as<u8>() + off_pdup) : nullptr;
-    job.npieces = (u32)npieces;
-    job.share_q8 = std::min<u32>(256, std::max<u32>(1, ph ? ph->share_q8 : 256u));
-    job.nslots = nslots;
-    job.hist_len = hist_len;
-    job.cs = cs;
-    job.k = k;
-    c->prof_begin(KC_SKM_PHASED);
-    kh_launch_skm_phased(job, std::min<u32>(std::max<u32>(1, nslots), 2u * (u32)std::max(1, c->cus)), st);
-    c->prof_end();
-    HIPCHK(hipGetLastError());
-    u32 h_ctl[4];
-    HIPCHK(hipMemcpyAsync(h_ctl, d_ws.b->p, 16, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(hist, d_ws.as<u8>() + off_hist, 8 * (size_t)hist_len, hipMemcpyDeviceToHost, st));
-    if (ph) {
-        ph->dup.assign(32 * (size_t)npieces, 0);
-        HIPCHK(hipMemcpyAsync(ph->dup.data(), d_ws.as<u8>() + off_pdup, 8 * 32 * (size_t)npieces, hipMemcpyDeviceToHost, st));
-    }
-    HIPCHK(hipStreamSynchronize(st));
-    if (h_ctl[0] & KH_ERR_CAPACITY) {
-        if (ph) return KH_OK;
-        return kh_fail(KH_E_CAPACITY, "kh_skm_phased_histogram: a slot held more k-mers than its table");
-    }
-    c->stat.setops++;
-    if (ph) ph->done = true;
-    return KH_OK;
-}
-extern "C" int kh_skm_phased_histogram(kh_ctx* c, int k, int npieces, const void* const* recs, const uint32_t* const* masks,
-                                       const uint32_t* const* counts, const uint32_t* const* offs, uint32_t nslots, uint32_t cs,
-                                       uint64_t* hist, uint32_t hist_len) {
-    return skm_phased_impl(c, k, npieces, recs, masks, counts, offs, nslots, cs, hist, hist_len, nullptr);
-}
-
-// One group of more than 64 genomes in the super-k-mer form (one-word keys): sub-batches of up to 32 genomes, each
-// turned into records tagged with the genome's number in the sub-batch, identical records merged (k_skm_pack, one
-// part); the sub-batches are the PHASES of one phased union (k_skm_phased): the counter of an entry ends as "in how
-// many genomes of the group", which is the group's step_4 histogram.  Distinct k-mers of a genome: its instances minus
-// the repeats under its tag (whole records at the merge, single k-mers at the insertion).  *done == false: the
-// caller takes the key-array sub-batches.
-static int exp1_big_group_skm(kh_ctx* c, int n, const uint8_t* const* seqs, const uint64_t* lens, int on_device, int k, u32 cs,
-                              uint64_t* whist, u32 hist_len, uint64_t* dist /* [n] or null */, bool* done) {
-    *done = false;
-    if (!skm_exchange_k(k) || getenv("KHOICE_NO_SKM") || getenv("KHOICE_NO_SKM_PHASED") || !whist) return KH_OK;
-    constexpr int SUB = 32;
-    const int P = (n + SUB - 1) / SUB;
-    if (P > (int)KH_SKM_PHASED_MAX_DUP_PIECES) return KH_OK;
-    std::vector<int> first(P + 1, 0);
-    for (int p = 0; p < P; ++p) first[p + 1] = first[p] + (n - first[p] + (P - p) - 1) / (P - p);   // balanced sizes
-    u64 pos_max = 0;
-    std::vector<u64> pos(P, 0);
-    for (int p = 0; p < P; ++p) {
-        pos[p] = kmer_positions(first[p + 1] - first[p], lens + first[p], k);
-        pos_max = std::max(pos_max, pos[p]);
-    }
-    if (!pos_max) return KH_OK;
-    u64 ns = 0;
-    double per_kmer = 0;
-    const bool dbg = getenv("KHOICE_SKM_DEBUG") != nullptr;
-    // How much the sub-batches of a group share decides how large a slot may be: its table holds one sub-batch's k-mers
-    // plus what each further one adds (`novelty` of its own).  Measured: the synthetic genomes (1 % divergence from one
-    // ancestor, independent per genome) add 0.7 — with 0.3 assumed a table overfilled and the repeated launch cost more
-    // than the 2.5 x larger slots saved (12.1 -> 14.0 ms) — so the default assumes unrelated sub-batches (1.0); real
-    // collections with a tree-like history share more: KHOICE_SKM_PHASED_NOVELTY (an overfilled table is caught and the
-    // launch repeated with rounds sized for unrelated pieces).
-    double novelty = 1.0;
-    if (const char* e = getenv("KHOICE_SKM_PHASED_NOVELTY")) novelty = std::min(1.0, std::max(0.05, atof(e)));
-    const double eff_parts = 1.0 + novelty * (double)(P - 1);
-    const u32 share_q8 = (u32)std::min(256.0, std::ceil(256.0 * eff_parts / (double)P));
-    if (!skm_exchange_geometry(k, pos_max, P, (u32)SUB, &ns, &per_kmer, eff_parts)) {
-        if (dbg) fprintf(stderr, "[skm phased] %d genomes in %d phases: no geometry for %llu positions per phase\n", n, P, (unsigned long long)pos_max);
-        return KH_OK;
-    }
-    const u32 nslots = (u32)ns;
-    if (dbg) fprintf(stderr, "[skm phased] %d genomes in %d phases, %u slots, %.0f positions per slot and phase\n", n, P, nslots, (double)pos_max / nslots);
-    HIPCHK(hipSetDevice(c->dev));
-    std::vector<std::unique_ptr<Tmp>> bufs;
-    std::vector<const void*> recs;
-    std::vector<const uint32_t*> masks, counts, offs;
-    SkmPhases ph;
-    auto add_piece = [&](const u8* b, size_t off_mask, size_t off_count, size_t off_off, u32 row, u32 join) {
-        recs.push_back(b);
-        masks.push_back(reinterpret_cast<const u32*>(b + off_mask));
-        counts.push_back(reinterpret_cast<const u32*>(b + off_count));
-        offs.push_back(reinterpret_cast<const u32*>(b + off_off));
-        ph.row.push_back(row);
-        ph.join.push_back(join);
-    };
-    std::vector<u64> inst_all(n, 0), dup_all(n, 0);
-    hipStream_t st = c->st;
-    for (int p = 0; p < P; ++p) {
-        const int m = first[p + 1] - first[p];
-        const u64 cap = skm_part_cap(pos[p], per_kmer, 1);
-        const size_t off_mask = 16 * (size_t)cap, off_count = off_mask + 4 * (size_t)cap, off_off = off_count + 4 * (size_t)((nslots + 3) & ~3u),
-                     bytes = off_off + 4 * (size_t)((nslots + 3) & ~3u);
-        bufs.emplace_back(new Tmp);
-        TMP_ALLOC(*bufs.back(), c, bytes);
-        u8* base = bufs.back()->as<u8>();
-        std::vector<int> tag(m);
-        for (int j = 0; j < m; ++j) tag[j] = j;
-        u64 part_n = 0;
-        SkmPackLocal loc;
-        KHCHK(skm_pack_impl(c, m, seqs + first[p], lens + first[p], on_device, tag.data(), k, nslots, 1, cap, base,
-                            reinterpret_cast<u32*>(base + off_mask), reinterpret_cast<u32*>(base + off_count),
-                            reinterpret_cast<u32*>(base + off_off), &part_n, &loc));
-        if (!loc.done) {
-            if (dbg) fprintf(stderr, "[skm phased] phase %d: the records did not fit\n", p);
-            return KH_OK;
-        }
-        if (dbg) fprintf(stderr, "[skm phased] phase %d: %llu records travel (cap %llu), %u on the side list\n", p, (unsigned long long)part_n,
-                         (unsigned long long)cap, loc.spill_n);
-        add_piece(base, off_mask, off_count, off_off, (u32)p, 0);
-        for (int j = 0; j < m; ++j) { inst_all[first[p] + j] = loc.inst[j]; dup_all[first[p] + j] = loc.dup[j]; }
-        if (loc.spill_n) {
-            // Overfull slots (low-complexity sequence): what the regions could not hold is on the side list, unmerged and
-            // in no order.  It joins the sub-batch's phase as extra pieces — sorted by slot on the host (rare, small),
-            // at most 1024 records of a slot per piece.
-            const u32 ns = loc.spill_n;
-            std::vector<uint4> hrec(ns);
-            std::vector<u32> hslot(ns), order(ns);
-            HIPCHK(hipMemcpyAsync(hrec.data(), loc.spill.b->p, 16 * (size_t)ns, hipMemcpyDeviceToHost, st));
-            HIPCHK(hipMemcpyAsync(hslot.data(), static_cast<const u8*>(loc.spill.b->p) + 16 * (size_t)SkmStage::spill_cap, 4 * (size_t)ns,
-                                  hipMemcpyDeviceToHost, st));
-            HIPCHK(hipStreamSynchronize(st));
-            for (u32 i = 0; i < ns; ++i) {
-                order[i] = i;
-                if (hslot[i] >= nslots) return kh_fail(KH_E_INTERNAL, "side list: slot %u of %u", hslot[i], nslots);
-            }
-            std::stable_sort(order.begin(), order.end(), [&](u32 a, u32 b) { return hslot[a] < hslot[b]; });
-            std::vector<u32> run(nslots, 0);
-            u32 longest = 0;
-            for (u32 i = 0; i < ns; ++i) longest = std::max(longest, ++run[hslot[i]]);
-            const u32 extra = (longest + 1023u) / 1024u;
-            ph.join.back() = 1;
-            for (u32 e = 0; e < extra; ++e) {
-                std::vector<uint4> prec;
-                std::vector<u32> pmask, pcount(nslots, 0), poff(nslots, 0);
-                for (u32 i = 0; i < ns;) {   // the sorted list, a slot's run at a time
-                    const u32 sl = hslot[order[i]], len = run[sl];
-                    const u32 lo = std::min(len, e * 1024u), hi = std::min(len, (e + 1) * 1024u);
-                    poff[sl] = (u32)prec.size();
-                    pcount[sl] = hi - lo;
-                    for (u32 j = lo; j < hi; ++j) {
-                        const uint4 r = hrec[order[i + j]];
-                        prec.push_back(r);
-                        pmask.push_back(1u << (SkmRec1::tag(r.w) & 31u));   // (tags of the exchange form are below 32)
-                    }
-                    i += len;
-                }
-                const size_t nrec_e = std::max<size_t>(1, prec.size());
-                const size_t e_mask = 16 * nrec_e, e_count = e_mask + ((4 * nrec_e + 15) & ~(size_t)15), e_off = e_count + 4 * (size_t)((nslots + 3) & ~3u),
-                             e_bytes = e_off + 4 * (size_t)((nslots + 3) & ~3u);
-                bufs.emplace_back(new Tmp);
-                TMP_ALLOC(*bufs.back(), c, e_bytes);
-                u8* eb = bufs.back()->as<u8>();
-                if (!prec.empty()) {
-                    HIPCHK(hipMemcpyAsync(eb, prec.data(), 16 * prec.size(), hipMemcpyHostToDevice, st));
-                    HIPCHK(hipMemcpyAsync(eb + e_mask, pmask.data(), 4 * pmask.size(), hipMemcpyHostToDevice, st));
-                }
-                HIPCHK(hipMemcpyAsync(eb + e_count, pcount.data(), 4 * (size_t)nslots, hipMemcpyHostToDevice, st));
-                HIPCHK(hipMemcpyAsync(eb + e_off, poff.data(), 4 * (size_t)nslots, hipMemcpyHostToDevice, st));
-                HIPCHK(hipStreamSynchronize(st));   // (the host vectors go out of scope)
-                add_piece(eb, e_mask, e_count, e_off, (u32)p, e + 1 < extra ? 1u : 0u);
-            }
-            c->stat.big_slots += (u64)std::count_if(run.begin(), run.end(), [](u32 v) { return v != 0; });
-        }
-    }
-    std::vector<u64> hist(hist_len, 0);
-    ph.share_q8 = share_q8;
-    KHCHK(skm_phased_impl(c, k, (int)recs.size(), recs.data(), masks.data(), counts.data(), offs.data(), nslots, cs, hist.data(), hist_len, &ph));
-    if (!ph.done && share_q8 < 256) {   // a table overfilled: the genomes share less than assumed — rounds for unrelated pieces
-        if (dbg) fprintf(stderr, "[skm phased] a table overfilled with rounds sized for shared k-mers: once more\n");
-        c->stat.retries++;
-        ph.share_q8 = 256;
-        KHCHK(skm_phased_impl(c, k, (int)recs.size(), recs.data(), masks.data(), counts.data(), offs.data(), nslots, cs, hist.data(), hist_len, &ph));
-    }
-    if (!ph.done) {
-        if (dbg) fprintf(stderr, "[skm phased] the phased union overflowed\n");
-        return KH_OK;
-    }
-    memcpy(whist, hist.data(), 8 * (size_t)hist_len);
-    u64 bases = 0, isum = 0, dsum = 0;
-    for (int p = 0; p < P; ++p)
-        for (int i = first[p]; i < first[p + 1]; ++i) {
-            const u64 d = inst_all[i] - dup_all[i] - ph.dup[(size_t)p * 32 + (i - first[p])];
-            if (dist) dist[i] = d;
-            bases += lens[i]; isum += inst_all[i]; dsum += d;
-        }
-    c->stat.bases += bases;
-    c->stat.builds += n;
-    c->stat.kmers += isum;
-    c->stat.distinct += dsum;
-    c->stat.setop_in += dsum;
-    *done = true;
-    return KH_OK;
 }
 
 // ------------------------------------------------------------------------------ host mix

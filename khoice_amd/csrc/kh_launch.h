@@ -127,7 +127,6 @@ struct KhTagJob {
 constexpr u32 KH_SKM_STAGE = KH_TUNE_SKM_STAGE;   // records counting-sorted in LDS per flush of the scatter
 constexpr u32 KH_SKM_MAX_COARSE = 256;    // coarse buckets (LDS counters of the scatter); 512 (KH_SKM2_MAX_COARSE) for inputs too large for 256
 constexpr u32 KH_SKM_MAX_FINE = 512;      // slots per coarse bucket (9 bits in the record)
-constexpr u32 KH_SKM_MAX_CAP2 = 1024;     // records of one slot with one-word keys: one per thread of the union
 constexpr int KH_SKM_MIN_K = 17, KH_SKM_MAX_K = 32;   // (below 17 the key arrays are faster; the kernels take k >= 15)
 #ifndef KH_TUNE_SKM_CUR1_STRIDE
 #define KH_TUNE_SKM_CUR1_STRIDE 1088
@@ -135,6 +134,24 @@ constexpr int KH_SKM_MIN_K = 17, KH_SKM_MAX_K = 32;   // (below 17 the key array
 // u32 words between the cursors of two coarse buckets: every flush of every workgroup adds to all of them,
 // so they are kept on different memory channels (4352 bytes apart) instead of sixteen to a cache line
 constexpr u32 KH_SKM_CUR1_STRIDE = KH_TUNE_SKM_CUR1_STRIDE;
+// the words of KhSkmJob::ctl (zeroed before the scatter, read back by the host after the union or the cross kernel)
+enum : u32 {
+    KH_SKM_CTL_ERR = 0,             // error bits (KH_ERR_CAPACITY, KH_ERR_ORDER)
+    KH_SKM_CTL_FULLEST = 1,         // k-mer instances of the fullest slot seen (above the table's size only)
+    KH_SKM_CTL_RECORDS = 2,         // records written by the scatter
+    KH_SKM_CTL_EXPANDED = 3,        // k-mer instances expanded from the records
+                                    // (word 4 is not used by the super-k-mer kernels)
+    KH_SKM_CTL_SPILLED = 5,         // records spilled to the side list (spill_rec / spill_slot)
+    KH_SKM_CTL_LISTED = 6,          // slots listed in big_list
+    KH_SKM_CTL_MULTI = 7,           // slots taken in more than one subset (k_skm_union) or round (k_skm_cross)
+    KH_SKM_CTL_WORDS = 8,
+};
+// the words of KhSkmPackJob::ctl and KhSkmPhasedJob::ctl; behind them, in the host's block of a pack, the part cursors
+enum : u32 {
+    KH_SKM_XCTL_ERR = 0,            // error bits
+    KH_SKM_XCTL_FULLEST = 1,        // k_skm_phased: k-mer instances of the fullest slot seen
+    KH_SKM_XCTL_CURSORS = 16,       // k_skm_pack: KhSkmPackJob::part_cursor starts here, [nparts][nsub]
+};
 struct KhSkmJob {
     const KhSeg* segs;
     const KhTile* tiles;
@@ -147,7 +164,7 @@ struct KhSkmJob {
     unsigned long long* dup;        // [64] instances whose (k-mer, genome) pair was seen before
     const u32* ginfo;               // as KhTagJob
     unsigned long long* hist;       // [reps][nbins]
-    u32* ctl;                       // [0] error bits, [1] fullest slot seen, [2] records written by the scatter
+    u32* ctl;                       // [KH_SKM_CTL_WORDS] zeroed: the control words, KH_SKM_CTL_*
     u32* claim;                     // zeroed, a 128-byte line of its own: the unions' slot claims (SkmSlotFeed, kh_skm_device.h)
     u32 tile_pos;
     int k, m;                       // m-mer length of the minimizer (<= 16)
@@ -159,17 +176,8 @@ struct KhSkmJob {
     uint4* spill_rec;               // [spill_cap] records (one or two uint4 each); nullptr: a full region is an error
     u32* spill_slot;                // [spill_cap]
     u32* big_list;                  // [big_cap] slots with more records than their region holds
-    u32 spill_cap, big_cap;         // counters: ctl[5] records spilled, ctl[6] slots listed
+    u32 spill_cap, big_cap;         // counters: ctl[KH_SKM_CTL_SPILLED], ctl[KH_SKM_CTL_LISTED]
 };
-bool kh_skm_supports_w(u32 w);   // m-mers per k-mer the scatter kernel is instantiated for
-size_t kh_skm_scatter_lds_bytes(u32 nb1);
-size_t kh_skm_union_lds_bytes();
-u32 kh_skm_union_max_cap2();   // records of a slot the union takes
-void kh_launch_skm_scatter(const KhSkmJob& job, u32 ntiles, hipStream_t st);
-void kh_launch_skm_regroup(const KhSkmJob& job, hipStream_t st);
-void kh_launch_skm_union(const KhSkmJob& job, u32 cs, u32 grid, hipStream_t st);   // persistent: grid workgroups walk the slots
-u32 kh_skm_union_per_cu();   // workgroups of the union that fit a CU
-void kh_launch_skm_big(const KhSkmJob& job, u32 cs, u32 nbig, hipStream_t st);   // the slots of big_list, one workgroup each
 // ---- experiment type 3 from the same records (k_skm_cross, kh_skm_device.h): the operands of the scatter are the
 // genomes in group-major order, then the pivots of the pass, every pivot a group of its own in `ginfo`.  What the
 // kernel needs beyond KhSkmJob, which stays as the other kernels know it:
@@ -180,9 +188,28 @@ struct KhSkmCrossJob {
     u32 nbins, reps;                // nbins = pivots * ngenomes <= 1024
     u32 nlisted;                    // 0: the direct launch over all slots; else the listed launch over big_list[0 .. nlisted)
 };
-u32 kh_skm_cross_round();           // k-mer instances of a slot the kernel takes in one round
-u32 kh_skm_cross_per_cu();          // workgroups of the direct launch that fit a CU
-void kh_launch_skm_cross(const KhSkmJob& job, const KhSkmCrossJob& cj, u32 grid, hipStream_t st);
+// What the host needs to know about a key width: one-word keys (k <= 32, 16-byte records, kh_skm.hip) and two-word
+// keys (k <= 63, 32-byte records: two uint4 per record in reg1 / reg2, kh_skm2.hip) fill one table each.
+constexpr int KH_SKM2_MAX_K = 63;         // k = 64: the all-ones low key word is a k-mer (A^32 T^32)
+constexpr u32 KH_SKM2_MAX_COARSE = 512;
+constexpr u32 KH_SKM2_MAX_FINE = 1024;    // slots per coarse bucket with two-word keys (10 bits in the record)
+struct KhSkmWidth {
+    u32 rec_bytes;
+    u32 max_coarse, max_fine;       // coarse buckets (LDS counters of the scatter), slots per coarse bucket (bits in the record)
+    u32 max_cap2;                   // records of a slot the union takes
+    u32 table;                      // entries of the union's hash set: the k-mer instances of a slot it takes per round
+    u32 union_per_cu, cross_per_cu; // workgroups of the persistent union / of the direct cross launch that fit a CU
+    u32 cross_round;                // k-mer instances of a slot the cross kernel takes in one round
+    bool (*supports_w)(u32 w);      // m-mers per k-mer the scatter kernel is instantiated for
+    void (*scatter)(const KhSkmJob& job, u32 ntiles, hipStream_t st);
+    void (*regroup)(const KhSkmJob& job, hipStream_t st);
+    void (*unite)(const KhSkmJob& job, u32 cs, u32 grid, hipStream_t st);    // persistent: grid workgroups walk the slots
+    void (*big)(const KhSkmJob& job, u32 cs, u32 nbig, hipStream_t st);      // the slots of big_list, one workgroup each
+    void (*cross)(const KhSkmJob& job, const KhSkmCrossJob& cj, u32 grid, hipStream_t st);
+};
+const KhSkmWidth& kh_skm_width1();     // kh_skm.hip
+const KhSkmWidth& kh_skm_width2();     // kh_skm2.hip
+inline const KhSkmWidth& kh_skm_width(bool two) { return two ? kh_skm_width2() : kh_skm_width1(); }
 // ---- the exchange form of the across-group step (multi-GPU; kh_skm.hip k_skm_pack / k_skm_phased)
 struct KhSkmPackJob {
     const uint4* reg2;              // [nslots][cap2] this rank's records by slot (tag = local group, < 32)
@@ -192,7 +219,7 @@ struct KhSkmPackJob {
     u32* part_cursor;               // [nparts] zeroed
     u32* slot_count;                // [nslots] records that travel
     u32* slot_off;                  // [nslots] where they start in their part's array
-    u32* ctl;                       // [0] error bits
+    u32* ctl;                       // KH_SKM_XCTL_ERR
     unsigned long long* dup;        // [32] or null: per tag, k-mer instances of records that repeat one of the SAME tag
     u64 part_cap;
     u32 cap2, nslots, spp;          // spp: slots per part (slot s belongs to part s / spp)
@@ -222,7 +249,7 @@ struct KhSkmPiece {                 // what one source rank sent for this rank's
 struct KhSkmPhasedJob {
     const KhSkmPiece* pieces;       // device array [npieces]
     unsigned long long* hist;       // [hist_len], zeroed
-    u32* ctl;                       // [0] error bits
+    u32* ctl;                       // KH_SKM_XCTL_ERR, KH_SKM_XCTL_FULLEST
     unsigned long long* dup;        // [npieces][32] or null: per (piece, tag), instances that repeat a k-mer of the same tag
     u32 npieces, nslots, hist_len, cs;
     u32 share_q8;                   // distinct k-mers expected per 256 instances of a slot (256: the pieces share nothing;
@@ -233,23 +260,6 @@ constexpr u32 KH_SKM_PHASED_MAX_DUP_PIECES = 32;   // pieces whose repeats can b
 size_t kh_skm_phased_lds_bytes();
 void kh_launch_skm_pack(const KhSkmPackJob& job, hipStream_t st);
 void kh_launch_skm_phased(const KhSkmPhasedJob& job, u32 grid, hipStream_t st);
-// the same three steps for two-word keys (kh_skm2.hip): 32-byte records (two uint4 per record in reg1 / reg2)
-constexpr int KH_SKM2_MAX_K = 63;         // k = 64: the all-ones low key word is a k-mer (A^32 T^32)
-constexpr u32 KH_SKM2_MAX_COARSE = 512;
-constexpr u32 KH_SKM2_MAX_FINE = 1024;    // slots per coarse bucket with two-word keys (10 bits in the record)
-bool kh_skm2_supports_w(u32 w);
-u32 kh_skm2_max_cap2();
-u32 kh_skm2_table();
-u32 kh_skm2_union_per_cu();   // workgroups of the two-word union that fit a CU
-void kh_launch_skm2_big(const KhSkmJob& job, u32 cs, u32 nbig, hipStream_t st);
-u32 kh_skm2_cross_round();
-u32 kh_skm2_cross_per_cu();
-void kh_launch_skm2_cross(const KhSkmJob& job, const KhSkmCrossJob& cj, u32 grid, hipStream_t st);
-size_t kh_skm2_scatter_lds_bytes(u32 nb1);
-size_t kh_skm2_union_lds_bytes(u32 nbins);
-void kh_launch_skm2_scatter(const KhSkmJob& job, u32 ntiles, hipStream_t st);
-void kh_launch_skm2_regroup(const KhSkmJob& job, hipStream_t st);
-void kh_launch_skm2_union(const KhSkmJob& job, u32 cs, u32 grid, hipStream_t st);   // persistent, as the one-word union
 
 // ---- presence-bitmap form of the fused path (kh_bmp.hip): k <= KH_BMP_MAX_K, histograms and distinct counts only.
 // k_bmp_build writes one partial bitmap of 4^k bits (at least one 64-bit word) per split of a genome, k_bmp_readout

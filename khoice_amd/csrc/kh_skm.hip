@@ -59,7 +59,7 @@ void kh_debug_set_stamps_skm(u64* p) { (void)hipMemcpyToSymbol(HIP_SYMBOL(g_skm_
 
 #include "kh_skm_device.h"   // (after SKM_STAMP: the shared flush carries stamps)
 
-size_t kh_skm_scatter_lds_bytes(u32 nb1) {
+static size_t kh_skm_scatter_lds_bytes(u32 nb1) {
     const u32 nbk = (nb1 + 3) & ~3u;
     return flush_lds_bytes<SKM_CAP>(nbk) + (size_t)SKM_CW * 4 + (((size_t)SKM_CW * 2 + 15) & ~(size_t)15) + 64 * 4 + 4 * 32 * 4 +
            (size_t)SKM_NT * 8 + 64;
@@ -327,7 +327,7 @@ __global__ __launch_bounds__(SKM_NT, KH_TUNE_SKM_SCATTER_WAVES) void k_skm_scatt
     __syncthreads();
     if (staged) skm_flush<SKM_NT, SKM_CAP, false>(L, staged, jb.nb1, jb.cur1, jb.reg1, jb.cap1, jb.ctl);
     if (tid == 0 && misc[1]) atomicAdd(&jb.inst[t.seg], (unsigned long long)misc[1]);
-    if (tid == 0 && tile_recs) atomicAdd(jb.ctl + 2, tile_recs);
+    if (tid == 0 && tile_recs) atomicAdd(jb.ctl + KH_SKM_CTL_RECORDS, tile_recs);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -363,6 +363,7 @@ constexpr u32 SKM_UE = KH_TUNE_SKM_UE;                // k-mers per chunk (2 or 
 constexpr u32 SKM_OB = SKM_UE == 2 ? 4 : 3;           // bits of a chunk's number inside its record (n <= 31)
 constexpr u32 SKM_PASSES = SKM_UE == 2 ? 3 : 2;       // chunks of a slot: at most SKM_PASSES per thread
 template <u32 NT, u32 T> struct SkmUnionGeo {
+    static constexpr u32 TABLE = T;                   // main table
     static constexpr u32 T2 = 128;                    // second table
     static constexpr u32 MAXREC = NT;                 // records of a slot (cap2 <= this): one per thread
     static constexpr u32 MAXCH = SKM_PASSES * NT;     // chunks of a slot (after the merge of identical records)
@@ -373,9 +374,7 @@ template <u32 NT, u32 T> struct SkmUnionGeo {
     static_assert((T & (T - 1u)) == 0u, "table indices wrap by a mask");
 };
 using SkmUnion = SkmUnionGeo<1024, 4096>;
-u32 kh_skm_union_max_cap2() { return SkmUnion::MAXREC; }
-u32 kh_skm_union_per_cu() { return 2u; }
-size_t kh_skm_union_lds_bytes() { return SkmUnion::LDS; }
+static_assert(SkmUnion::TABLE == 4096, "the slot geometry and its measurements (skm_plan) are the 4096-entry table's");
 
 __device__ __forceinline__ u32 key_hash2(u32 lo, u32 hi) { return (lo ^ hi) * 0x9E3779B1u; }
 
@@ -475,7 +474,7 @@ struct SkmClaim1 {
 // between subsets, and none of the scalars those keep alive.  A slot with N > T takes the MULTI one: R = ceil(N / T)
 // subsets of its keys, chosen by hash bits, inserted and read out one after the other on the same planes.  Both are
 // one piece of code with a compile-time flag; the masks-self-clean invariant (at the read-out) holds for either, so
-// lean and multi slots may follow each other in any order in one workgroup's walk.  ctl[7] counts the multi slots.
+// lean and multi slots may follow each other in any order in one workgroup's walk.  KH_SKM_CTL_MULTI counts the multi slots.
 // KT: k at compile time (17 .. 32; the masks and shifts of the expansion are immediates), 0: k from the job.
 #ifndef KH_TUNE_SKM_UNION_LEAN
 #define KH_TUNE_SKM_UNION_LEAN 1   // 0: every slot through the multi body (timing study)
@@ -605,7 +604,7 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs, 
         const uint4* __restrict__ reg = jb.reg2 + (u64)slot * cap2;
         if (!nrec && counts[slot] > fit) {   // uniform: an overfull slot
             if (tid0 == 0) {
-                const u32 at = atomicAdd(jb.ctl + 6, 1u);
+                const u32 at = atomicAdd(jb.ctl + KH_SKM_CTL_LISTED, 1u);
                 if (at < jb.big_cap) jb.big_list[at] = slot;
             }
         }
@@ -705,7 +704,7 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs, 
         if (C > G::MAXCH) {   // uniform: more chunks than are numbered here (long runs of one minimizer): k_skm_big takes the slot
             if (tid == 0) {
                 if (jb.big_list) {
-                    const u32 at = atomicAdd(jb.ctl + 6, 1u);
+                    const u32 at = atomicAdd(jb.ctl + KH_SKM_CTL_LISTED, 1u);
                     if (at < jb.big_cap) jb.big_list[at] = slot;
                 } else atomicOr(jb.ctl, KH_ERR_CAPACITY);
             }
@@ -938,7 +937,7 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs, 
         if (KH_TUNE_SKM_UNION_LEAN && R0 == 1u) {
             slot_body(std::false_type{});
         } else if (__builtin_expect(R0 != 0u, 0)) {   // (uniform, cold)
-            if (R0 > 1u && tid0 == 0) atomicAdd(jb.ctl + 7, 1u);   // slots taken in more than one subset
+            if (R0 > 1u && tid0 == 0) atomicAdd(jb.ctl + KH_SKM_CTL_MULTI, 1u);   // slots taken in more than one subset
             slot_body(std::true_type{});
         }
         SKM_USTAMP(8);
@@ -963,8 +962,8 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs, 
     }
     if (tid < (u32)KH_TAG_MAX_OPS && dupc[tid]) atomicAdd(&jb.dup[tid], (unsigned long long)dupc[tid]);
     if (tid == 0) {
-        if (st_full > T) atomicMax(jb.ctl + 1, st_full);
-        atomicAdd(jb.ctl + 3, st_exp);   // k-mer instances that were expanded
+        if (st_full > T) atomicMax(jb.ctl + KH_SKM_CTL_FULLEST, st_full);
+        atomicAdd(jb.ctl + KH_SKM_CTL_EXPANDED, st_exp);   // k-mer instances that were expanded
     }
 }
 
@@ -1250,7 +1249,7 @@ __global__ __launch_bounds__(SKM_PH_NT, 8) void k_skm_phased(const KhSkmPhasedJo
             }
             if (acc > NT) {
                 all_staged = false;
-                if (tid == 0) atomicMax(jb.ctl + 1, acc);
+                if (tid == 0) atomicMax(jb.ctl + KH_SKM_XCTL_FULLEST, acc);
             } else {
                 if (myph < NP) {
                     const u64 at = (u64)poff[myph] + myidx;
@@ -1418,8 +1417,8 @@ template <int WW> static void launch_scatter_w(const KhSkmJob& job, u32 ntiles, 
     skm_allow_lds(k_skm_scatter<WW>, lds);
     hipLaunchKernelGGL(k_skm_scatter<WW>, dim3(ntiles), dim3(SKM_NT), lds, st, job);
 }
-bool kh_skm_supports_w(u32 w) { return w >= (u32)SKM_WMIN && w <= (u32)SKM_WMAX; }
-void kh_launch_skm_scatter(const KhSkmJob& job, u32 ntiles, hipStream_t st) {
+static bool kh_skm_supports_w(u32 w) { return w >= (u32)SKM_WMIN && w <= (u32)SKM_WMAX; }
+static void kh_launch_skm_scatter(const KhSkmJob& job, u32 ntiles, hipStream_t st) {
     if (!ntiles) return;
     const size_t lds = kh_skm_scatter_lds_bytes(job.nb1);
     switch (job.w) {
@@ -1430,13 +1429,13 @@ void kh_launch_skm_scatter(const KhSkmJob& job, u32 ntiles, hipStream_t st) {
         default: break;   // the host asks kh_skm_supports_w first
     }
 }
-void kh_launch_skm_regroup(const KhSkmJob& job, hipStream_t st) { skm_launch_regroup<SkmRec1>(job, st); }
+static void kh_launch_skm_regroup(const KhSkmJob& job, hipStream_t st) { skm_launch_regroup<SkmRec1>(job, st); }
 template <int KT> static void launch_union_k(const KhSkmJob& job, u32 cs, u32 grid, hipStream_t st) {
-    const size_t lds = kh_skm_union_lds_bytes();
+    const size_t lds = SkmUnion::LDS;
     skm_allow_lds(k_skm_union<1024, 4096, KT>, lds);
     hipLaunchKernelGGL((k_skm_union<1024, 4096, KT>), dim3(grid), dim3(1024), lds, st, job, cs, skm_first_claimed(job.nslots, grid));
 }
-void kh_launch_skm_union(const KhSkmJob& job, u32 cs, u32 grid, hipStream_t st) {
+static void kh_launch_skm_union(const KhSkmJob& job, u32 cs, u32 grid, hipStream_t st) {
     switch (job.k) {
 #if KH_TUNE_SKM_UNION_KT
 #define SKM_K(KK) case KK: launch_union_k<KK>(job, cs, grid, st); break;
@@ -1470,9 +1469,14 @@ void kh_launch_skm_phased(const KhSkmPhasedJob& job, u32 grid, hipStream_t st) {
     skm_allow_lds(k_skm_phased, lds);
     hipLaunchKernelGGL(k_skm_phased, dim3(grid), dim3(SKM_PH_NT), lds, st, job);
 }
-void kh_launch_skm_big(const KhSkmJob& job, u32 cs, u32 nbig, hipStream_t st) { skm_launch_big<SkmBig1>(job, cs, nbig, st); }
 // k_skm_cross (kh_skm_device.h) with one-word keys
 constexpr bool SKM_CROSS1_VGPRS64 = true;   // resource report: 59 VGPRs, 78 SGPRs (53 more kept in VGPR lanes), no scratch, 8 waves per SIMD; 81280 bytes of LDS
-u32 kh_skm_cross_round() { return skm_cross_round<SkmBig1>(); }
-u32 kh_skm_cross_per_cu() { return skm_cross_per_cu<SkmBig1>(SKM_CROSS1_VGPRS64); }
-void kh_launch_skm_cross(const KhSkmJob& job, const KhSkmCrossJob& cj, u32 grid, hipStream_t st) { skm_launch_cross<SkmBig1>(job, cj, grid, st); }
+const KhSkmWidth& kh_skm_width1() {
+    static const KhSkmWidth wd = {
+        (u32)sizeof(uint4) * SkmRec1::Q, KH_SKM_MAX_COARSE, KH_SKM_MAX_FINE, SkmUnion::MAXREC, SkmUnion::TABLE,
+        2u /* two unions of 79 KB of LDS and 1024 threads fit a CU */, skm_cross_per_cu<SkmBig1>(SKM_CROSS1_VGPRS64), skm_cross_round<SkmBig1>(),
+        kh_skm_supports_w, kh_launch_skm_scatter, kh_launch_skm_regroup, kh_launch_skm_union, skm_launch_big<SkmBig1>,
+        skm_launch_cross<SkmBig1>,
+    };
+    return wd;
+}

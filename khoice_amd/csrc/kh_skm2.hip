@@ -54,7 +54,7 @@ constexpr u32 SKM2_CWN = 10;                    // code words a thread keeps: ba
 
 }   // namespace
 
-size_t kh_skm2_scatter_lds_bytes(u32 nb1) {
+static size_t kh_skm2_scatter_lds_bytes(u32 nb1) {
     const u32 nbk = (nb1 + 3) & ~3u;
     return flush_lds_bytes<SKM2_CAP, 8>(nbk) + (size_t)SKM_CW * 4 + (((size_t)SKM_CW * 2 + 15) & ~(size_t)15) + 64 * 4 + 4 * 64 * 4 + 64;
 }
@@ -263,7 +263,7 @@ __global__ __launch_bounds__(SKM_NT, 2) void k_skm2_scatter(const KhSkmJob jb) {
     __syncthreads();
     if (staged) skm_flush<SKM_NT, SKM2_CAP, false, 8>(L, staged, jb.nb1, jb.cur1, jb.reg1, jb.cap1, jb.ctl);
     if (tid == 0 && misc[1]) atomicAdd(&jb.inst[t.seg], (unsigned long long)misc[1]);
-    if (tid == 0 && tile_recs) atomicAdd(jb.ctl + 2, tile_recs);
+    if (tid == 0 && tile_recs) atomicAdd(jb.ctl + KH_SKM_CTL_RECORDS, tile_recs);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -291,13 +291,11 @@ constexpr u32 SKM2_MAXREC = SKM2_STAGE < SKM2_UNT ? SKM2_STAGE : SKM2_UNT;   // 
 constexpr u32 SKM2_DD = SKM2_UT * 2;               // entries of the set of record contents (the high key plane)
 constexpr u32 SKM2_PASSES = 4;
 constexpr u32 SKM2_MAXCH = SKM2_PASSES * SKM2_UNT; // chunks of a slot after the merge
-size_t kh_skm2_union_lds_bytes(u32) {
+static constexpr size_t kh_skm2_union_lds_bytes(u32) {
     return (size_t)SKM2_UT * 24 + (size_t)SKM2_UT2 * 24 + 1024 + 128 + 256 + (size_t)SKM_HSTRIPE_WORDS * 4 + (size_t)SKM2_MAXCH * 2 +
            (size_t)SKM2_MAXREC * 4;
 }
-u32 kh_skm2_max_cap2() { return SKM2_MAXREC; }
-u32 kh_skm2_table() { return SKM2_UT; }
-u32 kh_skm2_union_per_cu() { return kh_skm2_union_lds_bytes(0) * 3 <= 160 * 1024 && SKM2_UNT * 3 <= 2048 ? 3u : 2u; }
+static constexpr u32 kh_skm2_union_per_cu() { return kh_skm2_union_lds_bytes(0) * 3 <= 160 * 1024 && SKM2_UNT * 3 <= 2048 ? 3u : 2u; }
 
 __device__ __forceinline__ u32 key2_hash(u64 lo, u64 hi) { return ((u32)lo ^ (u32)(lo >> 32) ^ (u32)hi ^ (u32)(hi >> 32)) * 0x9E3779B1u; }
 
@@ -452,7 +450,7 @@ __global__ __launch_bounds__(SKM2_UNT, SKM2_UNT == 1024 ? 8 : 6) void k_skm2_uni
         lane = tid & (KH_WAVE - 1u);
         const uint4* __restrict__ reg = jb.reg2 + (u64)slot * cap2 * 2;
         if (counts[slot] > fit && tid0 == 0) {   // an overfull slot: listed for k_skm_big
-            const u32 at = atomicAdd(jb.ctl + 6, 1u);
+            const u32 at = atomicAdd(jb.ctl + KH_SKM_CTL_LISTED, 1u);
             if (at < jb.big_cap) jb.big_list[at] = slot;
         }
         // ---- stage this slot's records, one per thread
@@ -535,7 +533,7 @@ __global__ __launch_bounds__(SKM2_UNT, SKM2_UNT == 1024 ? 8 : 6) void k_skm2_uni
         if (C > SKM2_MAXCH) {   // uniform: more chunks than are numbered here: k_skm_big takes the slot
             if (tid == 0) {
                 if (jb.big_list) {
-                    const u32 at = atomicAdd(jb.ctl + 6, 1u);
+                    const u32 at = atomicAdd(jb.ctl + KH_SKM_CTL_LISTED, 1u);
                     if (at < jb.big_cap) jb.big_list[at] = slot;
                 } else atomicOr(jb.ctl, KH_ERR_CAPACITY);
             }
@@ -671,8 +669,8 @@ __global__ __launch_bounds__(SKM2_UNT, SKM2_UNT == 1024 ? 8 : 6) void k_skm2_uni
     tid = tid0;
     ro.flush(jb.hist + (u64)(blockIdx.x % jb.reps) * nbins, nbins, jb.dup, tid, NT);
     if (tid == 0) {
-        if (st_full > T) atomicMax(jb.ctl + 1, st_full);
-        atomicAdd(jb.ctl + 3, st_exp);
+        if (st_full > T) atomicMax(jb.ctl + KH_SKM_CTL_FULLEST, st_full);
+        atomicAdd(jb.ctl + KH_SKM_CTL_EXPANDED, st_exp);
     }
 }
 
@@ -703,8 +701,8 @@ template <int WW> static void launch_scatter2_w(const KhSkmJob& job, u32 ntiles,
 }
 // m-mers per k-mer the two-word scatter is instantiated for: every third value, so that one of the minimizer
 // lengths 14, 15, 16 fits any k
-bool kh_skm2_supports_w(u32 w) { return w >= 18 && w <= 51 && w % 3 == 0; }
-void kh_launch_skm2_scatter(const KhSkmJob& job, u32 ntiles, hipStream_t st) {
+static bool kh_skm2_supports_w(u32 w) { return w >= 18 && w <= 51 && w % 3 == 0; }
+static void kh_launch_skm2_scatter(const KhSkmJob& job, u32 ntiles, hipStream_t st) {
     if (!ntiles) return;
     const size_t lds = kh_skm2_scatter_lds_bytes(job.nb1);
     switch (job.w) {
@@ -714,15 +712,19 @@ void kh_launch_skm2_scatter(const KhSkmJob& job, u32 ntiles, hipStream_t st) {
         default: break;   // the host asks kh_skm2_supports_w first
     }
 }
-void kh_launch_skm2_regroup(const KhSkmJob& job, hipStream_t st) { skm_launch_regroup<SkmRec2>(job, st); }
-void kh_launch_skm2_union(const KhSkmJob& job, u32 cs, u32 grid, hipStream_t st) {
+static void kh_launch_skm2_union(const KhSkmJob& job, u32 cs, u32 grid, hipStream_t st) {
     const size_t lds = kh_skm2_union_lds_bytes(job.nbins);
     skm_allow_lds(k_skm2_union, lds);
     hipLaunchKernelGGL(k_skm2_union, dim3(grid), dim3(SKM2_UNT), lds, st, job, cs, skm_first_claimed(job.nslots, grid));
 }
-void kh_launch_skm2_big(const KhSkmJob& job, u32 cs, u32 nbig, hipStream_t st) { skm_launch_big<SkmBig2>(job, cs, nbig, st); }
 // k_skm_cross (kh_skm_device.h) with two-word keys
 constexpr bool SKM_CROSS2_VGPRS64 = true;   // resource report: 58 VGPRs, 78 SGPRs (66 more kept in VGPR lanes), no scratch, 8 waves per SIMD; 64384 bytes of LDS
-u32 kh_skm2_cross_round() { return skm_cross_round<SkmBig2>(); }
-u32 kh_skm2_cross_per_cu() { return skm_cross_per_cu<SkmBig2>(SKM_CROSS2_VGPRS64); }
-void kh_launch_skm2_cross(const KhSkmJob& job, const KhSkmCrossJob& cj, u32 grid, hipStream_t st) { skm_launch_cross<SkmBig2>(job, cj, grid, st); }
+const KhSkmWidth& kh_skm_width2() {
+    static const KhSkmWidth wd = {
+        (u32)sizeof(uint4) * SkmRec2::Q, KH_SKM2_MAX_COARSE, KH_SKM2_MAX_FINE, SKM2_MAXREC, SKM2_UT,
+        kh_skm2_union_per_cu(), skm_cross_per_cu<SkmBig2>(SKM_CROSS2_VGPRS64), skm_cross_round<SkmBig2>(),
+        kh_skm2_supports_w, kh_launch_skm2_scatter, skm_launch_regroup<SkmRec2>, kh_launch_skm2_union, skm_launch_big<SkmBig2>,
+        skm_launch_cross<SkmBig2>,
+    };
+    return wd;
+}

@@ -464,7 +464,7 @@ __global__ __launch_bounds__(SKM_RG_NT, 4) void k_skm_regroup(const KhSkmJob jb)
         }
         __syncthreads();
         SkmSpill sp;
-        sp.rec = jb.spill_rec; sp.slot = jb.spill_slot; sp.n = jb.ctl + 5; sp.cap = jb.spill_cap; sp.first_slot = first_slot;
+        sp.rec = jb.spill_rec; sp.slot = jb.spill_slot; sp.n = jb.ctl + KH_SKM_CTL_SPILLED; sp.cap = jb.spill_cap; sp.first_slot = first_slot;
         skm_flush<SKM_RG_NT, CAP, true, RW>(L, n, nfine, lcur, dst, jb.cap2, jb.ctl, sp);
     }
     for (u32 i = tid; i < nfine; i += SKM_RG_NT) jb.cur2[first_slot + i] = lcur[i];
@@ -530,7 +530,7 @@ __global__ __launch_bounds__(SKM_BIG_NT) void k_skm_big(const KhSkmJob jb, u32 c
     if (tid < 8) scratch[tid] = 0;
     __syncthreads();
     // ---- this slot's records on the side list
-    u32 nspill_all = jb.ctl[5];
+    u32 nspill_all = jb.ctl[KH_SKM_CTL_SPILLED];
     nspill_all = nspill_all < jb.spill_cap ? nspill_all : jb.spill_cap;
     for (u32 i = tid; i < nspill_all; i += NT) {
         if (jb.spill_slot[i] == slot) {
@@ -559,7 +559,7 @@ __global__ __launch_bounds__(SKM_BIG_NT) void k_skm_big(const KhSkmJob jb, u32 c
     __syncthreads();
     const u32 N = scratch[2];
     const u32 R = (N + ROUND - 1u) / ROUND;
-    if (tid == 0 && N > T) atomicMax(jb.ctl + 1, N);
+    if (tid == 0 && N > T) atomicMax(jb.ctl + KH_SKM_CTL_FULLEST, N);
     for (u32 q = blockIdx.y; q < R; q += gridDim.y) {   // (the rounds are independent: workgroups (slot, y) share them out)
         // a fresh table: key planes all ones, both mask planes zero
         for (u32 i = tid; i < T * Tr::KEY_BYTES / 16; i += NT) reinterpret_cast<uint4*>(kmain)[i] = make_uint4(0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu);
@@ -620,7 +620,7 @@ __global__ __launch_bounds__(SKM_BIG_NT) void k_skm_big(const KhSkmJob jb, u32 c
         __syncthreads();
     }
     ro.flush(jb.hist + (u64)(blockIdx.x % jb.reps) * jb.nbins, jb.nbins, jb.dup, tid, NT);
-    if (tid == 0 && blockIdx.y == 0) atomicAdd(jb.ctl + 3, N);
+    if (tid == 0 && blockIdx.y == 0) atomicAdd(jb.ctl + KH_SKM_CTL_EXPANDED, N);
 }
 template <class Tr> void skm_launch_big(const KhSkmJob& job, u32 cs, u32 nbig, hipStream_t st) {
     if (!nbig) return;
@@ -642,9 +642,9 @@ template <class Tr> void skm_launch_big(const KhSkmJob& job, u32 cs, u32 nbig, h
 // the two things types 2 and 4 will have to add to this read-out.
 //
 // Two launches of one body.  DIRECT (cj.nlisted == 0): persistent workgroups walk all slots grid-strided; a slot with
-// more records than its region holds is listed (big_list, ctl[6]) as the unions list it, and skipped.  LISTED: work
+// more records than its region holds is listed (big_list, KH_SKM_CTL_LISTED) as the unions list it, and skipped.  LISTED: work
 // item i is slot big_list[i], its region plus its records on the side list.  The bins stay in LDS over the whole walk
-// and go to one replica of the device block at the end.  ctl[7]: slots taken in more than one round.
+// and go to one replica of the device block at the end.  KH_SKM_CTL_MULTI: slots taken in more than one round.
 // Nothing is tuned: no merge of identical records, read-out by a scan of the table, one slot at a time.
 // ------------------------------------------------------------------------------------------
 constexpr u32 SKM_CROSS_BINS = 1024;   // pivots x genomes of a pass at most: 32 x 32 of 64 operands
@@ -697,7 +697,7 @@ __global__ __launch_bounds__(SKM_BIG_NT, 8) void k_skm_cross(const KhSkmJob jb, 
     for (u32 i = tid; i < SKM_CROSS_BINS; i += NT) bins[i] = 0;
     u32 nspill_all = 0;
     if (listed) {
-        nspill_all = jb.ctl[5];
+        nspill_all = jb.ctl[KH_SKM_CTL_SPILLED];
         nspill_all = nspill_all < jb.spill_cap ? nspill_all : jb.spill_cap;
     }
     // one occupied entry: the pivots of its mask against every group of its genomes
@@ -733,7 +733,7 @@ __global__ __launch_bounds__(SKM_BIG_NT, 8) void k_skm_cross(const KhSkmJob jb, 
             if (!have) continue;
             if (have > cap2) {   // an overfull slot: listed for the second launch, as the unions list theirs
                 if (tid == 0) {
-                    const u32 at = atomicAdd(jb.ctl + 6, 1u);
+                    const u32 at = atomicAdd(jb.ctl + KH_SKM_CTL_LISTED, 1u);
                     if (at < jb.big_cap) jb.big_list[at] = slot;
                 }
                 continue;
@@ -837,9 +837,9 @@ __global__ __launch_bounds__(SKM_BIG_NT, 8) void k_skm_cross(const KhSkmJob jb, 
         if (bins[i]) atomicAdd(&rep[i], (unsigned long long)bins[i]);
     if (tid < (u32)KH_TAG_MAX_OPS && dupc[tid]) atomicAdd(&jb.dup[tid], (unsigned long long)dupc[tid]);
     if (tid == 0) {
-        if (st_full > T) atomicMax(jb.ctl + 1, st_full);
-        if (st_exp) atomicAdd(jb.ctl + 3, st_exp);
-        if (st_multi) atomicAdd(jb.ctl + 7, st_multi);
+        if (st_full > T) atomicMax(jb.ctl + KH_SKM_CTL_FULLEST, st_full);
+        if (st_exp) atomicAdd(jb.ctl + KH_SKM_CTL_EXPANDED, st_exp);
+        if (st_multi) atomicAdd(jb.ctl + KH_SKM_CTL_MULTI, st_multi);
     }
 }
 // workgroups of k_skm_cross<Tr> a CU holds in the direct launch: by its LDS (160 KB a CU) and by its 1024 threads

@@ -430,6 +430,23 @@ def test_exp3_skm_coarse_overflow_falls_back(eng, cross_on):
     assert same(got, sets) and d["skm_scatter"] == 0, d
 
 
+@functools.lru_cache(maxsize=None)
+def coarse_overflow_case_two_words():
+    """The same with two-word keys (k = 41): a record holds at most 63 k-mers, so a tandem repeat of 200 000 positions
+    makes at least 3 174 records for one coarse bucket, whose region holds 2 048 and a hundredth of the mean."""
+    seqs, group_of, pivots = small_species()
+    return seqs, group_of, pivots + [b"AC" * 100_000]
+
+
+@pytest.mark.gpu
+def test_exp3_skm_coarse_overflow_falls_back_two_word_keys(eng, cross_on):
+    seqs, group_of, pivots = coarse_overflow_case_two_words()
+    want = X3.oracle(seqs, group_of, pivots, 41)
+    cross_on.setenv("KHOICE_SKM_SLACK", "0.01")
+    got, d = by_sets(eng, seqs, group_of, pivots, 41, retries=1, want=want)
+    assert d["skm_scatter"] == 1 and d["builds"] == len(seqs) + len(pivots), d
+
+
 # ---------------------------------------------------------------- 7. clamps
 @pytest.mark.gpu
 @pytest.mark.parametrize("cs", (1, 2, 5000))
