@@ -985,6 +985,8 @@ struct SkmBig1 {
         return SkmClaim1{reinterpret_cast<unsigned long long*>(kmain), okey_off, ~0ull, K};
     }
 };
+static_assert(skm_big_lds_bytes<SkmBig1>() == 94720, "k_skm_big<SkmBig1>: the walk's LDS with 288 stripe words and the side-list index");
+static_assert(skm_cross_lds_bytes<SkmBig1>(false) == 81280 && skm_cross_lds_bytes<SkmBig1>(true) == 97664, "k_skm_cross<SkmBig1>: direct and listed launch");
 
 // ------------------------------------------------------------------------------------------
 // The exchange form (multi-GPU step 7-8): slots are a GLOBAL function of the minimizer, so ranks
@@ -1184,7 +1186,7 @@ __global__ __launch_bounds__(SKM_PH_NT, 8) void k_skm_phased(const KhSkmPhasedJo
             if (e >= cnt) return;
             const unsigned long long K = ((u64)ch << 32) | cl;
             const u32 H = key_hash2(cl, ch);
-            if (R != 1 && (((H >> 4) & 0xffffu) * R) >> 16 != q) return;   // another round's key
+            if (R != 1 && skm_round_of(H, R) != q) return;   // another round's key
             skm_probe_walk<T, T2>(H, jb.ctl, SkmClaim1{tkey, OKEY_OFF, emptyv, K}, [&](const bool second, const u32 S, const bool fresh) __attribute__((always_inline)) {
                 u32* const mp = tmlo + (second ? OMLO_OFF : 0u) + S;
                 if (want_dup) {   // uniform: bits set already = a second instance under that tag (rare: global counters)
@@ -1470,11 +1472,11 @@ void kh_launch_skm_phased(const KhSkmPhasedJob& job, u32 grid, hipStream_t st) {
     hipLaunchKernelGGL(k_skm_phased, dim3(grid), dim3(SKM_PH_NT), lds, st, job);
 }
 // k_skm_cross (kh_skm_device.h) with one-word keys
-constexpr bool SKM_CROSS1_VGPRS64 = true;   // resource report: 59 VGPRs, 78 SGPRs (53 more kept in VGPR lanes), no scratch, 8 waves per SIMD; 81280 bytes of LDS
+constexpr bool SKM_CROSS1_VGPRS64 = true;   // resource report: 59 VGPRs, 78 SGPRs (54 more kept in VGPR lanes), no scratch, 8 waves per SIMD; 81280 bytes of LDS
 const KhSkmWidth& kh_skm_width1() {
     static const KhSkmWidth wd = {
         (u32)sizeof(uint4) * SkmRec1::Q, KH_SKM_MAX_COARSE, KH_SKM_MAX_FINE, SkmUnion::MAXREC, SkmUnion::TABLE,
-        2u /* two unions of 79 KB of LDS and 1024 threads fit a CU */, skm_cross_per_cu<SkmBig1>(SKM_CROSS1_VGPRS64), skm_cross_round<SkmBig1>(),
+        2u /* two unions of 79 KB of LDS and 1024 threads fit a CU */, skm_cross_per_cu<SkmBig1>(SKM_CROSS1_VGPRS64), skm_walk_round<SkmBig1>(),
         kh_skm_supports_w, kh_launch_skm_scatter, kh_launch_skm_regroup, kh_launch_skm_union, skm_launch_big<SkmBig1>,
         skm_launch_cross<SkmBig1>,
     };

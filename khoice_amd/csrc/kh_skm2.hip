@@ -691,6 +691,8 @@ struct SkmBig2 {
         return SkmClaim2{reinterpret_cast<unsigned long long*>(kmain), T, okey_off, T2, K};
     }
 };
+static_assert(skm_big_lds_bytes<SkmBig2>() == 77824, "k_skm_big<SkmBig2>: the walk's LDS with 288 stripe words and the side-list index");
+static_assert(skm_cross_lds_bytes<SkmBig2>(false) == 64384 && skm_cross_lds_bytes<SkmBig2>(true) == 80768, "k_skm_cross<SkmBig2>: direct and listed launch");
 
 // ------------------------------------------------------------------------------------------
 // launchers
@@ -718,11 +720,11 @@ static void kh_launch_skm2_union(const KhSkmJob& job, u32 cs, u32 grid, hipStrea
     hipLaunchKernelGGL(k_skm2_union, dim3(grid), dim3(SKM2_UNT), lds, st, job, cs, skm_first_claimed(job.nslots, grid));
 }
 // k_skm_cross (kh_skm_device.h) with two-word keys
-constexpr bool SKM_CROSS2_VGPRS64 = true;   // resource report: 58 VGPRs, 78 SGPRs (66 more kept in VGPR lanes), no scratch, 8 waves per SIMD; 64384 bytes of LDS
+constexpr bool SKM_CROSS2_VGPRS64 = true;   // resource report: 56 VGPRs, 78 SGPRs (66 more kept in VGPR lanes), no scratch, 8 waves per SIMD; 64384 bytes of LDS
 const KhSkmWidth& kh_skm_width2() {
     static const KhSkmWidth wd = {
         (u32)sizeof(uint4) * SkmRec2::Q, KH_SKM2_MAX_COARSE, KH_SKM2_MAX_FINE, SKM2_MAXREC, SKM2_UT,
-        kh_skm2_union_per_cu(), skm_cross_per_cu<SkmBig2>(SKM_CROSS2_VGPRS64), skm_cross_round<SkmBig2>(),
+        kh_skm2_union_per_cu(), skm_cross_per_cu<SkmBig2>(SKM_CROSS2_VGPRS64), skm_walk_round<SkmBig2>(),
         kh_skm2_supports_w, kh_launch_skm2_scatter, skm_launch_regroup<SkmRec2>, kh_launch_skm2_union, skm_launch_big<SkmBig2>,
         skm_launch_cross<SkmBig2>,
     };

@@ -1,7 +1,8 @@
 // khoice_amd — device helpers shared by the two super-k-mer kernel files (kh_skm.hip: one-word keys,
 // kh_skm2.hip: two-word keys): minimizer hashing, sliding minimum, the LDS counting-sort flush, code-word prefetch,
 // and the pieces both key widths are built from: the record formats (kh_skm_rec.h), the one-key probe walk, the
-// read-out of genome masks into histogram bins, the regroup kernel and the kernel of the overfull slots.
+// read-out of genome masks into histogram bins, the regroup kernel, the walk of one slot and the two kernels built on
+// it (k_skm_big: the overfull slots; k_skm_cross: experiment type 3).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -284,6 +285,9 @@ __device__ __forceinline__ void skm_probe_walk(const u32 H, u32* __restrict__ ct
         }
     }
 }
+// the round (of R < 65536) in which a slot taken in R rounds of key subsets inserts a key: sixteen hash bits scaled to
+// [0, R) (k_skm_big, k_skm_cross, k_skm_phased; the unions decide the same for all keys of a thread at once)
+__device__ __forceinline__ u32 skm_round_of(const u32 H, const u32 R) { return (((H >> 4) & 0xffffu) * R) >> 16; }
 
 // ------------------------------------------------------------------------------------------
 // Read-out: the genome mask of one distinct k-mer -> histogram bins, kept in LDS until the workgroup ends.
@@ -294,6 +298,13 @@ __device__ __forceinline__ void skm_probe_walk(const u32 H, u32* __restrict__ ct
 // from an opaque copy of threadIdx.x (LDS addresses formed from them are then not kept live across the slot loop).
 // ------------------------------------------------------------------------------------------
 constexpr u32 SKM_HSTRIPE_WORDS = 288;
+// an operand's entry of a group table: the mask of its group (two halves) from its ginfo word g (first operand of the
+// group, operands in it, first bin: 8 + 8 + 16 bits), and a third word that is the read-out's own
+__device__ __forceinline__ uint4 skm_group_entry(const u32 g, const u32 z) {
+    const u32 g0 = g & 0xffu, gn = (g >> 8) & 0xffu;
+    const u64 gm = gn ? (gn >= 64u ? ~0ull : ((1ull << gn) - 1ull)) << g0 : 0ull;
+    return make_uint4((u32)gm, (u32)(gm >> 32), z, 0u);
+}
 struct SkmReadout {
     uint4* gtab;    // [KH_TAG_MAX_OPS] per operand: its group's mask (two halves), first bin << sshift
     u32* hstripe;   // [SKM_HSTRIPE_WORDS]
@@ -304,9 +315,8 @@ struct SkmReadout {
         sshift = nbins <= 72u ? 2u : (nbins <= 144u ? 1u : 0u);
         abase = abase_;
         if (tid < (u32)KH_TAG_MAX_OPS) {
-            const u32 g = ginfo[tid], g0 = g & 0xffu, gn = (g >> 8) & 0xffu;
-            const u64 gm = gn ? (gn >= 64u ? ~0ull : ((1ull << gn) - 1ull)) << g0 : 0ull;
-            gtab[tid] = make_uint4((u32)gm, (u32)(gm >> 32), (g >> 16) << sshift, 0u);
+            const u32 g = ginfo[tid];
+            gtab[tid] = skm_group_entry(g, (g >> 16) << sshift);
             dupc[tid] = 0;
         }
         if (tid < SKM_HSTRIPE_WORDS) hstripe[tid] = 0;
@@ -476,151 +486,207 @@ template <class Rec> void skm_launch_regroup(const KhSkmJob& job, hipStream_t st
 }
 
 // ------------------------------------------------------------------------------------------
-// Overfull slots.  A minimizer that far more k-mers share than a hash predicts — poly-A, a tandem repeat's unit, an
-// insertion sequence in 50 copies — fills its slot's region; the regroup puts what does not fit on a side list and
-// the union leaves such slots alone (as it does slots with more chunks than it numbers).  Here one workgroup takes
-// one of them whatever its size: the records in the region, then its records on the side list (found by a scan of
-// the list: it is short), every k-mer into the table by the probe walk above, in rounds of key subsets shared out
-// over blockIdx.y; no merge of identical records, read-out by a scan of the table.  A handful of slots per run:
-// nothing here is tuned, it only has to be right and to keep the run in the fast form.
+// The walk of ONE slot whatever its size, by one workgroup (k_skm_big: the slots the unions leave alone; k_skm_cross:
+// every slot of experiment type 3).  The records in the slot's region, then — where asked — its records on the side
+// list (found by a scan of the list: it is short); their k-mer instances are counted (N) and taken in
+// R = ceil(N / skm_walk_round) rounds of key subsets (skm_round_of).  A round clears the table, numbers the chunks of
+// the records in batches of Tr::BATCH, puts every k-mer of its subset into the table by the probe walk above, the bit
+// of the record's operand into the mask plane of its half, and hands the table to the read-out the caller supplies,
+// which scans it with for_each_occupied.  No merge of identical records: nothing here is tuned, it only has to be right.
 //
-// One kernel for both key widths.  Tr (SkmBig1 in kh_skm.hip, SkmBig2 in kh_skm2.hip) supplies:
+// One walk for both key widths.  Tr (SkmBig1 in kh_skm.hip, SkmBig2 in kh_skm2.hip) supplies:
 //   Rec, Consts, Key         the record format, the per-launch constants of the expander, a canonical key
 //   T, T2, KEY_BYTES         main and second table; per entry KEY_BYTES of key planes (u64 planes, the first of
-//                            which is all ones in an empty entry), then two u32 planes: the halves of the genome mask
+//                            which is all ones in an empty entry), then two u32 planes: the halves of the operand mask
 //   BATCH, OB, E             records numbered at a time; bits of a chunk's number inside its record; k-mers per chunk
 //   expand(r, first, kc, f)  the chunk expander: f(e, key) for the E k-mers from k-mer `first` of record r on
 //   hash(key), claim(main, off, key)      the table hash; the claim functor of the probe walk (key planes of the main
 //                            table, the second table's `off` u64 behind them)
 // ------------------------------------------------------------------------------------------
 constexpr u32 SKM_BIG_NT = 1024, SKM_BIG_IDX = 4096;   // threads; records of one slot on the side list that are indexed
-template <class Tr> constexpr size_t skm_big_lds_bytes() {
-    return (size_t)(Tr::T + Tr::T2) * (Tr::KEY_BYTES + 8) + 1024 + 128 + 256 + (size_t)SKM_HSTRIPE_WORDS * 4 +
-           (size_t)(Tr::BATCH << Tr::OB) * 2 + (size_t)SKM_BIG_IDX * 4;
-}
+template <class Tr> constexpr u32 skm_walk_round() { return Tr::T - Tr::T / 4; }   // k-mer instances a round takes
+
+// The walk's LDS.  BINW: the words a kernel keeps for its bins.  sidx comes last: a launch that reads no side list
+// leaves it out (bytes(false)).
+template <class Tr, u32 BINW> struct SkmWalkLds {
+    static constexpr u32 T = Tr::T, T2 = Tr::T2, KB = Tr::KEY_BYTES, MAXCH = Tr::BATCH << Tr::OB;
+    static constexpr u32 KMAIN = 0, TMLO = KMAIN + T * KB, TMHI = TMLO + T * 4, KSECOND = TMHI + T * 4, OMLO = KSECOND + T2 * KB,
+                         OMHI = OMLO + T2 * 4, GTAB = OMHI + T2 * 4, SCRATCH = GTAB + 1024, DUPC = SCRATCH + 128, BINS = DUPC + 256,
+                         OWNER = BINS + BINW * 4, SIDX = OWNER + MAXCH * 2;
+    static constexpr size_t bytes(bool side) { return SIDX + (side ? SKM_BIG_IDX * 4 : 0); }
+    // the second table behind the main one: its mask planes from tmlo in words, its key planes from kmain in u64 (one
+    // base pointer and integer offsets: a choice between two pointers held by reference is a choice between their
+    // homes in memory)
+    static constexpr u32 OMASK_OFF = (OMLO - TMLO) / 4, OKEY_OFF = (KSECOND - KMAIN) / 8;
+    u8* kmain;      // [T * KB] key planes of the main table
+    u32* tmlo;      // [T] [T] the two halves of its operand masks (tmhi follows tmlo)
+    u32* tmhi;
+    u8* ksecond;    // [T2 * KB] [T2] [T2] the second table, likewise
+    u32* omlo;
+    u32* omhi;
+    uint4* gtab;    // [KH_TAG_MAX_OPS] per operand: its group's mask (skm_group_entry)
+    u32* scratch;   // [0] chunks, [2] k-mers, [3] side-list records
+    u32* dupc;      // [KH_TAG_MAX_OPS] per operand: instances whose (k-mer, operand) pair was seen before
+    u32* bins;      // [BINW]
+    u16* owner;     // [MAXCH] a chunk's record inside the batch << OB | its number inside the record
+    u32* sidx;      // [SKM_BIG_IDX] this slot's records on the side list
+    __device__ __forceinline__ explicit SkmWalkLds(u8* b)
+        : kmain(b + KMAIN), tmlo(reinterpret_cast<u32*>(b + TMLO)), tmhi(reinterpret_cast<u32*>(b + TMHI)), ksecond(b + KSECOND),
+          omlo(reinterpret_cast<u32*>(b + OMLO)), omhi(reinterpret_cast<u32*>(b + OMHI)), gtab(reinterpret_cast<uint4*>(b + GTAB)),
+          scratch(reinterpret_cast<u32*>(b + SCRATCH)), dupc(reinterpret_cast<u32*>(b + DUPC)), bins(reinterpret_cast<u32*>(b + BINS)),
+          owner(reinterpret_cast<u16*>(b + OWNER)), sidx(reinterpret_cast<u32*>(b + SIDX)) {}
+};
+
+template <class Tr, u32 BINW> struct SkmSlotWalk {
+    using Rec = typename Tr::Rec;
+    using Lds = SkmWalkLds<Tr, BINW>;
+    static constexpr u32 NT = SKM_BIG_NT, T = Tr::T, T2 = Tr::T2, Q = Rec::Q, MAXCH = Lds::MAXCH, E = (u32)Tr::E;
+    static constexpr u64 EMPTY = ~0ull;
+    const Lds L;
+    const KhSkmJob& jb;
+    const typename Tr::Consts kc;
+    const u32 tid, lane;
+    // the slot in hand (open): its region, records there and in all, k-mer instances, rounds
+    const uint4* __restrict__ reg;
+    u32 nreg, nall, N, R;
+    __device__ __forceinline__ SkmSlotWalk(u8* lds, const KhSkmJob& jb_) : L(lds), jb(jb_), kc(jb_.k), tid(threadIdx.x), lane(lane_id()) {}
+    // (a barrier follows before open)
+    __device__ __forceinline__ void reset() const { if (tid < 8) L.scratch[tid] = 0; }
+    __device__ __forceinline__ u32 side_records() const {
+        const u32 n = jb.ctl[KH_SKM_CTL_SPILLED];
+        return n < jb.spill_cap ? n : jb.spill_cap;
+    }
+    // uint4 q of record i; the header sits in the last word of uint4 Q - 1
+    __device__ __forceinline__ uint4 rec_q(const u32 i, const u32 q) const {
+        return i < nreg ? reg[(u64)Q * i + q] : jb.spill_rec[(u64)Q * L.sidx[i - nreg] + q];
+    }
+    // Slot `slot` with `have` records written to its region; side (uniform): also its records among the `nspill` of
+    // the side list.  Behind it N and R are known to every thread.
+    __device__ __forceinline__ void open(const u32 slot, const u32 have, const bool side, const u32 nspill) {
+        u32 nside = 0;
+        if (side) {
+            for (u32 i = tid; i < nspill; i += NT) {
+                if (jb.spill_slot[i] == slot) {
+                    const u32 at = atomicAdd(&L.scratch[3], 1u);
+                    if (at < SKM_BIG_IDX) L.sidx[at] = i;
+                }
+            }
+            __syncthreads();
+            nside = L.scratch[3];
+            if (nside > SKM_BIG_IDX) {   // (more than the walk indexes: the host falls back)
+                if (tid == 0) atomicOr(jb.ctl, KH_ERR_CAPACITY);
+                nside = SKM_BIG_IDX;
+            }
+        }
+        nreg = have < jb.cap2 ? have : jb.cap2;   // (full for an overfull slot; a slot listed for its chunks may hold fewer)
+        reg = jb.reg2 + (u64)slot * jb.cap2 * Q;
+        nall = nreg + nside;
+        {
+            u32 mine = 0;
+            for (u32 i = tid; i < nall; i += NT) mine += Rec::n(rec_q(i, Q - 1).w);
+            const u32 tot = wave_scan_add(mine);
+            if (lane == KH_WAVE - 1 && tot) atomicAdd(&L.scratch[2], tot);
+        }
+        __syncthreads();
+        N = L.scratch[2];
+        R = (N + skm_walk_round<Tr>() - 1u) / skm_walk_round<Tr>();
+    }
+    // Rounds q0, q0 + qstep, ... of the slot: readout() is called with the round's masks final, a barrier follows it.
+    template <class Readout> __device__ __forceinline__ void rounds(const u32 q0, const u32 qstep, Readout&& readout) {
+        for (u32 q = q0; q < R; q += qstep) {
+            // a fresh table: key planes all ones, both mask planes zero
+            for (u32 i = tid; i < T * Tr::KEY_BYTES / 16; i += NT) reinterpret_cast<uint4*>(L.kmain)[i] = make_uint4(0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu);
+            for (u32 i = tid; i < T2 * Tr::KEY_BYTES / 16; i += NT) reinterpret_cast<uint4*>(L.ksecond)[i] = make_uint4(0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu);
+            for (u32 i = tid; i < T / 2; i += NT) reinterpret_cast<uint4*>(L.tmlo)[i] = make_uint4(0u, 0u, 0u, 0u);
+            if (tid < T2) { L.omlo[tid] = 0u; L.omhi[tid] = 0u; }
+            __syncthreads();
+            for (u32 b0 = 0; b0 < nall; b0 += Tr::BATCH) {   // batches of records, one per thread of the first waves
+                const u32 mine_i = b0 + tid;
+                const u32 nj = tid < Tr::BATCH && mine_i < nall ? Rec::n(rec_q(mine_i, Q - 1).w) : 0u;
+                const u32 nch = (nj + E - 1u) / E;
+                {
+                    const u32 incl = wave_scan_add(nch);
+                    u32 wbase = 0;
+                    if (lane == KH_WAVE - 1 && incl) wbase = atomicAdd(&L.scratch[0], incl);
+                    wbase = (u32)__builtin_amdgcn_readlane((int)wbase, KH_WAVE - 1);
+                    const u32 cstart = wbase + incl - nch;
+                    if (cstart + nch <= MAXCH)
+                        for (u32 cc = 0; cc < nch; ++cc) L.owner[cstart + cc] = (u16)((tid << Tr::OB) | cc);
+                }
+                __syncthreads();
+                u32 C = L.scratch[0];
+                if (C > MAXCH) {   // (cannot happen: a record has at most 1 << OB chunks)
+                    if (tid == 0) atomicOr(jb.ctl, KH_ERR_CAPACITY);
+                    C = 0;
+                }
+                for (u32 c = tid; c < C; c += NT) {
+                    const u32 o = L.owner[c], ri = b0 + (o >> Tr::OB), first = (o & ((1u << Tr::OB) - 1u)) * E;
+                    SkmRecord<Q> r0;
+#pragma unroll
+                    for (u32 qq = 0; qq < Q; ++qq) r0.v[qq] = rec_q(ri, qq);
+                    const u32 hw = r0.v[Q - 1].w;
+                    const u32 tg = Rec::tag(hw), bit = 1u << (tg & 31u), half = Rec::half(hw);
+                    const u32 cnt = Rec::n(hw) - first;   // k-mers of the record from `first` on: the chunk holds min(cnt, E)
+                    Tr::expand(r0, first, kc, [&](const u32 e, const typename Tr::Key& K) __attribute__((always_inline)) {
+                        if (e >= cnt) return;
+                        const u32 H = Tr::hash(K);
+                        if (R != 1 && skm_round_of(H, R) != q) return;   // another round's key
+                        skm_probe_walk<T, T2>(H, jb.ctl, Tr::claim(L.kmain, Lds::OKEY_OFF, K), [&](const bool second, const u32 S, bool) __attribute__((always_inline)) {
+                            u32* const mp = L.tmlo + (second ? Lds::OMASK_OFF + half * T2 : half * T) + S;
+                            if (atomicOr(mp, bit) & bit) atomicAdd(&L.dupc[tg], 1u);   // this operand had the k-mer already
+                        });
+                    });
+                }
+                __syncthreads();
+                if (tid == 0) L.scratch[0] = 0;
+                __syncthreads();
+            }
+            readout();
+            __syncthreads();
+        }
+    }
+    // f(mlo, mhi): the operand mask of every occupied entry of the round's table
+    template <class F> __device__ __forceinline__ void for_each_occupied(F&& f) const {
+        for (u32 i = tid; i < T; i += NT)
+            if (reinterpret_cast<const u64*>(L.kmain)[i] != EMPTY) f(L.tmlo[i], L.tmhi[i]);
+        if (tid < T2 && reinterpret_cast<const u64*>(L.ksecond)[tid] != EMPTY) f(L.omlo[tid], L.omhi[tid]);
+    }
+};
+
+// ------------------------------------------------------------------------------------------
+// Overfull slots.  A minimizer that far more k-mers share than a hash predicts — poly-A, a tandem repeat's unit, an
+// insertion sequence in 50 copies — fills its slot's region; the regroup puts what does not fit on a side list and
+// the union leaves such slots alone (as it does slots with more chunks than it numbers).  Here one workgroup takes
+// one of them by the walk above, always with its records on the side list; the rounds are shared out over
+// blockIdx.y, and each is read out through SkmReadout into the histograms of experiment type 1.  A handful of slots
+// per run.  KH_SKM_CTL_FULLEST: an atomic per slot; KH_SKM_CTL_EXPANDED: by the workgroup of blockIdx.y == 0.
+// ------------------------------------------------------------------------------------------
+template <class Tr> constexpr size_t skm_big_lds_bytes() { return SkmWalkLds<Tr, SKM_HSTRIPE_WORDS>::bytes(true); }
 template <class Tr>
 __global__ __launch_bounds__(SKM_BIG_NT) void k_skm_big(const KhSkmJob jb, u32 cs) {
     extern __shared__ __attribute__((aligned(16))) u8 lds_raw[];
-    using Rec = typename Tr::Rec;
-    constexpr u32 NT = SKM_BIG_NT, T = Tr::T, T2 = Tr::T2, Q = Rec::Q, MAXCH = Tr::BATCH << Tr::OB;
-    constexpr u32 ROUND = T - T / 4;   // k-mer instances a round takes
-    constexpr u32 E = (u32)Tr::E;
-    constexpr u64 EMPTY = ~0ull;
-    u8* p = lds_raw;
-    u8* kmain = p;                                                         p += (size_t)T * Tr::KEY_BYTES;
-    u32* tmlo = reinterpret_cast<u32*>(p);                                 p += (size_t)T * 4;
-    u32* tmhi = reinterpret_cast<u32*>(p);                                 p += (size_t)T * 4;
-    u8* ksecond = p;                                                       p += (size_t)T2 * Tr::KEY_BYTES;
-    u32* omlo = reinterpret_cast<u32*>(p);                                 p += (size_t)T2 * 4;
-    u32* omhi = reinterpret_cast<u32*>(p);                                 p += (size_t)T2 * 4;
-    constexpr u32 omask_off = (T * 8 + T2 * Tr::KEY_BYTES) / 4;            // omlo - tmlo
-    constexpr u32 okey_off = T * (Tr::KEY_BYTES + 8) / 8;                  // the second table's key planes behind the main one's, in u64
+    SkmSlotWalk<Tr, SKM_HSTRIPE_WORDS> w(lds_raw, jb);
     SkmReadout ro;
-    ro.gtab = reinterpret_cast<uint4*>(p);                                 p += 1024;
-    u32* scratch = reinterpret_cast<u32*>(p);                              p += 128;   // [0] chunks, [2] k-mers, [3] side-list records
-    ro.dupc = reinterpret_cast<u32*>(p);                                   p += 256;
-    ro.hstripe = reinterpret_cast<u32*>(p);                                p += (size_t)SKM_HSTRIPE_WORDS * 4;
-    u16* owner = reinterpret_cast<u16*>(p);                                p += (size_t)MAXCH * 2;
-    u32* sidx = reinterpret_cast<u32*>(p);                                 // [SKM_BIG_IDX] this slot's records on the side list
-    const u32 tid = threadIdx.x, lane = lane_id();
-    const u32 cap2 = jb.cap2;
+    ro.gtab = w.L.gtab;
+    ro.dupc = w.L.dupc;
+    ro.hstripe = w.L.bins;
     const u32 slot = jb.big_list[blockIdx.x];
-    const typename Tr::Consts kc(jb.k);
-    ro.init(jb.ginfo, jb.nbins, jb.abase, tid);
-    if (tid < 8) scratch[tid] = 0;
+    ro.init(jb.ginfo, jb.nbins, jb.abase, w.tid);
+    w.reset();
     __syncthreads();
-    // ---- this slot's records on the side list
-    u32 nspill_all = jb.ctl[KH_SKM_CTL_SPILLED];
-    nspill_all = nspill_all < jb.spill_cap ? nspill_all : jb.spill_cap;
-    for (u32 i = tid; i < nspill_all; i += NT) {
-        if (jb.spill_slot[i] == slot) {
-            const u32 at = atomicAdd(&scratch[3], 1u);
-            if (at < SKM_BIG_IDX) sidx[at] = i;
-        }
-    }
-    __syncthreads();
-    u32 nside = scratch[3];
-    if (nside > SKM_BIG_IDX) {   // (more than this kernel indexes: the host falls back)
-        if (tid == 0) atomicOr(jb.ctl, KH_ERR_CAPACITY);
-        nside = SKM_BIG_IDX;
-    }
-    const u32 nreg = jb.cur2[slot] < cap2 ? jb.cur2[slot] : cap2;   // (full for an overfull slot; a slot listed for its chunks may hold fewer)
-    const uint4* __restrict__ reg = jb.reg2 + (u64)slot * cap2 * Q;
-    const u32 nall = nreg + nside;
-    // uint4 q of record i; the header sits in the last word of uint4 Q - 1
-    auto rec_q = [&](u32 i, u32 q) __attribute__((always_inline)) -> uint4 { return i < nreg ? reg[(u64)Q * i + q] : jb.spill_rec[(u64)Q * sidx[i - nreg] + q]; };
-    // ---- k-mer instances of the slot -> rounds
-    {
-        u32 mine = 0;
-        for (u32 i = tid; i < nall; i += NT) mine += Rec::n(rec_q(i, Q - 1).w);
-        const u32 tot = wave_scan_add(mine);
-        if (lane == KH_WAVE - 1 && tot) atomicAdd(&scratch[2], tot);
-    }
-    __syncthreads();
-    const u32 N = scratch[2];
-    const u32 R = (N + ROUND - 1u) / ROUND;
-    if (tid == 0 && N > T) atomicMax(jb.ctl + KH_SKM_CTL_FULLEST, N);
-    for (u32 q = blockIdx.y; q < R; q += gridDim.y) {   // (the rounds are independent: workgroups (slot, y) share them out)
-        // a fresh table: key planes all ones, both mask planes zero
-        for (u32 i = tid; i < T * Tr::KEY_BYTES / 16; i += NT) reinterpret_cast<uint4*>(kmain)[i] = make_uint4(0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu);
-        for (u32 i = tid; i < T2 * Tr::KEY_BYTES / 16; i += NT) reinterpret_cast<uint4*>(ksecond)[i] = make_uint4(0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu);
-        for (u32 i = tid; i < T / 2; i += NT) reinterpret_cast<uint4*>(tmlo)[i] = make_uint4(0u, 0u, 0u, 0u);
-        if (tid < T2) { omlo[tid] = 0u; omhi[tid] = 0u; }
-        __syncthreads();
-        for (u32 b0 = 0; b0 < nall; b0 += Tr::BATCH) {   // batches of records, one per thread of the first waves
-            const u32 mine_i = b0 + tid;
-            const u32 nj = tid < Tr::BATCH && mine_i < nall ? Rec::n(rec_q(mine_i, Q - 1).w) : 0u;
-            const u32 nch = (nj + E - 1u) / E;
-            {
-                const u32 incl = wave_scan_add(nch);
-                u32 wbase = 0;
-                if (lane == KH_WAVE - 1 && incl) wbase = atomicAdd(&scratch[0], incl);
-                wbase = (u32)__builtin_amdgcn_readlane((int)wbase, KH_WAVE - 1);
-                const u32 cstart = wbase + incl - nch;
-                if (cstart + nch <= MAXCH)
-                    for (u32 cc = 0; cc < nch; ++cc) owner[cstart + cc] = (u16)((tid << Tr::OB) | cc);
-            }
-            __syncthreads();
-            u32 C = scratch[0];
-            if (C > MAXCH) {   // (cannot happen: a record has at most 1 << OB chunks)
-                if (tid == 0) atomicOr(jb.ctl, KH_ERR_CAPACITY);
-                C = 0;
-            }
-            for (u32 c = tid; c < C; c += NT) {
-                const u32 o = owner[c], ri = b0 + (o >> Tr::OB), first = (o & ((1u << Tr::OB) - 1u)) * E;
-                SkmRecord<Q> r0;
-#pragma unroll
-                for (u32 qq = 0; qq < Q; ++qq) r0.v[qq] = rec_q(ri, qq);
-                const u32 hw = r0.v[Q - 1].w;
-                const u32 tg = Rec::tag(hw), bit = 1u << (tg & 31u), half = Rec::half(hw);
-                const u32 cnt = Rec::n(hw) - first;   // k-mers of the record from `first` on: the chunk holds min(cnt, E)
-                Tr::expand(r0, first, kc, [&](const u32 e, const typename Tr::Key& K) __attribute__((always_inline)) {
-                    if (e >= cnt) return;
-                    const u32 H = Tr::hash(K);
-                    if (R != 1 && (((H >> 4) & 0xffffu) * R) >> 16 != q) return;   // another round's key
-                    skm_probe_walk<T, T2>(H, jb.ctl, Tr::claim(kmain, okey_off, K), [&](const bool second, const u32 S, bool) __attribute__((always_inline)) {
-                        // (the planes of the two mask halves follow each other; one base pointer and integer offsets:
-                        // a choice between two pointers held by reference is a choice between their homes in memory)
-                        u32* const mp = tmlo + (second ? omask_off + half * T2 : half * T) + S;
-                        if (atomicOr(mp, bit) & bit) atomicAdd(&ro.dupc[tg], 1u);   // this genome had the k-mer already
-                    });
-                });
-            }
-            __syncthreads();
-            if (tid == 0) scratch[0] = 0;
-            __syncthreads();
-        }
-        // ---- read-out: every occupied entry
-        u32 ones = 0;
-        for (u32 i = tid; i < T; i += NT)
-            if (reinterpret_cast<const u64*>(kmain)[i] != EMPTY && ro.eval_mask(lane, tmlo[i], tmhi[i], cs)) ++ones;
-        if (tid < T2 && reinterpret_cast<const u64*>(ksecond)[tid] != EMPTY && ro.eval_mask(lane, omlo[tid], omhi[tid], cs)) ++ones;
+    w.open(slot, jb.cur2[slot], true, w.side_records());
+    if (w.tid == 0 && w.N > Tr::T) atomicMax(jb.ctl + KH_SKM_CTL_FULLEST, w.N);
+    // (the rounds are independent: workgroups (slot, y) share them out)
+    w.rounds(blockIdx.y, gridDim.y, [&]() __attribute__((always_inline)) {
+        u32 ones = 0;   // entries in exactly one group: counted per wave
+        w.for_each_occupied([&](const u32 mlo, const u32 mhi) __attribute__((always_inline)) {
+            if (ro.eval_mask(w.lane, mlo, mhi, cs)) ++ones;
+        });
         ones = wave_scan_add(ones);
-        if (lane == KH_WAVE - 1 && ones) ro.add_single_group(ones);
-        __syncthreads();
-    }
-    ro.flush(jb.hist + (u64)(blockIdx.x % jb.reps) * jb.nbins, jb.nbins, jb.dup, tid, NT);
-    if (tid == 0 && blockIdx.y == 0) atomicAdd(jb.ctl + KH_SKM_CTL_EXPANDED, N);
+        if (w.lane == KH_WAVE - 1 && ones) ro.add_single_group(ones);
+    });
+    ro.flush(jb.hist + (u64)(blockIdx.x % jb.reps) * jb.nbins, jb.nbins, jb.dup, w.tid, SKM_BIG_NT);
+    if (w.tid == 0 && blockIdx.y == 0) atomicAdd(jb.ctl + KH_SKM_CTL_EXPANDED, w.N);
 }
 template <class Tr> void skm_launch_big(const KhSkmJob& job, u32 cs, u32 nbig, hipStream_t st) {
     if (!nbig) return;
@@ -634,72 +700,40 @@ template <class Tr> void skm_launch_big(const KhSkmJob& job, u32 cs, u32 nbig, h
 // ------------------------------------------------------------------------------------------
 // Experiment type 3 (kh_exp3_run above the bitmaps): pivots against groups from the same records.  The operands are
 // the genomes in group-major order, then the pivots (read sets) of the pass as further tags: bit t of a key's 64-bit
-// mask says that operand t holds it.  k_skm_big's walk of one slot — count the instances, rounds of key subsets,
-// chunks numbered in batches, every k-mer into the table by the probe walk, the operand's bit into the mask plane of
-// its half — and a read-out that knows the pivots: an entry whose mask holds pivots P and, of group g, c >= 1
-// genomes adds one to bin q * ngenomes + (first genome of g) + c - 1 for every q in P (k_bmp_cross's bins; the host
-// clamps the counts).  An entry no pivot holds counts nowhere.  No counter across groups, no own-group exception:
-// the two things types 2 and 4 will have to add to this read-out.
+// mask says that operand t holds it.  The walk above, every round of a slot in turn, and a read-out that knows the
+// pivots: an entry whose mask holds pivots P and, of group g, c >= 1 genomes adds one to bin
+// q * ngenomes + (first genome of g) + c - 1 for every q in P (k_bmp_cross's bins; the host clamps the counts).  An
+// entry no pivot holds counts nowhere.  No counter across groups, no own-group exception: the two things types 2 and
+// 4 will have to add, each as a read-out of its own beside count_entry.
 //
 // Two launches of one body.  DIRECT (cj.nlisted == 0): persistent workgroups walk all slots grid-strided; a slot with
 // more records than its region holds is listed (big_list, KH_SKM_CTL_LISTED) as the unions list it, and skipped.  LISTED: work
 // item i is slot big_list[i], its region plus its records on the side list.  The bins stay in LDS over the whole walk
-// and go to one replica of the device block at the end.  KH_SKM_CTL_MULTI: slots taken in more than one round.
-// Nothing is tuned: no merge of identical records, read-out by a scan of the table, one slot at a time.
+// and go to one replica of the device block at the end; so do the statistics, kept in registers until then.
+// KH_SKM_CTL_MULTI: slots taken in more than one round.
 // ------------------------------------------------------------------------------------------
 constexpr u32 SKM_CROSS_BINS = 1024;   // pivots x genomes of a pass at most: 32 x 32 of 64 operands
-template <class Tr> constexpr u32 skm_cross_round() { return Tr::T - Tr::T / 4; }   // k-mer instances a round takes (k_skm_big's ROUND)
-// the round (of R < 65536) a key belongs to: k_skm_big's rule, sixteen hash bits scaled to [0, R)
-__device__ __forceinline__ u32 skm_cross_round_of(const u32 H, const u32 R) {
-    const u32 part = (H >> 4) & 0xffffu;
-    return (part * R) >> 16;
-}
-template <class Tr> constexpr size_t skm_cross_lds_bytes(bool listed) {
-    return (size_t)(Tr::T + Tr::T2) * (Tr::KEY_BYTES + 8) + 1024 + 128 + 256 + (size_t)SKM_CROSS_BINS * 4 +
-           (size_t)(Tr::BATCH << Tr::OB) * 2 + (listed ? (size_t)SKM_BIG_IDX * 4 : 0);
-}
+template <class Tr> constexpr size_t skm_cross_lds_bytes(bool listed) { return SkmWalkLds<Tr, SKM_CROSS_BINS>::bytes(listed); }
 template <class Tr>
 __global__ __launch_bounds__(SKM_BIG_NT, 8) void k_skm_cross(const KhSkmJob jb, const KhSkmCrossJob cj) {
     extern __shared__ __attribute__((aligned(16))) u8 lds_raw[];
-    using Rec = typename Tr::Rec;
-    constexpr u32 NT = SKM_BIG_NT, T = Tr::T, T2 = Tr::T2, Q = Rec::Q, MAXCH = Tr::BATCH << Tr::OB;
-    constexpr u32 ROUND = skm_cross_round<Tr>();
-    constexpr u32 E = (u32)Tr::E;
-    constexpr u64 EMPTY = ~0ull;
-    u8* p = lds_raw;
-    u8* kmain = p;                                                         p += (size_t)T * Tr::KEY_BYTES;
-    u32* tmlo = reinterpret_cast<u32*>(p);                                 p += (size_t)T * 4;
-    u32* tmhi = reinterpret_cast<u32*>(p);                                 p += (size_t)T * 4;
-    u8* ksecond = p;                                                       p += (size_t)T2 * Tr::KEY_BYTES;
-    u32* omlo = reinterpret_cast<u32*>(p);                                 p += (size_t)T2 * 4;
-    u32* omhi = reinterpret_cast<u32*>(p);                                 p += (size_t)T2 * 4;
-    constexpr u32 omask_off = (T * 8 + T2 * Tr::KEY_BYTES) / 4;            // omlo - tmlo
-    constexpr u32 okey_off = T * (Tr::KEY_BYTES + 8) / 8;                  // the second table's key planes behind the main one's, in u64
-    uint4* gtab = reinterpret_cast<uint4*>(p);                             p += 1024;   // [KH_TAG_MAX_OPS] per operand: its group's mask (two halves), the group's first genome
-    u32* scratch = reinterpret_cast<u32*>(p);                              p += 128;    // [0] chunks, [2] k-mers, [3] side-list records
-    u32* dupc = reinterpret_cast<u32*>(p);                                 p += 256;    // [KH_TAG_MAX_OPS] per operand: instances whose (k-mer, operand) pair was seen before
-    u32* bins = reinterpret_cast<u32*>(p);                                 p += (size_t)SKM_CROSS_BINS * 4;
-    u16* owner = reinterpret_cast<u16*>(p);                                p += (size_t)MAXCH * 2;
-    u32* sidx = reinterpret_cast<u32*>(p);                                 // [SKM_BIG_IDX] listed launch only: this slot's records on the side list
-    const u32 tid = threadIdx.x, lane = lane_id();
+    constexpr u32 NT = SKM_BIG_NT;
+    SkmSlotWalk<Tr, SKM_CROSS_BINS> w(lds_raw, jb);
+    uint4* const gtab = w.L.gtab;   // .z: the group's first genome
+    u32* const bins = w.L.bins;
+    const u32 tid = w.tid;
     const u32 cap2 = jb.cap2;
     const bool listed = cj.nlisted != 0u;
     const u32 nwork = listed ? (cj.nlisted < jb.big_cap ? cj.nlisted : jb.big_cap) : jb.nslots;
     const u32 nbins = cj.nbins < SKM_CROSS_BINS ? cj.nbins : SKM_CROSS_BINS;
     const u32 ngen = cj.ngenomes, pmlo = cj.pmlo, pmhi = cj.pmhi;
-    const typename Tr::Consts kc(jb.k);
     if (tid < (u32)KH_TAG_MAX_OPS) {
-        const u32 g = jb.ginfo[tid], g0 = g & 0xffu, gn = (g >> 8) & 0xffu;
-        const u64 gm = gn ? (gn >= 64u ? ~0ull : ((1ull << gn) - 1ull)) << g0 : 0ull;
-        gtab[tid] = make_uint4((u32)gm, (u32)(gm >> 32), g0, 0u);
-        dupc[tid] = 0;
+        const u32 g = jb.ginfo[tid];
+        gtab[tid] = skm_group_entry(g, g & 0xffu);
+        w.L.dupc[tid] = 0;
     }
     for (u32 i = tid; i < SKM_CROSS_BINS; i += NT) bins[i] = 0;
-    u32 nspill_all = 0;
-    if (listed) {
-        nspill_all = jb.ctl[KH_SKM_CTL_SPILLED];
-        nspill_all = nspill_all < jb.spill_cap ? nspill_all : jb.spill_cap;
-    }
+    const u32 nspill_all = listed ? w.side_records() : 0u;
     // one occupied entry: the pivots of its mask against every group of its genomes
     auto count_entry = [&](u32 mlo, u32 mhi) __attribute__((always_inline)) {
         const u32 plo = mlo & pmlo, phi = mhi & pmhi;
@@ -739,105 +773,22 @@ __global__ __launch_bounds__(SKM_BIG_NT, 8) void k_skm_cross(const KhSkmJob jb, 
                 continue;
             }
         }
-        if (tid < 8) scratch[tid] = 0;
+        w.reset();
         __syncthreads();
-        // ---- this slot's records on the side list
-        u32 nside = 0;
-        if (listed) {
-            for (u32 i = tid; i < nspill_all; i += NT) {
-                if (jb.spill_slot[i] == slot) {
-                    const u32 at = atomicAdd(&scratch[3], 1u);
-                    if (at < SKM_BIG_IDX) sidx[at] = i;
-                }
-            }
-            __syncthreads();
-            nside = scratch[3];
-            if (nside > SKM_BIG_IDX) {   // (more than this kernel indexes: the host falls back)
-                if (tid == 0) atomicOr(jb.ctl, KH_ERR_CAPACITY);
-                nside = SKM_BIG_IDX;
-            }
-        }
-        const u32 nreg = have < cap2 ? have : cap2;
-        const uint4* __restrict__ reg = jb.reg2 + (u64)slot * cap2 * Q;
-        const u32 nall = nreg + nside;
-        // uint4 q of record i; the header sits in the last word of uint4 Q - 1
-        auto rec_q = [&](u32 i, u32 q) __attribute__((always_inline)) -> uint4 { return i < nreg ? reg[(u64)Q * i + q] : jb.spill_rec[(u64)Q * sidx[i - nreg] + q]; };
-        // ---- k-mer instances of the slot -> rounds
-        {
-            u32 mine = 0;
-            for (u32 i = tid; i < nall; i += NT) mine += Rec::n(rec_q(i, Q - 1).w);
-            const u32 tot = wave_scan_add(mine);
-            if (lane == KH_WAVE - 1 && tot) atomicAdd(&scratch[2], tot);
-        }
-        __syncthreads();
-        const u32 N = scratch[2];
-        const u32 R = (N + ROUND - 1u) / ROUND;
-        st_full = N > st_full ? N : st_full;
-        st_exp += N;
-        st_multi += R > 1u ? 1u : 0u;
-        for (u32 q = 0; q < R; ++q) {
-            // a fresh table: key planes all ones, both mask planes zero
-            for (u32 i = tid; i < T * Tr::KEY_BYTES / 16; i += NT) reinterpret_cast<uint4*>(kmain)[i] = make_uint4(0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu);
-            for (u32 i = tid; i < T2 * Tr::KEY_BYTES / 16; i += NT) reinterpret_cast<uint4*>(ksecond)[i] = make_uint4(0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu);
-            for (u32 i = tid; i < T / 2; i += NT) reinterpret_cast<uint4*>(tmlo)[i] = make_uint4(0u, 0u, 0u, 0u);
-            if (tid < T2) { omlo[tid] = 0u; omhi[tid] = 0u; }
-            __syncthreads();
-            for (u32 b0 = 0; b0 < nall; b0 += Tr::BATCH) {   // batches of records, one per thread of the first waves
-                const u32 mine_i = b0 + tid;
-                const u32 nj = tid < Tr::BATCH && mine_i < nall ? Rec::n(rec_q(mine_i, Q - 1).w) : 0u;
-                const u32 nch = (nj + E - 1u) / E;
-                {
-                    const u32 incl = wave_scan_add(nch);
-                    u32 wbase = 0;
-                    if (lane == KH_WAVE - 1 && incl) wbase = atomicAdd(&scratch[0], incl);
-                    wbase = (u32)__builtin_amdgcn_readlane((int)wbase, KH_WAVE - 1);
-                    const u32 cstart = wbase + incl - nch;
-                    if (cstart + nch <= MAXCH)
-                        for (u32 cc = 0; cc < nch; ++cc) owner[cstart + cc] = (u16)((tid << Tr::OB) | cc);
-                }
-                __syncthreads();
-                u32 C = scratch[0];
-                if (C > MAXCH) {   // (cannot happen: a record has at most 1 << OB chunks)
-                    if (tid == 0) atomicOr(jb.ctl, KH_ERR_CAPACITY);
-                    C = 0;
-                }
-                for (u32 c = tid; c < C; c += NT) {
-                    const u32 o = owner[c], ri = b0 + (o >> Tr::OB), first = (o & ((1u << Tr::OB) - 1u)) * E;
-                    SkmRecord<Q> r0;
-#pragma unroll
-                    for (u32 qq = 0; qq < Q; ++qq) r0.v[qq] = rec_q(ri, qq);
-                    const u32 hw = r0.v[Q - 1].w;
-                    const u32 tg = Rec::tag(hw), bit = 1u << (tg & 31u), half = Rec::half(hw);
-                    const u32 cnt = Rec::n(hw) - first;   // k-mers of the record from `first` on: the chunk holds min(cnt, E)
-                    Tr::expand(r0, first, kc, [&](const u32 e, const typename Tr::Key& K) __attribute__((always_inline)) {
-                        if (e >= cnt) return;
-                        const u32 H = Tr::hash(K);
-                        if (R != 1 && skm_cross_round_of(H, R) != q) return;   // another round's key
-                        skm_probe_walk<T, T2>(H, jb.ctl, Tr::claim(kmain, okey_off, K), [&](const bool second, const u32 S, bool) __attribute__((always_inline)) {
-                            u32* const mp = tmlo + (second ? omask_off + half * T2 : half * T) + S;
-                            if (atomicOr(mp, bit) & bit) atomicAdd(&dupc[tg], 1u);   // this operand had the k-mer already
-                        });
-                    });
-                }
-                __syncthreads();
-                if (tid == 0) scratch[0] = 0;
-                __syncthreads();
-            }
-            // ---- read-out: every occupied entry
-            for (u32 i = tid; i < T; i += NT)
-                if (reinterpret_cast<const u64*>(kmain)[i] != EMPTY) count_entry(tmlo[i], tmhi[i]);
-            if (tid < T2 && reinterpret_cast<const u64*>(ksecond)[tid] != EMPTY) count_entry(omlo[tid], omhi[tid]);
-            __syncthreads();
-        }
+        w.open(slot, have, listed, nspill_all);
+        st_full = w.N > st_full ? w.N : st_full;
+        st_exp += w.N;
+        st_multi += w.R > 1u ? 1u : 0u;
+        w.rounds(0u, 1u, [&]() __attribute__((always_inline)) { w.for_each_occupied(count_entry); });
         __syncthreads();   // (a slot without a round: scratch is written again only behind this)
     }
     __syncthreads();
     unsigned long long* __restrict__ rep = cj.bins + (u64)(blockIdx.x % cj.reps) * cj.nbins;
     for (u32 i = tid; i < nbins; i += NT)
         if (bins[i]) atomicAdd(&rep[i], (unsigned long long)bins[i]);
-    if (tid < (u32)KH_TAG_MAX_OPS && dupc[tid]) atomicAdd(&jb.dup[tid], (unsigned long long)dupc[tid]);
+    if (tid < (u32)KH_TAG_MAX_OPS && w.L.dupc[tid]) atomicAdd(&jb.dup[tid], (unsigned long long)w.L.dupc[tid]);
     if (tid == 0) {
-        if (st_full > T) atomicMax(jb.ctl + KH_SKM_CTL_FULLEST, st_full);
+        if (st_full > Tr::T) atomicMax(jb.ctl + KH_SKM_CTL_FULLEST, st_full);
         if (st_exp) atomicAdd(jb.ctl + KH_SKM_CTL_EXPANDED, st_exp);
         if (st_multi) atomicAdd(jb.ctl + KH_SKM_CTL_MULTI, st_multi);
     }

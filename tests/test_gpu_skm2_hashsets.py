@@ -315,6 +315,16 @@ def big_overflow_case():
     return recs, spread(recs, 40, 10)
 
 
+BIG_TWO_ROUND_RECORDS = 560    # x 4 keys = 2240 instances: two of k_skm_big's rounds of 1536
+
+
+@memo
+def big_two_round_case():
+    """k = 41: 560 records of 4 k-mers, all keys distinct and in whichever subset their hash says."""
+    recs = run_records(41, BIG_TWO_ROUND_RECORDS, 4105, None, 4)
+    return recs, spread(recs, 40, 10)
+
+
 @memo
 def handover_case(k, over):
     """Filler records whose chunks fill the union's chunk table exactly, and one short record of 8 k-mers (4 chunks) -
@@ -358,7 +368,8 @@ def test_constants_match_sources():
     assert UT * 8 // 32 == U_CAP <= U_NT
     big = re.search(r"struct SkmBig2 \{.*?static constexpr u32 T = (\d+), T2 = (\d+),", skm2, re.S)
     assert (int(big.group(1)), int(big.group(2))) == (BT, BT2)
-    assert "constexpr u32 ROUND = T - T / 4;" in dev and "const u32 R = (N + ROUND - 1u) / ROUND;" in dev
+    assert "constexpr u32 skm_walk_round() { return Tr::T - Tr::T / 4; }" in dev
+    assert "R = (N + skm_walk_round<Tr>() - 1u) / skm_walk_round<Tr>();" in dev
     assert "const u32 R = (N + T - 1) / T;" in skm2
     assert skm2.count("round < 8u") == 1 and "probes >= 8u" in dev                # the second-table chain
     assert ">> 27; }   // T2 = 32" in skm2
@@ -368,7 +379,9 @@ def test_constants_match_sources():
     assert "S = ((H >> (32 - HBITS)) + (u32)KH_TUNE_SKM_FULL_ROUNDS) & (T - 1u);" in dev
     assert ("key2_hash(u64 lo, u64 hi) { return ((u32)lo ^ (u32)(lo >> 32) ^ (u32)hi ^ (u32)(hi >> 32)) * 0x9E3779B1u; }"
             in skm2)
-    assert "(((h >> 4) & 0xffffu) * R) >> 16 == q" in skm2 and "(((H >> 4) & 0xffffu) * R) >> 16 != q" in dev
+    assert "(((h >> 4) & 0xffffu) * R) >> 16 == q" in skm2
+    assert "skm_round_of(const u32 H, const u32 R) { return (((H >> 4) & 0xffffu) * R) >> 16; }" in dev
+    assert "if (R != 1 && skm_round_of(H, R) != q) return;" in dev
     assert "if ((sc0 & 0xffffu) > SKM2_MAXCH)" in skm2 and "if (C > SKM2_MAXCH)" in skm2
     # the planner's clamp (kh_engine.cpp) and the one-word union of the hand-over's twin
     eng = _src("kh_engine.cpp")
@@ -485,6 +498,16 @@ def test_big_overflow_preconditions():
     recs, (seqs, _) = big_overflow_case()
     keys = check_run_records(recs, 41, 4, 0)
     assert BT + BT2 + 100 < len(keys) <= 2 * B_ROUND and len(keys) == instances(seqs, 41)   # R = 2 in k_skm_big
+    assert len(recs) > U_CAP                                                              # k_skm_big's under any slack
+    assert all(len(s) < 2048 for s in seqs)
+
+
+def test_big_two_round_preconditions():
+    recs, (seqs, _) = big_two_round_case()
+    keys = check_run_records(recs, 41, 4, None)
+    assert B_ROUND < len(keys) <= 2 * B_ROUND and len(keys) == instances(seqs, 41)          # R = 2 in k_skm_big
+    per_subset = [sum(subset(key2_hash(c & M64, c >> 64), 2) == q for c in keys) for q in (0, 1)]
+    assert 0 < min(per_subset) and max(per_subset) <= BT + BT2                              # both rounds work, both fit
     assert len(recs) > U_CAP                                                              # k_skm_big's under any slack
     assert all(len(s) < 2048 for s in seqs)
 
@@ -629,6 +652,22 @@ def test_big_deep_tiers(eng, capfd, skm_env, k):
     for err in check(eng, capfd, seqs, group_of, k, BIG):
         d = skm_line(err)
         assert d["overfull"] >= 1 and d["slot_max"] > d["cap"] and d["spilled"] > 0 and d["errors"] == 0, d
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("big_y", [1, 2, 16])
+def test_big_two_rounds(eng, capfd, skm_env, big_y):
+    """k_skm_big completes a slot in R = ceil(2240 / 1536) = 2 rounds, neither subset above its tables; more records than
+    the union's region holds, so part of them comes from the side list.  The rounds are shared out over KHOICE_SKM_BIG_Y
+    workgroups: with 1 one workgroup clears the table between its two rounds, with 2 each runs one, with 16 fourteen
+    have no round and only flush."""
+    skm_env.setenv("KHOICE_SKM_SLACK", "50")
+    skm_env.setenv("KHOICE_SKM_BIG_Y", str(big_y))
+    recs, (seqs, group_of) = big_two_round_case()
+    for err in check(eng, capfd, seqs, group_of, 41, BIG):
+        d = skm_line(err)
+        assert d["cap"] == U_CAP and d["overfull"] >= 1 and d["slot_max"] > d["cap"] and d["errors"] == 0, d
+        assert d["spilled"] == len(recs) - U_CAP, d
 
 
 # ---- F. k_skm_big: a subset with more keys than both tables hold

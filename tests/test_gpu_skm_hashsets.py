@@ -346,7 +346,10 @@ def test_constants_match_sources():
     assert skm.count("probes >= 8u") == 2                          # the second-table chain: the union's, the shared walk's
     assert "key_hash2(u32 lo, u32 hi) { return (lo ^ hi) * 0x9E3779B1u; }" in skm
     assert skm.count("(H ^ (H >> 15)) * 0x85EBCA77u") == 2
-    assert skm.count("((H >> 4) & 0xffffu) * R) >> 16") == 2 and "((h >> 4) & 0xffffu) * R) >> 16 == q" in skm
+    # the subset rule: skm_round_of once, called by the slot walk and by k_skm_phased; the union's own line
+    assert skm.count("skm_round_of(const u32 H, const u32 R) { return (((H >> 4) & 0xffffu) * R) >> 16; }") == 1
+    assert skm.count("skm_round_of(H, R) != q") == 2 and skm.count("((H >> 4) & 0xffffu) * R) >> 16") == 1
+    assert "((h >> 4) & 0xffffu) * R) >> 16 == q" in skm
     assert "k_union_hash<512, 4096>" in ker and "constexpr u32 T2 = T / 8;" in ker
     assert "KH_PROBE_ROUNDS(ovf, T2 - 1u, T2)" in ker and "KH_PROBE_ROUNDS(tbl, T - 1u, T)" in ker
 
@@ -508,6 +511,21 @@ def test_big_deep_tiers(eng, capfd, skm_env, k):
     skm_env.setenv("KHOICE_SKM_SLACK", "0.3")
     seqs, group_of = deep_case(k)
     for err in check(eng, capfd, seqs, group_of, k, BIG):
+        d = skm_line(err)
+        assert d["overfull"] >= 1 and d["slot_max"] > d["cap"] and d["errors"] == 0, d
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("big_y", [1, 2, 16])
+def test_big_two_rounds(eng, capfd, skm_env, big_y):
+    """two_round_case with slot 0 above its region: 4096 < N <= 6144 instances (test_two_round_preconditions) are R = 2
+    rounds of k_skm_big's 3072, and no subset outgrows the tables: the slot is completed, no fall-back.  The rounds are
+    shared out over KHOICE_SKM_BIG_Y workgroups: with 1 one workgroup clears the table between its two rounds, with 2
+    each runs one, with 16 fourteen have no round and only flush."""
+    skm_env.setenv("KHOICE_SKM_SLACK", "0.3")
+    skm_env.setenv("KHOICE_SKM_BIG_Y", str(big_y))
+    _, _, (seqs, group_of) = two_round_case()
+    for err in check(eng, capfd, seqs, group_of, 31, BIG):
         d = skm_line(err)
         assert d["overfull"] >= 1 and d["slot_max"] > d["cap"] and d["errors"] == 0, d
 
