@@ -264,7 +264,19 @@ int kh_exp1_run(kh_ctx *ctx, int nseq, const uint8_t *const *seqs, const uint64_
  * bitmap build, one read-out kernel counts every pivot against its group's and the groups' bit-sliced counters);
  * otherwise, and whenever the bitmaps do not fit (1023 genomes per group, 1023 groups, 4096 bins and counters, the
  * memory budget), the calls above on sets in device memory.  Switches as for kh_exp1_run: KHOICE_NO_BMP,
- * KHOICE_NO_SKM, KHOICE_BMP_MAX_K, KHOICE_BMP_MAX_BYTES. */
+ * KHOICE_NO_SKM, KHOICE_BMP_MAX_K, KHOICE_BMP_MAX_BYTES.
+ *
+ * KHOICE_EXP2_SKM=1 (read at the call; any other value or unset: as above) adds a third form for 17 <= k <= 63, at
+ * least one pivot and at most 63 genomes: genomes and pivots go through the super-k-mer scatter and regroup of
+ * kh_exp1_run as one list of at most 64 operands, and kh_exp3_run's kernel (k_skm_cross) with a read-out of its own
+ * counts, per slot, every k-mer of a pivot once by the genomes of its own group that hold it and once by the OTHER
+ * groups that do.  A pass takes pivots in the caller's order while genomes + pivots <= 64 and their bins (per pivot
+ * the size of its group + 1 + ngroups) <= 1024; further pivots go in further passes, which stage the genomes again.
+ * It declines (the set form answers, nothing counted) without a pivot, with 64 genomes or more, for a pass without a
+ * k-mer position, where the slot geometry or the memory does not fit, under KHOICE_NO_SKM, and for k > 32 under
+ * KHOICE_NO_SKM2; an overflow on the way, or a later pass that does not fit, counts one retry in kh_stats and the set
+ * form answers.  KH_E_INTERNAL: a pivot's bins do not add up to its distinct k-mers.  The default above k = 12 stays
+ * the set form (DESIGN.md section 3 has the measured table). */
 int kh_exp2_run(kh_ctx *ctx, int nseq, const uint8_t *const *seqs, const uint64_t *lens, int on_device,
                 const int *group_of, int ngroups, int npivots, const uint8_t *const *pivot_seqs,
                 const uint64_t *pivot_lens, const int *pivot_group, int k, uint32_t cs,

@@ -3533,6 +3533,151 @@ static int exp2_bmp(kh_ctx* c, const Exp2In& in, const Exp2Out& out, bool* done)
     *done = true;
     return KH_OK;
 }
+// The super-k-mer form (k_skm_cross with the read-out SkmCrossOwn, kh_skm_device.h; k = 17 .. 63, taken only with KHOICE_EXP2_SKM=1 — the set form
+// stays the default): exp3_skm's run with the type-2 read-out on the slot walk.  Genomes and pivots go through the
+// unchanged scatter and regroup as ONE list of texts, the pivots behind the genomes and every pivot a group of its own
+// to TagLayout (its tag is nseq + q); the kernel learns a pivot's OWN group from KhSkmPivotJob::pinfo.  A pass takes
+// pivots in the caller's order while genomes + pivots <= 64 and their bins (size of the own group + 1 within, ngroups
+// across) <= 1024; every pass stages, scatters and walks the genomes AGAIN (exp3_skm's known waste), the genomes'
+// distinct counts are the first pass's.  *done == false and no retry counted: the form does not apply (switch, k,
+// KHOICE_NO_SKM / KHOICE_NO_SKM2, no pivot, more than 63 genomes, a pass without a k-mer position, geometry, memory),
+// nothing of the outputs was written.  A capacity or order error of a kernel, more spilled records or listed slots than
+// are kept, or a later pass that does not stage: retries++, and the set form answers.
+static int exp2_skm(kh_ctx* c, const Exp2In& in, const Exp2Out& out, bool* done) {
+    *done = false;
+    const int k = in.k, nseq = in.nseq, ngroups = in.ngroups, npiv = in.npivots;
+    const char* sw = getenv("KHOICE_EXP2_SKM");
+    if (!sw || atoi(sw) != 1 || !skm_form_k(k)) return KH_OK;
+    if (!npiv || nseq >= KH_TAG_MAX_OPS) return KH_OK;
+    constexpr u32 max_bins = 1024;   // SKM_CROSS_BINS of kh_skm_device.h: the bins the walk keeps in LDS
+    std::vector<u32> gsize(ngroups, 0), gstart(ngroups, 0);   // group-major order, as TagLayout numbers the operands
+    u32 fan = 1;
+    for (int i = 0; i < nseq; ++i) fan = std::max(fan, ++gsize[in.group_of[i]]);
+    for (int g = 1; g < ngroups; ++g) gstart[g] = gstart[g - 1] + gsize[g - 1];
+    auto bins_of = [&](int p) { return gsize[in.pivot_group[p]] + 1 + (u32)ngroups; };
+    std::vector<int> pass0;   // first pivot of every pass, and npiv
+    {
+        u32 bins = 0;
+        for (int p = 0; p < npiv; ++p) {
+            const int np = pass0.empty() ? 0 : p - pass0.back();
+            if (pass0.empty() || nseq + np + 1 > KH_TAG_MAX_OPS || bins + bins_of(p) > max_bins) {
+                pass0.push_back(p);
+                bins = 0;
+            }
+            bins += bins_of(p);
+        }
+        pass0.push_back(npiv);
+    }
+    const int npasses = (int)pass0.size() - 1;
+    u64 gbases = 0, pbases = 0;
+    const u64 gpos = kmer_positions(nseq, in.lens, k, &gbases);
+    for (int b = 0; b < npasses; ++b)   // (a pass without a k-mer position has no geometry)
+        if (!(gpos + kmer_positions(pass0[b + 1] - pass0[b], in.pivot_lens + pass0[b], k))) return KH_OK;
+    kmer_positions(npiv, in.pivot_lens, k, &pbases);
+    const KhSkmWidth& wd = kh_skm_width(k > KH_SKM_MAX_K);
+    std::vector<u64> dseq(nseq, 0), dpiv(npiv, 0);
+    std::vector<std::vector<u64>> occ(npiv);   // occ[p]: the pivot's within bins, then its across bins
+    u64 kmers = 0, records = 0, multi = 0, big = 0;
+    for (int b = 0; b < npasses; ++b) {
+        const int p0 = pass0[b], np = pass0[b + 1] - p0, nops = nseq + np;
+        std::vector<const uint8_t*> seqs(in.seqs, in.seqs + nseq);
+        std::vector<uint64_t> lens(in.lens, in.lens + nseq);
+        std::vector<int> group_of(in.group_of, in.group_of + nseq);
+        KhSkmPivotJob pj{};
+        KhSkmCrossJob& cj = pj.cj;
+        for (int q = 0; q < np; ++q) {
+            seqs.push_back(in.pivot_seqs[p0 + q]);
+            lens.push_back(in.pivot_lens[p0 + q]);
+            group_of.push_back(ngroups + q);
+            const int g = in.pivot_group[p0 + q];
+            pj.pinfo[nseq + q] = gstart[g] | (gsize[g] << 8) | (cj.nbins << 16);
+            cj.nbins += bins_of(p0 + q);
+        }
+        SkmRun s(c);
+        // fan hint: a pivot brings its copy of a locus to the slot of the group it was held out of — one more than the
+        // largest group
+        KHCHK(skm_prepare(c, nops, seqs.data(), lens.data(), in.on_device, group_of.data(), ngroups + np, k, false, 0, fan + 1, &s, wd.cross_round));
+        if (!s.staged) {
+            if (b) c->stat.retries++;   // (a later pass whose geometry or memory does not fit: work was done for nothing)
+            return KH_OK;
+        }
+        const KhSkmJob& job = s.job;
+        hipStream_t st = c->st;
+        cj.ngenomes = (u32)nseq;
+        const u64 pm = ((1ull << np) - 1ull) << nseq;   // (1 <= np <= 63)
+        cj.pmlo = (u32)pm; cj.pmhi = (u32)(pm >> 32);
+        const u32 grid = std::min<u32>(s.g.nslots, wd.pivot_per_cu * (u32)std::max(1, c->cus));
+        cj.reps = std::min<u32>(grid, 64);
+        const size_t bins_bytes = 8 * (size_t)cj.reps * cj.nbins;
+        Tmp d_bins;
+        TMP_ALLOC(d_bins, c, bins_bytes);
+        Pinned pin{c};
+        PIN_ALLOC(pin, bins_bytes);
+        cj.bins = d_bins.as<unsigned long long>();
+        HIPCHK(hipMemsetAsync(cj.bins, 0, bins_bytes, st));
+        KHCHK(timed_launch(c, KC_SKM_CROSS, [&] { wd.pivot(job, pj, grid, st); }));
+        bool declines = false;
+        KHCHK(s.settle(s.off.ctl, [&](u32 nlisted) {   // ([ctl .. dup] of the workspace; the bins are read back below)
+            big += nlisted;
+            cj.nlisted = nlisted;
+            return timed_launch(c, KC_SKM_CROSS, [&] { wd.pivot(job, pj, nlisted, st); });
+        }, &declines));
+        if (declines) return KH_OK;   // the set form takes over
+        HIPCHK(hipMemcpyAsync(pin.p, cj.bins, bins_bytes, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        records += s.h_ctl()[KH_SKM_CTL_RECORDS];
+        multi += s.h_ctl()[KH_SKM_CTL_MULTI];
+        s.per_text([&](int t, u64 inst, u64 d) {   // text t of this pass: the genomes, then its pivots
+            if (t >= nseq) { dpiv[p0 + t - nseq] = d; kmers += inst; }
+            else if (b == 0) { dseq[t] = d; kmers += inst; }
+        });
+        const u64* h_bins = static_cast<const u64*>(pin.p);
+        for (int q = 0; q < np; ++q) {
+            const u32 w0 = pj.pinfo[nseq + q] >> 16, n = bins_of(p0 + q);
+            std::vector<u64>& o = occ[p0 + q];
+            o.assign(n, 0);
+            for (u32 r = 0; r < cj.reps; ++r)
+                for (u32 i = 0; i < n; ++i) o[i] += h_bins[(size_t)r * cj.nbins + w0 + i];
+        }
+    }
+    // ---- every pass went through.  Every distinct k-mer of a pivot was counted once within and once across
+    for (int p = 0; p < npiv; ++p) {
+        const u32 nw = gsize[in.pivot_group[p]] + 1;
+        u64 ws = 0, as = 0;
+        for (u32 i = 0; i < nw; ++i) ws += occ[p][i];
+        for (u32 i = 0; i < (u32)ngroups; ++i) as += occ[p][nw + i];
+        if (ws != dpiv[p] || as != dpiv[p])
+            return kh_fail(KH_E_INTERNAL, "kh_exp2_run: pivot %d has %llu distinct k-mers, its within bins hold %llu and its across bins %llu",
+                           p, (unsigned long long)dpiv[p], (unsigned long long)ws, (unsigned long long)as);
+    }
+    // ---- the outputs, and the accounting of exp2_bmp
+    out.clear(in);
+    u64 dsum = 0, held = 0;
+    for (int i = 0; i < nseq; ++i) {
+        dsum += dseq[i];
+        if (out.distinct_per_seq) out.distinct_per_seq[i] = dseq[i];
+    }
+    for (int p = 0; p < npiv; ++p) {
+        const u32 nw = gsize[in.pivot_group[p]] + 1;
+        dsum += dpiv[p];
+        if (out.distinct_per_pivot) out.distinct_per_pivot[p] = dpiv[p];
+        for (u32 v = 0; v < nw; ++v) out.add(in, p, false, v, occ[p][v]);
+        for (u32 v = 0; v < (u32)ngroups; ++v) out.add(in, p, true, v, occ[p][nw + v]);
+        held += dpiv[p] - occ[p][0];
+    }
+    c->stat.skm_records += records;
+    c->stat.cross_multi_slots += multi;
+    c->stat.big_slots += big;
+    c->stat.bases += gbases + pbases;
+    c->stat.builds += (u64)nseq + (u64)npiv;
+    c->stat.kmers += kmers;
+    c->stat.distinct += dsum;
+    c->stat.setop_in += dsum;
+    c->stat.setop_out += held;   // pivot k-mers their own group holds
+    c->stat.setops++;
+    *done = true;
+    return KH_OK;
+}
 // The set form: the calls of exp_type_2.smk:289-507 on sets that stay in device memory — one batched plain build of
 // genomes and pivots, the -cs{cs} union of every group, set_counts 1, per pivot group the union of the other groups,
 // and intersect -ocsum / kmers_subtract of every pivot with both.
@@ -3595,6 +3740,8 @@ extern "C" int kh_exp2_run(kh_ctx* c, int nseq, const uint8_t* const* seqs, cons
     HIPCHK(hipSetDevice(c->dev));
     bool done = false;
     KHCHK(exp2_bmp(c, in, out, &done));
+    if (done) return KH_OK;
+    KHCHK(exp2_skm(c, in, out, &done));   // (KHOICE_EXP2_SKM=1 only)
     if (done) return KH_OK;
     return exp2_sets(c, in, out);
 }

@@ -188,6 +188,15 @@ struct KhSkmCrossJob {
     u32 nbins, reps;                // nbins = pivots * ngenomes <= 1024
     u32 nlisted;                    // 0: the direct launch over all slots; else the listed launch over big_list[0 .. nlisted)
 };
+// ---- experiment type 2 from the same records (k_skm_cross with the read-out SkmCrossOwn): the same operands, the same walk; every pivot is counted
+// against its own group (in how many of its genomes: size + 1 within bins from w0, count 0 included) and against the
+// groups (in how many OTHER groups: ngroups across bins from a0 = w0 + size + 1).  cj as above with
+// bins: [reps][nbins], nbins = the sum of size + 1 + ngroups over the pivots of the pass <= 1024.
+struct KhSkmPivotJob {
+    KhSkmCrossJob cj;
+    u32 pinfo[KH_TAG_MAX_OPS];      // per pivot OPERAND (entries of genomes unused), as a ginfo word: first genome of its own
+                                    // group | genomes in that group << 8 | w0 << 16
+};
 // What the host needs to know about a key width: one-word keys (k <= 32, 16-byte records, kh_skm.hip) and two-word
 // keys (k <= 63, 32-byte records: two uint4 per record in reg1 / reg2, kh_skm2.hip) fill one table each.
 constexpr int KH_SKM2_MAX_K = 63;         // k = 64: the all-ones low key word is a k-mer (A^32 T^32)
@@ -199,6 +208,7 @@ struct KhSkmWidth {
     u32 max_cap2;                   // records of a slot the union takes
     u32 table;                      // entries of the union's hash set: the k-mer instances of a slot it takes per round
     u32 union_per_cu, cross_per_cu; // workgroups of the persistent union / of the direct cross launch that fit a CU
+    u32 pivot_per_cu;               // likewise of the direct launch with the type-2 read-out
     u32 cross_round;                // k-mer instances of a slot the cross kernel takes in one round
     bool (*supports_w)(u32 w);      // m-mers per k-mer the scatter kernel is instantiated for
     void (*scatter)(const KhSkmJob& job, u32 ntiles, hipStream_t st);
@@ -206,6 +216,7 @@ struct KhSkmWidth {
     void (*unite)(const KhSkmJob& job, u32 cs, u32 grid, hipStream_t st);    // persistent: grid workgroups walk the slots
     void (*big)(const KhSkmJob& job, u32 cs, u32 nbig, hipStream_t st);      // the slots of big_list, one workgroup each
     void (*cross)(const KhSkmJob& job, const KhSkmCrossJob& cj, u32 grid, hipStream_t st);
+    void (*pivot)(const KhSkmJob& job, const KhSkmPivotJob& pj, u32 grid, hipStream_t st);
 };
 const KhSkmWidth& kh_skm_width1();     // kh_skm.hip
 const KhSkmWidth& kh_skm_width2();     // kh_skm2.hip

@@ -1473,12 +1473,15 @@ void kh_launch_skm_phased(const KhSkmPhasedJob& job, u32 grid, hipStream_t st) {
 }
 // k_skm_cross (kh_skm_device.h) with one-word keys
 constexpr bool SKM_CROSS1_VGPRS64 = true;   // resource report: 59 VGPRs, 78 SGPRs (54 more kept in VGPR lanes), no scratch, 8 waves per SIMD; 81280 bytes of LDS
+// k_skm_cross with the type-2 read-out (SkmCrossOwn) and one-word keys
+constexpr bool SKM_PIVOT1_VGPRS64 = true;   // resource report: 59 VGPRs, 78 SGPRs (54 more kept in VGPR lanes), no scratch, 8 waves per SIMD; 81280 bytes of LDS
 const KhSkmWidth& kh_skm_width1() {
     static const KhSkmWidth wd = {
         (u32)sizeof(uint4) * SkmRec1::Q, KH_SKM_MAX_COARSE, KH_SKM_MAX_FINE, SkmUnion::MAXREC, SkmUnion::TABLE,
-        2u /* two unions of 79 KB of LDS and 1024 threads fit a CU */, skm_cross_per_cu<SkmBig1>(SKM_CROSS1_VGPRS64), skm_walk_round<SkmBig1>(),
+        2u /* two unions of 79 KB of LDS and 1024 threads fit a CU */, skm_cross_per_cu<SkmBig1>(SKM_CROSS1_VGPRS64),
+        skm_cross_per_cu<SkmBig1>(SKM_PIVOT1_VGPRS64), skm_walk_round<SkmBig1>(),
         kh_skm_supports_w, kh_launch_skm_scatter, kh_launch_skm_regroup, kh_launch_skm_union, skm_launch_big<SkmBig1>,
-        skm_launch_cross<SkmBig1>,
+        skm_launch_cross<SkmBig1>, skm_launch_pivot<SkmBig1>,
     };
     return wd;
 }

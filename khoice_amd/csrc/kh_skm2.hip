@@ -721,12 +721,15 @@ static void kh_launch_skm2_union(const KhSkmJob& job, u32 cs, u32 grid, hipStrea
 }
 // k_skm_cross (kh_skm_device.h) with two-word keys
 constexpr bool SKM_CROSS2_VGPRS64 = true;   // resource report: 56 VGPRs, 78 SGPRs (66 more kept in VGPR lanes), no scratch, 8 waves per SIMD; 64384 bytes of LDS
+// k_skm_cross with the type-2 read-out (SkmCrossOwn) and two-word keys
+constexpr bool SKM_PIVOT2_VGPRS64 = true;   // resource report: 57 VGPRs, 78 SGPRs (66 more kept in VGPR lanes), no scratch, 8 waves per SIMD; 64384 bytes of LDS
 const KhSkmWidth& kh_skm_width2() {
     static const KhSkmWidth wd = {
         (u32)sizeof(uint4) * SkmRec2::Q, KH_SKM2_MAX_COARSE, KH_SKM2_MAX_FINE, SKM2_MAXREC, SKM2_UT,
-        kh_skm2_union_per_cu(), skm_cross_per_cu<SkmBig2>(SKM_CROSS2_VGPRS64), skm_walk_round<SkmBig2>(),
+        kh_skm2_union_per_cu(), skm_cross_per_cu<SkmBig2>(SKM_CROSS2_VGPRS64), skm_cross_per_cu<SkmBig2>(SKM_PIVOT2_VGPRS64),
+        skm_walk_round<SkmBig2>(),
         kh_skm2_supports_w, kh_launch_skm2_scatter, skm_launch_regroup<SkmRec2>, kh_launch_skm2_union, skm_launch_big<SkmBig2>,
-        skm_launch_cross<SkmBig2>,
+        skm_launch_cross<SkmBig2>, skm_launch_pivot<SkmBig2>,
     };
     return wd;
 }

@@ -703,8 +703,14 @@ template <class Tr> void skm_launch_big(const KhSkmJob& job, u32 cs, u32 nbig, h
 // mask says that operand t holds it.  The walk above, every round of a slot in turn, and a read-out that knows the
 // pivots: an entry whose mask holds pivots P and, of group g, c >= 1 genomes adds one to bin
 // q * ngenomes + (first genome of g) + c - 1 for every q in P (k_bmp_cross's bins; the host clamps the counts).  An
-// entry no pivot holds counts nowhere.  No counter across groups, no own-group exception: the two things types 2 and
-// 4 will have to add, each as a read-out of its own beside count_entry.
+// entry no pivot holds counts nowhere.  No counter across groups, no own-group exception (SkmCrossGroups).
+//
+// Experiment type 2 (kh_exp2_run above the bitmaps) is the same kernel with another read-out: every pivot
+// was held out of ONE group, its own.  An entry with genome bits G and pivots P has T = the groups with a genome in G;
+// for every q in P, with c = the genomes of q's own group in G: one to q's within bin c (0 .. size of the group) and
+// one to its across bin T - (c > 0) (0 .. ngroups - 1 OTHER groups) — every distinct k-mer of a pivot counts once in
+// each (SkmCrossOwn).  Pivot q owns size + 1 + ngroups consecutive bins; the host says where (KhSkmPivotJob::pinfo).
+// Type 4 will need a read-out of its own beside these two.
 //
 // Two launches of one body.  DIRECT (cj.nlisted == 0): persistent workgroups walk all slots grid-strided; a slot with
 // more records than its region holds is listed (big_list, KH_SKM_CTL_LISTED) as the unions list it, and skipped.  LISTED: work
@@ -712,30 +718,20 @@ template <class Tr> void skm_launch_big(const KhSkmJob& job, u32 cs, u32 nbig, h
 // and go to one replica of the device block at the end; so do the statistics, kept in registers until then.
 // KH_SKM_CTL_MULTI: slots taken in more than one round.
 // ------------------------------------------------------------------------------------------
-constexpr u32 SKM_CROSS_BINS = 1024;   // pivots x genomes of a pass at most: 32 x 32 of 64 operands
+constexpr u32 SKM_CROSS_BINS = 1024;   // bins of a pass at most (type 3: pivots x genomes, 32 x 32 of 64 operands)
 template <class Tr> constexpr size_t skm_cross_lds_bytes(bool listed) { return SkmWalkLds<Tr, SKM_CROSS_BINS>::bytes(listed); }
-template <class Tr>
-__global__ __launch_bounds__(SKM_BIG_NT, 8) void k_skm_cross(const KhSkmJob jb, const KhSkmCrossJob cj) {
-    extern __shared__ __attribute__((aligned(16))) u8 lds_raw[];
-    constexpr u32 NT = SKM_BIG_NT;
-    SkmSlotWalk<Tr, SKM_CROSS_BINS> w(lds_raw, jb);
-    uint4* const gtab = w.L.gtab;   // .z: the group's first genome
-    u32* const bins = w.L.bins;
-    const u32 tid = w.tid;
-    const u32 cap2 = jb.cap2;
-    const bool listed = cj.nlisted != 0u;
-    const u32 nwork = listed ? (cj.nlisted < jb.big_cap ? cj.nlisted : jb.big_cap) : jb.nslots;
-    const u32 nbins = cj.nbins < SKM_CROSS_BINS ? cj.nbins : SKM_CROSS_BINS;
-    const u32 ngen = cj.ngenomes, pmlo = cj.pmlo, pmhi = cj.pmhi;
-    if (tid < (u32)KH_TAG_MAX_OPS) {
+// The read-outs: what the body below needs of one, both static.  entry(jb, xj, ngen, tid): operand tid's word of gtab
+// (threads 0 .. 63, before the first barrier); count(...): one occupied entry of a round's table, counted into `bins`.
+// Type 3: the pivots of the mask against every group of its genomes.  gtab .z: the group's first genome.
+struct SkmCrossGroups {
+    using Job = KhSkmCrossJob;
+    static __device__ __forceinline__ const KhSkmCrossJob& cross(const Job& xj) { return xj; }
+    static __device__ __forceinline__ uint4 entry(const KhSkmJob& jb, const KhSkmCrossJob&, const u32, const u32 tid) {
         const u32 g = jb.ginfo[tid];
-        gtab[tid] = skm_group_entry(g, g & 0xffu);
-        w.L.dupc[tid] = 0;
+        return skm_group_entry(g, g & 0xffu);
     }
-    for (u32 i = tid; i < SKM_CROSS_BINS; i += NT) bins[i] = 0;
-    const u32 nspill_all = listed ? w.side_records() : 0u;
-    // one occupied entry: the pivots of its mask against every group of its genomes
-    auto count_entry = [&](u32 mlo, u32 mhi) __attribute__((always_inline)) {
+    static __device__ __forceinline__ void count(const uint4* const gtab, u32* const bins, const u32 nbins, const u32 ngen, const u32 pmlo,
+                                                 const u32 pmhi, u32 mlo, u32 mhi) {
         const u32 plo = mlo & pmlo, phi = mhi & pmhi;
         if (!(plo | phi)) return;
         mlo &= ~pmlo;
@@ -756,7 +752,73 @@ __global__ __launch_bounds__(SKM_BIG_NT, 8) void k_skm_cross(const KhSkmJob jb, 
             mlo &= ~g.x & (mlo - 1u);
             mhi &= ~g.y & keep_hi;
         }
-    };
+    }
+};
+// Type 2: every pivot of the mask against its own group and against the number of groups.  gtab of a genome: its
+// group's mask; of a pivot operand (never looked up by the group walk: the pivots' bits are masked off before it): the
+// mask of its OWN group's genomes, .z its first within bin, .w its first across bin.
+struct SkmCrossOwn {
+    using Job = KhSkmPivotJob;
+    static __device__ __forceinline__ const KhSkmCrossJob& cross(const Job& xj) { return xj.cj; }
+    static __device__ __forceinline__ uint4 entry(const KhSkmJob& jb, const KhSkmPivotJob& pj, const u32 ngen, const u32 tid) {
+        if (tid < ngen) return skm_group_entry(jb.ginfo[tid], 0u);
+        const u32 g = pj.pinfo[tid];
+        uint4 e = skm_group_entry(g, g >> 16);
+        e.w = e.z + ((g >> 8) & 0xffu) + 1u;
+        return e;
+    }
+    static __device__ __forceinline__ void count(const uint4* const gtab, u32* const bins, const u32 nbins, const u32, const u32 pmlo,
+                                                 const u32 pmhi, const u32 mlo, const u32 mhi) {
+        u32 ql = mlo & pmlo, qh = mhi & pmhi;
+        if (!(ql | qh)) return;
+        const u32 glo = mlo & ~pmlo, ghi = mhi & ~pmhi;
+        u32 T = 0;   // groups with a genome in the mask
+        {
+            u32 a = glo, b = ghi;
+            while (a | b) {
+                const u32 first = a ? (u32)__builtin_ctz(a) : 32u + (u32)__builtin_ctz(b);
+                const uint4 g = gtab[first];
+                ++T;
+                const u32 keep_hi = a ? ~0u : b - 1u;   // (the lowest bit goes in any case: the loop ends)
+                a &= ~g.x & (a - 1u);
+                b &= ~g.y & keep_hi;
+            }
+        }
+        while (ql | qh) {
+            const u32 op = ql ? (u32)__builtin_ctz(ql) : 32u + (u32)__builtin_ctz(qh);
+            const uint4 e = gtab[op];
+            const u32 c = (u32)__popc(glo & e.x) + (u32)__popc(ghi & e.y);
+            const u32 wbin = e.z + c, abin = e.w + T - (c ? 1u : 0u);
+            if (wbin < nbins) atomicAdd(&bins[wbin], 1u);
+            if (abin < nbins) atomicAdd(&bins[abin], 1u);
+            if (ql) ql &= ql - 1u; else qh &= qh - 1u;
+        }
+    }
+};
+// One kernel, the read-out its second template parameter.  xj: the read-out's job (KhSkmCrossJob itself, or the
+// KhSkmPivotJob that holds one).
+template <class Tr, class Readout>
+__global__ __launch_bounds__(SKM_BIG_NT, 8) void k_skm_cross(const KhSkmJob jb, const typename Readout::Job xj) {
+    extern __shared__ __attribute__((aligned(16))) u8 lds_raw[];
+    const KhSkmCrossJob& cj = Readout::cross(xj);
+    constexpr u32 NT = SKM_BIG_NT;
+    SkmSlotWalk<Tr, SKM_CROSS_BINS> w(lds_raw, jb);
+    uint4* const gtab = w.L.gtab;
+    u32* const bins = w.L.bins;
+    const u32 tid = w.tid;
+    const u32 cap2 = jb.cap2;
+    const bool listed = cj.nlisted != 0u;
+    const u32 nwork = listed ? (cj.nlisted < jb.big_cap ? cj.nlisted : jb.big_cap) : jb.nslots;
+    const u32 nbins = cj.nbins < SKM_CROSS_BINS ? cj.nbins : SKM_CROSS_BINS;
+    const u32 ngen = cj.ngenomes, pmlo = cj.pmlo, pmhi = cj.pmhi;
+    if (tid < (u32)KH_TAG_MAX_OPS) {
+        gtab[tid] = Readout::entry(jb, xj, ngen, tid);
+        w.L.dupc[tid] = 0;
+    }
+    for (u32 i = tid; i < SKM_CROSS_BINS; i += NT) bins[i] = 0;
+    const u32 nspill_all = listed ? w.side_records() : 0u;
+    // one occupied entry
+    auto count_entry = [&](u32 mlo, u32 mhi) __attribute__((always_inline)) { Readout::count(gtab, bins, nbins, ngen, pmlo, pmhi, mlo, mhi); };
     u32 st_full = 0, st_exp = 0, st_multi = 0;   // fullest slot seen, k-mer instances expanded, slots of several rounds (uniform)
     __syncthreads();
     for (u32 it = blockIdx.x; it < nwork; it += gridDim.x) {
@@ -793,13 +855,18 @@ __global__ __launch_bounds__(SKM_BIG_NT, 8) void k_skm_cross(const KhSkmJob jb, 
         if (st_multi) atomicAdd(jb.ctl + KH_SKM_CTL_MULTI, st_multi);
     }
 }
-// workgroups of k_skm_cross<Tr> a CU holds in the direct launch: by its LDS (160 KB a CU) and by its 1024 threads
-// (sixteen waves: two workgroups when the kernel keeps to 64 VGPRs, which `vgprs64` says it does)
+// workgroups of k_skm_cross<Tr, Readout> a CU holds in the direct launch: by its LDS (160 KB a CU) and by its
+// 1024 threads (sixteen waves: two workgroups when the kernel keeps to 64 VGPRs, which `vgprs64` says it does)
 template <class Tr> constexpr u32 skm_cross_per_cu(bool vgprs64) {
     return vgprs64 && 2 * skm_cross_lds_bytes<Tr>(false) <= 160 * 1024 ? 2u : 1u;
 }
 template <class Tr> void skm_launch_cross(const KhSkmJob& job, const KhSkmCrossJob& cj, u32 grid, hipStream_t st) {
     if (!grid) return;
-    skm_allow_lds(k_skm_cross<Tr>, skm_cross_lds_bytes<Tr>(true));
-    hipLaunchKernelGGL(k_skm_cross<Tr>, dim3(grid), dim3(SKM_BIG_NT), skm_cross_lds_bytes<Tr>(cj.nlisted != 0u), st, job, cj);
+    skm_allow_lds(k_skm_cross<Tr, SkmCrossGroups>, skm_cross_lds_bytes<Tr>(true));
+    hipLaunchKernelGGL((k_skm_cross<Tr, SkmCrossGroups>), dim3(grid), dim3(SKM_BIG_NT), skm_cross_lds_bytes<Tr>(cj.nlisted != 0u), st, job, cj);
+}
+template <class Tr> void skm_launch_pivot(const KhSkmJob& job, const KhSkmPivotJob& pj, u32 grid, hipStream_t st) {
+    if (!grid) return;
+    skm_allow_lds(k_skm_cross<Tr, SkmCrossOwn>, skm_cross_lds_bytes<Tr>(true));
+    hipLaunchKernelGGL((k_skm_cross<Tr, SkmCrossOwn>), dim3(grid), dim3(SKM_BIG_NT), skm_cross_lds_bytes<Tr>(pj.cj.nlisted != 0u), st, job, pj);
 }

@@ -562,7 +562,11 @@ class Engine:
         """Device side of exp_type_2.smk:289-507 for one k: every pivot against the genomes of the group it was held
         out of and against the other groups.  Returns a dict with within_hist / across_hist[npivots, hist_len] (the
         `intersect -ocsum` histograms), within_only / across_only[npivots] (the `kmers_subtract` counts),
-        distinct_per_seq[nseq] and distinct_per_pivot[npivots].  seqs and pivots: host bytes or device-resident texts."""
+        distinct_per_seq[nseq] and distinct_per_pivot[npivots].  seqs and pivots: host bytes or device-resident texts.
+        Forms: presence bitmaps for k <= 12, the set operations inside the library above; with KHOICE_EXP2_SKM=1 in the
+        environment at the call (os.environ; read every time) k = 17 .. 63 is answered from super-k-mer records by
+        k_skm_cross with the own-group read-out when there are pivots and at most 63 genomes, in passes of at most 64
+        operands and 1024 bins — the same numbers, `skm_cross` in stats()."""
         ptrs, lens, on_dev, keep = self._seq_args(seqs)
         n, npv = len(seqs), len(pivots)
         pptrs, plens, p_on_dev, pkeep = self._seq_args(pivots) if npv else (None, np.zeros(1, dtype=np.uint64), on_dev, [])

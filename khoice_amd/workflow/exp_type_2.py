@@ -200,7 +200,10 @@ def run_batched(work_root: str, k_values: Sequence, num_datasets: int, device: i
 def run_fused(work_root: str, k_values: Sequence, num_datasets: int, device: int = 0):
     """The files and CSVs of run_batched from one Engine.exp2_run per k (kh_exp2_run: presence bitmaps for k <= 12,
     the set operations inside the library above): the texts are read once, the intersect histogram is the call's
-    within_hist / across_hist, the kmers_subtract histogram its within_only / across_only in line 1."""
+    within_hist / across_hist, the kmers_subtract histogram its within_only / across_only in line 1.  With
+    KHOICE_EXP2_SKM=1 in the environment the library answers k = 17 .. 63 from super-k-mer records (k_skm_cross with
+    the own-group read-out) instead — the switch is read inside kh_exp2_run at every call, so this runner gets the form
+    without a change; the files are the same."""
     from concurrent.futures import ThreadPoolExecutor
     import numpy as np
     from .. import engine as E
