@@ -347,7 +347,9 @@ __global__ __launch_bounds__(SKM_NT, KH_TUNE_SKM_SCATTER_WAVES) void k_skm_scatt
 //    moves to a small second table with an independent hash, and from a full second table back to unbounded
 //    probing of the main one; occupied entries stay occupied, so every copy of a key takes the same decisions as
 //    the first.  (Measured and rejected: finishing the keys that lost round 1 one per lane in a loop — fewer
-//    instructions, but a chain of ~20 dependent LDS round trips per wave: 2.63 ms against 2.30.)
+//    instructions, but a chain of ~20 dependent LDS round trips per wave: 2.63 ms against 2.30; and the same keys
+//    packed into the wave's first lanes, all walking at once: KH_TUNE_SKM_UNION_COMPACT at the kernel.)
+//    The waves that hold records run the merge of identical records at a raised priority (KH_TUNE_SKM_UNION_PRIO).
 // 4. Read-out: the thread whose compare-and-swap CREATED an entry remembers where; once all masks are final it
 //    turns its own entries into histogram bins (popcount per group / number of groups).  Nobody scans the table,
 //    no key is read again, waves without chunks have nothing to do.  The read is an exchange that stores zero: the
@@ -482,6 +484,42 @@ struct SkmClaim1 {
 #ifndef KH_TUNE_SKM_UNION_KT
 #define KH_TUNE_SKM_UNION_KT 1     // 0: only the runtime-k instantiation (timing study)
 #endif
+// WAVE PRIORITY for phases in which few waves of a workgroup work and the rest wait at a barrier behind them
+// (KH_TUNE_SKM_UNION_PRIO, a bit mask; s_setprio ignores EXEC, so every guard is a ballot or a scalar and compiles to
+// an s_cbranch).  Arbitration goes by priority, then by age: in the merge of identical records only the ~6 waves of 16
+// that hold records work, and in the younger workgroup of a CU they queued behind the bulk insertion of the older one.
+//   bit 0: the waves that hold records, from barrier 1 to barrier 2 (the merge)      ON: union 1.258 -> 1.226 ms
+//   bit 1: the one-key-per-lane finish (or the packed walk, below)                   alone 1.245; on top of bit 0 1.223
+//   bit 2: the wave that draws the next claim                                        mask 7: 1.227
+// (five runs each, spreads 0.003 .. 0.007: only bit 0 passes "three times the larger spread" by itself; levels 1 and 3
+// time the same, 1.2257 / 1.2257 for mask 1 and 1.2232 / 1.2234 for mask 3.  profiles/README.md has every number.)
+#ifndef KH_TUNE_SKM_UNION_PRIO
+#define KH_TUNE_SKM_UNION_PRIO 1
+#endif
+#ifndef KH_TUNE_SKM_UNION_PRIO_LEVEL
+#define KH_TUNE_SKM_UNION_PRIO_LEVEL 1
+#endif
+// THE PROBE TAIL of the lean body PACKED (KH_TUNE_SKM_UNION_COMPACT; measured and rejected, off).  Round 1 places about
+// 82 % of a thread's keys; rounds 2 .. KH_TUNE_SKM_FULL_ROUNDS run at full width for the rest, then one key per lane.
+// With the switch on, the wave numbers the keys that lost round 1 (two ballots of `act`, e = 0 first, each in lane
+// order) and every loser pushes key, next probe position, genome bits and mask half to lane `rank` with ds_permute (no
+// LDS memory: there is none left); the L <= 64 packed lanes walk one key each through the same tiers, entered at
+// probe 2.  Every copy of a key takes the same decisions, so entries and masks do not change.  A wave with more than 64
+// losers (a table more than half full when the pass begins) takes the rounds and the finish behind a cold branch and
+// counts itself in KH_SKM_CTL_TAILWIDE.
+//   0: rounds and finish as they were
+//   1: the walking lane is the creator of what it creates (a per-pass field next to `made`, evaluated by the read-out
+//      like the others) and adds the repeats it meets to `dupc`                     union 1.258 -> 1.417 ms
+//   2: the place of a created entry is sent back to the lane that lost (ds_bpermute by its rank), which stays the
+//      creator: `made` and the read-out are untouched                               union 1.258 -> 1.347 ms
+// Fewer instructions (the rounds' 129 static vector instructions become 40), but the walk is a chain of dependent LDS
+// round trips per wave where the rounds make one trip for all keys: the same finding as the one-per-lane loop above.
+// With priority on the walk (mask 3) the two forms reach 1.363 and 1.299: still slower.
+#ifndef KH_TUNE_SKM_UNION_COMPACT
+#define KH_TUNE_SKM_UNION_COMPACT 0
+#endif
+#define SKM_UNION_PRIO_UP(bit)   do { if ((KH_TUNE_SKM_UNION_PRIO) & (bit)) __builtin_amdgcn_s_setprio(KH_TUNE_SKM_UNION_PRIO_LEVEL); } while (0)
+#define SKM_UNION_PRIO_DOWN(bit) do { if ((KH_TUNE_SKM_UNION_PRIO) & (bit)) __builtin_amdgcn_s_setprio(0); } while (0)
 template <u32 NT, u32 T, int KT>
 __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs, u32 first_claimed) {
     extern __shared__ __attribute__((aligned(16))) u8 lds_raw[];
@@ -635,6 +673,7 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs, 
         // record that stays takes its chunks from a counter (chunks in the low half, k-mers in the high half) and
         // enters them into the chunk table at once: no block scan, no phase of its own.
         if (__builtin_amdgcn_ballot_w64(nj != 0)) {   // (waves without records go straight to the barrier)
+            SKM_UNION_PRIO_UP(1);
             u32 h = rx * 0x9E3779B1u ^ ry * 0x85EBCA77u ^ rz * 0xC2B2AE3Du ^ SkmRec1::content_hash_word(rw) * 0x27D4EB2Fu;
             h ^= h >> 15;
             h *= 0x2C1B3C6Du;
@@ -679,6 +718,7 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs, 
                         if (cc < nch) owner[cstart + cc] = (u16)((tid << SKM_OB) | cc);
                 }
             }
+            SKM_UNION_PRIO_DOWN(1);
         }
         SKM_MARK("dedup_end");
         SKM_USTAMP(2);
@@ -735,6 +775,13 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs, 
                 for (u32 ps = 0; ps < SKM_PASSES; ++ps)
 #pragma unroll
                     for (int e = 0; e < E / 2; ++e) made[ps][e] = 0u;
+                // the probe tail packed (see KH_TUNE_SKM_UNION_COMPACT); WALKER: the lane that walks a key is the creator
+                // of its entry and keeps the place here, one 16-bit field per pass, laid out like `made`
+                constexpr bool COMPACT = !MULTI && KH_TUNE_SKM_UNION_COMPACT != 0 && E == 2;
+                constexpr bool WALKER = COMPACT && KH_TUNE_SKM_UNION_COMPACT == 1;
+                u32 walked[(SKM_PASSES + 1) / 2];
+#pragma unroll
+                for (u32 ps = 0; ps < (SKM_PASSES + 1) / 2; ++ps) walked[ps] = 0u;
                 u32 ones = 0;   // keys that sit in exactly one group
 #pragma unroll
                 for (u32 pass = 0; pass < SKM_PASSES; ++pass) {
@@ -794,7 +841,8 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs, 
 #pragma unroll
                     for (int e = 0; e < E; ++e) was[e] = 0u;
                     u32 mk = 0;   // keys whose compare-and-swap created the entry
-                    for (u32 round = 0; round < (u32)KH_TUNE_SKM_FULL_ROUNDS && __builtin_amdgcn_ballot_w64(act != 0); ++round) {
+                    // one probe round, all of a thread's keys
+                    auto probe_round = [&]() __attribute__((always_inline)) {
                         unsigned long long old[E];
 #pragma unroll
                         for (int e = 0; e < E; ++e)
@@ -812,38 +860,33 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs, 
                                 }
                             }
                         }
-                    }
-                    SKM_USTAMP(9);
-                    SKM_MARK("rounds_done");
+                    };
                     u32 f16[E];   // where each key's entry is, if this thread created it
-#pragma unroll
-                    for (int e = 0; e < E; ++e) f16[e] = (mk >> e) & 1u ? (0x8000u | slot_[e]) : 0u;
-                    // the few keys still homeless: one per lane at a time, second table, then the main one again
-                    while (__builtin_amdgcn_ballot_w64(act != 0)) {
-                        const bool have_one = act != 0;
-                        const u32 es = have_one ? (u32)__builtin_ctz(act) : 0u;
-                        u64 K = 0;
-#pragma unroll
-                        for (int e = 0; e < E; ++e)
-                            if (es == (u32)e) K = kreg[e];
-                        const u32 H = key_hash2((u32)K, (u32)(K >> 32));
-                        // level 1: second table, 2: main table, unbounded
-                        u32 S = ((H ^ (H >> 15)) * 0x85EBCA77u) >> T2SH, probes = 0, level = 1;
-                        bool mine = have_one;
-                        u32 where = 0;
+                    auto chain_home = [&](const u32 H) __attribute__((always_inline)) -> u32 { return ((H ^ (H >> 15)) * 0x85EBCA77u) >> T2SH; };
+                    // One key per lane through the tiers, from entry S on; -> where the lane created an entry.  Level 1: second
+                    // table, 2: main table, unbounded; FROM_MAIN (the packed walk alone) enters at level 0: the main table up to
+                    // KH_TUNE_SKM_FULL_ROUNDS probes, `probes` of them made already.  The lane counts the repeats it meets.
+                    auto tier_walk = [&](auto from_main_, const unsigned long long K, const u32 H, const u32 kbits, const u32 khalf,
+                                         u32 S, u32 probes, bool mine) __attribute__((always_inline)) -> u32 {
+                        constexpr bool FROM_MAIN = decltype(from_main_)::value;
+                        u32* const kmp = khalf ? tmhi : tmlo;
+                        u32 level = FROM_MAIN ? 0u : 1u, where = 0;
                         while (__builtin_amdgcn_ballot_w64(mine)) {
                             if (mine) {
                                 unsigned long long* kp = level == 1 ? okey : tkey;
-                                const unsigned long long o2 = atomicCAS(&kp[S], emptyv, (unsigned long long)K);
+                                const unsigned long long o2 = atomicCAS(&kp[S], emptyv, K);
                                 if (o2 == emptyv || o2 == K) {
-                                    u32* mp2 = level == 1 ? (half ? omhi : omlo) : mp;
-                                    u32 d = atomicOr(mp2 + S, bits) & bits;
-                                    while (d) { atomicAdd(&dupc[half * 32u + (u32)__builtin_ctz(d)], 1u); d &= d - 1u; }
+                                    u32* mp2 = level == 1 ? (khalf ? omhi : omlo) : kmp;
+                                    u32 d = atomicOr(mp2 + S, kbits) & kbits;
+                                    while (d) { atomicAdd(&dupc[khalf * 32u + (u32)__builtin_ctz(d)], 1u); d &= d - 1u; }
                                     if (o2 == emptyv) where = 0x8000u | (level == 1 ? 0x4000u : 0u) | S;
                                     mine = false;
                                 } else {
                                     ++probes;
-                                    if (level == 1 && probes >= 8u) {   // a crowded second table: on in the main one
+                                    if (FROM_MAIN && level == 0 && probes >= (u32)KH_TUNE_SKM_FULL_ROUNDS) {
+                                        level = 1; probes = 0;
+                                        S = chain_home(H);
+                                    } else if (level == 1 && probes >= 8u) {   // a crowded second table: on in the main one
                                         level = 2; probes = 0;
                                         S = (u32)(((u64)H * T) >> 32) + (u32)KH_TUNE_SKM_FULL_ROUNDS;
                                         S = S & (T - 1u);
@@ -860,11 +903,89 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs, 
                                 }
                             }
                         }
-                        if (have_one) {
-                            act &= ~(1u << es);
+                        return where;
+                    };
+                    // the few keys still homeless: one per lane at a time, second table, then the main one again
+                    auto serial_finish = [&]() __attribute__((always_inline)) {
+                        while (__builtin_amdgcn_ballot_w64(act != 0)) {
+                            const bool have_one = act != 0;
+                            const u32 es = have_one ? (u32)__builtin_ctz(act) : 0u;
+                            u64 K = 0;
 #pragma unroll
                             for (int e = 0; e < E; ++e)
-                                if (es == (u32)e) f16[e] = where;
+                                if (es == (u32)e) K = kreg[e];
+                            const u32 H = key_hash2((u32)K, (u32)(K >> 32));
+                            const u32 where = tier_walk(std::false_type{}, (unsigned long long)K, H, bits, half, chain_home(H), 0u, have_one);
+                            if (have_one) {
+                                act &= ~(1u << es);
+#pragma unroll
+                                for (int e = 0; e < E; ++e)
+                                    if (es == (u32)e) f16[e] = where;
+                            }
+                        }
+                    };
+                    if (!COMPACT) {
+                        for (u32 round = 0; round < (u32)KH_TUNE_SKM_FULL_ROUNDS && __builtin_amdgcn_ballot_w64(act != 0); ++round) probe_round();
+                        SKM_USTAMP(9);
+                        SKM_MARK("rounds_done");
+#pragma unroll
+                        for (int e = 0; e < E; ++e) f16[e] = (mk >> e) & 1u ? (0x8000u | slot_[e]) : 0u;
+                        if (((KH_TUNE_SKM_UNION_PRIO) & 2) && !MULTI) {
+                            if (__builtin_amdgcn_ballot_w64(act != 0)) {   // (uniform)
+                                SKM_UNION_PRIO_UP(2);
+                                serial_finish();
+                                SKM_UNION_PRIO_DOWN(2);
+                            }
+                        } else {
+                            serial_finish();
+                        }
+                    } else {
+                        probe_round();
+                        SKM_USTAMP(9);
+                        SKM_MARK("rounds_done");
+#pragma unroll
+                        for (int e = 0; e < E; ++e) f16[e] = (mk >> e) & 1u ? (0x8000u | slot_[e]) : 0u;
+                        // the keys that lost round 1: e = 0 first, then e = 1, each in lane order
+                        const u64 b0 = __builtin_amdgcn_ballot_w64((act & 1u) != 0), b1 = __builtin_amdgcn_ballot_w64((act & 2u) != 0);
+                        const u32 L0 = (u32)__popcll(b0), L = L0 + (u32)__popcll(b1);   // (uniform)
+                        if (L > KH_WAVE) {   // (uniform, cold: a crowded table) the remaining rounds and the finish
+                            if (lane == 0) atomicAdd(jb.ctl + KH_SKM_CTL_TAILWIDE, 1u);
+                            for (u32 round = 1; round < (u32)KH_TUNE_SKM_FULL_ROUNDS && __builtin_amdgcn_ballot_w64(act != 0); ++round) probe_round();
+#pragma unroll
+                            for (int e = 0; e < E; ++e) f16[e] = (mk >> e) & 1u ? (0x8000u | slot_[e]) : 0u;
+                            serial_finish();
+                        } else if (L) {
+                            SKM_UNION_PRIO_UP(2);
+                            // Every lane pushes, so that no lane depends on EXEC for what it receives: per key register the
+                            // destinations are a permutation of the lanes (ds_permute takes the lane modulo 64) that sends
+                            // the losers to their ranks and everybody else behind them.
+                            const u32 n0 = __builtin_amdgcn_mbcnt_hi((u32)(b0 >> 32), __builtin_amdgcn_mbcnt_lo((u32)b0, 0u));
+                            const u32 n1 = __builtin_amdgcn_mbcnt_hi((u32)(b1 >> 32), __builtin_amdgcn_mbcnt_lo((u32)b1, 0u));
+                            const u32 d0 = ((act & 1u) ? n0 : L0 + (lane - n0)) << 2;
+                            const u32 d1 = ((act & 2u) ? L0 + n1 : L + (lane - n1)) << 2;
+                            const bool sel0 = lane < L0;
+                            auto packed = [&](const u32 v0, const u32 v1) __attribute__((always_inline)) -> u32 {
+                                const u32 r0 = (u32)__builtin_amdgcn_ds_permute((int)d0, (int)v0);
+                                const u32 r1 = (u32)__builtin_amdgcn_ds_permute((int)d1, (int)v1);
+                                return sel0 ? r0 : r1;
+                            };
+                            const u32 wkl = packed((u32)kreg[0], (u32)kreg[1]), wkh = packed((u32)(kreg[0] >> 32), (u32)(kreg[1] >> 32));
+                            const u32 wph = packed(slot_[0] | (half << 16), slot_[1] | (half << 16));   // the next probe position, the mask half
+                            const u32 wbits = packed(bits, bits);
+                            const unsigned long long K = ((unsigned long long)wkh << 32) | wkl;
+                            // the tiers of rounds and finish, entered at probe 2 of the main table
+                            static_assert(!COMPACT || KH_TUNE_SKM_FULL_ROUNDS >= 2, "the packed walk enters the main table's rounds at probe 2");
+                            const u32 where = tier_walk(std::true_type{}, K, key_hash2(wkl, wkh), wbits, wph >> 16, wph & 0xffffu, 1u, lane < L);
+                            if (WALKER) {
+                                walked[pass >> 1] |= where << (16u * (pass & 1u));
+                            } else {   // the place goes back to the lane that lost: it stays the creator
+                                const u32 w0 = (u32)__builtin_amdgcn_ds_bpermute((int)d0, (int)where);
+                                const u32 w1 = (u32)__builtin_amdgcn_ds_bpermute((int)d1, (int)where);
+                                if (act & 1u) f16[0] = w0;
+                                if (act & 2u) f16[1] = w1;
+                            }
+                            act = 0;
+                            SKM_UNION_PRIO_DOWN(2);
                         }
                     }
                     SKM_MARK("serial_done");
@@ -887,7 +1008,13 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs, 
                 SKM_USTAMP(5);
                 // the next claim: one lane of the last wave, which runs out of chunks first; the barrier below and the
                 // next slot's first one lie between this store and the threads that read it
-                if (draw && q == 0 && tid0 == NT - KH_WAVE) feed.draw(jb.claim, scratch + 1);
+                if ((KH_TUNE_SKM_UNION_PRIO) & 4) {
+                    if (draw && q == 0 && wid == NW - 1u) {   // (scalars: the whole wave takes the branch)
+                        SKM_UNION_PRIO_UP(4);
+                        if (tid0 == NT - KH_WAVE) feed.draw(jb.claim, scratch + 1);
+                        SKM_UNION_PRIO_DOWN(4);
+                    }
+                } else if (draw && q == 0 && tid0 == NT - KH_WAVE) feed.draw(jb.claim, scratch + 1);
                 __syncthreads();
                 SKM_USTAMP(6);
                 // ---- all masks are final: every thread turns the entries it created into histogram bins.
@@ -895,7 +1022,8 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs, 
                 // the barrier after the insertion, and the read stores zero — so both planes of both tables are zero when
                 // the next insertion phase (next subset, next slot) begins.  A mask is only ever ORed into behind a
                 // compare-and-swap that found its key or created it, and whoever created it recorded the place in `made`:
-                // in the probe rounds (`mk`), one key per lane (`where`, either table).  A key dropped under
+                // in the probe rounds (`mk`), one key per lane (`where`, either table), or as the lane that walked a packed
+                // loser (`walked`: the lane whose key it was records nothing for it).  A key dropped under
                 // KH_ERR_CAPACITY touched no mask; a slot handed on inserts nothing (C = 0); with R > 1 each subset's
                 // read-out zeroes what that subset created before the barrier that precedes the next one.
 #pragma unroll
@@ -903,13 +1031,15 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs, 
                     u32 any = 0;
 #pragma unroll
                     for (int e = 0; e < E / 2; ++e) any |= made[pass][e];
+                    const u32 walked_f = WALKER ? (walked[pass >> 1] >> (16u * (pass & 1u))) & 0xffffu : 0u;
+                    any |= walked_f;
 #if defined(KH_ABLATE) && KH_ABLATE == 3
                     if (any != 0x7654321u) any = 0;   // timing study: no read-out
 #endif
                     if (!__builtin_amdgcn_ballot_w64(any != 0)) continue;
 #pragma unroll
-                    for (int e = 0; e < E; ++e) {
-                        const u32 f = (made[pass][e >> 1] >> (16 * (e & 1))) & 0xffffu;
+                    for (int e = 0; e < E + (WALKER ? 1 : 0); ++e) {
+                        const u32 f = e < E ? (made[pass][(e < E ? e : 0) >> 1] >> (16 * (e & 1))) & 0xffffu : walked_f;
                         if (f & 0x8000u) {
                             const u32 at = f & 0x3fffu;
                             const bool second = f & 0x4000u;
