@@ -442,10 +442,12 @@ void kh_debug_set_stamps_skm2(u64* p);
 // -DKH_STAMPS_WG: when every workgroup of the persistent union began and ended its walk, one line per workgroup
 // appended to $KHOICE_WG_DUMP (tools/wg_ends.py reads it): call, workgroup, hardware id, XCC, shader clock at the
 // beginning and the end, constant-rate clock at the beginning and the end
-static void dump_wg_ends(kh_ctx* c, DevBuf* sb, u32 grid) {
-    const char* path = getenv("KHOICE_WG_DUMP");
+// ($KHOICE_WG_DUMP_SCATTER: the same for the workgroups of k_skm_scatter, a tile each)
+static void dump_wg_ends(kh_ctx* c, DevBuf* sb, u32 grid, bool scatter = false) {
+    const char* path = getenv(scatter ? "KHOICE_WG_DUMP_SCATTER" : "KHOICE_WG_DUMP");
     if (!path) return;
-    static int call = 0;
+    static int calls[2] = {0, 0};
+    int& call = calls[scatter];
     std::vector<u64> h((size_t)grid * 16);
     (void)hipMemcpyAsync(h.data(), sb->p, (size_t)grid * 128, hipMemcpyDeviceToHost, c->st);
     (void)hipStreamSynchronize(c->st);
@@ -1862,7 +1864,8 @@ template <class F> static int timed_launch(kh_ctx* c, int cls, F launch) {
 // by slot; settle() (exp1_skm, exp3_skm) or read_back() (skm_pack_impl); then h_ctl(), h_hist() and per_text().
 // Workspace: [hist: reps x nbins u64][ctl: KH_SKM_CTL_WORDS u32][inst: nseq u64][dup: 64 u64] (zeroed, read back)
 // [cur1: nb1 x KH_SKM_CUR1_STRIDE u32][cur2: nslots u32][claim: a 128-byte line of its own] (zeroed) [ginfo: 64 u32]
-// [tags: nseq u8][segs][tiles] (one upload)
+// [tags: nseq u8][segs][tiles] (fetched from the pinned staging).  No copy engine on the way: k_skm_ws_init zeroes and
+// fetches in front of the scatter, k_skm_ws_down stores [hist .. dup] to the pinned staging behind the form's kernel.
 struct SkmRun {
     kh_ctx* c;
     TagLayout L;
@@ -1879,6 +1882,10 @@ struct SkmRun {
     // what a slot's region cannot hold goes to a side list (d_spill: [spill_cap] records, [spill_cap] u32 slots, [big_cap]
     // u32 listed slots), the slot to a launch of its own
     static constexpr u32 spill_cap = 1u << 20, big_cap = 16384u;
+    // Replicas of the histogram: a union workgroup adds its bins to replica blockIdx.x % reps once, at its end, so a few
+    // spread those atomics enough (union time with 1 / 4 / 8 / 32 / one per workgroup: 1.226 / 1.224 / 1.225 / 1.226 /
+    // 1.223 ms), and what is zeroed, read back and summed per call shrinks from 290 KB to 5 KB on the headline shape
+    static constexpr u32 hist_reps = 8u;
 #ifdef KH_STAMPS
     Tmp d_stamps;
 #endif
@@ -1895,12 +1902,13 @@ struct SkmRun {
         off.tags = off.ginfo + 256;
         off.segs = off.tags + (((size_t)nseq + 15) & ~(size_t)15);
         off.tiles = off.segs + sizeof(KhSeg) * nseq;
-        off.bytes = off.tiles + sizeof(KhTile) * (size_t)std::max<u32>(1, ntiles);
+        off.bytes = (off.tiles + sizeof(KhTile) * (size_t)std::max<u32>(1, ntiles) + 15) & ~(size_t)15;   // (fetched in 16-byte words)
     }
     template <class T> T* dev(size_t o) const { return reinterpret_cast<T*>(d_ws.as<u8>() + o); }
     // [from, dup's end) of the workspace into h_down, and the wait for it
     int read_back(size_t from) {
-        HIPCHK(hipMemcpyAsync(h_down + from, d_ws.as<u8>() + from, off.cur1 - from, hipMemcpyDeviceToHost, c->st));
+        kh_launch_skm_ws_down(h_down + from, d_ws.as<u8>() + from, off.cur1 - from, c->st);
+        HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(c->st));
         return KH_OK;
     }
@@ -1976,7 +1984,7 @@ static int skm_prepare(kh_ctx* c, int nseq, const uint8_t* const* seqs, const ui
         for (u32 t = 0; t < sg.ntiles; ++t) tiles.push_back(KhTile{(u32)i, t});
     }
     const u32 ntiles = s->ntiles = (u32)tiles.size();
-    const u32 reps = g.ugrid;
+    const u32 reps = std::min(g.ugrid, SkmRun::hist_reps);
     s->layout((size_t)reps * L->nbins, nseq);
     const SkmRun::Layout& off = s->off;
     const u32 spill_cap = SkmRun::spill_cap;
@@ -1995,8 +2003,8 @@ static int skm_prepare(kh_ctx* c, int nseq, const uint8_t* const* seqs, const ui
     memcpy(h_up + (off.segs - off.ginfo), segs.data(), sizeof(KhSeg) * nseq);
     if (ntiles) memcpy(h_up + (off.tiles - off.ginfo), tiles.data(), sizeof(KhTile) * (size_t)ntiles);
     L->words(reinterpret_cast<u32*>(h_up), h_up + (off.tags - off.ginfo), group_of);
-    HIPCHK(hipMemsetAsync(s->d_ws.b->p, 0, off.ginfo, st));
-    HIPCHK(hipMemcpyAsync(s->dev<u8>(off.ginfo), h_up, up_bytes, hipMemcpyHostToDevice, st));
+    kh_launch_skm_ws_init(s->d_ws.b->p, off.ginfo, h_up, up_bytes, st);
+    HIPCHK(hipGetLastError());
     c->prof_end();
 
     KhSkmJob& job = s->job;
@@ -2031,7 +2039,11 @@ static int skm_prepare(kh_ctx* c, int nseq, const uint8_t* const* seqs, const ui
     c->prof_begin(KC_SKM_SCATTER);
     wd.scatter(job, ntiles, st);
     c->prof_end();
-#ifdef KH_STAMPS
+#if defined(KH_STAMPS) && defined(KH_STAMPS_WG)
+    dump_wg_ends(c, s->d_stamps.b, ntiles, true);
+    HIPCHK(hipMemsetAsync(s->d_stamps.b->p, 0, 128 * nst, st));
+    kh_debug_set_stamps_skm(nullptr);
+#elif defined(KH_STAMPS)
     report_stamps(c, "skm_scatter (second sub-tile: codes / hashes / minima / slots+count / - / append / barrier / -)", s->d_stamps.b, ntiles);
     HIPCHK(hipMemsetAsync(s->d_stamps.b->p, 0, 128 * nst, st));
     kh_debug_set_stamps_skm(nullptr);

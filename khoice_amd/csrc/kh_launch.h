@@ -221,6 +221,10 @@ struct KhSkmWidth {
 const KhSkmWidth& kh_skm_width1();     // kh_skm.hip
 const KhSkmWidth& kh_skm_width2();     // kh_skm2.hip
 inline const KhSkmWidth& kh_skm_width(bool two) { return two ? kh_skm_width2() : kh_skm_width1(); }
+// the workspace of a super-k-mer run zeroed and its descriptors fetched from the pinned staging in one kernel; its
+// results stored to the pinned staging by a kernel (kh_skm.hip: k_skm_ws_init, k_skm_ws_down)
+void kh_launch_skm_ws_init(void* ws, size_t zero_bytes, const void* up, size_t up_bytes, hipStream_t st);   // multiples of 16
+void kh_launch_skm_ws_down(void* down, const void* ws, size_t bytes, hipStream_t st);                       // a multiple of 8
 // ---- the exchange form of the across-group step (multi-GPU; kh_skm.hip k_skm_pack / k_skm_phased)
 struct KhSkmPackJob {
     const uint4* reg2;              // [nslots][cap2] this rank's records by slot (tag = local group, < 32)

@@ -43,6 +43,41 @@ void kh_debug_set_stamps_skm(u64* p) { (void)hipMemcpyToSymbol(HIP_SYMBOL(g_skm_
 #else
 #define SKM_STAMP(idx) do {} while (0)
 #endif
+// (-DKH_STAMPS_WG with -DKH_STAMPS: two stamps per workgroup, the beginning and the end of its walk, instead of the
+// per-slot ones: when do the workgroups of the persistent union finish?  Word 1: the hardware id of the wave, word 2:
+// the XCC; words 3 and 11: the constant-rate clock, which all XCCs share.)
+#if defined(KH_STAMPS) && defined(KH_STAMPS_WG)
+#define SKM_USTAMP(idx) do {} while (0)
+#define SKM_WGSTAMP(idx)                                                                   \
+    do {                                                                                   \
+        __builtin_amdgcn_sched_barrier(0);                                                 \
+        if (threadIdx.x == 0 && g_skm_stamps) {                                            \
+            u64* const sp_ = g_skm_stamps + (u64)blockIdx.x * 16;                          \
+            sp_[(idx)] = __builtin_amdgcn_s_memtime();                                     \
+            sp_[(idx) + 3] = wall_clock64();                                               \
+            if ((idx) == 0) {                                                              \
+                sp_[1] = __builtin_amdgcn_s_getreg(4 | (31 << 11));                        \
+                sp_[2] = __builtin_amdgcn_s_getreg(20 | (31 << 11));                       \
+            }                                                                              \
+        }                                                                                  \
+        __builtin_amdgcn_sched_barrier(0);                                                 \
+    } while (0)
+#elif defined(KH_STAMPS)
+#define SKM_WGSTAMP(idx) do {} while (0)
+#define SKM_USTAMP(idx)                                                                    \
+    do {                                                                                   \
+        __builtin_amdgcn_sched_barrier(0);                                                 \
+        if (threadIdx.x == 0 && g_skm_stamps) g_skm_stamps[(u64)slot * 16 + (idx)] = __builtin_amdgcn_s_memtime(); \
+        __builtin_amdgcn_sched_barrier(0);                                                 \
+    } while (0)
+#else
+#define SKM_USTAMP(idx) do {} while (0)
+#define SKM_WGSTAMP(idx) do {} while (0)
+#endif
+#if defined(KH_STAMPS) && defined(KH_STAMPS_WG)   // (the scatter's workgroups likewise; its phase stamps share the words: off)
+#undef SKM_STAMP
+#define SKM_STAMP(idx) do {} while (0)
+#endif
 
 // ISA study only (-DKH_MARKS with --cuda-device-only -S): comments that delimit the sections of the union in the assembly
 #ifdef KH_MARKS
@@ -93,6 +128,7 @@ __global__ __launch_bounds__(SKM_NT, KH_TUNE_SKM_SCATTER_WAVES) void k_skm_scatt
     const u64 tile_pos0 = (u64)t.tile_in_seg * jb.tile_pos;
     const int subtiles = (int)(jb.tile_pos / SKM_SUB);
 
+    SKM_WGSTAMP(0);
     for (u32 i = tid; i < nbk; i += SKM_NT) L.bcnt[i] = 0;
     if (tid < 4) misc[tid] = 0;
     u32 staged = 0, tile_recs = 0;   // uniform
@@ -328,6 +364,10 @@ __global__ __launch_bounds__(SKM_NT, KH_TUNE_SKM_SCATTER_WAVES) void k_skm_scatt
     if (staged) skm_flush<SKM_NT, SKM_CAP, false>(L, staged, jb.nb1, jb.cur1, jb.reg1, jb.cap1, jb.ctl);
     if (tid == 0 && misc[1]) atomicAdd(&jb.inst[t.seg], (unsigned long long)misc[1]);
     if (tid == 0 && tile_recs) atomicAdd(jb.ctl + KH_SKM_CTL_RECORDS, tile_recs);
+#if defined(KH_STAMPS) && defined(KH_STAMPS_WG)
+    __syncthreads();   // (the workgroup's end, not thread 0's)
+#endif
+    SKM_WGSTAMP(8);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -429,38 +469,6 @@ struct SkmClaim1 {
         return o2 == empty ? SKM_FRESH : (o2 == K ? SKM_SAME_KEY : SKM_OTHER_KEY);
     }
 };
-
-// (-DKH_STAMPS_WG with -DKH_STAMPS: two stamps per workgroup, the beginning and the end of its walk, instead of the
-// per-slot ones: when do the workgroups of the persistent union finish?  Word 1: the hardware id of the wave, word 2:
-// the XCC; words 3 and 11: the constant-rate clock, which all XCCs share.)
-#if defined(KH_STAMPS) && defined(KH_STAMPS_WG)
-#define SKM_USTAMP(idx) do {} while (0)
-#define SKM_WGSTAMP(idx)                                                                   \
-    do {                                                                                   \
-        __builtin_amdgcn_sched_barrier(0);                                                 \
-        if (threadIdx.x == 0 && g_skm_stamps) {                                            \
-            u64* const sp_ = g_skm_stamps + (u64)blockIdx.x * 16;                          \
-            sp_[(idx)] = __builtin_amdgcn_s_memtime();                                     \
-            sp_[(idx) + 3] = wall_clock64();                                               \
-            if ((idx) == 0) {                                                              \
-                sp_[1] = __builtin_amdgcn_s_getreg(4 | (31 << 11));                        \
-                sp_[2] = __builtin_amdgcn_s_getreg(20 | (31 << 11));                       \
-            }                                                                              \
-        }                                                                                  \
-        __builtin_amdgcn_sched_barrier(0);                                                 \
-    } while (0)
-#elif defined(KH_STAMPS)
-#define SKM_WGSTAMP(idx) do {} while (0)
-#define SKM_USTAMP(idx)                                                                    \
-    do {                                                                                   \
-        __builtin_amdgcn_sched_barrier(0);                                                 \
-        if (threadIdx.x == 0 && g_skm_stamps) g_skm_stamps[(u64)slot * 16 + (idx)] = __builtin_amdgcn_s_memtime(); \
-        __builtin_amdgcn_sched_barrier(0);                                                 \
-    } while (0)
-#else
-#define SKM_USTAMP(idx) do {} while (0)
-#define SKM_WGSTAMP(idx) do {} while (0)
-#endif
 
 // PERSISTENT: the grid is two workgroups per CU (what the LDS allows); a workgroup walks slots blockIdx.x,
 // blockIdx.x + gridDim.x, ... for the first half of its rounds and takes the rest by claim from a device counter
@@ -1577,6 +1585,33 @@ static void kh_launch_skm_union(const KhSkmJob& job, u32 cs, u32 grid, hipStream
 #endif
         default: launch_union_k<0>(job, cs, grid, st); break;   // any other k that reaches here: k from the job
     }
+}
+// ------------------------------------------------------------------------------------------
+// The workspace of a run (SkmRun, kh_engine.cpp) at both ends of the stream, as kernels: a copy engine between two
+// kernels costs a hand-over of the queue each way (10 .. 17 us before k_skm_scatter, 10 us behind the union), a kernel
+// that reads or writes the pinned staging itself costs none.
+// k_skm_ws_init: ws[0, zero16) = 0, ws[zero16, zero16 + up16) = up[0, up16), in 16-byte words
+// k_skm_ws_down: down[0, n8) = ws[0, n8), in 8-byte words
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_skm_ws_init(uint4* __restrict__ ws, const u32 zero16, const uint4* __restrict__ up, const u32 up16) {
+    const u32 n = zero16 + up16, step = gridDim.x * 256u;
+    for (u32 i = blockIdx.x * 256u + threadIdx.x; i < n; i += step)
+        ws[i] = i < zero16 ? make_uint4(0u, 0u, 0u, 0u) : up[i - zero16];
+}
+__global__ __launch_bounds__(256) void k_skm_ws_down(unsigned long long* __restrict__ down, const unsigned long long* __restrict__ ws, const u32 n8) {
+    for (u32 i = blockIdx.x * 256u + threadIdx.x; i < n8; i += gridDim.x * 256u) down[i] = ws[i];
+}
+void kh_launch_skm_ws_init(void* ws, size_t zero_bytes, const void* up, size_t up_bytes, hipStream_t st) {   // both multiples of 16
+    const u32 zero16 = (u32)(zero_bytes / 16), up16 = (u32)(up_bytes / 16);
+    if (!(zero16 + up16)) return;
+    const u32 want = (zero16 + up16 + 255u) / 256u, grid = want < 1024u ? want : 1024u;
+    hipLaunchKernelGGL(k_skm_ws_init, dim3(grid), dim3(256), 0, st, static_cast<uint4*>(ws), zero16, static_cast<const uint4*>(up), up16);
+}
+void kh_launch_skm_ws_down(void* down, const void* ws, size_t bytes, hipStream_t st) {   // a multiple of 8
+    const u32 n8 = (u32)(bytes / 8);
+    if (!n8) return;
+    const u32 want = (n8 + 255u) / 256u, grid = want < 64u ? want : 64u;
+    hipLaunchKernelGGL(k_skm_ws_down, dim3(grid), dim3(256), 0, st, static_cast<unsigned long long*>(down), static_cast<const unsigned long long*>(ws), n8);
 }
 void kh_launch_skm_pack(const KhSkmPackJob& job, hipStream_t st) {
     if (!job.nslots) return;

@@ -4,6 +4,7 @@
 #        tools/build_diag.sh wg [-DKH_TUNE_SKM_CLAIM=0 ...]: two stamps per workgroup of the persistent unions instead
 #        (-DKH_STAMPS_WG) -> khoice_amd/lib/diag/libkhoice_hip_diag_wg.so; KHOICE_WG_DUMP=file appends one line per
 #        workgroup and call, tools/wg_ends.py reads the file.
+#        KHOICE_WG_DUMP_SCATTER=file: the same for the workgroups of k_skm_scatter (tools/wg_ends.py file --resident 768).
 set -e
 cd "$(dirname "$0")/.."
 if [ "${1:-}" = wg ]; then

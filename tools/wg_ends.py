@@ -59,15 +59,43 @@ def analyse(rows):
     return out
 
 
+def occupancy(rows, resident):
+    """A launch of more workgroups than the chip holds (k_skm_scatter, $KHOICE_WG_DUMP_SCATTER): the filled share of the
+    `resident` workgroup places over the launch (sum of the workgroups' lives / (resident x span)), the mean
+    concurrency in every tenth of the span, and when the workgroups end."""
+    start, end = rows[:, 6].astype(np.float64), rows[:, 7].astype(np.float64)
+    t0, span = start.min(), end.max() - start.min()
+    edges = t0 + span * np.linspace(0.0, 1.0, 11)
+    conc = [float(np.clip(np.minimum(end, hi) - np.maximum(start, lo), 0, None).sum() / (hi - lo)) for lo, hi in zip(edges, edges[1:])]
+    frac = (end - t0) / span
+    q = np.quantile(frac, [0.0, 0.25, 0.5, 0.75, 1.0])
+    life = end - start
+    return {"workgroups": int(len(rows)), "resident": int(resident), "span_ticks": float(span),
+            "filled_share": float(life.sum() / (resident * span)), "mean_concurrency": float(life.sum() / span),
+            "concurrency_by_tenth": [round(c, 1) for c in conc],
+            "life_ticks": {"mean": float(life.mean()), "min": float(life.min()), "max": float(life.max())},
+            "end": {"min": float(q[0]), "q1": float(q[1]), "median": float(q[2]), "q3": float(q[3]),
+                    "share_before_0.9": float((frac < 0.9).mean())}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("dump")
     ap.add_argument("--call", type=int, default=None)
     ap.add_argument("--json", default=None)
+    ap.add_argument("--resident", type=int, default=0, help="a scatter dump: workgroups the chip holds at a time")
     a = ap.parse_args()
     rows = np.loadtxt(a.dump, dtype=np.uint64, ndmin=2)
     calls = np.unique(rows[:, 0])
     call = calls[-1] if a.call is None else a.call
+    if a.resident:
+        res = {"dump": a.dump, "calls_in_file": int(len(calls)), "call": int(call), **occupancy(rows[rows[:, 0] == call], a.resident)}
+        res["last_calls_filled_share"] = [round(occupancy(rows[rows[:, 0] == c], a.resident)["filled_share"], 4) for c in calls[-5:]]
+        print(json.dumps(res, indent=1))
+        if a.json:
+            with open(a.json, "w") as fh:
+                json.dump(res, fh, indent=1)
+        return
     res = {"dump": a.dump, "calls_in_file": int(len(calls)), "call": int(call), **analyse(rows[rows[:, 0] == call])}
     # how stable the picture is: the share before 0.9 and the idle wave-slot share (1 - mean end) of every call
     per_call = [analyse(rows[rows[:, 0] == c])["constant_clock"] for c in calls[-5:]]
