@@ -436,6 +436,19 @@ static void report_stamps(kh_ctx* c, const char* what, DevBuf* sb, u64 nparts) {
         }
         fprintf(stderr, "[stamps] %s offsets from t0:%s\n", what, line.c_str());
     }
+    // $KHOICE_STAMP_DUMP: every part's sixteen words, one line per part, appended (tools/union_stamps.py reads the
+    // union's: words 12 and 13 are the workgroup + 1 and the slot's place in its walk)
+    if (const char* path = getenv("KHOICE_STAMP_DUMP")) {
+        if (FILE* f = fopen(path, "a")) {
+            fprintf(f, "# %s\n", what);
+            for (u64 q = 0; q < nparts; ++q) {
+                fprintf(f, "%llu", (unsigned long long)q);
+                for (int i = 0; i < 16; ++i) fprintf(f, " %llu", (unsigned long long)h[q * 16 + i]);
+                fprintf(f, "\n");
+            }
+            fclose(f);
+        }
+    }
 }
 #ifdef KH_STAMPS_WG
 void kh_debug_set_stamps_skm2(u64* p);

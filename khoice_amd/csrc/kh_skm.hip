@@ -70,9 +70,21 @@ void kh_debug_set_stamps_skm(u64* p) { (void)hipMemcpyToSymbol(HIP_SYMBOL(g_skm_
         if (threadIdx.x == 0 && g_skm_stamps) g_skm_stamps[(u64)slot * 16 + (idx)] = __builtin_amdgcn_s_memtime(); \
         __builtin_amdgcn_sched_barrier(0);                                                 \
     } while (0)
+// (words 12 and 13 of a slot: the workgroup that walked it and the slot's place in that walk, so that a reader can put
+// a workgroup's slots behind each other: tools/union_stamps.py)
+#define SKM_USTAMP_WALK(seq)                                                               \
+    do {                                                                                   \
+        if (threadIdx.x == 0 && g_skm_stamps) {                                            \
+            g_skm_stamps[(u64)slot * 16 + 12] = blockIdx.x + 1u;                           \
+            g_skm_stamps[(u64)slot * 16 + 13] = (seq);                                     \
+        }                                                                                  \
+    } while (0)
 #else
 #define SKM_USTAMP(idx) do {} while (0)
 #define SKM_WGSTAMP(idx) do {} while (0)
+#endif
+#ifndef SKM_USTAMP_WALK
+#define SKM_USTAMP_WALK(seq) do {} while (0)
 #endif
 #if defined(KH_STAMPS) && defined(KH_STAMPS_WG)   // (the scatter's workgroups likewise; its phase stamps share the words: off)
 #undef SKM_STAMP
@@ -393,7 +405,9 @@ __global__ __launch_bounds__(SKM_NT, KH_TUNE_SKM_SCATTER_WAVES) void k_skm_scatt
 // 4. Read-out: the thread whose compare-and-swap CREATED an entry remembers where; once all masks are final it
 //    turns its own entries into histogram bins (popcount per group / number of groups).  Nobody scans the table,
 //    no key is read again, waves without chunks have nothing to do.  The read is an exchange that stores zero: the
-//    mask planes are clean for the next slot without being cleared (1.430 -> 1.407 ms).
+//    mask planes are clean for the next slot without being cleared (1.430 -> 1.407 ms).  A lean slot's read-out
+//    waits for the next slot's first barrier and shares a barrier interval with that slot's merge of identical
+//    records (KH_TUNE_SKM_UNION_OVERLAP at the kernel).
 //
 // Geometry <NT, T>: threads and table entries of a workgroup.  <1024, 4096>: 79 KB of LDS, two workgroups per CU.
 // (<512, 2048> with four per CU and <640, 2560> with three were measured slower: DESIGN.md §3, §8.)
@@ -526,7 +540,34 @@ struct SkmClaim1 {
 #ifndef KH_TUNE_SKM_UNION_COMPACT
 #define KH_TUNE_SKM_UNION_COMPACT 0
 #endif
-#define SKM_UNION_PRIO_UP(bit)   do { if ((KH_TUNE_SKM_UNION_PRIO) & (bit)) __builtin_amdgcn_s_setprio(KH_TUNE_SKM_UNION_PRIO_LEVEL); } while (0)
+// THE READ-OUT OF A LEAN SLOT IN THE NEXT SLOT'S MERGE INTERVAL (KH_TUNE_SKM_UNION_OVERLAP).  Read as written, a slot is
+//   stage + clear dd | B1 | merge identical records | B2 | clear keys | B3 | expand + insert | B4 | read-out | (next slot)
+// and two of these phases leave most of the workgroup idle on disjoint memory: in the merge only the waves that hold a
+// record work (key plane, rmask, owner, scratch[0]; adds to dupc), in the read-out only the creators of entries (mask
+// planes, gtab, hstripe; adds to dupc).  With the switch on a lean slot's insertion leaves `made` in registers and the
+// read-out runs behind the NEXT slot's barrier 1, in one barrier interval with that slot's merge:
+//   B4(s) | stage(s+1) + clear dd | B1 | { read-out(s)  ||  merge(s+1) } | B2 | clear keys | B3 | expand + insert(s+1) | B4(s+1)
+// No barrier moves and none is added: the first slot of a walk finds nothing to read out, the last slot's read-out
+// runs alone behind the loop, an empty slot (R0 = 0: three barriers, no insertion) reads out its predecessor like any
+// other and leaves nothing behind.  A multi-subset slot keeps all its read-outs where they were (every subset needs its
+// masks evaluated before the next one is inserted, the last one included: the slot leaves nothing behind either).
+//   0: the read-out directly behind barrier 4, as it was
+//   1: behind the next barrier 1; a wave with both jobs reads out first (`made` is dead before the merge)
+//   2: the same; a wave with both jobs merges first (at the raised priority of KH_TUNE_SKM_UNION_PRIO bit 0)
+// KH_TUNE_SKM_UNION_CHUNK_REV 1: chunks numbered from the last thread down (ctid = NT - 1 - tid), so that the waves
+// that hold records (threads 0 .. nrec - 1) are the last to get chunks, and the first wave draws the claim.
+// Measured (five runs each in one job, spreads 0.002 .. 0.004; profiles/README.md has every number): union 1.227 ms
+// with 0 (the same instructions as before the switch), 1.180 with 1, 1.171 with 2 — SHIPPED; with the chunks
+// reversed 1.215 and 1.212: off (why the reversed numbering costs 0.035 .. 0.04 was not looked into; it also reverses
+// the insertion's lane order against the record loads).  Priority bit 0 still holds against read-out waves: 1.180 ->
+// 1.209 without it.  61 VGPRs against 60, no scratch either way.
+#ifndef KH_TUNE_SKM_UNION_OVERLAP
+#define KH_TUNE_SKM_UNION_OVERLAP 2
+#endif
+#ifndef KH_TUNE_SKM_UNION_CHUNK_REV
+#define KH_TUNE_SKM_UNION_CHUNK_REV 0
+#endif
+#define SKM_UNION_PRIO_UP(bit)  do { if ((KH_TUNE_SKM_UNION_PRIO) & (bit)) __builtin_amdgcn_s_setprio(KH_TUNE_SKM_UNION_PRIO_LEVEL); } while (0)
 #define SKM_UNION_PRIO_DOWN(bit) do { if ((KH_TUNE_SKM_UNION_PRIO) & (bit)) __builtin_amdgcn_s_setprio(0); } while (0)
 template <u32 NT, u32 T, int KT>
 __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs, u32 first_claimed) {
@@ -634,6 +675,78 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs, 
         return false;
     };
     u32 st_full = 0, st_exp = 0;   // fullest slot seen, k-mer instances expanded (uniform)
+    constexpr int OVERLAP = KH_TUNE_SKM_UNION_OVERLAP;
+    constexpr bool LEAN_WALKER = KH_TUNE_SKM_UNION_COMPACT == 1 && E == 2;
+    constexpr u32 DRAW_WID = KH_TUNE_SKM_UNION_CHUNK_REV ? 0u : NW - 1u;   // the wave that runs out of chunks first
+    // ---- the read-out: every thread turns the entries it created (16-bit fields of `made`, per pass; `walked`: see
+    // KH_TUNE_SKM_UNION_COMPACT) into histogram bins.
+    // Invariant (MASKS_SELF_CLEAN): every non-zero mask has exactly one creator; it is read once, here, behind
+    // the barrier after the insertion, and the read stores zero — so both planes of both tables are zero when
+    // the next insertion phase (next subset, next slot) begins.  A mask is only ever ORed into behind a
+    // compare-and-swap that found its key or created it, and whoever created it recorded the place in `made`:
+    // in the probe rounds (`mk`), one key per lane (`where`, either table), or as the lane that walked a packed
+    // loser (`walked`: the lane whose key it was records nothing for it).  A key dropped under
+    // KH_ERR_CAPACITY touched no mask; a slot handed on inserts nothing (C = 0); with R > 1 each subset's
+    // read-out zeroes what that subset created before the barrier that precedes the next one.
+    // With KH_TUNE_SKM_UNION_OVERLAP the read-out of a lean slot s runs between barriers 1 and 2 of slot s + 1: behind
+    // B4(s), which ends the insertions of s, and before B3(s + 1), which the insertions of s + 1 follow.  In that
+    // interval nobody else touches the mask planes, gtab or hstripe (the merge works on the key plane, rmask, owner and
+    // scratch[0]); dupc is added to from both sides, and additions commute.
+    auto read_out = [&](auto walker_, u32 (&made)[SKM_PASSES][E / 2], u32 (&walked)[(SKM_PASSES + 1) / 2]) __attribute__((always_inline)) {
+        constexpr bool WALKER = decltype(walker_)::value;
+        u32 ones = 0;   // keys that sit in exactly one group
+#pragma unroll
+        for (u32 pass = 0; pass < SKM_PASSES; ++pass) {
+            u32 any = 0;
+#pragma unroll
+            for (int e = 0; e < E / 2; ++e) any |= made[pass][e];
+            const u32 walked_f = WALKER ? (walked[pass >> 1] >> (16u * (pass & 1u))) & 0xffffu : 0u;
+            any |= walked_f;
+#if defined(KH_ABLATE) && KH_ABLATE == 3
+            if (any != 0x7654321u) any = 0;   // timing study: no read-out
+#endif
+            if (!__builtin_amdgcn_ballot_w64(any != 0)) continue;
+#pragma unroll
+            for (int e = 0; e < E + (WALKER ? 1 : 0); ++e) {
+                const u32 f = e < E ? (made[pass][(e < E ? e : 0) >> 1] >> (16 * (e & 1))) & 0xffffu : walked_f;
+                if (f & 0x8000u) {
+                    const u32 at = f & 0x3fffu;
+                    const bool second = f & 0x4000u;
+                    u32 mlo, mhi;
+                    if (MASKS_SELF_CLEAN) {
+                        mlo = atomicExch((second ? omlo : tmlo) + at, 0u);
+                        mhi = atomicExch((second ? omhi : tmhi) + at, 0u);
+                    } else {
+                        mlo = (second ? omlo : tmlo)[at];
+                        mhi = (second ? omhi : tmhi)[at];
+                    }
+                    if (eval_mask(mlo, mhi)) ++ones;
+                }
+            }
+        }
+        if (__builtin_amdgcn_ballot_w64(ones != 0)) {
+            ones = wave_scan_add(ones);
+            if (lane == KH_WAVE - 1) atomicAdd(&hstripe[(jb.abase + 1u) << sshift], ones);
+        }
+        SKM_MARK("readout_done");
+    };
+    // what a lean slot's insertion leaves for the read-out behind the next barrier 1 (all zero: nothing)
+    u32 made_d[SKM_PASSES][E / 2], walked_d[(SKM_PASSES + 1) / 2];
+#pragma unroll
+    for (u32 ps = 0; ps < SKM_PASSES; ++ps)
+#pragma unroll
+        for (int e = 0; e < E / 2; ++e) made_d[ps][e] = 0u;
+#pragma unroll
+    for (u32 ps = 0; ps < (SKM_PASSES + 1) / 2; ++ps) walked_d[ps] = 0u;
+    auto read_out_deferred = [&]() __attribute__((always_inline)) {
+        read_out(std::integral_constant<bool, LEAN_WALKER>{}, made_d, walked_d);
+#pragma unroll
+        for (u32 ps = 0; ps < SKM_PASSES; ++ps)
+#pragma unroll
+            for (int e = 0; e < E / 2; ++e) made_d[ps][e] = 0u;
+#pragma unroll
+        for (u32 ps = 0; ps < (SKM_PASSES + 1) / 2; ++ps) walked_d[ps] = 0u;
+    };
     // ---- pipeline prologue: this slot's record, the next slot's count
     SkmSlotFeed feed(gridDim.x, nslots, first_claimed);
     u32 slot = blockIdx.x, slot_next = slot + gridDim.x;
@@ -641,6 +754,7 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs, 
     u32 nrec_next = count_of(slot_next);
     uint4 rr = tid < nrec ? (jb.reg2 + (u64)slot * cap2)[tid] : make_uint4(0, 0, 0, 0);
     SKM_WGSTAMP(0);
+    [[maybe_unused]] u32 walk_seq = 0;   // (stamp build)
     while (slot < nslots) {
         // (the thread number through an opaque copy, per slot: the many LDS addresses formed from it are worked out
         // where they are used instead of being kept in registers — and spilled — across the whole loop)
@@ -654,7 +768,8 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs, 
                 if (at < jb.big_cap) jb.big_list[at] = slot;
             }
         }
-        // ---- stage this slot's records, one per thread
+        // ---- stage this slot's records, one per thread (behind the previous slot's barrier 4: the key plane, rmask,
+        // owner and scratch[0] had their last readers in its insertions; its read-out, wherever it runs, reads none of them)
         u32 nj = 0;   // k-mers of this thread's record while it is alive
         const u32 tg = SkmRec1::tag(rr.w);
         const u32 rx = rr.x, ry = rr.y, rz = rr.z, rw = rr.w;   // (this slot's record; `rr` is loaded again below)
@@ -669,6 +784,7 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs, 
             rmask[tid] = 1u << (tg & 31u);
         }
         SKM_USTAMP(0);
+        SKM_USTAMP_WALK(walk_seq++);
         __syncthreads();
         SKM_USTAMP(1);
         // the slot after the next one (a claim drawn during the previous slot has arrived in LDS) and its count:
@@ -676,6 +792,9 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs, 
         const u32 slot_after = feed.take(scratch + 1);
         const u32 nrec_after = count_of(slot_after);
         const bool draw = feed.wants();   // (uniform)
+        // ---- the previous slot's read-out (lean slots; see KH_TUNE_SKM_UNION_OVERLAP): in this barrier interval with
+        // the merge below.  A wave with both jobs reads out first (1) or merges first (2).
+        if (OVERLAP == 1) { read_out_deferred(); SKM_USTAMP(7); }
         SKM_MARK("dedup");
         // ---- identical records meet: the first keeps its place, the others add their genome bit to its mask.  A
         // record that stays takes its chunks from a counter (chunks in the low half, k-mers in the high half) and
@@ -729,8 +848,10 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs, 
             SKM_UNION_PRIO_DOWN(1);
         }
         SKM_MARK("dedup_end");
+        if (OVERLAP == 2) { read_out_deferred(); SKM_USTAMP(7); }
         SKM_USTAMP(2);
-        __syncthreads();   // the staged records and the set of contents are dead, the previous slot's masks are read: the table is made
+        __syncthreads();   // barrier 2: the staged records and the set of contents are dead, the previous slot's masks are read and zero: the table is made
+        SKM_USTAMP(10);
         const u32 sc0 = scratch[0];   // chunks | k-mers << 16 of the merged records (reset behind the next barrier)
         if ((sc0 & 0xffffu) > G::MAXCH) {   // uniform, rare: the slot is handed to k_skm_big below; what the merge has counted is taken back
             if (tid < nrec && rmask[tid] == 0u) {
@@ -772,7 +893,8 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs, 
         auto slot_body = [&](auto multi_) __attribute__((always_inline)) {
             constexpr bool MULTI = decltype(multi_)::value;
             const u32 R = MULTI ? R0 : 1u;
-            const u32 ctid = tid;   // (a rotated numbering of the waves — other SIMDs busy from slot to slot — changed nothing)
+            // (a rotated numbering of the waves — other SIMDs busy from slot to slot — changed nothing)
+            const u32 ctid = KH_TUNE_SKM_UNION_CHUNK_REV ? NT - 1u - tid : tid;
             for (u32 q = 0; q < R; ++q) {
                 if (q) { clear_keys(); clear_masks(); __syncthreads(); }
                 unsigned long long emptyv = EMPTY;   // (opaque: made here, or the compiler keeps the constant in two VGPRs across the loop and spills it)
@@ -790,7 +912,6 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs, 
                 u32 walked[(SKM_PASSES + 1) / 2];
 #pragma unroll
                 for (u32 ps = 0; ps < (SKM_PASSES + 1) / 2; ++ps) walked[ps] = 0u;
-                u32 ones = 0;   // keys that sit in exactly one group
 #pragma unroll
                 for (u32 pass = 0; pass < SKM_PASSES; ++pass) {
                     if (pass * NT >= C) break;   // uniform
@@ -1014,61 +1135,29 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs, 
                 }
                 SKM_MARK("insert_done");
                 SKM_USTAMP(5);
-                // the next claim: one lane of the last wave, which runs out of chunks first; the barrier below and the
+                // the next claim: one lane of the wave that runs out of chunks first (DRAW_WID); the barrier below and the
                 // next slot's first one lie between this store and the threads that read it
                 if ((KH_TUNE_SKM_UNION_PRIO) & 4) {
-                    if (draw && q == 0 && wid == NW - 1u) {   // (scalars: the whole wave takes the branch)
+                    if (draw && q == 0 && wid == DRAW_WID) {   // (scalars: the whole wave takes the branch)
                         SKM_UNION_PRIO_UP(4);
-                        if (tid0 == NT - KH_WAVE) feed.draw(jb.claim, scratch + 1);
+                        if (tid0 == DRAW_WID * KH_WAVE) feed.draw(jb.claim, scratch + 1);
                         SKM_UNION_PRIO_DOWN(4);
                     }
-                } else if (draw && q == 0 && tid0 == NT - KH_WAVE) feed.draw(jb.claim, scratch + 1);
-                __syncthreads();
+                } else if (draw && q == 0 && tid0 == DRAW_WID * KH_WAVE) feed.draw(jb.claim, scratch + 1);
+                __syncthreads();   // barrier 4: the insertions are over, the KEY plane is dead, all masks are final
                 SKM_USTAMP(6);
-                // ---- all masks are final: every thread turns the entries it created into histogram bins.
-                // Invariant (MASKS_SELF_CLEAN): every non-zero mask has exactly one creator; it is read once, here, behind
-                // the barrier after the insertion, and the read stores zero — so both planes of both tables are zero when
-                // the next insertion phase (next subset, next slot) begins.  A mask is only ever ORed into behind a
-                // compare-and-swap that found its key or created it, and whoever created it recorded the place in `made`:
-                // in the probe rounds (`mk`), one key per lane (`where`, either table), or as the lane that walked a packed
-                // loser (`walked`: the lane whose key it was records nothing for it).  A key dropped under
-                // KH_ERR_CAPACITY touched no mask; a slot handed on inserts nothing (C = 0); with R > 1 each subset's
-                // read-out zeroes what that subset created before the barrier that precedes the next one.
+                if (!MULTI && OVERLAP != 0) {
+                    // the read-out waits for the next slot's barrier 1 (`read_out`, above): what this thread created goes along
 #pragma unroll
-                for (u32 pass = 0; pass < SKM_PASSES; ++pass) {
-                    u32 any = 0;
+                    for (u32 ps = 0; ps < SKM_PASSES; ++ps)
 #pragma unroll
-                    for (int e = 0; e < E / 2; ++e) any |= made[pass][e];
-                    const u32 walked_f = WALKER ? (walked[pass >> 1] >> (16u * (pass & 1u))) & 0xffffu : 0u;
-                    any |= walked_f;
-#if defined(KH_ABLATE) && KH_ABLATE == 3
-                    if (any != 0x7654321u) any = 0;   // timing study: no read-out
-#endif
-                    if (!__builtin_amdgcn_ballot_w64(any != 0)) continue;
+                        for (int e = 0; e < E / 2; ++e) made_d[ps][e] = made[ps][e];
 #pragma unroll
-                    for (int e = 0; e < E + (WALKER ? 1 : 0); ++e) {
-                        const u32 f = e < E ? (made[pass][(e < E ? e : 0) >> 1] >> (16 * (e & 1))) & 0xffffu : walked_f;
-                        if (f & 0x8000u) {
-                            const u32 at = f & 0x3fffu;
-                            const bool second = f & 0x4000u;
-                            u32 mlo, mhi;
-                            if (MASKS_SELF_CLEAN) {
-                                mlo = atomicExch((second ? omlo : tmlo) + at, 0u);
-                                mhi = atomicExch((second ? omhi : tmhi) + at, 0u);
-                            } else {
-                                mlo = (second ? omlo : tmlo)[at];
-                                mhi = (second ? omhi : tmhi)[at];
-                            }
-                            if (eval_mask(mlo, mhi)) ++ones;
-                        }
-                    }
+                    for (u32 ps = 0; ps < (SKM_PASSES + 1) / 2; ++ps) walked_d[ps] = walked[ps];
+                } else {
+                    read_out(std::integral_constant<bool, WALKER>{}, made, walked);
+                    SKM_USTAMP(7);
                 }
-                if (__builtin_amdgcn_ballot_w64(ones != 0)) {
-                    ones = wave_scan_add(ones);
-                    if (lane == KH_WAVE - 1) atomicAdd(&hstripe[(jb.abase + 1u) << sshift], ones);
-                }
-                SKM_MARK("readout_done");
-                SKM_USTAMP(7);
                 if (q + 1 < R) __syncthreads();
             }
         };
@@ -1079,15 +1168,19 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs, 
             slot_body(std::true_type{});
         }
         SKM_USTAMP(8);
-        if (draw && R0 == 0 && tid0 == NT - KH_WAVE) feed.draw(jb.claim, scratch + 1);   // (an empty slot: nothing was inserted)
-        // ---- on to the next slot: its record has arrived in the meantime.  No barrier here: what the next slot writes
-        // before its first barrier (staged records, the set of contents: the KEY plane; this thread's record mask)
-        // is read by nobody in the read-out.
+        if (draw && R0 == 0 && tid0 == DRAW_WID * KH_WAVE) feed.draw(jb.claim, scratch + 1);   // (an empty slot: nothing was inserted)
+        // ---- on to the next slot: its record has arrived in the meantime (it set out behind barrier 2 and had the
+        // key clear, the insertion and barrier 4 to arrive; the next load is issued where `rr` is free again, behind the
+        // next barrier 2).  No barrier here: what the next slot writes before its first barrier (staged records, the
+        // set of contents: the KEY plane, whose last readers were the insertions that barrier 4 ended — with R > 1 the
+        // last subset's barrier 4; this thread's record mask, read by those insertions too) is read by nobody in a
+        // read-out, whether that runs here (multi, or the switch at 0) or behind the next barrier 1.
         nrec = nrec_next;
         nrec_next = nrec_after;
         slot = slot_next;
         slot_next = slot_after;
     }
+    if (OVERLAP != 0) read_out_deferred();   // the walk's last lean slot (a workgroup without slots: nothing)
     SKM_WGSTAMP(8);
     __syncthreads();
     tid = tid0;
