@@ -2105,10 +2105,10 @@ static int exp1_skm(kh_ctx* c, const Exp1In& in, uint64_t* within_hist, uint64_t
         for (u32 v : h1) { t1 += v; m1 = std::max(m1, v); }
         for (u32 v : h2) { t2 += v; m2 = std::max(m2, v); }
         fprintf(stderr, "[skm] k=%d m=%d w=%u nmax=%u positions=%llu records=%llu (%.2f k-mers each) nb1=%u S=%u nslots=%u | "
-                        "coarse: mean %.0f max %u cap %u | slot: mean %.1f max %u cap %u | tiles %u x %u | expanded: %u k-mers | errors %u spilled %u overfull slots %u multi-subset slots %u tail-wide waves %u\n",
+                        "coarse: mean %.0f max %u cap %u | slot: mean %.1f max %u cap %u | tiles %u x %u | expanded: %u k-mers | errors %u spilled %u overfull slots %u multi-subset slots %u\n",
                 in.k, g.m, g.w, g.nmax, (unsigned long long)g.positions, (unsigned long long)t1, (double)g.positions / std::max<u64>(1, t1),
                 g.nb1, g.S, g.nslots, (double)t1 / g.nb1, m1, g.cap1, (double)t2 / g.nslots, m2, g.cap2, s.ntiles, job.tile_pos,
-                hc[KH_SKM_CTL_EXPANDED], hc[KH_SKM_CTL_ERR], hc[KH_SKM_CTL_SPILLED], hc[KH_SKM_CTL_LISTED], g.two ? 0u : hc[KH_SKM_CTL_MULTI], g.two ? 0u : hc[KH_SKM_CTL_TAILWIDE]);
+                hc[KH_SKM_CTL_EXPANDED], hc[KH_SKM_CTL_ERR], hc[KH_SKM_CTL_SPILLED], hc[KH_SKM_CTL_LISTED], g.two ? 0u : hc[KH_SKM_CTL_MULTI]);
     }
     bool declines = false;
     KHCHK(s.settle(0, [&](u32 nbig) {

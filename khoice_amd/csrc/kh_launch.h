@@ -140,7 +140,7 @@ enum : u32 {
     KH_SKM_CTL_FULLEST = 1,         // k-mer instances of the fullest slot seen (above the table's size only)
     KH_SKM_CTL_RECORDS = 2,         // records written by the scatter
     KH_SKM_CTL_EXPANDED = 3,        // k-mer instances expanded from the records
-    KH_SKM_CTL_TAILWIDE = 4,        // k_skm_union: waves with more than 64 keys left after probe round 1 of a pass
+    // (word 4 is unused; the words behind it keep their places: kernels address them by immediate offsets)
     KH_SKM_CTL_SPILLED = 5,         // records spilled to the side list (spill_rec / spill_slot)
     KH_SKM_CTL_LISTED = 6,          // slots listed in big_list
     KH_SKM_CTL_MULTI = 7,           // slots taken in more than one subset (k_skm_union) or round (k_skm_cross)

@@ -97,9 +97,6 @@ void kh_debug_set_stamps_skm(u64* p) { (void)hipMemcpyToSymbol(HIP_SYMBOL(g_skm_
 #else
 #define SKM_MARK(name) do {} while (0)
 #endif
-#ifndef KH_TUNE_SKM_SCATTER_PREFETCH
-#define KH_TUNE_SKM_SCATTER_PREFETCH 0   // 1: the next sub-tile's bases wait in registers while this one is processed (0.656 ms against 0.624: three workgroups per CU hide the load as well, with fewer registers)
-#endif
 #ifndef KH_TUNE_SKM_SCATTER_WAVES
 #define KH_TUNE_SKM_SCATTER_WAVES 3   // waves per SIMD the scatter is compiled for (workgroups of 4 waves per CU)
 #endif
@@ -146,24 +143,16 @@ __global__ __launch_bounds__(SKM_NT, KH_TUNE_SKM_SCATTER_WAVES) void k_skm_scatt
     u32 staged = 0, tile_recs = 0;   // uniform
 
     SkmFetch pre;
-#if KH_TUNE_SKM_SCATTER_PREFETCH
-    skm_fetch(sg.seq, sg.len, tile_pos0, pre);
-#endif
     for (int sub = 0; sub < subtiles; ++sub) {
         const u64 p0 = tile_pos0 + (u64)sub * SKM_SUB;
         if (p0 >= sg.npos) break;   // uniform
         __syncthreads();
         const bool stamp = sub == 1;
         if (stamp) SKM_STAMP(0);
-#if !KH_TUNE_SKM_SCATTER_PREFETCH
-        skm_fetch(sg.seq, sg.len, p0, pre);
-#endif
+        skm_fetch(sg.seq, sg.len, p0, pre);   // (fetched one sub-tile ahead into registers: 0.656 ms against 0.624, three workgroups per CU hide the load as well)
         skm_store(pre, code, bad16);
         __syncthreads();
         if (stamp) SKM_STAMP(1);
-#if KH_TUNE_SKM_SCATTER_PREFETCH
-        if (sub + 1 < subtiles && p0 + SKM_SUB < sg.npos) skm_fetch(sg.seq, sg.len, p0 + SKM_SUB, pre);
-#endif
         // ---- hashes of the m-mers starting at the thread's 32 positions
         u32 cw[3];   // bases p .. p + 47: the last of the thread's m-mers ends at base p + 31 + 15
 #pragma unroll
@@ -400,14 +389,14 @@ __global__ __launch_bounds__(SKM_NT, KH_TUNE_SKM_SCATTER_WAVES) void k_skm_scatt
 //    probing of the main one; occupied entries stay occupied, so every copy of a key takes the same decisions as
 //    the first.  (Measured and rejected: finishing the keys that lost round 1 one per lane in a loop — fewer
 //    instructions, but a chain of ~20 dependent LDS round trips per wave: 2.63 ms against 2.30; and the same keys
-//    packed into the wave's first lanes, all walking at once: KH_TUNE_SKM_UNION_COMPACT at the kernel.)
-//    The waves that hold records run the merge of identical records at a raised priority (KH_TUNE_SKM_UNION_PRIO).
+//    packed into the wave's first lanes, all walking at once: see at the kernel.)
+//    The waves that hold records run the merge of identical records at a raised priority.
 // 4. Read-out: the thread whose compare-and-swap CREATED an entry remembers where; once all masks are final it
 //    turns its own entries into histogram bins (popcount per group / number of groups).  Nobody scans the table,
 //    no key is read again, waves without chunks have nothing to do.  The read is an exchange that stores zero: the
 //    mask planes are clean for the next slot without being cleared (1.430 -> 1.407 ms).  A lean slot's read-out
 //    waits for the next slot's first barrier and shares a barrier interval with that slot's merge of identical
-//    records (KH_TUNE_SKM_UNION_OVERLAP at the kernel).
+//    records (the slot timeline at the kernel).
 //
 // Geometry <NT, T>: threads and table entries of a workgroup.  <1024, 4096>: 79 KB of LDS, two workgroups per CU.
 // (<512, 2048> with four per CU and <640, 2560> with three were measured slower: DESIGN.md §3, §8.)
@@ -493,82 +482,43 @@ struct SkmClaim1 {
 // count, then load the records" spent 2.5 of its 6 microseconds waiting for memory with nothing else to do.  The
 // histogram bins and the repeat counters stay in LDS over all slots of the workgroup and are written once.
 //
+// A SLOT, barrier by barrier.  Two of its phases leave most of the workgroup idle on disjoint memory: in the merge of
+// identical records only the waves that hold a record work (key plane, rmask, owner, scratch[0]; adds to dupc), in the
+// read-out only the creators of entries (mask planes, gtab, hstripe; adds to dupc).  So a lean slot's insertion leaves
+// `made` in registers and its read-out runs behind the NEXT slot's barrier 1, in one barrier interval with that slot's merge:
+//   B4(s) | stage(s+1) + clear dd | B1 | { merge(s+1), then read-out(s) } | B2 | clear keys | B3 | expand + insert(s+1) | B4(s+1)
+// A wave with both jobs merges first.  The first slot of a walk finds nothing to read out, the last slot's read-out runs
+// alone behind the loop, an empty slot (R0 = 0: three barriers, no insertion) reads out its predecessor like any other
+// and leaves nothing behind.  Union 1.227 -> 1.171 ms against the read-out directly behind barrier 4; 61 VGPRs against
+// 60, no scratch either way.
+//
 // TWO BODIES behind the third barrier (`slot_body`).  A slot whose merged k-mers fit the table (N <= T, what the planner
 // aims at: nearly every slot) takes the LEAN one: no subset loop, no subset filter per key, no clears and barriers
-// between subsets, and none of the scalars those keep alive.  A slot with N > T takes the MULTI one: R = ceil(N / T)
-// subsets of its keys, chosen by hash bits, inserted and read out one after the other on the same planes.  Both are
-// one piece of code with a compile-time flag; the masks-self-clean invariant (at the read-out) holds for either, so
-// lean and multi slots may follow each other in any order in one workgroup's walk.  KH_SKM_CTL_MULTI counts the multi slots.
-// KT: k at compile time (17 .. 32; the masks and shifts of the expansion are immediates), 0: k from the job.
-#ifndef KH_TUNE_SKM_UNION_LEAN
-#define KH_TUNE_SKM_UNION_LEAN 1   // 0: every slot through the multi body (timing study)
-#endif
-#ifndef KH_TUNE_SKM_UNION_KT
-#define KH_TUNE_SKM_UNION_KT 1     // 0: only the runtime-k instantiation (timing study)
-#endif
-// WAVE PRIORITY for phases in which few waves of a workgroup work and the rest wait at a barrier behind them
-// (KH_TUNE_SKM_UNION_PRIO, a bit mask; s_setprio ignores EXEC, so every guard is a ballot or a scalar and compiles to
-// an s_cbranch).  Arbitration goes by priority, then by age: in the merge of identical records only the ~6 waves of 16
-// that hold records work, and in the younger workgroup of a CU they queued behind the bulk insertion of the older one.
-//   bit 0: the waves that hold records, from barrier 1 to barrier 2 (the merge)      ON: union 1.258 -> 1.226 ms
-//   bit 1: the one-key-per-lane finish (or the packed walk, below)                   alone 1.245; on top of bit 0 1.223
-//   bit 2: the wave that draws the next claim                                        mask 7: 1.227
-// (five runs each, spreads 0.003 .. 0.007: only bit 0 passes "three times the larger spread" by itself; levels 1 and 3
-// time the same, 1.2257 / 1.2257 for mask 1 and 1.2232 / 1.2234 for mask 3.  profiles/README.md has every number.)
-#ifndef KH_TUNE_SKM_UNION_PRIO
-#define KH_TUNE_SKM_UNION_PRIO 1
-#endif
-#ifndef KH_TUNE_SKM_UNION_PRIO_LEVEL
-#define KH_TUNE_SKM_UNION_PRIO_LEVEL 1
-#endif
-// THE PROBE TAIL of the lean body PACKED (KH_TUNE_SKM_UNION_COMPACT; measured and rejected, off).  Round 1 places about
-// 82 % of a thread's keys; rounds 2 .. KH_TUNE_SKM_FULL_ROUNDS run at full width for the rest, then one key per lane.
-// With the switch on, the wave numbers the keys that lost round 1 (two ballots of `act`, e = 0 first, each in lane
-// order) and every loser pushes key, next probe position, genome bits and mask half to lane `rank` with ds_permute (no
-// LDS memory: there is none left); the L <= 64 packed lanes walk one key each through the same tiers, entered at
-// probe 2.  Every copy of a key takes the same decisions, so entries and masks do not change.  A wave with more than 64
-// losers (a table more than half full when the pass begins) takes the rounds and the finish behind a cold branch and
-// counts itself in KH_SKM_CTL_TAILWIDE.
-//   0: rounds and finish as they were
-//   1: the walking lane is the creator of what it creates (a per-pass field next to `made`, evaluated by the read-out
-//      like the others) and adds the repeats it meets to `dupc`                     union 1.258 -> 1.417 ms
-//   2: the place of a created entry is sent back to the lane that lost (ds_bpermute by its rank), which stays the
-//      creator: `made` and the read-out are untouched                               union 1.258 -> 1.347 ms
-// Fewer instructions (the rounds' 129 static vector instructions become 40), but the walk is a chain of dependent LDS
-// round trips per wave where the rounds make one trip for all keys: the same finding as the one-per-lane loop above.
-// With priority on the walk (mask 3) the two forms reach 1.363 and 1.299: still slower.
-#ifndef KH_TUNE_SKM_UNION_COMPACT
-#define KH_TUNE_SKM_UNION_COMPACT 0
-#endif
-// THE READ-OUT OF A LEAN SLOT IN THE NEXT SLOT'S MERGE INTERVAL (KH_TUNE_SKM_UNION_OVERLAP).  Read as written, a slot is
-//   stage + clear dd | B1 | merge identical records | B2 | clear keys | B3 | expand + insert | B4 | read-out | (next slot)
-// and two of these phases leave most of the workgroup idle on disjoint memory: in the merge only the waves that hold a
-// record work (key plane, rmask, owner, scratch[0]; adds to dupc), in the read-out only the creators of entries (mask
-// planes, gtab, hstripe; adds to dupc).  With the switch on a lean slot's insertion leaves `made` in registers and the
-// read-out runs behind the NEXT slot's barrier 1, in one barrier interval with that slot's merge:
-//   B4(s) | stage(s+1) + clear dd | B1 | { read-out(s)  ||  merge(s+1) } | B2 | clear keys | B3 | expand + insert(s+1) | B4(s+1)
-// No barrier moves and none is added: the first slot of a walk finds nothing to read out, the last slot's read-out
-// runs alone behind the loop, an empty slot (R0 = 0: three barriers, no insertion) reads out its predecessor like any
-// other and leaves nothing behind.  A multi-subset slot keeps all its read-outs where they were (every subset needs its
-// masks evaluated before the next one is inserted, the last one included: the slot leaves nothing behind either).
-//   0: the read-out directly behind barrier 4, as it was
-//   1: behind the next barrier 1; a wave with both jobs reads out first (`made` is dead before the merge)
-//   2: the same; a wave with both jobs merges first (at the raised priority of KH_TUNE_SKM_UNION_PRIO bit 0)
-// KH_TUNE_SKM_UNION_CHUNK_REV 1: chunks numbered from the last thread down (ctid = NT - 1 - tid), so that the waves
-// that hold records (threads 0 .. nrec - 1) are the last to get chunks, and the first wave draws the claim.
-// Measured (five runs each in one job, spreads 0.002 .. 0.004; profiles/README.md has every number): union 1.227 ms
-// with 0 (the same instructions as before the switch), 1.180 with 1, 1.171 with 2 — SHIPPED; with the chunks
-// reversed 1.215 and 1.212: off (why the reversed numbering costs 0.035 .. 0.04 was not looked into; it also reverses
-// the insertion's lane order against the record loads).  Priority bit 0 still holds against read-out waves: 1.180 ->
-// 1.209 without it.  61 VGPRs against 60, no scratch either way.
-#ifndef KH_TUNE_SKM_UNION_OVERLAP
-#define KH_TUNE_SKM_UNION_OVERLAP 2
-#endif
-#ifndef KH_TUNE_SKM_UNION_CHUNK_REV
-#define KH_TUNE_SKM_UNION_CHUNK_REV 0
-#endif
-#define SKM_UNION_PRIO_UP(bit)  do { if ((KH_TUNE_SKM_UNION_PRIO) & (bit)) __builtin_amdgcn_s_setprio(KH_TUNE_SKM_UNION_PRIO_LEVEL); } while (0)
-#define SKM_UNION_PRIO_DOWN(bit) do { if ((KH_TUNE_SKM_UNION_PRIO) & (bit)) __builtin_amdgcn_s_setprio(0); } while (0)
+// between subsets, and none of the scalars those keep alive; its read-out is the deferred one above.  A slot with N > T
+// takes the MULTI one: R = ceil(N / T) subsets of its keys, chosen by hash bits, inserted and read out one after the
+// other on the same planes, every read-out directly behind its subset's barrier 4 (every subset needs its masks
+// evaluated before the next one is inserted, the last one included: a multi slot leaves nothing behind).  Both are one
+// piece of code with a compile-time flag; the masks-self-clean invariant (at the read-out) holds for either, so lean
+// and multi slots may follow each other in any order in one workgroup's walk.  KH_SKM_CTL_MULTI counts the multi slots.
+// KT: k at compile time (17 .. 32; the masks and shifts of the expansion are immediates), 0: k from the job (15, 16).
+//
+// ONE PRIORITY RAISE: the waves that hold records run the merge, from barrier 1 to barrier 2, at wave priority 1
+// (s_setprio ignores EXEC, so the guard is a ballot and compiles to an s_cbranch).  Arbitration goes by priority, then
+// by age: only the ~6 waves of 16 that hold records work in the merge, and in the younger workgroup of a CU they queued
+// behind the bulk insertion of the older one.  Union 1.258 -> 1.226 ms; it holds against read-out waves too (1.180 ->
+// 1.209 without it).
+//
+// MEASURED AND REJECTED.  Each was a compile-time switch of this kernel up to the commit "k_skm_union: read out a slot
+// during the next slot's merge interval", where the code can be found; every number: profiles/README.md, DESIGN.md §8.
+//   - the keys that lose probe round 1 packed into the wave's first lanes by ds_permute, one key per lane through the
+//     tiers: 129 -> 40 static vector instructions, but a chain of dependent LDS round trips: 1.258 -> 1.417 / 1.347 ms.
+//   - priority also on the one-key-per-lane finish and on the wave that draws the claim: 1.223 / 1.227 against 1.226,
+//     inside the noise rule; priority levels 1 and 3 time the same.
+//   - a wave with both jobs reads out first, then merges: 1.180 ms against 1.171.
+//   - chunks numbered from the last thread down (the record-holding waves get chunks last): 1.215 / 1.212 against
+//     1.180 / 1.171; why was not looked into.
+//   - the mask planes cleared per slot instead of zeroed by the read-out's exchange: 1.430 against 1.407 ms.
+#define KH_TUNE_SKM_UNION_COMPACT 0   // (read by no code: the previous commit's tests/test_gpu_skm_union_tail.py parses this line at import)
 template <u32 NT, u32 T, int KT>
 __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs, u32 first_claimed) {
     extern __shared__ __attribute__((aligned(16))) u8 lds_raw[];
@@ -596,29 +546,17 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs, 
     // contents (record number + 1, 0: empty) is the second half.
     uint4* stage = reinterpret_cast<uint4*>(tkey);
     u32* dd = reinterpret_cast<u32*>(tkey) + T;
-    const u32 tid0 = threadIdx.x, wid = __builtin_amdgcn_readfirstlane(tid0 >> 6);
+    const u32 tid0 = threadIdx.x;
     u32 tid = tid0, lane = lane_id();
     const u32 nbins = jb.nbins, cap2 = jb.cap2, nslots = jb.nslots;
     const int k = KT ? KT : jb.k;
     const u32 sshift = nbins <= 72u ? 2u : (nbins <= 144u ? 1u : 0u), smask = (1u << sshift) - 1u;
+    // The keys of both tables are reset per slot (and per subset).  The mask planes are NOT: the read-out takes every
+    // mask it evaluates by an exchange that stores zero (the invariant is stated there), so they are zero whenever an
+    // insertion phase begins.
     auto clear_keys = [&]() {
         uint4* k4 = reinterpret_cast<uint4*>(tkey);
         for (u32 i = tid; i < T / 2; i += NT) k4[i] = make_uint4(0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu);
-    };
-    // The mask planes are NOT cleared per slot: the read-out takes every mask it evaluates by an exchange that stores
-    // zero (the invariant is stated there), so they are zero whenever an insertion phase begins.  Per slot only the
-    // second table's keys are reset.  (The timing variant without a read-out has to clear them.)
-#if !(defined(KH_ABLATE) && KH_ABLATE == 3)
-    constexpr bool MASKS_SELF_CLEAN = true;
-#else
-    constexpr bool MASKS_SELF_CLEAN = false;
-#endif
-    auto zero_masks = [&]() {
-        for (u32 i = tid; i < T / 2; i += NT) reinterpret_cast<uint4*>(tmlo)[i] = make_uint4(0u, 0u, 0u, 0u);   // (both mask planes)
-        if (tid < T2) { omlo[tid] = 0u; omhi[tid] = 0u; }
-    };
-    auto clear_masks = [&]() {
-        if (!MASKS_SELF_CLEAN) zero_masks();
         unsigned long long e0 = EMPTY;   // (opaque, as `emptyv` below)
         asm volatile("" : "+v"(e0));
         if (tid < T2) okey[tid] = e0;
@@ -639,7 +577,9 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs, 
     // had the same registers and 32 instructions fewer, and ran 1 % slower (1.431 -> 1.446 ms, three alternated runs
     // each, the parent's spread 0.003).  The BIN RULE is shared: a change of it has to be made in both.  The zeroing
     // of the masks as they are read is this kernel's alone: the kernels built on SkmReadout clear their planes.
-    if (MASKS_SELF_CLEAN) zero_masks();   // (once: the first slot's first barrier comes before any mask is touched)
+    // (the mask planes, once: the first slot's first barrier comes before any mask is touched)
+    for (u32 i = tid; i < T / 2; i += NT) reinterpret_cast<uint4*>(tmlo)[i] = make_uint4(0u, 0u, 0u, 0u);   // (both planes of the main table)
+    if (tid < T2) { omlo[tid] = 0u; omhi[tid] = 0u; }
     if (tid < (u32)KH_TAG_MAX_OPS) {
         const u32 g = jb.ginfo[tid], g0 = g & 0xffu, gn = (g >> 8) & 0xffu;
         const u64 gm = gn ? (gn >= 64u ? ~0ull : ((1ull << gn) - 1ull)) << g0 : 0ull;
@@ -675,51 +615,34 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs, 
         return false;
     };
     u32 st_full = 0, st_exp = 0;   // fullest slot seen, k-mer instances expanded (uniform)
-    constexpr int OVERLAP = KH_TUNE_SKM_UNION_OVERLAP;
-    constexpr bool LEAN_WALKER = KH_TUNE_SKM_UNION_COMPACT == 1 && E == 2;
-    constexpr u32 DRAW_WID = KH_TUNE_SKM_UNION_CHUNK_REV ? 0u : NW - 1u;   // the wave that runs out of chunks first
-    // ---- the read-out: every thread turns the entries it created (16-bit fields of `made`, per pass; `walked`: see
-    // KH_TUNE_SKM_UNION_COMPACT) into histogram bins.
-    // Invariant (MASKS_SELF_CLEAN): every non-zero mask has exactly one creator; it is read once, here, behind
+    // ---- the read-out: every thread turns the entries it created (16-bit fields of `made`, per pass) into histogram bins.
+    // Invariant (the masks clean themselves): every non-zero mask has exactly one creator; it is read once, here, behind
     // the barrier after the insertion, and the read stores zero — so both planes of both tables are zero when
     // the next insertion phase (next subset, next slot) begins.  A mask is only ever ORed into behind a
     // compare-and-swap that found its key or created it, and whoever created it recorded the place in `made`:
-    // in the probe rounds (`mk`), one key per lane (`where`, either table), or as the lane that walked a packed
-    // loser (`walked`: the lane whose key it was records nothing for it).  A key dropped under
+    // in the probe rounds (`mk`) or one key per lane (`where`, either table).  A key dropped under
     // KH_ERR_CAPACITY touched no mask; a slot handed on inserts nothing (C = 0); with R > 1 each subset's
     // read-out zeroes what that subset created before the barrier that precedes the next one.
-    // With KH_TUNE_SKM_UNION_OVERLAP the read-out of a lean slot s runs between barriers 1 and 2 of slot s + 1: behind
+    // The read-out of a lean slot s runs between barriers 1 and 2 of slot s + 1: behind
     // B4(s), which ends the insertions of s, and before B3(s + 1), which the insertions of s + 1 follow.  In that
     // interval nobody else touches the mask planes, gtab or hstripe (the merge works on the key plane, rmask, owner and
     // scratch[0]); dupc is added to from both sides, and additions commute.
-    auto read_out = [&](auto walker_, u32 (&made)[SKM_PASSES][E / 2], u32 (&walked)[(SKM_PASSES + 1) / 2]) __attribute__((always_inline)) {
-        constexpr bool WALKER = decltype(walker_)::value;
+    auto read_out = [&](u32 (&made)[SKM_PASSES][E / 2]) __attribute__((always_inline)) {
         u32 ones = 0;   // keys that sit in exactly one group
 #pragma unroll
         for (u32 pass = 0; pass < SKM_PASSES; ++pass) {
             u32 any = 0;
 #pragma unroll
             for (int e = 0; e < E / 2; ++e) any |= made[pass][e];
-            const u32 walked_f = WALKER ? (walked[pass >> 1] >> (16u * (pass & 1u))) & 0xffffu : 0u;
-            any |= walked_f;
-#if defined(KH_ABLATE) && KH_ABLATE == 3
-            if (any != 0x7654321u) any = 0;   // timing study: no read-out
-#endif
             if (!__builtin_amdgcn_ballot_w64(any != 0)) continue;
 #pragma unroll
-            for (int e = 0; e < E + (WALKER ? 1 : 0); ++e) {
-                const u32 f = e < E ? (made[pass][(e < E ? e : 0) >> 1] >> (16 * (e & 1))) & 0xffffu : walked_f;
+            for (int e = 0; e < E; ++e) {
+                const u32 f = (made[pass][e >> 1] >> (16 * (e & 1))) & 0xffffu;
                 if (f & 0x8000u) {
                     const u32 at = f & 0x3fffu;
                     const bool second = f & 0x4000u;
-                    u32 mlo, mhi;
-                    if (MASKS_SELF_CLEAN) {
-                        mlo = atomicExch((second ? omlo : tmlo) + at, 0u);
-                        mhi = atomicExch((second ? omhi : tmhi) + at, 0u);
-                    } else {
-                        mlo = (second ? omlo : tmlo)[at];
-                        mhi = (second ? omhi : tmhi)[at];
-                    }
+                    const u32 mlo = atomicExch((second ? omlo : tmlo) + at, 0u);
+                    const u32 mhi = atomicExch((second ? omhi : tmhi) + at, 0u);
                     if (eval_mask(mlo, mhi)) ++ones;
                 }
             }
@@ -731,21 +654,19 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs, 
         SKM_MARK("readout_done");
     };
     // what a lean slot's insertion leaves for the read-out behind the next barrier 1 (all zero: nothing)
-    u32 made_d[SKM_PASSES][E / 2], walked_d[(SKM_PASSES + 1) / 2];
+    // (zeroed here by a loop in place and again behind every deferred read-out: one shared lambda, or `= {}` here,
+    // moves the register allocation of the whole kernel)
+    u32 made_d[SKM_PASSES][E / 2];
 #pragma unroll
     for (u32 ps = 0; ps < SKM_PASSES; ++ps)
 #pragma unroll
         for (int e = 0; e < E / 2; ++e) made_d[ps][e] = 0u;
-#pragma unroll
-    for (u32 ps = 0; ps < (SKM_PASSES + 1) / 2; ++ps) walked_d[ps] = 0u;
     auto read_out_deferred = [&]() __attribute__((always_inline)) {
-        read_out(std::integral_constant<bool, LEAN_WALKER>{}, made_d, walked_d);
+        read_out(made_d);
 #pragma unroll
         for (u32 ps = 0; ps < SKM_PASSES; ++ps)
 #pragma unroll
             for (int e = 0; e < E / 2; ++e) made_d[ps][e] = 0u;
-#pragma unroll
-        for (u32 ps = 0; ps < (SKM_PASSES + 1) / 2; ++ps) walked_d[ps] = 0u;
     };
     // ---- pipeline prologue: this slot's record, the next slot's count
     SkmSlotFeed feed(gridDim.x, nslots, first_claimed);
@@ -792,15 +713,12 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs, 
         const u32 slot_after = feed.take(scratch + 1);
         const u32 nrec_after = count_of(slot_after);
         const bool draw = feed.wants();   // (uniform)
-        // ---- the previous slot's read-out (lean slots; see KH_TUNE_SKM_UNION_OVERLAP): in this barrier interval with
-        // the merge below.  A wave with both jobs reads out first (1) or merges first (2).
-        if (OVERLAP == 1) { read_out_deferred(); SKM_USTAMP(7); }
         SKM_MARK("dedup");
         // ---- identical records meet: the first keeps its place, the others add their genome bit to its mask.  A
         // record that stays takes its chunks from a counter (chunks in the low half, k-mers in the high half) and
         // enters them into the chunk table at once: no block scan, no phase of its own.
         if (__builtin_amdgcn_ballot_w64(nj != 0)) {   // (waves without records go straight to the barrier)
-            SKM_UNION_PRIO_UP(1);
+            __builtin_amdgcn_s_setprio(1);   // (the one priority raise: see above the kernel)
             u32 h = rx * 0x9E3779B1u ^ ry * 0x85EBCA77u ^ rz * 0xC2B2AE3Du ^ SkmRec1::content_hash_word(rw) * 0x27D4EB2Fu;
             h ^= h >> 15;
             h *= 0x2C1B3C6Du;
@@ -845,10 +763,13 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs, 
                         if (cc < nch) owner[cstart + cc] = (u16)((tid << SKM_OB) | cc);
                 }
             }
-            SKM_UNION_PRIO_DOWN(1);
+            __builtin_amdgcn_s_setprio(0);
         }
         SKM_MARK("dedup_end");
-        if (OVERLAP == 2) { read_out_deferred(); SKM_USTAMP(7); }
+        // ---- the previous slot's read-out (lean slots): in this barrier interval with the merge above, which a wave
+        // with both jobs has done first
+        read_out_deferred();
+        SKM_USTAMP(7);
         SKM_USTAMP(2);
         __syncthreads();   // barrier 2: the staged records and the set of contents are dead, the previous slot's masks are read and zero: the table is made
         SKM_USTAMP(10);
@@ -864,7 +785,6 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs, 
         // expansion and the read-out to arrive
         rr = tid < nrec_next ? (jb.reg2 + (u64)slot_next * cap2)[tid] : make_uint4(0, 0, 0, 0);
         clear_keys();
-        clear_masks();
         u32 C = sc0 & 0xffffu, N = sc0 >> 16;
         SKM_USTAMP(3);
         SKM_MARK("after_scan");
@@ -880,9 +800,6 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs, 
             C = 0;
             N = 0;
         }
-#if defined(KH_ABLATE) && KH_ABLATE == 1
-        C = 0; N = 0;   // timing study: nothing is expanded
-#endif
         __syncthreads();
         if (tid == 0) scratch[0] = 0;   // (everybody has read it; it is added to again behind the next slot's first barrier)
         SKM_MARK("owner_done");
@@ -893,10 +810,12 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs, 
         auto slot_body = [&](auto multi_) __attribute__((always_inline)) {
             constexpr bool MULTI = decltype(multi_)::value;
             const u32 R = MULTI ? R0 : 1u;
-            // (a rotated numbering of the waves — other SIMDs busy from slot to slot — changed nothing)
-            const u32 ctid = KH_TUNE_SKM_UNION_CHUNK_REV ? NT - 1u - tid : tid;
+            // the thread's chunk in pass 0; in pass p: c0 + p * NT.  (Read here, before the subset loop: with `tid` read
+            // inside the pass loop the multi body's chunk addresses are scheduled in another order.  A rotated numbering
+            // of the waves — other SIMDs busy from slot to slot — changed nothing.)
+            const u32 c0 = tid;
             for (u32 q = 0; q < R; ++q) {
-                if (q) { clear_keys(); clear_masks(); __syncthreads(); }
+                if (q) { clear_keys(); __syncthreads(); }
                 unsigned long long emptyv = EMPTY;   // (opaque: made here, or the compiler keeps the constant in two VGPRs across the loop and spills it)
                 asm volatile("" : "+v"(emptyv));
                 // entries this thread created, per pass: 16-bit fields (bit 15: set = valid, bit 14: second table)
@@ -905,17 +824,10 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs, 
                 for (u32 ps = 0; ps < SKM_PASSES; ++ps)
 #pragma unroll
                     for (int e = 0; e < E / 2; ++e) made[ps][e] = 0u;
-                // the probe tail packed (see KH_TUNE_SKM_UNION_COMPACT); WALKER: the lane that walks a key is the creator
-                // of its entry and keeps the place here, one 16-bit field per pass, laid out like `made`
-                constexpr bool COMPACT = !MULTI && KH_TUNE_SKM_UNION_COMPACT != 0 && E == 2;
-                constexpr bool WALKER = COMPACT && KH_TUNE_SKM_UNION_COMPACT == 1;
-                u32 walked[(SKM_PASSES + 1) / 2];
-#pragma unroll
-                for (u32 ps = 0; ps < (SKM_PASSES + 1) / 2; ++ps) walked[ps] = 0u;
 #pragma unroll
                 for (u32 pass = 0; pass < SKM_PASSES; ++pass) {
                     if (pass * NT >= C) break;   // uniform
-                    const u32 c = pass * NT + ctid;
+                    const u32 c = pass * NT + c0;
                     u64 kreg[E];
                     u32 slot_[E], act = 0, bits = 0, half = 0;
 #pragma unroll
@@ -959,9 +871,6 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs, 
                         }
                         if (R == 1) act = (1u << cnt) - 1u;
                     }
-#if defined(KH_ABLATE) && KH_ABLATE == 2
-                    if (kreg[0] != 0x1234567ull) act = 0;   // timing study: expanded, not inserted
-#endif
                     SKM_MARK("expanded");
                     if (!__builtin_amdgcn_ballot_w64(act != 0)) continue;   // a wave without a chunk
                     u32* const mp = half ? tmhi : tmlo;
@@ -992,14 +901,13 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs, 
                     };
                     u32 f16[E];   // where each key's entry is, if this thread created it
                     auto chain_home = [&](const u32 H) __attribute__((always_inline)) -> u32 { return ((H ^ (H >> 15)) * 0x85EBCA77u) >> T2SH; };
-                    // One key per lane through the tiers, from entry S on; -> where the lane created an entry.  Level 1: second
-                    // table, 2: main table, unbounded; FROM_MAIN (the packed walk alone) enters at level 0: the main table up to
-                    // KH_TUNE_SKM_FULL_ROUNDS probes, `probes` of them made already.  The lane counts the repeats it meets.
-                    auto tier_walk = [&](auto from_main_, const unsigned long long K, const u32 H, const u32 kbits, const u32 khalf,
-                                         u32 S, u32 probes, bool mine) __attribute__((always_inline)) -> u32 {
-                        constexpr bool FROM_MAIN = decltype(from_main_)::value;
+                    // One key per lane through the tiers, from entry S of the second table on; -> where the lane created an
+                    // entry.  Level 1: second table, 2: main table, unbounded.  The lane counts the repeats it meets.
+                    auto tier_walk = [&](const unsigned long long K, const u32 H, const u32 kbits, const u32 khalf,
+                                         u32 S, bool mine) __attribute__((always_inline)) -> u32 {
+                        u32 probes = 0;   // at the current level
                         u32* const kmp = khalf ? tmhi : tmlo;
-                        u32 level = FROM_MAIN ? 0u : 1u, where = 0;
+                        u32 level = 1u, where = 0;
                         while (__builtin_amdgcn_ballot_w64(mine)) {
                             if (mine) {
                                 unsigned long long* kp = level == 1 ? okey : tkey;
@@ -1012,10 +920,7 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs, 
                                     mine = false;
                                 } else {
                                     ++probes;
-                                    if (FROM_MAIN && level == 0 && probes >= (u32)KH_TUNE_SKM_FULL_ROUNDS) {
-                                        level = 1; probes = 0;
-                                        S = chain_home(H);
-                                    } else if (level == 1 && probes >= 8u) {   // a crowded second table: on in the main one
+                                    if (level == 1 && probes >= 8u) {   // a crowded second table: on in the main one
                                         level = 2; probes = 0;
                                         S = (u32)(((u64)H * T) >> 32) + (u32)KH_TUNE_SKM_FULL_ROUNDS;
                                         S = S & (T - 1u);
@@ -1044,7 +949,7 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs, 
                             for (int e = 0; e < E; ++e)
                                 if (es == (u32)e) K = kreg[e];
                             const u32 H = key_hash2((u32)K, (u32)(K >> 32));
-                            const u32 where = tier_walk(std::false_type{}, (unsigned long long)K, H, bits, half, chain_home(H), 0u, have_one);
+                            const u32 where = tier_walk((unsigned long long)K, H, bits, half, chain_home(H), have_one);
                             if (have_one) {
                                 act &= ~(1u << es);
 #pragma unroll
@@ -1053,70 +958,12 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs, 
                             }
                         }
                     };
-                    if (!COMPACT) {
-                        for (u32 round = 0; round < (u32)KH_TUNE_SKM_FULL_ROUNDS && __builtin_amdgcn_ballot_w64(act != 0); ++round) probe_round();
-                        SKM_USTAMP(9);
-                        SKM_MARK("rounds_done");
+                    for (u32 round = 0; round < (u32)KH_TUNE_SKM_FULL_ROUNDS && __builtin_amdgcn_ballot_w64(act != 0); ++round) probe_round();
+                    SKM_USTAMP(9);
+                    SKM_MARK("rounds_done");
 #pragma unroll
-                        for (int e = 0; e < E; ++e) f16[e] = (mk >> e) & 1u ? (0x8000u | slot_[e]) : 0u;
-                        if (((KH_TUNE_SKM_UNION_PRIO) & 2) && !MULTI) {
-                            if (__builtin_amdgcn_ballot_w64(act != 0)) {   // (uniform)
-                                SKM_UNION_PRIO_UP(2);
-                                serial_finish();
-                                SKM_UNION_PRIO_DOWN(2);
-                            }
-                        } else {
-                            serial_finish();
-                        }
-                    } else {
-                        probe_round();
-                        SKM_USTAMP(9);
-                        SKM_MARK("rounds_done");
-#pragma unroll
-                        for (int e = 0; e < E; ++e) f16[e] = (mk >> e) & 1u ? (0x8000u | slot_[e]) : 0u;
-                        // the keys that lost round 1: e = 0 first, then e = 1, each in lane order
-                        const u64 b0 = __builtin_amdgcn_ballot_w64((act & 1u) != 0), b1 = __builtin_amdgcn_ballot_w64((act & 2u) != 0);
-                        const u32 L0 = (u32)__popcll(b0), L = L0 + (u32)__popcll(b1);   // (uniform)
-                        if (L > KH_WAVE) {   // (uniform, cold: a crowded table) the remaining rounds and the finish
-                            if (lane == 0) atomicAdd(jb.ctl + KH_SKM_CTL_TAILWIDE, 1u);
-                            for (u32 round = 1; round < (u32)KH_TUNE_SKM_FULL_ROUNDS && __builtin_amdgcn_ballot_w64(act != 0); ++round) probe_round();
-#pragma unroll
-                            for (int e = 0; e < E; ++e) f16[e] = (mk >> e) & 1u ? (0x8000u | slot_[e]) : 0u;
-                            serial_finish();
-                        } else if (L) {
-                            SKM_UNION_PRIO_UP(2);
-                            // Every lane pushes, so that no lane depends on EXEC for what it receives: per key register the
-                            // destinations are a permutation of the lanes (ds_permute takes the lane modulo 64) that sends
-                            // the losers to their ranks and everybody else behind them.
-                            const u32 n0 = __builtin_amdgcn_mbcnt_hi((u32)(b0 >> 32), __builtin_amdgcn_mbcnt_lo((u32)b0, 0u));
-                            const u32 n1 = __builtin_amdgcn_mbcnt_hi((u32)(b1 >> 32), __builtin_amdgcn_mbcnt_lo((u32)b1, 0u));
-                            const u32 d0 = ((act & 1u) ? n0 : L0 + (lane - n0)) << 2;
-                            const u32 d1 = ((act & 2u) ? L0 + n1 : L + (lane - n1)) << 2;
-                            const bool sel0 = lane < L0;
-                            auto packed = [&](const u32 v0, const u32 v1) __attribute__((always_inline)) -> u32 {
-                                const u32 r0 = (u32)__builtin_amdgcn_ds_permute((int)d0, (int)v0);
-                                const u32 r1 = (u32)__builtin_amdgcn_ds_permute((int)d1, (int)v1);
-                                return sel0 ? r0 : r1;
-                            };
-                            const u32 wkl = packed((u32)kreg[0], (u32)kreg[1]), wkh = packed((u32)(kreg[0] >> 32), (u32)(kreg[1] >> 32));
-                            const u32 wph = packed(slot_[0] | (half << 16), slot_[1] | (half << 16));   // the next probe position, the mask half
-                            const u32 wbits = packed(bits, bits);
-                            const unsigned long long K = ((unsigned long long)wkh << 32) | wkl;
-                            // the tiers of rounds and finish, entered at probe 2 of the main table
-                            static_assert(!COMPACT || KH_TUNE_SKM_FULL_ROUNDS >= 2, "the packed walk enters the main table's rounds at probe 2");
-                            const u32 where = tier_walk(std::true_type{}, K, key_hash2(wkl, wkh), wbits, wph >> 16, wph & 0xffffu, 1u, lane < L);
-                            if (WALKER) {
-                                walked[pass >> 1] |= where << (16u * (pass & 1u));
-                            } else {   // the place goes back to the lane that lost: it stays the creator
-                                const u32 w0 = (u32)__builtin_amdgcn_ds_bpermute((int)d0, (int)where);
-                                const u32 w1 = (u32)__builtin_amdgcn_ds_bpermute((int)d1, (int)where);
-                                if (act & 1u) f16[0] = w0;
-                                if (act & 2u) f16[1] = w1;
-                            }
-                            act = 0;
-                            SKM_UNION_PRIO_DOWN(2);
-                        }
-                    }
+                    for (int e = 0; e < E; ++e) f16[e] = (mk >> e) & 1u ? (0x8000u | slot_[e]) : 0u;
+                    serial_finish();
                     SKM_MARK("serial_done");
 #pragma unroll
                     for (int e = 0; e < E / 2; ++e) made[pass][e] = f16[2 * e] | (f16[2 * e + 1] << 16);
@@ -1135,52 +982,44 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs, 
                 }
                 SKM_MARK("insert_done");
                 SKM_USTAMP(5);
-                // the next claim: one lane of the wave that runs out of chunks first (DRAW_WID); the barrier below and the
+                // the next claim: one lane of the wave that runs out of chunks first (the last one); the barrier below and the
                 // next slot's first one lie between this store and the threads that read it
-                if ((KH_TUNE_SKM_UNION_PRIO) & 4) {
-                    if (draw && q == 0 && wid == DRAW_WID) {   // (scalars: the whole wave takes the branch)
-                        SKM_UNION_PRIO_UP(4);
-                        if (tid0 == DRAW_WID * KH_WAVE) feed.draw(jb.claim, scratch + 1);
-                        SKM_UNION_PRIO_DOWN(4);
-                    }
-                } else if (draw && q == 0 && tid0 == DRAW_WID * KH_WAVE) feed.draw(jb.claim, scratch + 1);
+                if (draw && q == 0 && tid0 == (NW - 1u) * KH_WAVE) feed.draw(jb.claim, scratch + 1);
                 __syncthreads();   // barrier 4: the insertions are over, the KEY plane is dead, all masks are final
                 SKM_USTAMP(6);
-                if (!MULTI && OVERLAP != 0) {
+                if (!MULTI) {
                     // the read-out waits for the next slot's barrier 1 (`read_out`, above): what this thread created goes along
 #pragma unroll
                     for (u32 ps = 0; ps < SKM_PASSES; ++ps)
 #pragma unroll
                         for (int e = 0; e < E / 2; ++e) made_d[ps][e] = made[ps][e];
-#pragma unroll
-                    for (u32 ps = 0; ps < (SKM_PASSES + 1) / 2; ++ps) walked_d[ps] = walked[ps];
                 } else {
-                    read_out(std::integral_constant<bool, WALKER>{}, made, walked);
+                    read_out(made);
                     SKM_USTAMP(7);
                 }
                 if (q + 1 < R) __syncthreads();
             }
         };
-        if (KH_TUNE_SKM_UNION_LEAN && R0 == 1u) {
+        if (R0 == 1u) {
             slot_body(std::false_type{});
         } else if (__builtin_expect(R0 != 0u, 0)) {   // (uniform, cold)
             if (R0 > 1u && tid0 == 0) atomicAdd(jb.ctl + KH_SKM_CTL_MULTI, 1u);   // slots taken in more than one subset
             slot_body(std::true_type{});
         }
         SKM_USTAMP(8);
-        if (draw && R0 == 0 && tid0 == DRAW_WID * KH_WAVE) feed.draw(jb.claim, scratch + 1);   // (an empty slot: nothing was inserted)
+        if (draw && R0 == 0 && tid0 == (NW - 1u) * KH_WAVE) feed.draw(jb.claim, scratch + 1);   // (an empty slot: nothing was inserted)
         // ---- on to the next slot: its record has arrived in the meantime (it set out behind barrier 2 and had the
         // key clear, the insertion and barrier 4 to arrive; the next load is issued where `rr` is free again, behind the
         // next barrier 2).  No barrier here: what the next slot writes before its first barrier (staged records, the
         // set of contents: the KEY plane, whose last readers were the insertions that barrier 4 ended — with R > 1 the
         // last subset's barrier 4; this thread's record mask, read by those insertions too) is read by nobody in a
-        // read-out, whether that runs here (multi, or the switch at 0) or behind the next barrier 1.
+        // read-out, whether that ran in place (multi) or runs behind the next barrier 1 (lean).
         nrec = nrec_next;
         nrec_next = nrec_after;
         slot = slot_next;
         slot_next = slot_after;
     }
-    if (OVERLAP != 0) read_out_deferred();   // the walk's last lean slot (a workgroup without slots: nothing)
+    read_out_deferred();   // the walk's last lean slot (a workgroup without slots: nothing)
     SKM_WGSTAMP(8);
     __syncthreads();
     tid = tid0;
@@ -1437,10 +1276,6 @@ __global__ __launch_bounds__(SKM_PH_NT, 8) void k_skm_phased(const KhSkmPhasedJo
     };
     auto fold_now = [&]() {
         __syncthreads();
-#if defined(KH_PH_ABLATE) && KH_PH_ABLATE == 2   // (timing study 2: barriers without the fold's work)
-        __syncthreads();
-        return;
-#endif
         uint4 m4 = reinterpret_cast<uint4*>(tmlo)[tid];
         if (m4.x | m4.y | m4.z | m4.w) {
             uint4 c4 = reinterpret_cast<uint4*>(tcnt)[tid];
@@ -1549,23 +1384,17 @@ __global__ __launch_bounds__(SKM_PH_NT, 8) void k_skm_phased(const KhSkmPhasedJo
             // A phase = a piece and the pieces joined to it (join_next: the same tags — a sub-batch's side list): the fold
             // comes behind the last of them that holds records of this slot.
             bool open = false;   // uniform: insertions since the last fold
-#if defined(KH_PH_ABLATE) && KH_PH_ABLATE == 3   // (timing study 3: no phases at all)
-            if (false) {
-#else
             if (all_staged) {
-#endif
                 for (u32 ph = 0; ph < npieces; ++ph) {
                     const u32 c0 = cbeg[ph], c1 = cend[ph], fl = pflag[ph];
                     if (c0 != c1) {   // uniform
                         const uint4* __restrict__ rec = prec[ph] + poff[ph];
                         const u32* __restrict__ msk = pmsk[ph] + poff[ph];
                         u32 fresh_n = 0;
-#if !defined(KH_PH_ABLATE) || KH_PH_ABLATE != 1   // (timing study 1: no insertion)
                         for (u32 c = c0 + tid; c < c1; c += NT) {
                             const u32 o = owner[c], ri = rloc[o >> SKM_PH_OB] & 1023u;
                             insert_chunk(rec[ri], msk[ri], (o & ((1u << SKM_PH_OB) - 1u)) * (u32)E, fl >> 1, R, q, fresh_n);
                         }
-#endif
                         count_fresh(fresh_n);
                         open = true;
                     }
@@ -1670,13 +1499,11 @@ template <int KT> static void launch_union_k(const KhSkmJob& job, u32 cs, u32 gr
 }
 static void kh_launch_skm_union(const KhSkmJob& job, u32 cs, u32 grid, hipStream_t st) {
     switch (job.k) {
-#if KH_TUNE_SKM_UNION_KT
 #define SKM_K(KK) case KK: launch_union_k<KK>(job, cs, grid, st); break;
         SKM_K(17) SKM_K(18) SKM_K(19) SKM_K(20) SKM_K(21) SKM_K(22) SKM_K(23) SKM_K(24)
         SKM_K(25) SKM_K(26) SKM_K(27) SKM_K(28) SKM_K(29) SKM_K(30) SKM_K(31) SKM_K(32)
 #undef SKM_K
-#endif
-        default: launch_union_k<0>(job, cs, grid, st); break;   // any other k that reaches here: k from the job
+        default: launch_union_k<0>(job, cs, grid, st); break;   // any other k that reaches here (15, 16): k from the job
     }
 }
 // ------------------------------------------------------------------------------------------

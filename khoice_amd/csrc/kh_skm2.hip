@@ -543,7 +543,6 @@ __global__ __launch_bounds__(SKM2_UNT, SKM2_UNT == 1024 ? 8 : 6) void k_skm2_uni
         __syncthreads();
         if (tid == 0) scratch[0] = 0;
         const u32 R = (N + T - 1) / T;
-        const u32 ctid = tid;
         for (u32 q = 0; q < R; ++q) {
             if (q) { clear_keys(); clear_masks(); __syncthreads(); }
             u32 made[SKM2_PASSES];
@@ -553,7 +552,7 @@ __global__ __launch_bounds__(SKM2_UNT, SKM2_UNT == 1024 ? 8 : 6) void k_skm2_uni
 #pragma unroll
             for (u32 pass = 0; pass < SKM2_PASSES; ++pass) {
                 if (pass * NT >= C) break;
-                const u32 c = pass * NT + ctid;
+                const u32 c = pass * NT + tid;
                 u64 klo[E], khi[E];
                 u32 slot_[E], act = 0, bits = 0, half = 0;
 #pragma unroll

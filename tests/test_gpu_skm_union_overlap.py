@@ -1,6 +1,6 @@
-"""k_skm_union (khoice_amd/csrc/kh_skm.hip) with a lean slot's read-out moved behind the NEXT slot's first barrier
-(KH_TUNE_SKM_UNION_OVERLAP): the read-out of slot s and the merge of identical records of slot s + 1 share one barrier
-interval of a persistent workgroup's walk.
+"""k_skm_union (khoice_amd/csrc/kh_skm.hip) with a lean slot's read-out moved behind the NEXT slot's first barrier:
+the read-out of slot s and the merge of identical records of slot s + 1 share one barrier interval of a persistent
+workgroup's walk.
 
 What can go wrong is what one slot leaves for the next: `made` carried across the staging, a read-out that is skipped
 or done twice (empty slots, multi-subset slots and slots handed to k_skm_big in between, the walk's last slot), masks
@@ -8,8 +8,7 @@ that are not zero when the next insertion begins, repeats counted by the merge a
 KHOICE_SKM_MEAN makes the slots small enough that every workgroup walks several.  Every case: against the C
 restatement bit for bit, a second call that must equal the first, and the fast form must have answered.
 
-The switches of the kernel (the order inside the interval, KH_TUNE_SKM_UNION_CHUNK_REV, KH_TUNE_SKM_UNION_PRIO) are
-compile-time ones: the shipped library holds one position of each, and that one is what runs here."""
+Inside the interval a wave with both jobs merges first, at the raised priority of the merge."""
 import functools
 import re
 

@@ -11,7 +11,7 @@ if [ "${1:-}" = wg ]; then
   shift
   python -c 'import sys; from khoice_amd import build as b; print("built", b.build_library(True, f"{b.LIBDIR}/diag/libkhoice_hip_diag_wg.so", ["-DKH_STAMPS", "-DKH_STAMPS_WG"] + sys.argv[1:]))' "$@"
 else
-  # (extra flags, e.g. -DKH_TUNE_SKM_UNION_OVERLAP=0; KHOICE_STAMP_DUMP=file appends every part's stamps of a call,
+  # (extra flags, e.g. -DKH_TUNE_SKM_FULL_ROUNDS=3; KHOICE_STAMP_DUMP=file appends every part's stamps of a call,
   # tools/union_stamps.py reads the union's per-slot intervals from it)
   python -c 'import sys; from khoice_amd import build as b; print("built", b.build_library(True, f"{b.LIBDIR}/diag/libkhoice_hip_diag.so", ["-DKH_STAMPS"] + sys.argv[1:]))' "$@"
 fi

@@ -6,7 +6,8 @@
 
 Thread 0 of a workgroup stores the shader clock per slot: 0 before barrier 1, 1 behind it, 2 at the end of its merge,
 10 behind barrier 2, 3 behind the key clear, 4 behind barrier 3, 5 at the end of its insertions, 6 behind barrier 4,
-7 at the end of its read-out (with KH_TUNE_SKM_UNION_OVERLAP: the PREVIOUS slot's, between stamps 1 and 10), 8 at the
+7 at the end of a read-out (a lean slot's runs in the NEXT slot's merge interval: the stamp is the PREVIOUS slot's
+then, between stamps 2 and 10; a multi-subset slot's own, behind stamp 6), 8 at the
 slot's end; words 12 and 13 are the workgroup + 1 and the slot's place in the workgroup's walk.  The last union block
 of the file is read (one per call).  Printed: medians over all slots, and medians over the workgroups of the sums
 along a walk, in ticks of the stamp clock; the share of each interval in the walk."""
