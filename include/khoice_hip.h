@@ -156,6 +156,29 @@ int kh_membership(kh_ctx *ctx, const kh_set *pivot, const kh_set *const *sets, i
  * of 1/len(M)*count for d in M; *unique_pivot_count = sum of counts of k-mers no set holds. */
 int kh_confusion_row(kh_ctx *ctx, const kh_set *pivot, const kh_set *const *sets, int nsets,
                      double *row, uint64_t *unique_pivot_count);
+/* ---------------------------------------------------------------- experiment type 6 (read level)
+ * src/merge_lists.py:151-183 for one pivot, everything but the draw.  For every read, in text order, each k-mer that
+ * the sets M hold adds 1/len(M) to the vote of every set in M (:165-171: one rounding per addition, in window order,
+ * bit for bit what CPython computes); the read then belongs to a set of the highest vote, drawn among the ties by
+ * random.choice (:178-180).  The draw is the caller's: this returns the ties.
+ *   reads, read_off      read i is reads[read_off[i] .. read_off[i+1]-1) and one '\n' follows every read, so
+ *                        read_off[nreads] is the length of the text.  `reads` is a host or a device buffer
+ *                        (on_device; the layout of a device buffer is not checked), read_off always a host array
+ *   sets, check          what kh_membership takes: only the keys are read.  check (may be NULL) stands for the pivot
+ *                        dictionary of :167
+ *   tie_masks [nreads * nwords], nwords = max(1, (nsets+63)/64): bit d%64 of word d/64 = "sets[d] has the highest
+ *                        vote of the read".  A read without k-mers has every vote 0.0: all sets tie
+ *   votes [nreads * nsets] (may be NULL), unmatched [nreads] (may be NULL): the k-mers of the read no set holds
+ * KH_E_ARG: nsets < 1 (the reference's max([]) raises), more than 1024 sets, k outside 1..64, a read of at least k
+ * bytes with a byte outside upper-case ACGT (KeyError at :66), with `check` a k-mer it does not hold (KeyError at
+ * :167); the message names the lowest such read.  KH_E_KMISMATCH: a set of another k.  A read shorter than k may hold
+ * any bytes but '\n'; nreads == 0 is KH_OK.  On an error the outputs are unspecified.
+ * The masks of all windows take 8 * nwords bytes per byte of text on the device: a text above a quarter of the free
+ * memory runs as batches of whole reads (KHOICE_READS_MAX_POS lowers that budget, in bytes of text). */
+int kh_read_votes(kh_ctx *ctx, const uint8_t *reads, const uint64_t *read_off, uint64_t nreads, int on_device,
+                  int k, const kh_set *const *sets, int nsets, const kh_set *check /* may be NULL */,
+                  uint64_t *tie_masks /* [nreads*nwords] */, double *votes /* [nreads*nsets] or NULL */,
+                  uint32_t *unmatched /* [nreads] or NULL */);
 
 /* text form consumed at exp_type_1.smk:210-212: lines "c<TAB>n", c = 1..cmax */
 int kh_histogram_file(kh_ctx *ctx, const kh_set *set, uint32_t cmax, const char *path);
@@ -357,6 +380,23 @@ int kh_exp4_run(kh_ctx *ctx, int nseq, const uint8_t *const *seqs, const uint64_
                 uint64_t *within_hist, uint32_t hist_len,      /* [ngroups * hist_len] */
                 double *rows, uint64_t *unique_pivot_count,    /* [npivots * ngroups], [npivots] */
                 uint64_t *distinct_per_seq, uint64_t *distinct_per_pivot);
+
+/* ---------------------------------------------------------------- fused experiment type 6
+ * The device side of exp_type_6.smk:164-344 for one k and one read type: the rules of type 4 up to the last one, which
+ * runs src/merge_lists.py with -r.  Builds, -cs{cs} unions and `set_counts 1` as in the set form of kh_exp4_run, then
+ * kh_read_votes for every pivot's reads against the unions of ALL groups (no check set: every k-mer of a read is in the
+ * database built from the same reads).
+ *   pivot_reads[p], pivot_read_off[p], pivot_nreads[p]   the reads of pivot p in the layout of kh_read_votes (host or
+ *                                   device like seqs; the offsets always on the host)
+ *   within_hist [ngroups * hist_len], distinct_per_seq [nseq]   as for kh_exp4_run; may be NULL
+ *   tie_masks [sum(pivot_nreads) * nwords], unmatched [sum(pivot_nreads)]   pivot after pivot; unmatched may be NULL
+ * Errors: those of kh_exp4_run's arguments and of kh_read_votes. */
+int kh_exp6_run(kh_ctx *ctx, int nseq, const uint8_t *const *seqs, const uint64_t *lens, int on_device,
+                const int *group_of, int ngroups,
+                int npivots, const uint8_t *const *pivot_reads, const uint64_t *const *pivot_read_off,
+                const uint64_t *pivot_nreads,
+                int k, uint32_t cs, uint64_t *within_hist, uint32_t hist_len,
+                uint64_t *tie_masks /* concatenated per pivot */, uint32_t *unmatched, uint64_t *distinct_per_seq);
 
 /* ---------------------------------------------------------------- multi-GPU exchange (RCCL over xGMI)
  * Steps 7-8 of exp_type_1.smk:243-259 when the groups are sharded over several GPUs, one process

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "kh_common.h"
+#include "kh_launch.h"
 
 #define KH_WAVE 64
 
@@ -39,7 +40,27 @@ __device__ __forceinline__ u32 wave_scan_max(u32 v) {
     return v;
 }
 
-constexpr int KH_HALO = 96;                                   // k-1 <= 63 bases + two words of slack for the funnel shifts
+// Does the set `sv` (distinct MIXED keys, ascending) hold the mixed key `key`?  top = kh_top32(key, k) << 32.  Mixed
+// keys are uniform, so the search starts from an interpolated window of +-(4 sqrt(n) + 64) records and falls back to
+// the whole set when the window misses.  Shared by k_membership (kh_kernels.hip) and k_read_masks (kh_reads.hip).
+template <int W>
+__device__ __forceinline__ bool kh_set_holds(const KhSetView sv, const KmerKey<W> key, const u64 top) {
+    if (!sv.n) return false;
+    const KmerKey<W>* __restrict__ keys = reinterpret_cast<const KmerKey<W>*>(sv.keys);
+    const u64 est = __umul64hi(top, sv.n);
+    const u64 rad = (u64)(4.0f * sqrtf((float)sv.n)) + 64;
+    u64 lo = est > rad ? est - rad : 0;
+    u64 hi = est + rad < sv.n ? est + rad : sv.n;
+    if (lo > 0 && !key_lt(keys[lo - 1], key)) lo = 0;        // answer lies left of the window
+    if (hi < sv.n && key_lt(keys[hi], key)) hi = sv.n;       // ... or right of it
+    while (lo < hi) {
+        const u64 mid = (lo + hi) >> 1;
+        if (key_lt(keys[mid], key)) lo = mid + 1; else hi = mid;
+    }
+    return lo < sv.n && key_eq(keys[lo], key);
+}
+
+constexpr int KH_HALO = 96;                                  // k-1 <= 63 bases + two words of slack for the funnel shifts
 
 // 16 ASCII bases -> 16 two-bit codes + 16 "not ACGTacgt" flags, four bytes at a time (SWAR):
 //   code = ((c >> 1) ^ (c >> 2)) & 3 maps A C G T (either case) to 0 1 2 3; the letter that code stands for is

@@ -231,7 +231,8 @@ static const char* kClsNames[KC_COUNT] = {"extract_hist", "bucket_plan", "extrac
                                           "bucket_sort_rle", "range_bounds", "setop", "histogram",
                                           "remix", "copy_in", "union_tagged", "skm_scatter",
                                           "skm_regroup", "skm_union", "skm_big", "skm_pack", "skm_phased", "bmp_build",
-                                          "bmp_readout", "bmp_pivot", "bmp_cross", "bmp_count", "bmp_present", "bmp_member", "skm_cross"};
+                                          "bmp_readout", "bmp_pivot", "bmp_cross", "bmp_count", "bmp_present", "bmp_member", "skm_cross",
+                                          "read_masks", "read_fold"};
 
 // ------------------------------------------------------------------------------ ctx API
 extern "C" int kh_device_count(void) {
@@ -1398,6 +1399,109 @@ extern "C" int kh_confusion_row(kh_ctx* c, const kh_set* pivot, const kh_set* co
     Membership m;
     KHCHK(membership_compute(c, pivot, sets, nsets, m));
     confusion_sum(m.masks.data(), m.counts.data(), m.order.data(), pivot->n, m.nwords, nsets, row, unique_pivot_count);
+    return KH_OK;
+}
+
+// ------------------------------------------------------------------- read-level votes
+// Experiment type 6 (src/merge_lists.py:151-183): per read the votes, the k-mers no set holds and the sets that tie
+// for the highest vote; the draw among them (:180) stays with the caller.  Device: k_read_masks, k_read_fold
+// (kh_reads.hip).  The mask buffer costs 8 * nwords bytes per text position: a quarter of the free HBM is its budget,
+// and a text above it runs as batches of whole reads (KHOICE_READS_MAX_POS lowers the budget, in positions).
+static u64 reads_max_pos(kh_ctx* c, u32 nwords) {
+    u64 budget = 1ull << 30;
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) budget = (free_b + c->pool.cached_bytes) / 4;
+    u64 pos = std::max<u64>(1, budget / (8ull * nwords + 1));
+    if (const char* e = getenv("KHOICE_READS_MAX_POS")) pos = std::min(pos, std::max<u64>(1, strtoull(e, nullptr, 10)));
+    return pos;
+}
+extern "C" int kh_read_votes(kh_ctx* c, const uint8_t* reads, const uint64_t* read_off, uint64_t nreads, int on_device,
+                             int k, const kh_set* const* sets, int nsets, const kh_set* check, uint64_t* tie_masks,
+                             double* votes, uint32_t* unmatched) {
+    if (!c || !read_off) return kh_fail(KH_E_ARG, "kh_read_votes: NULL argument");
+    if (nsets < 1 || !sets) return kh_fail(KH_E_ARG, "kh_read_votes: at least one set is needed (nsets = %d)", nsets);
+    if ((u32)nsets > KH_READS_MAX_SETS)
+        return kh_fail(KH_E_ARG, "kh_read_votes: more than %u sets are not supported", KH_READS_MAX_SETS);
+    KHCHK(check_k(k));
+    for (int i = 0; i < nsets; ++i) {
+        if (!sets[i]) return kh_fail(KH_E_ARG, "kh_read_votes: NULL set");
+        if (sets[i]->k != k) return kh_fail(KH_E_KMISMATCH, "kh_read_votes: k differs (set %d has %d, asked %d)", i, sets[i]->k, k);
+    }
+    if (check && check->k != k) return kh_fail(KH_E_KMISMATCH, "kh_read_votes: k differs (check set has %d, asked %d)", check->k, k);
+    if (!nreads) return KH_OK;
+    if (!reads || !tie_masks) return kh_fail(KH_E_ARG, "kh_read_votes: NULL argument");
+    if (nreads >= 0xffffffffull) return kh_fail(KH_E_ARG, "kh_read_votes: 2^32 - 1 reads or more are not supported");
+    for (u64 i = 0; i < nreads; ++i) {
+        if (read_off[i + 1] <= read_off[i])
+            return kh_fail(KH_E_ARG, "kh_read_votes: read_off[%llu] leaves no room for read %llu and its newline",
+                           (unsigned long long)(i + 1), (unsigned long long)i);
+        if (on_device) continue;   // (a device text is the caller's word)
+        const u8* b = reads + read_off[i];
+        const u64 len = read_off[i + 1] - 1 - read_off[i];
+        if (b[len] != '\n' || memchr(b, '\n', len))
+            return kh_fail(KH_E_ARG, "kh_read_votes: read %llu is not one line followed by a newline", (unsigned long long)i);
+    }
+    HIPCHK(hipSetDevice(c->dev));
+    const int W = k <= 32 ? 1 : 2;
+    const u32 nwords = (u32)((nsets + 63) / 64);
+    std::vector<KhSetView> v((size_t)nsets + 1);
+    for (int i = 0; i < nsets; ++i) v[i] = KhSetView{sets[i]->n ? sets[i]->keys_ptr() : nullptr, nullptr, sets[i]->n, 1, 0};
+    v[nsets] = check ? KhSetView{check->n ? check->keys_ptr() : nullptr, nullptr, check->n, 1, 0} : KhSetView{nullptr, nullptr, 0, 1, 0};
+    std::vector<double> inv(64 * (size_t)nwords + 1, 0.0);
+    for (size_t L = 1; L < inv.size(); ++L) inv[L] = 1.0 / (double)L;     // Python: 1 / len(matches)
+    Tmp d_view, d_inv;
+    TMP_ALLOC(d_view, c, sizeof(KhSetView) * v.size());
+    TMP_ALLOC(d_inv, c, 8 * inv.size());
+    HIPCHK(hipMemcpyAsync(d_view.b->p, v.data(), sizeof(KhSetView) * v.size(), hipMemcpyHostToDevice, c->st));
+    HIPCHK(hipMemcpyAsync(d_inv.b->p, inv.data(), 8 * inv.size(), hipMemcpyHostToDevice, c->st));
+    const u64 max_pos = reads_max_pos(c, nwords);
+    std::vector<u64> rel;
+    for (u64 b0 = 0; b0 < nreads;) {
+        u64 b1 = b0 + 1;                                                   // a batch holds at least one read
+        while (b1 < nreads && read_off[b1 + 1] - read_off[b0] <= max_pos) ++b1;
+        const u64 nb = b1 - b0, npos = read_off[b1] - read_off[b0];
+        rel.resize(nb + 1);
+        for (u64 i = 0; i <= nb; ++i) rel[i] = read_off[b0 + i] - read_off[b0];
+        const u32 ctl0[4] = {0, 0xffffffffu, 0xffffffffu, 0};
+        u32 ctl[4];
+        Tmp d_text, d_off, d_masks, d_tie, d_votes, d_unm, d_ctl;
+        TMP_ALLOC(d_off, c, 8 * (nb + 1));
+        TMP_ALLOC(d_masks, c, 8 * (u64)nwords * npos);
+        TMP_ALLOC(d_tie, c, 8 * (u64)nwords * nb);
+        TMP_ALLOC(d_ctl, c, sizeof ctl0);
+        if (votes) TMP_ALLOC(d_votes, c, 8 * (u64)nsets * nb);
+        if (unmatched) TMP_ALLOC(d_unm, c, 4 * nb);
+        const u8* text = reads + read_off[b0];
+        if (!on_device) {
+            TMP_ALLOC(d_text, c, npos);
+            HIPCHK(hipMemcpyAsync(d_text.b->p, text, npos, hipMemcpyHostToDevice, c->st));
+            text = d_text.as<u8>();
+        }
+        HIPCHK(hipMemcpyAsync(d_off.b->p, rel.data(), 8 * (nb + 1), hipMemcpyHostToDevice, c->st));
+        HIPCHK(hipMemcpyAsync(d_ctl.b->p, ctl0, sizeof ctl0, hipMemcpyHostToDevice, c->st));
+        KhReadsJob job{text, npos, d_off.as<u64>(), (u32)nb, (u32)b0, d_view.as<KhSetView>(),
+                       check ? d_view.as<KhSetView>() + nsets : nullptr, (u32)nsets, nwords, k, d_masks.as<u64>(), d_ctl.as<u32>()};
+        c->prof_begin(KC_READ_MASKS);
+        kh_launch_read_masks(W, job, c->st);
+        c->prof_end();
+        const u32 grid = (u32)std::min<u64>((nb + 3) / 4, (u64)std::max(1, c->cus) * 8);
+        c->prof_begin(KC_READ_FOLD);
+        kh_launch_read_fold(job, d_inv.as<double>(), d_tie.as<u64>(), votes ? d_votes.as<double>() : nullptr,
+                            unmatched ? d_unm.as<u32>() : nullptr, grid, c->st);
+        c->prof_end();
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(ctl, d_ctl.b->p, sizeof ctl, hipMemcpyDeviceToHost, c->st));
+        HIPCHK(hipMemcpyAsync(tie_masks + b0 * nwords, d_tie.b->p, 8 * (u64)nwords * nb, hipMemcpyDeviceToHost, c->st));
+        if (votes) HIPCHK(hipMemcpyAsync(votes + b0 * (u64)nsets, d_votes.b->p, 8 * (u64)nsets * nb, hipMemcpyDeviceToHost, c->st));
+        if (unmatched) HIPCHK(hipMemcpyAsync(unmatched + b0, d_unm.b->p, 4 * nb, hipMemcpyDeviceToHost, c->st));
+        HIPCHK(hipStreamSynchronize(c->st));
+        // reads are batched in order, so the first batch with an error holds the lowest such read
+        if (ctl[1] <= ctl[2] && ctl[1] != 0xffffffffu)
+            return kh_fail(KH_E_ARG, "kh_read_votes: read %u holds a byte outside upper-case ACGT (src/merge_lists.py:66)", ctl[1]);
+        if (ctl[2] != 0xffffffffu)
+            return kh_fail(KH_E_ARG, "kh_read_votes: read %u has a k-mer that the check set does not hold (src/merge_lists.py:167)", ctl[2]);
+        b0 = b1;
+    }
     return KH_OK;
 }
 
@@ -3948,6 +4052,36 @@ extern "C" int kh_exp4_run(kh_ctx* c, int nseq, const uint8_t* const* seqs, cons
     KHCHK(exp4_bmp(c, in, out, &done));
     if (done) return KH_OK;
     return exp4_sets(c, in, out);
+}
+
+// ------------------------------------------------------------------------------ fused experiment type 6
+// exp_type_6.smk:164-344 has the rules of type 4 up to the last one, which runs src/merge_lists.py with -r: the genomes'
+// plain builds, the -cs{cs} union of every group with its histogram and `set_counts 1`, as exp4_sets makes them, then
+// kh_read_votes per pivot's reads against those unions.  No pivot database: every k-mer of a read is in the database
+// built from the same reads, so the KeyError of :167 cannot happen and there is nothing to check against.
+extern "C" int kh_exp6_run(kh_ctx* c, int nseq, const uint8_t* const* seqs, const uint64_t* lens, int on_device,
+                           const int* group_of, int ngroups, int npivots, const uint8_t* const* pivot_reads,
+                           const uint64_t* const* pivot_read_off, const uint64_t* pivot_nreads, int k, uint32_t cs,
+                           uint64_t* within_hist, uint32_t hist_len, uint64_t* tie_masks, uint32_t* unmatched,
+                           uint64_t* distinct_per_seq) {
+    KHCHK(exp_check_args("kh_exp6_run", c, nseq, seqs, lens, group_of, ngroups, npivots, pivot_reads, pivot_read_off, false, nullptr,
+                         hist_len, k, cs, nullptr));
+    if (npivots && !pivot_nreads) return kh_fail(KH_E_ARG, "kh_exp6_run: bad argument");
+    HIPCHK(hipSetDevice(c->dev));
+    SetBag plain, unions, gsets;
+    KHCHK(build_plain(c, nseq, seqs, lens, 0, nullptr, nullptr, on_device, k, &plain));
+    for (int i = 0; i < nseq; ++i)
+        if (distinct_per_seq) distinct_per_seq[i] = plain.v[i]->n;
+    KHCHK(group_unions(c, plain.v.data(), nseq, group_of, ngroups, cs, &unions, within_hist, hist_len));
+    KHCHK(group_ones(c, unions, &gsets));
+    const u64 nwords = (u64)std::max(1, (ngroups + 63) / 64);
+    u64 r0 = 0;
+    for (int p = 0; p < npivots; ++p) {
+        KHCHK(kh_read_votes(c, pivot_reads[p], pivot_read_off[p], pivot_nreads[p], on_device, k, gsets.v.data(), ngroups, nullptr,
+                            tie_masks ? tie_masks + r0 * nwords : nullptr, nullptr, unmatched ? unmatched + r0 : nullptr));
+        r0 += pivot_nreads[p];
+    }
+    return KH_OK;
 }
 
 // ------------------------------------------------------------------------------ fused experiment type 3

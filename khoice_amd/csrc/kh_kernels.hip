@@ -2334,8 +2334,7 @@ __global__ __launch_bounds__(256) void k_table_hist(const C* __restrict__ table,
 // ------------------------------------------------------------------------------------------
 // Membership matrix (experiment type 4, src/merge_lists.py:14-33): for every key of the pivot
 // set, bit d of its mask = "set d holds the key".  One thread per pivot key; every operand is
-// sorted by MIXED key and mixed keys are uniform, so the search starts from an interpolated
-// window of +-(4 sqrt(n) + 64) records and falls back to the whole set when the window misses.
+// sorted by MIXED key; the interpolated window search is kh_set_holds (kh_device.h).
 // ------------------------------------------------------------------------------------------
 template <int W>
 __global__ __launch_bounds__(256) void k_membership(const KmerKey<W>* __restrict__ pivot, u64 n,
@@ -2348,22 +2347,8 @@ __global__ __launch_bounds__(256) void k_membership(const KmerKey<W>* __restrict
     for (u32 w = 0; w < nwords; ++w) {
         u64 m = 0;
         const u32 dend = min(nsets, (w + 1) * 64);
-        for (u32 d = w * 64; d < dend; ++d) {
-            const KhSetView sv = sets[d];
-            if (!sv.n) continue;
-            const KmerKey<W>* __restrict__ keys = reinterpret_cast<const KmerKey<W>*>(sv.keys);
-            const u64 est = __umul64hi(top, sv.n);
-            const u64 rad = (u64)(4.0f * sqrtf((float)sv.n)) + 64;
-            u64 lo = est > rad ? est - rad : 0;
-            u64 hi = est + rad < sv.n ? est + rad : sv.n;
-            if (lo > 0 && !key_lt(keys[lo - 1], key)) lo = 0;        // answer lies left of the window
-            if (hi < sv.n && key_lt(keys[hi], key)) hi = sv.n;       // ... or right of it
-            while (lo < hi) {
-                const u64 mid = (lo + hi) >> 1;
-                if (key_lt(keys[mid], key)) lo = mid + 1; else hi = mid;
-            }
-            if (lo < sv.n && key_eq(keys[lo], key)) m |= 1ull << (d & 63);
-        }
+        for (u32 d = w * 64; d < dend; ++d)
+            if (kh_set_holds<W>(sets[d], key, top)) m |= 1ull << (d & 63);
         masks[i * nwords + w] = m;
     }
 }

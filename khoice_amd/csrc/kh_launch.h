@@ -439,6 +439,28 @@ void kh_launch_unmix(int W, const void* in, void* out, u64 n, int k, hipStream_t
 void kh_launch_fill_u32(u32* p, u64 n, u32 v, hipStream_t st);
 void kh_launch_membership(int W, const void* pivot, u64 n, const KhSetView* sets, u32 nsets, int k,
                           u32 nwords, u64* masks, hipStream_t st);
+// ---- read-level votes (kh_reads.hip; src/merge_lists.py:151-183 but for the draw) ----
+// One batch of whole reads: read i is buf[off[i], off[i + 1] - 1), the byte behind it is '\n'.
+constexpr u32 KH_READS_MAX_SETS = 1024;   // k_read_fold keeps 8 bytes of LDS per set and wave
+struct KhReadsJob {
+    const u8* buf;           // the batch's text
+    u64 npos;                // its bytes = off[nreads]
+    const u64* off;          // [nreads + 1], relative to buf
+    u32 nreads;
+    u32 read0;               // index of the batch's first read in the whole call (error reports)
+    const KhSetView* sets;
+    const KhSetView* check;  // one view, or nullptr
+    u32 nsets, nwords;
+    int k;
+    u64* masks;              // [npos][nwords]; only positions that start a window are written and read
+    u32* ctl;                // [0] read counter of the fold, [1] lowest read with a byte outside ACGT in a window,
+                             // [2] lowest read with a k-mer that `check` lacks (both start at 0xffffffff)
+};
+void kh_launch_read_masks(int W, const KhReadsJob& job, hipStream_t st);
+// inv[L] = 1.0 / L for L = 0 .. 64 * nwords (host IEEE division; [0] unused); tie [nreads][nwords];
+// votes [nreads][nsets] or null; unmatched [nreads] or null
+void kh_launch_read_fold(const KhReadsJob& job, const double* inv, u64* tie, double* votes, u32* unmatched, u32 grid,
+                         hipStream_t st);
 void kh_launch_table_add(const void* keys, u64 n, int k, void* table, u32 cell_bytes, hipStream_t st);
 void kh_launch_table_hist(const void* table, u32 cell_bytes, u64 lo, u64 hi, u32 cs,
                           unsigned long long* hist, u32 hist_len, hipStream_t st);

@@ -103,6 +103,11 @@ def load_library(path: Optional[str] = None):
         "kh_exp4_run": (C.c_int, [vp, C.c_int, C.POINTER(vp), u64p, C.c_int, C.POINTER(C.c_int), C.c_int,
                                   C.c_int, C.POINTER(vp), u64p, C.c_int, C.c_uint32, C.c_uint32,
                                   u64p, C.c_uint32, C.POINTER(C.c_double), u64p, u64p, u64p]),
+        "kh_read_votes": (C.c_int, [vp, vp, u64p, C.c_uint64, C.c_int, C.c_int, C.POINTER(vp), C.c_int, vp,
+                                    u64p, C.POINTER(C.c_double), u32p]),
+        "kh_exp6_run": (C.c_int, [vp, C.c_int, C.POINTER(vp), u64p, C.c_int, C.POINTER(C.c_int), C.c_int,
+                                  C.c_int, C.POINTER(vp), C.POINTER(vp), u64p, C.c_int, C.c_uint32,
+                                  u64p, C.c_uint32, u64p, u32p, u64p]),
         "kh_comm_unique_id": (C.c_int, [C.c_char_p]),
         "kh_comm_init": (C.c_int, [vp, C.c_int, C.c_int, C.c_char_p, C.POINTER(vp)]),
         "kh_comm_destroy": (None, [vp]),
@@ -129,7 +134,7 @@ ABI_SYMBOLS = [
     "kh_profile_enable", "kh_stats_reset", "kh_sync", "kh_trim", "kh_build_batch", "kh_build_fasta",
     "kh_read_fasta", "kh_free_host", "kh_ingest_fasta", "kh_seqs_count", "kh_seqs_get", "kh_seqs_free",
     "kh_write_histogram_text", "kh_set_counts", "kh_union_sum", "kh_union_histogram", "kh_simple", "kh_histogram",
-    "kh_histogram_file", "kh_membership", "kh_confusion_row",
+    "kh_histogram_file", "kh_membership", "kh_confusion_row", "kh_read_votes", "kh_exp6_run",
     "kh_table_add_set", "kh_table_histogram", "kh_dump_sorted", "kh_set_free", "kh_set_info", "kh_set_counter_max",
     "kh_set_download",
     "kh_set_upload", "kh_set_device_ptrs", "kh_set_from_device", "kh_set_export_device",
@@ -487,6 +492,78 @@ class Engine:
         _check(self._lib.kh_confusion_row(self._ctx, pivot._h, arr, len(sets),
                                           row.ctypes.data_as(C.POINTER(C.c_double)), C.byref(uniq)))
         return row[:len(sets)], int(uniq.value)
+
+    # -- experiment type 6: read-level votes
+    @staticmethod
+    def _reads_arg(reads, offsets):
+        """(pointer, offsets as uint64, on_device, what to keep alive) of one read text: bytes / uint8 ndarray (host)
+        or a (device_ptr, length) tuple, read i = text[offsets[i] : offsets[i+1]-1], a newline behind every read."""
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        if off.ndim != 1 or off.size < 1:
+            raise ValueError("offsets: nreads + 1 entries are needed")
+        if isinstance(reads, tuple):
+            ptr, size, dev, keep = int(reads[0]), int(reads[1]), 1, None
+        else:
+            keep = np.frombuffer(reads, dtype=np.uint8) if isinstance(reads, (bytes, bytearray, memoryview)) else \
+                np.ascontiguousarray(reads, dtype=np.uint8)
+            ptr, size, dev = (keep.ctypes.data if keep.size else 0), keep.size, 0
+        if int(off[-1]) > size:
+            raise ValueError("offsets run past the end of the text")
+        return C.c_void_p(ptr), off, dev, keep
+
+    def read_votes(self, reads, offsets, k: int, sets: Sequence[KmerSet], check: Optional[KmerSet] = None,
+                   want_votes: bool = False, want_unmatched: bool = False) -> dict:
+        """src/merge_lists.py:151-183 for one pivot, everything but the draw: {"tie_masks": uint64[nreads, nwords]}
+        (bit d of a read's mask = sets[d] has its highest vote), with want_votes "votes": float64[nreads, nsets] (bit
+        for bit the reference's sums), with want_unmatched "unmatched": uint32[nreads] (k-mers no set holds).  `check`
+        stands for the pivot dictionary: a k-mer of a read that it lacks is an error, as is a byte outside ACGT in a
+        read of at least k bytes."""
+        ptr, off, dev, keep = self._reads_arg(reads, offsets)
+        nreads, ns = off.size - 1, len(sets)
+        nw = max(1, (ns + 63) // 64)
+        res = {"tie_masks": np.zeros((nreads, nw), dtype=np.uint64)}
+        if want_votes:
+            res["votes"] = np.zeros((nreads, ns), dtype=np.float64)
+        if want_unmatched:
+            res["unmatched"] = np.zeros(nreads, dtype=np.uint32)
+        arr = (C.c_void_p * max(1, ns))(*[s._h for s in sets])
+        votes = res["votes"].ctypes.data_as(C.POINTER(C.c_double)) if want_votes and res["votes"].size else None
+        unm = res["unmatched"].ctypes.data_as(C.POINTER(C.c_uint32)) if want_unmatched and nreads else None
+        _check(self._lib.kh_read_votes(self._ctx, ptr, _u64p(off), nreads, dev, k, arr, ns,
+                                       check._h if check is not None else None,
+                                       _u64p(res["tie_masks"]) if nreads else None, votes, unm))
+        return res
+
+    def exp6_run(self, seqs: Sequence, group_of: Sequence[int], pivot_reads: Sequence, k: int, cs: int = 5000,
+                 hist_len: int = 5001) -> dict:
+        """Device side of exp_type_6.smk:164-344 for one k and one read type.  pivot_reads[p] = (text, offsets) as for
+        `read_votes`, host or device like seqs.  Returns tie_masks and unmatched (one array per pivot),
+        within_hist[ngroups, hist_len] and distinct_per_seq[nseq] (what `exp4_run` gives for the same genomes)."""
+        ptrs, lens, on_dev, keep = self._seq_args(seqs)
+        n, npv = len(seqs), len(pivot_reads)
+        if len(group_of) != n:
+            raise ValueError("one group per sequence")
+        ng = max(group_of) + 1
+        nw = max(1, (ng + 63) // 64)
+        gof = (C.c_int * n)(*[int(g) for g in group_of])
+        args = [self._reads_arg(t, o) for t, o in pivot_reads]
+        if any(a[2] != on_dev for a in args):
+            raise ValueError("mix of host and device sequences in one call")
+        pptrs = (C.c_void_p * max(1, npv))(*[a[0] for a in args])
+        poffs = (C.c_void_p * max(1, npv))(*[a[1].ctypes.data for a in args])
+        pn = np.array([a[1].size - 1 for a in args] + [0], dtype=np.uint64)
+        total = int(pn.sum())
+        tie = np.zeros((total, nw), dtype=np.uint64)
+        unm = np.zeros(total, dtype=np.uint32)
+        res = {"within_hist": np.zeros((ng, hist_len), dtype=np.uint64), "distinct_per_seq": np.zeros(n, dtype=np.uint64)}
+        _check(self._lib.kh_exp6_run(self._ctx, n, ptrs, _u64p(lens), on_dev, gof, ng, npv, pptrs, poffs, _u64p(pn),
+                                     k, cs, _u64p(res["within_hist"]), hist_len, _u64p(tie) if total else None,
+                                     unm.ctypes.data_as(C.POINTER(C.c_uint32)) if total else None,
+                                     _u64p(res["distinct_per_seq"])))
+        cuts = np.cumsum(pn[:npv])[:-1].astype(np.int64) if npv else []
+        res["tie_masks"] = np.split(tie, cuts) if npv else []
+        res["unmatched"] = np.split(unm, cuts) if npv else []
+        return res
 
     # -- direct-addressed occurrence table (k <= 16)
     def table_add_set(self, s: KmerSet, table_ptr: int, cell_bytes: int):

@@ -1,4 +1,4 @@
-"""Experiment type 4's confusion matrix (feature level) on the MI355X engine.
+"""Experiment type 4's confusion matrix (feature level) and type 6's (read level) on the MI355X engine.
 
 Host-side mirror of the reference's src/merge_lists.py — same command line, same three output
 files, byte for byte — with the text-dump dictionaries (build_dictionary / update_dictionary,
@@ -11,13 +11,21 @@ src/merge_lists.py:14-33) replaced by one membership search on the device
                                  (exp_type_4.smk:216-271): pivot databases against the D
                                  rest-of-set unions directly.
 
-Read-level analysis (`-r`, src/merge_lists.py:147-182) breaks ties with `random.choice`, so it
-has no reproducible answer; it is refused.
+Read-level analysis (`-r DIR`, src/merge_lists.py:151-183; exp_type_6.smk) breaks ties with
+`random.choice`.  Everything up to the draw is deterministic and comes from the device
+(`kh_read_votes`): per read the datasets that tie for the highest vote.  The draws are made here, on
+the module-level `random` in the reference's order (per pivot, per read), so they repeat the
+reference's once `random` is seeded: `-r` is served only together with `--seed N` (or
+$KHOICE_READ_LEVEL_SEED), and stays refused without one.
+
+  * `read_level_reads(path)`     the reads of a `pivot_N.fa` by the reference's line rules (:153-159)
+  * `read_level_outputs(...)`    tie masks per pivot -> the draws -> the texts of the three files
 """
 from __future__ import annotations
 
 import argparse
 import os
+import random
 import sys
 from typing import List, Sequence
 
@@ -114,6 +122,48 @@ def run_from_databases(eng, pivot_prefixes: Sequence[str], union_prefixes: Seque
     return files
 
 
+# ------------------------------------------------------------------ read level (experiment type 6)
+def read_level_reads(path: str):
+    """The reads of a pivot's FASTA as src/merge_lists.py:153-159 takes them: text mode, every line without a '>' is
+    a read after `str.strip()`; a blank line is a read of length 0, the last line needs no newline.  Returns
+    (text uint8[...], offsets uint64[nreads + 1]) in the layout of `Engine.read_votes`: read i is
+    text[offsets[i] : offsets[i+1]-1] and a newline follows every read.  A character outside ASCII becomes one '?'
+    (one character, one byte: the read keeps its length and fails as it does in the reference, KeyError at :66)."""
+    with open(path, "r") as fh:
+        reads = [line.strip() for line in fh.readlines() if ">" not in line]
+    text = "".join(r + "\n" for r in reads).encode("ascii", "replace")
+    offsets = np.zeros(len(reads) + 1, dtype=np.uint64)
+    if reads:
+        offsets[1:] = np.cumsum([len(r) + 1 for r in reads], dtype=np.uint64)
+    return np.frombuffer(text, dtype=np.uint8), offsets
+
+
+def read_level_outputs(tie_masks_per_pivot: Sequence, num_datasets: int, k) -> dict:
+    """tie_masks_per_pivot[p] = uint64[nreads, nwords] as `Engine.read_votes` returns it -> the texts of the three
+    files.  Per pivot in order, per read in order, one `random.choice` among the tied datasets on the module-level
+    `random`, called on what the reference calls it on (src/merge_lists.py:178-180): the draw depends only on the
+    number of ties and on the order of the calls, so under the same `random.seed` it is the reference's.  The read
+    adds 1 to both matrices (:182-183); the cells stay int, the last column stays 0, nothing is smeared."""
+    cm = [[0 for _ in range(num_datasets + 1)] for _ in range(num_datasets)]
+    cm_ucol = [[0 for _ in range(num_datasets + 1)] for _ in range(num_datasets)]
+    for p, masks in enumerate(tie_masks_per_pivot):
+        masks = np.ascontiguousarray(masks, dtype="<u8").reshape(len(masks), -1)
+        bits = np.unpackbits(masks.view(np.uint8), axis=1, bitorder="little")[:, :num_datasets]
+        for mask_bits in bits:
+            class_decision = random.choice(np.where(mask_bits)[0])
+            cm[p][class_decision] += 1
+            cm_ucol[p][class_decision] += 1
+    return format_outputs(cm, cm_ucol, num_datasets, k)
+
+
+def read_level_seed(args):
+    """--seed N, else $KHOICE_READ_LEVEL_SEED, else None (read-level analysis is then refused)."""
+    if args.seed is not None:
+        return args.seed
+    env = os.environ.get("KHOICE_READ_LEVEL_SEED", "")
+    return int(env) if env.strip() else None
+
+
 _CODE = np.full(256, 255, dtype=np.uint8)
 for _i, _ch in enumerate(b"ACGT"):
     _CODE[_ch] = _i
@@ -162,6 +212,8 @@ def parse_arguments(argv=None):
     ap.add_argument("-o", "--output_path", dest="output_path", required=True)
     ap.add_argument("-k", "--k_value", dest="k", required=True)
     ap.add_argument("-r", "--read-level", dest="read_level", nargs=1)
+    ap.add_argument("--seed", type=int, default=None,
+                    help="seed of the read-level tie-breaks (random.seed); default $KHOICE_READ_LEVEL_SEED")
     ap.add_argument("--device", type=int, default=int(os.environ.get("KHOICE_GPU_DEVICE", "0")))
     return ap.parse_args(argv)
 
@@ -175,10 +227,16 @@ def main(argv=None) -> int:
     if args.num_datasets <= 0:
         print("Error: The number of datasets needs to be positive integer.")
         return 1
+    seed = None
     if args.read_level is not None:
-        print("Error: read-level analysis draws random tie-breaks (src/merge_lists.py:180) and is not "
-              "reproducible; only the feature level is implemented.", file=sys.stderr)
-        return 1
+        seed = read_level_seed(args)
+        if seed is None:
+            print("Error: read-level analysis draws random tie-breaks (src/merge_lists.py:180) and is not "
+                  "reproducible without a seed; give one with --seed N or $KHOICE_READ_LEVEL_SEED.", file=sys.stderr)
+            return 1
+        if not os.path.isdir(args.read_level[0]):
+            print("Error: the path provided for read-level analysis is not valid.")
+            return 1
     with open(args.pivot_filelist) as fh:
         pivot_files = [x.strip() for x in fh.readlines()]
     with open(args.intersect_list) as fh:
@@ -192,6 +250,28 @@ def main(argv=None) -> int:
         print("Error: the intersection list needs num_datasets entries per pivot", file=sys.stderr)
         return 1
     from khoice_amd import engine as E
+    if args.read_level is not None:
+        read_files = [f"{args.read_level[0]}pivot_{p + 1}.fa" for p in range(len(pivot_files))]   # :152
+        for path in read_files:
+            if not os.path.isfile(path):
+                print(f"Error: no reads for read-level analysis at {path}", file=sys.stderr)
+                return 1
+        random.seed(seed)                    # once, before the first pivot
+        with E.Engine(args.device) as eng:
+            ties = []
+            for p, path in enumerate(pivot_files):
+                keys, _ = read_dump(path, k)
+                check = eng.upload(k, keys, None)          # the pivot dictionary of :119,167
+                cols = [None] * n
+                for j in range(n):
+                    pos = p * n + j
+                    ikeys, _ = read_dump(intersect_files[pos], k)
+                    cols[pos % n] = eng.upload(k, ikeys, None)
+                text, offsets = read_level_reads(read_files[p])
+                ties.append(eng.read_votes(text, offsets, k, cols, check=check)["tie_masks"])
+            files = read_level_outputs(ties, n, args.k)
+        write_outputs(args.output_path, files)
+        return 0
     with E.Engine(args.device) as eng:
         pivots, per_pivot = [], []
         for p, path in enumerate(pivot_files):
