@@ -383,9 +383,15 @@ int kh_exp4_run(kh_ctx *ctx, int nseq, const uint8_t *const *seqs, const uint64_
 
 /* ---------------------------------------------------------------- fused experiment type 6
  * The device side of exp_type_6.smk:164-344 for one k and one read type: the rules of type 4 up to the last one, which
- * runs src/merge_lists.py with -r.  Builds, -cs{cs} unions and `set_counts 1` as in the set form of kh_exp4_run, then
- * kh_read_votes for every pivot's reads against the unions of ALL groups (no check set: every k-mer of a read is in the
- * database built from the same reads).
+ * runs src/merge_lists.py with -r.  Two forms, the same outputs bit for bit:
+ *   set form     builds, -cs{cs} unions and `set_counts 1` as in the set form of kh_exp4_run, then kh_read_votes for
+ *                every pivot's reads against the unions of ALL groups (no check set: every k-mer of a read is in the
+ *                database built from the same reads).
+ *   bitmap form  k <= 12 (KHOICE_BMP_MAX_K: up to 13; KHOICE_NO_BMP: never), at most 1024 groups of at most 1023
+ *                genomes, and the bitmaps and the table within the budget (KHOICE_BMP_MAX_BYTES): presence bitmaps of
+ *                the genomes, the groups' presence rows transposed into a table of one mask per canonical code, and
+ *                per window of a read one direct-addressed load of its mask; the fold of kh_read_votes unchanged.
+ *                Where it does not apply the set form answers.
  *   pivot_reads[p], pivot_read_off[p], pivot_nreads[p]   the reads of pivot p in the layout of kh_read_votes (host or
  *                                   device like seqs; the offsets always on the host)
  *   within_hist [ngroups * hist_len], distinct_per_seq [nseq]   as for kh_exp4_run; may be NULL

@@ -1,4 +1,4 @@
-// khoice_amd — presence-bitmap forms of the fused experiment types 1-4 for small k (gfx950).
+// khoice_amd — presence-bitmap forms of the fused experiment types 1-4 and 6 for small k (gfx950).
 //
 // A k-mer of k <= 13 is a number below 2^26: "which genomes hold it" is one bit per genome in a directly addressed
 // bitmap of 4^k bits, and every histogram of the forms is a count over those bits.  There is no genome mask: any number
@@ -13,9 +13,10 @@
 //   k_bmp_readout   type 1: the bins per count of every group and the bins of the counter over groups
 //   k_bmp_pivot     type 2: a pivot's word masks the counter of its group, then the counter over groups
 //   k_bmp_cross     type 3: every pivot's word, kept in LDS, masks the counter of every group
-//   k_bmp_present   type 4: the within-group bins, the groups' presence words, the pivots' words and popcounts
-// And one kernel of its own shape:
+//   k_bmp_present   types 4 and 6: the within-group bins, the groups' presence words, the pivots' words and popcounts
+// And two kernels of their own shape:
 //   k_bmp_member    type 4: one (membership mask, count) record per pivot k-mer in code order
+//   k_bmp_group_masks  type 6: the groups' presence words transposed into one mask of groups per code
 // The launchers share one dispatch on k (bmp_for_k) and one body for the four walk kernels (launch_walk).
 #include <type_traits>
 
@@ -654,6 +655,32 @@ __global__ __launch_bounds__(BMP_MEMBER_WAVES * KH_WAVE) void k_bmp_member(const
     }
 }
 
+// k_bmp_group_masks: the groups' presence rows transposed into the mask table of the read-level votes (type 6):
+// table[code * mwords + j] bit g = group 64 j + g holds canonical code `code`.  blockDim = (64, BMP_MASKS_WAVES); a
+// workgroup owns 64 consecutive bitmap words (blockIdx.x) and one mask word j (blockIdx.y).  The 64 x 64 tile
+// present[64 j + g][w0 + i] is loaded into LDS, lane = i, a wave every fourth g; groups from ngroups on load as 0.  A
+// wave then owns every fourth word i, lane = bit: one broadcast read of tile[g][i] per group, bit `lane` of it goes to
+// bit g of the lane's cell.  One writer per cell, nothing atomic; every cell of the words below nwords is written,
+// zeros included (the table comes from the pool, k_read_fold counts whole words).
+constexpr u32 BMP_MASKS_WAVES = 4;
+__global__ __launch_bounds__(BMP_MASKS_WAVES * KH_WAVE) void k_bmp_group_masks(const u64* __restrict__ present, u64* __restrict__ table,
+                                                                              const u64 nwords, const u32 ngroups, const u32 mwords) {
+    __shared__ u64 tile[KH_WAVE][KH_WAVE];                     // [group of the mask word][bitmap word of the block]: 32 KiB
+    const u32 lane = threadIdx.x, y = threadIdx.y, j = blockIdx.y;
+    const u64 w0 = (u64)blockIdx.x * KH_WAVE;                  // < nwords: the grid is ceil(nwords / 64)
+    for (u32 g = y; g < KH_WAVE; g += BMP_MASKS_WAVES) {
+        const u32 grp = j * KH_WAVE + g;
+        tile[g][lane] = grp < ngroups && w0 + lane < nwords ? present[(size_t)grp * nwords + w0 + lane] : 0ull;
+    }
+    __syncthreads();
+    for (u32 i = y; i < KH_WAVE && w0 + i < nwords; i += BMP_MASKS_WAVES) {
+        u64 m = 0;
+#pragma unroll 8
+        for (u32 g = 0; g < KH_WAVE; ++g) m |= ((tile[g][i] >> lane) & 1ull) << g;
+        table[((w0 + i) * KH_WAVE + lane) * mwords + j] = m;
+    }
+}
+
 template <class K> void bmp_allow_lds(K kern, size_t bytes) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
@@ -722,4 +749,8 @@ void kh_launch_bmp_member(const KhBmpMemberJob& job, hipStream_t st) {
     bmp_allow_lds(k_bmp_member, lds);
     hipLaunchKernelGGL(k_bmp_member, dim3((job.nblocks + BMP_MEMBER_RUN - 1) / BMP_MEMBER_RUN, job.npivots),
                        dim3(KH_WAVE, BMP_MEMBER_WAVES), lds, st, job);
+}
+void kh_launch_bmp_group_masks(const u64* present, u64* table, u64 nwords, u32 ngroups, u32 mwords, hipStream_t st) {
+    hipLaunchKernelGGL(k_bmp_group_masks, dim3((u32)((nwords + KH_WAVE - 1) / KH_WAVE), mwords), dim3(KH_WAVE, BMP_MASKS_WAVES), 0, st,
+                       present, table, nwords, ngroups, mwords);
 }

@@ -143,6 +143,7 @@ void buf_unref(DevBuf* b) {
 struct Tmp {
     DevBuf* b = nullptr;
     ~Tmp() { buf_unref(b); }
+    void release() { buf_unref(b); b = nullptr; }   // ahead of the scope's end (stream-ordered, as every release)
     template <class T> T* as() const { return reinterpret_cast<T*>(b->p); }
 };
 #define TMP_ALLOC(tmp, ctx, bytes)                                                        \
@@ -232,7 +233,7 @@ static const char* kClsNames[KC_COUNT] = {"extract_hist", "bucket_plan", "extrac
                                           "remix", "copy_in", "union_tagged", "skm_scatter",
                                           "skm_regroup", "skm_union", "skm_big", "skm_pack", "skm_phased", "bmp_build",
                                           "bmp_readout", "bmp_pivot", "bmp_cross", "bmp_count", "bmp_present", "bmp_member", "skm_cross",
-                                          "read_masks", "read_fold"};
+                                          "read_masks", "read_fold", "bmp_group_masks", "read_lookup"};
 
 // ------------------------------------------------------------------------------ ctx API
 extern "C" int kh_device_count(void) {
@@ -1415,19 +1416,13 @@ static u64 reads_max_pos(kh_ctx* c, u32 nwords) {
     if (const char* e = getenv("KHOICE_READS_MAX_POS")) pos = std::min(pos, std::max<u64>(1, strtoull(e, nullptr, 10)));
     return pos;
 }
-extern "C" int kh_read_votes(kh_ctx* c, const uint8_t* reads, const uint64_t* read_off, uint64_t nreads, int on_device,
-                             int k, const kh_set* const* sets, int nsets, const kh_set* check, uint64_t* tie_masks,
-                             double* votes, uint32_t* unmatched) {
-    if (!c || !read_off) return kh_fail(KH_E_ARG, "kh_read_votes: NULL argument");
-    if (nsets < 1 || !sets) return kh_fail(KH_E_ARG, "kh_read_votes: at least one set is needed (nsets = %d)", nsets);
-    if ((u32)nsets > KH_READS_MAX_SETS)
-        return kh_fail(KH_E_ARG, "kh_read_votes: more than %u sets are not supported", KH_READS_MAX_SETS);
-    KHCHK(check_k(k));
-    for (int i = 0; i < nsets; ++i) {
-        if (!sets[i]) return kh_fail(KH_E_ARG, "kh_read_votes: NULL set");
-        if (sets[i]->k != k) return kh_fail(KH_E_KMISMATCH, "kh_read_votes: k differs (set %d has %d, asked %d)", i, sets[i]->k, k);
-    }
-    if (check && check->k != k) return kh_fail(KH_E_KMISMATCH, "kh_read_votes: k differs (check set has %d, asked %d)", check->k, k);
+// What both forms of the votes do alike, from the layout checks of the reads to the read-back: the batches of whole
+// reads, every batch's text, offsets and control words uploaded, its masks, the fold, its outputs and the two errors.
+// mask_launch(job) queues the kernel that fills job.masks (k_read_masks against sorted sets, which also sets job.sets
+// and job.check; k_read_lookup against a mask table) and returns a status.
+template <class F>
+static int read_votes_batches(kh_ctx* c, const uint8_t* reads, const uint64_t* read_off, uint64_t nreads, int on_device, int k, int nsets,
+                              uint64_t* tie_masks, double* votes, uint32_t* unmatched, F mask_launch) {
     if (!nreads) return KH_OK;
     if (!reads || !tie_masks) return kh_fail(KH_E_ARG, "kh_read_votes: NULL argument");
     if (nreads >= 0xffffffffull) return kh_fail(KH_E_ARG, "kh_read_votes: 2^32 - 1 reads or more are not supported");
@@ -1442,17 +1437,11 @@ extern "C" int kh_read_votes(kh_ctx* c, const uint8_t* reads, const uint64_t* re
             return kh_fail(KH_E_ARG, "kh_read_votes: read %llu is not one line followed by a newline", (unsigned long long)i);
     }
     HIPCHK(hipSetDevice(c->dev));
-    const int W = k <= 32 ? 1 : 2;
     const u32 nwords = (u32)((nsets + 63) / 64);
-    std::vector<KhSetView> v((size_t)nsets + 1);
-    for (int i = 0; i < nsets; ++i) v[i] = KhSetView{sets[i]->n ? sets[i]->keys_ptr() : nullptr, nullptr, sets[i]->n, 1, 0};
-    v[nsets] = check ? KhSetView{check->n ? check->keys_ptr() : nullptr, nullptr, check->n, 1, 0} : KhSetView{nullptr, nullptr, 0, 1, 0};
     std::vector<double> inv(64 * (size_t)nwords + 1, 0.0);
     for (size_t L = 1; L < inv.size(); ++L) inv[L] = 1.0 / (double)L;     // Python: 1 / len(matches)
-    Tmp d_view, d_inv;
-    TMP_ALLOC(d_view, c, sizeof(KhSetView) * v.size());
+    Tmp d_inv;
     TMP_ALLOC(d_inv, c, 8 * inv.size());
-    HIPCHK(hipMemcpyAsync(d_view.b->p, v.data(), sizeof(KhSetView) * v.size(), hipMemcpyHostToDevice, c->st));
     HIPCHK(hipMemcpyAsync(d_inv.b->p, inv.data(), 8 * inv.size(), hipMemcpyHostToDevice, c->st));
     const u64 max_pos = reads_max_pos(c, nwords);
     std::vector<u64> rel;
@@ -1479,11 +1468,9 @@ extern "C" int kh_read_votes(kh_ctx* c, const uint8_t* reads, const uint64_t* re
         }
         HIPCHK(hipMemcpyAsync(d_off.b->p, rel.data(), 8 * (nb + 1), hipMemcpyHostToDevice, c->st));
         HIPCHK(hipMemcpyAsync(d_ctl.b->p, ctl0, sizeof ctl0, hipMemcpyHostToDevice, c->st));
-        KhReadsJob job{text, npos, d_off.as<u64>(), (u32)nb, (u32)b0, d_view.as<KhSetView>(),
-                       check ? d_view.as<KhSetView>() + nsets : nullptr, (u32)nsets, nwords, k, d_masks.as<u64>(), d_ctl.as<u32>()};
-        c->prof_begin(KC_READ_MASKS);
-        kh_launch_read_masks(W, job, c->st);
-        c->prof_end();
+        KhReadsJob job{text, npos, d_off.as<u64>(), (u32)nb, (u32)b0, nullptr, nullptr, (u32)nsets, nwords, k, d_masks.as<u64>(),
+                       d_ctl.as<u32>()};
+        KHCHK(mask_launch(job));
         const u32 grid = (u32)std::min<u64>((nb + 3) / 4, (u64)std::max(1, c->cus) * 8);
         c->prof_begin(KC_READ_FOLD);
         kh_launch_read_fold(job, d_inv.as<double>(), d_tie.as<u64>(), votes ? d_votes.as<double>() : nullptr,
@@ -1503,6 +1490,38 @@ extern "C" int kh_read_votes(kh_ctx* c, const uint8_t* reads, const uint64_t* re
         b0 = b1;
     }
     return KH_OK;
+}
+extern "C" int kh_read_votes(kh_ctx* c, const uint8_t* reads, const uint64_t* read_off, uint64_t nreads, int on_device,
+                             int k, const kh_set* const* sets, int nsets, const kh_set* check, uint64_t* tie_masks,
+                             double* votes, uint32_t* unmatched) {
+    if (!c || !read_off) return kh_fail(KH_E_ARG, "kh_read_votes: NULL argument");
+    if (nsets < 1 || !sets) return kh_fail(KH_E_ARG, "kh_read_votes: at least one set is needed (nsets = %d)", nsets);
+    if ((u32)nsets > KH_READS_MAX_SETS)
+        return kh_fail(KH_E_ARG, "kh_read_votes: more than %u sets are not supported", KH_READS_MAX_SETS);
+    KHCHK(check_k(k));
+    for (int i = 0; i < nsets; ++i) {
+        if (!sets[i]) return kh_fail(KH_E_ARG, "kh_read_votes: NULL set");
+        if (sets[i]->k != k) return kh_fail(KH_E_KMISMATCH, "kh_read_votes: k differs (set %d has %d, asked %d)", i, sets[i]->k, k);
+    }
+    if (check && check->k != k) return kh_fail(KH_E_KMISMATCH, "kh_read_votes: k differs (check set has %d, asked %d)", check->k, k);
+    const int W = k <= 32 ? 1 : 2;
+    std::vector<KhSetView> v;     // the sets' views, then the check set's: uploaded in front of the first batch's masks
+    Tmp d_view;
+    return read_votes_batches(c, reads, read_off, nreads, on_device, k, nsets, tie_masks, votes, unmatched, [&](KhReadsJob& job) {
+        if (!d_view.b) {
+            v.resize((size_t)nsets + 1);
+            for (int i = 0; i < nsets; ++i) v[i] = KhSetView{sets[i]->n ? sets[i]->keys_ptr() : nullptr, nullptr, sets[i]->n, 1, 0};
+            v[nsets] = check ? KhSetView{check->n ? check->keys_ptr() : nullptr, nullptr, check->n, 1, 0} : KhSetView{nullptr, nullptr, 0, 1, 0};
+            TMP_ALLOC(d_view, c, sizeof(KhSetView) * v.size());
+            HIPCHK(hipMemcpyAsync(d_view.b->p, v.data(), sizeof(KhSetView) * v.size(), hipMemcpyHostToDevice, c->st));
+        }
+        job.sets = d_view.as<KhSetView>();
+        job.check = check ? d_view.as<KhSetView>() + nsets : nullptr;
+        c->prof_begin(KC_READ_MASKS);
+        kh_launch_read_masks(W, job, c->st);
+        c->prof_end();
+        return (int)KH_OK;
+    });
 }
 
 // ------------------------------------------------------------------------------ transfer
@@ -2668,7 +2687,7 @@ static int exp1_big_group_skm(kh_ctx* c, int n, const uint8_t* const* seqs, cons
     return KH_OK;
 }
 
-// What the presence-bitmap forms (exp1_bmp .. exp4_bmp) share: the switches, the geometry of the build, the tables of
+// What the presence-bitmap forms (exp1_bmp .. exp4_bmp, exp6_bmp) share: the switches, the geometry of the build, the tables of
 // splits and operands, the copy-in of the texts, and the run that strings them together (BmpRun).
 static bool bmp_form_k(int k) {
     int max_k = KH_BMP_MAX_K;
@@ -2805,7 +2824,7 @@ static bool bmp_group_table(const BmpOperands& o, std::vector<KhBmpGroup>* group
     }
     return true;
 }
-// One run of a presence-bitmap form, what exp1_bmp .. exp4_bmp do alike.  In this order: plan(); layout(); table() for
+// One run of a presence-bitmap form, what exp1_bmp .. exp4_bmp and exp6_bmp do alike.  In this order: plan(); layout(); table() for
 // every table of the form's own; upload(); build(); the form's launches (timed_launch); download(); then bins(), inst()
 // and account().
 // Workspace: [hist: blocks x reps x nb u64][inst: nops u64] (zeroed, read back) [splits][ops][the form's tables] (one
@@ -4055,10 +4074,109 @@ extern "C" int kh_exp4_run(kh_ctx* c, int nseq, const uint8_t* const* seqs, cons
 }
 
 // ------------------------------------------------------------------------------ fused experiment type 6
-// exp_type_6.smk:164-344 has the rules of type 4 up to the last one, which runs src/merge_lists.py with -r: the genomes'
-// plain builds, the -cs{cs} union of every group with its histogram and `set_counts 1`, as exp4_sets makes them, then
-// kh_read_votes per pivot's reads against those unions.  No pivot database: every k-mer of a read is in the database
-// built from the same reads, so the KeyError of :167 cannot happen and there is nothing to check against.
+// exp_type_6.smk:164-344 has the rules of type 4 up to the last one, which runs src/merge_lists.py with -r: per read the
+// votes over the groups' k-mer sets.  No pivot database: every k-mer of a read is in the database built from the same
+// reads, so the KeyError of :167 cannot happen and there is nothing to check against.
+struct Exp6In {   // the arguments of kh_exp6_run that both forms read
+    int nseq; const uint8_t* const* seqs; const uint64_t* lens; int on_device;
+    const int* group_of; int ngroups;
+    int npivots; const uint8_t* const* pivot_reads; const uint64_t* const* pivot_read_off; const uint64_t* pivot_nreads;
+    int k; u32 cs, hist_len;
+};
+struct Exp6Out {   // within_hist, unmatched and distinct_per_seq may be NULL
+    uint64_t* within_hist; uint64_t* tie_masks; uint32_t* unmatched; uint64_t* distinct_per_seq;
+};
+// The presence-bitmap form (kh_bmp.hip, kh_reads.hip): the genomes (group-major) are the operands of the unchanged
+// k_bmp_build; k_bmp_present without pivots leaves the within-group bins, the distinct counters and the groups' presence
+// words; k_bmp_group_masks transposes those into the mask table; per pivot the batches of read_votes_batches, whose masks
+// k_read_lookup loads from the table by the window's canonical code.  *done == false: the form does not apply (nothing
+// was launched, no retry is counted).
+static int exp6_bmp(kh_ctx* c, const Exp6In& in, const Exp6Out& out, bool* done) {
+    *done = false;
+    const int k = in.k, nseq = in.nseq, ngroups = in.ngroups;
+    if (!bmp_form_k(k) || (u32)ngroups > KH_READS_MAX_SETS) return KH_OK;   // (too many groups: the set form reports them)
+    const BmpOperands o = bmp_operands(nseq, in.seqs, in.lens, in.group_of, ngroups);   // (reads are not operands)
+    std::vector<KhBmpGroup> groups;
+    u64 nbins = 0;
+    if (!bmp_group_table(o, &groups, &nbins)) return KH_OK;
+    if (nbins + (u64)nseq > KH_BMP_MAX_BINS) return KH_OK;
+    // ---- memory beside the partial bitmaps, in rows of one bitmap: present, and the table (64 nwords cells of mwords
+    // words: 64 mwords rows)
+    const u64 nwords = k >= 3 ? 1ull << (2 * k - 6) : 1;
+    const u32 mwords = (u32)std::max(1, (ngroups + 63) / 64);
+    BmpRun run(c, k, in.on_device, o);
+    bool fits = false;
+    KHCHK(run.plan((u64)ngroups + 64ull * mwords, &fits));
+    if (!fits) return KH_OK;
+
+    hipStream_t st = c->st;
+    run.layout(1, (u32)nbins + (u32)nseq);
+    const size_t off_groups = run.table(groups);
+    Tmp d_present, d_table;
+    TMP_ALLOC(d_present, c, (size_t)((u64)ngroups * nwords * 8));
+    TMP_ALLOC(d_table, c, (size_t)(64 * nwords * mwords * 8));
+    KHCHK(run.upload());
+    KHCHK(run.build());
+    KhBmpMemberJob job{};            // no pivots: pword, cnt, blk and the records stay null and untouched
+    job.splits = run.dev<const KhBmpSplit>(run.off_splits);
+    job.ops = run.ops();
+    job.groups = run.dev<const KhBmpGroup>(off_groups);
+    job.partial = run.d_partial.as<u64>();
+    job.present = d_present.as<u64>();
+    job.hist = run.hist(0);
+    job.nwords = nwords; job.ncells = 64 * nwords;
+    job.nops = (u32)nseq; job.ngenomes = (u32)nseq; job.ngroups = (u32)ngroups; job.npivots = 0;
+    job.nbins = (u32)nbins; job.reps = run.reps; job.nblocks = (u32)((nwords + 63) / 64);
+    job.psplit0 = (u32)run.s.nsplits; job.npsplits = 0;
+    job.tile_pos = run.s.tile_pos; job.pivot_cs = 1; job.k = k;
+    KHCHK(timed_launch(c, KC_BMP_PRESENT, [&] { kh_launch_bmp_present(job, run.s.rgrid, run.s.rwaves, st); }));
+    KHCHK(timed_launch(c, KC_BMP_GROUP_MASKS,
+                       [&] { kh_launch_bmp_group_masks(d_present.as<u64>(), d_table.as<u64>(), nwords, (u32)ngroups, mwords, st); }));
+    KHCHK(run.download());
+    run.d_partial.release();         // the votes need the table alone: their mask buffer is sized by what is free now
+    d_present.release();
+
+    // ---- the bins folded as exp1_bmp folds them
+    std::vector<u64> bins;
+    run.bins(0, run.nb, &bins);
+    fold_within(groups, bins, in.cs, out.within_hist, in.hist_len);
+    u64 in_groups = 0;               // the groups' distinct k-mers: what the unions of the set form put out
+    for (const KhBmpGroup& g : groups)
+        for (u32 cnt = 1; cnt <= g.size; ++cnt) in_groups += bins[g.bin0 + cnt];
+    run.account(run.distinct(bins, nbins, out.distinct_per_seq), in_groups);
+
+    // ---- the votes, pivot by pivot
+    const u64* table = d_table.as<u64>();
+    u64 r0 = 0;
+    for (int p = 0; p < in.npivots; ++p) {
+        if (!in.pivot_read_off[p]) return kh_fail(KH_E_ARG, "kh_read_votes: NULL argument");   // (as the set form's call says it)
+        KHCHK(read_votes_batches(c, in.pivot_reads[p], in.pivot_read_off[p], in.pivot_nreads[p], in.on_device, k, ngroups,
+                                 out.tie_masks ? out.tie_masks + r0 * mwords : nullptr, nullptr, out.unmatched ? out.unmatched + r0 : nullptr,
+                                 [&](KhReadsJob& rj) { return timed_launch(c, KC_READ_LOOKUP, [&] { kh_launch_read_lookup(rj, table, st); }); }));
+        r0 += in.pivot_nreads[p];
+    }
+    *done = true;
+    return KH_OK;
+}
+// The set form: the genomes' plain builds, the -cs{cs} union of every group with its histogram and `set_counts 1`, as
+// exp4_sets makes them, then kh_read_votes per pivot's reads against those unions.
+static int exp6_sets(kh_ctx* c, const Exp6In& in, const Exp6Out& out) {
+    const int nseq = in.nseq, ngroups = in.ngroups;
+    SetBag plain, unions, gsets;
+    KHCHK(build_plain(c, nseq, in.seqs, in.lens, 0, nullptr, nullptr, in.on_device, in.k, &plain));
+    for (int i = 0; i < nseq; ++i)
+        if (out.distinct_per_seq) out.distinct_per_seq[i] = plain.v[i]->n;
+    KHCHK(group_unions(c, plain.v.data(), nseq, in.group_of, ngroups, in.cs, &unions, out.within_hist, in.hist_len));
+    KHCHK(group_ones(c, unions, &gsets));
+    const u64 nwords = (u64)std::max(1, (ngroups + 63) / 64);
+    u64 r0 = 0;
+    for (int p = 0; p < in.npivots; ++p) {
+        KHCHK(kh_read_votes(c, in.pivot_reads[p], in.pivot_read_off[p], in.pivot_nreads[p], in.on_device, in.k, gsets.v.data(), ngroups,
+                            nullptr, out.tie_masks ? out.tie_masks + r0 * nwords : nullptr, nullptr, out.unmatched ? out.unmatched + r0 : nullptr));
+        r0 += in.pivot_nreads[p];
+    }
+    return KH_OK;
+}
 extern "C" int kh_exp6_run(kh_ctx* c, int nseq, const uint8_t* const* seqs, const uint64_t* lens, int on_device,
                            const int* group_of, int ngroups, int npivots, const uint8_t* const* pivot_reads,
                            const uint64_t* const* pivot_read_off, const uint64_t* pivot_nreads, int k, uint32_t cs,
@@ -4067,21 +4185,13 @@ extern "C" int kh_exp6_run(kh_ctx* c, int nseq, const uint8_t* const* seqs, cons
     KHCHK(exp_check_args("kh_exp6_run", c, nseq, seqs, lens, group_of, ngroups, npivots, pivot_reads, pivot_read_off, false, nullptr,
                          hist_len, k, cs, nullptr));
     if (npivots && !pivot_nreads) return kh_fail(KH_E_ARG, "kh_exp6_run: bad argument");
+    const Exp6In in{nseq, seqs, lens, on_device, group_of, ngroups, npivots, pivot_reads, pivot_read_off, pivot_nreads, k, cs, hist_len};
+    const Exp6Out out{within_hist, tie_masks, unmatched, distinct_per_seq};
     HIPCHK(hipSetDevice(c->dev));
-    SetBag plain, unions, gsets;
-    KHCHK(build_plain(c, nseq, seqs, lens, 0, nullptr, nullptr, on_device, k, &plain));
-    for (int i = 0; i < nseq; ++i)
-        if (distinct_per_seq) distinct_per_seq[i] = plain.v[i]->n;
-    KHCHK(group_unions(c, plain.v.data(), nseq, group_of, ngroups, cs, &unions, within_hist, hist_len));
-    KHCHK(group_ones(c, unions, &gsets));
-    const u64 nwords = (u64)std::max(1, (ngroups + 63) / 64);
-    u64 r0 = 0;
-    for (int p = 0; p < npivots; ++p) {
-        KHCHK(kh_read_votes(c, pivot_reads[p], pivot_read_off[p], pivot_nreads[p], on_device, k, gsets.v.data(), ngroups, nullptr,
-                            tie_masks ? tie_masks + r0 * nwords : nullptr, nullptr, unmatched ? unmatched + r0 : nullptr));
-        r0 += pivot_nreads[p];
-    }
-    return KH_OK;
+    bool done = false;
+    KHCHK(exp6_bmp(c, in, out, &done));
+    if (done) return KH_OK;
+    return exp6_sets(c, in, out);
 }
 
 // ------------------------------------------------------------------------------ fused experiment type 3

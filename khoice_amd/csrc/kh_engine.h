@@ -32,7 +32,7 @@ enum KernelClass {
     KC_EXTRACT_HIST = 0, KC_BUCKET_PLAN, KC_EXTRACT_SCATTER, KC_BUCKET_SORT, KC_RANGE_BOUNDS,
     KC_SETOP, KC_HISTOGRAM, KC_REMIX, KC_COPY_IN, KC_UNION_TAGGED, KC_SKM_SCATTER, KC_SKM_REGROUP, KC_SKM_UNION,
     KC_SKM_BIG, KC_SKM_PACK, KC_SKM_PHASED, KC_BMP_BUILD, KC_BMP_READOUT, KC_BMP_PIVOT, KC_BMP_CROSS, KC_BMP_COUNT,
-    KC_BMP_PRESENT, KC_BMP_MEMBER, KC_SKM_CROSS, KC_READ_MASKS, KC_READ_FOLD, KC_COUNT
+    KC_BMP_PRESENT, KC_BMP_MEMBER, KC_SKM_CROSS, KC_READ_MASKS, KC_READ_FOLD, KC_BMP_GROUP_MASKS, KC_READ_LOOKUP, KC_COUNT
 };
 struct ProfEvt { int cls; hipEvent_t a, b; };
 struct Stats {

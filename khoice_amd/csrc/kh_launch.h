@@ -386,6 +386,13 @@ void kh_launch_bmp_count(const KhBmpMemberJob& job, hipStream_t st);     // one 
 void kh_launch_bmp_present(const KhBmpMemberJob& job, u32 grid, u32 waves, hipStream_t st);   // launch shape and LDS of the read-out
 void kh_launch_bmp_member(const KhBmpMemberJob& job, hipStream_t st);    // (runs of blocks) x pivots workgroups
 
+// ---- experiment type 6 from the same bitmaps (kh_exp6_run): the operands of k_bmp_build are the genomes in group-major
+// order; k_bmp_present with no pivots leaves the within-group bins, the distinct counters and present[ngroups][nwords].
+// k_bmp_group_masks transposes `present` into the mask table of the votes: table[code * mwords + j] (64 * nwords codes,
+// mwords = max(1, (ngroups + 63) / 64) = KhReadsJob::nwords), bit g & 63 of word g >> 6: group g holds canonical code
+// `code`.  Every cell is written, the bits of groups >= ngroups are 0.
+void kh_launch_bmp_group_masks(const u64* present, u64* table, u64 nwords, u32 ngroups, u32 mwords, hipStream_t st);
+
 struct KhLookback {      // workspace of one ordered single-pass launch
     u64* desc;           // [nparts] tile descriptors, zeroed before launch
     u32* ticket;         // zeroed before launch
@@ -457,6 +464,9 @@ struct KhReadsJob {
                              // [2] lowest read with a k-mer that `check` lacks (both start at 0xffffffff)
 };
 void kh_launch_read_masks(int W, const KhReadsJob& job, hipStream_t st);
+// the masks by direct address (k <= KH_BMP_INST_MAX_K): masks[p] = table[canonical code of the window at p], nwords words
+// each, the table of k_bmp_group_masks.  job.sets and job.check are not read.
+void kh_launch_read_lookup(const KhReadsJob& job, const u64* table, hipStream_t st);
 // inv[L] = 1.0 / L for L = 0 .. 64 * nwords (host IEEE division; [0] unused); tie [nreads][nwords];
 // votes [nreads][nsets] or null; unmatched [nreads] or null
 void kh_launch_read_fold(const KhReadsJob& job, const double* inv, u64* tie, double* votes, u32* unmatched, u32 grid,

@@ -7,6 +7,8 @@
 //
 //   k_read_masks   one thread per text position: the window's canonical key, mixed, searched in every set
 //                  (kh_set_holds, the search of k_membership) -> nwords mask words per position
+//   k_read_lookup  the same for k <= 13 without a search: the window's canonical code addresses the mask table that
+//                  k_bmp_group_masks (kh_bmp.hip) made of the groups' presence bitmaps
 //   k_read_fold    one wave per read, reads claimed from a counter: the masks of a read in window order, 64 at a
 //                  time; lane d owns dataset d (d, d + 64, ... beyond 64 sets); v += inv[L] — additions only, one
 //                  rounding each, in window order, which is what CPython does with `votes[m] += 1/len(matches)`
@@ -80,6 +82,42 @@ __global__ __launch_bounds__(256) void k_read_masks(const KhReadsJob j) {
         out[w] = m;
     }
     if (j.check && !kh_set_holds<W>(*j.check, key, top)) atomicMin(&j.ctl[2], read_of(j, p));
+}
+
+// The masks of k <= 13 by direct address: the staging, the byte-by-byte decode and the three outcomes of k_read_masks
+// (the decode restated on 32-bit codes; k_read_masks works on KmerKey<W>), but the canonical code is not mixed and not
+// searched for: it indexes the mask table that k_bmp_group_masks made of the groups' presence bitmaps, first base most
+// significant, A C G T = 0 1 2 3, the smaller of the two strands — the numbering of k_bmp_build.
+__global__ __launch_bounds__(256) void k_read_lookup(const KhReadsJob j, const u64* __restrict__ table) {
+    __shared__ u8 raw[KH_RD_STAGE];
+    const u32 k = (u32)j.k;
+    const u64 p0 = (u64)blockIdx.x * KH_RD_TILE;            // < npos: the grid is ceil(npos / 256)
+    const u64 left = j.npos - p0;
+    const u32 nst = left < KH_RD_TILE + k - 1 ? (u32)left : KH_RD_TILE + k - 1;
+    for (u32 i = threadIdx.x; i < nst; i += KH_RD_TILE) raw[i] = j.buf[p0 + i];
+    __syncthreads();
+    const u32 t = threadIdx.x;
+    if (t + k > nst) return;                                // the window would run past the text
+    const u64 p = p0 + t;
+    u32 f = 0, r = 0;                                       // the window and its reverse complement: 2 k <= 26 bits
+    bool sep = false, bad = false;
+    for (u32 i = 0; i < k; ++i) {
+        const u32 ch = raw[t + i];
+        const u32 code = ((ch >> 1) ^ (ch >> 2)) & 3u;      // A C G T -> 0 1 2 3
+        sep |= ch == (u32)'\n';
+        bad |= ch != ((0x54474341u >> (8 * code)) & 0xffu); // "ACGT"[code]
+        f = (f << 2) | code;
+        r |= (3u - code) << (2 * i);
+    }
+    if (sep) return;                                        // no window here: nothing written, the fold never looks
+    u64* __restrict__ out = j.masks + p * j.nwords;
+    if (bad) {
+        atomicMin(&j.ctl[1], read_of(j, p));
+        for (u32 w = 0; w < j.nwords; ++w) out[w] = 0;
+        return;
+    }
+    const u64* __restrict__ cell = table + (u64)(f < r ? f : r) * j.nwords;
+    for (u32 w = 0; w < j.nwords; ++w) out[w] = cell[w];
 }
 
 __device__ __forceinline__ u64 readlane64(const u64 v, const u32 i) {
@@ -166,6 +204,12 @@ void kh_launch_read_masks(int W, const KhReadsJob& job, hipStream_t st) {
     const u32 grid = (u32)((job.npos + KH_RD_TILE - 1) / KH_RD_TILE);
     if (W == 1) hipLaunchKernelGGL((k_read_masks<1>), dim3(grid), dim3(KH_RD_TILE), 0, st, job);
     else hipLaunchKernelGGL((k_read_masks<2>), dim3(grid), dim3(KH_RD_TILE), 0, st, job);
+}
+
+void kh_launch_read_lookup(const KhReadsJob& job, const u64* table, hipStream_t st) {
+    if (!job.npos) return;
+    const u32 grid = (u32)((job.npos + KH_RD_TILE - 1) / KH_RD_TILE);
+    hipLaunchKernelGGL(k_read_lookup, dim3(grid), dim3(KH_RD_TILE), 0, st, job, table);
 }
 
 void kh_launch_read_fold(const KhReadsJob& job, const double* inv, u64* tie, double* votes, u32* unmatched, u32 grid,

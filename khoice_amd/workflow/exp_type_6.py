@@ -77,7 +77,7 @@ def run_batched(work_root: str, k_values: Sequence, num_datasets: int, seed: int
                 device: int = 0, trial: int = 1):
     """The files of exp6_accuracies/{read_type}/ and the two concatenated CSVs from one resident engine.  The genome
     texts are read once; per k and read type one Engine.exp6_run (builds, unions, `set_counts 1`, the votes of every
-    read), then the seeded draws on the host.  The unions' histograms go where union_histogram_exp6 writes them."""
+    read; for k <= 12 the library answers the same from presence bitmaps and a mask table), then the seeded draws on the host.  The unions' histograms go where union_histogram_exp6 writes them."""
     from .. import engine as E
     from concurrent.futures import ThreadPoolExecutor
     k_values = [str(k) for k in k_values]
