@@ -508,6 +508,13 @@ struct SkmClaim1 {
 // behind the bulk insertion of the older one.  Union 1.258 -> 1.226 ms; it holds against read-out waves too (1.180 ->
 // 1.209 without it).
 //
+// LDS ROUND TRIPS BETWEEN BARRIERS 1 AND 2.  The merge loop makes two dependent round trips per iteration (the
+// compare-and-swap on `dd`, one 16-byte read of the staged record, compared without a branch per word); a copy's OR
+// into the survivor's mask is issued once behind the loop and waited for behind the chunk numbering.  With the compare
+// as an `&&` chain (three dependent reads) and the OR waited for inside the loop it made five: union 1.170 -> 1.090 ms,
+// B1->B2 7700 -> 7164 ticks per slot.  The read-out makes four per pass with both fields set (the exchange pair, the
+// gtab read, per entry) and was NOT brought down, see below.
+//
 // MEASURED AND REJECTED.  Each was a compile-time switch of this kernel up to the commit "k_skm_union: read out a slot
 // during the next slot's merge interval", where the code can be found; every number: profiles/README.md, DESIGN.md §8.
 //   - the keys that lose probe round 1 packed into the wave's first lanes by ds_permute, one key per lane through the
@@ -518,6 +525,16 @@ struct SkmClaim1 {
 //   - chunks numbered from the last thread down (the record-holding waves get chunks last): 1.215 / 1.212 against
 //     1.180 / 1.171; why was not looked into.
 //   - the mask planes cleared per slot instead of zeroed by the read-out's exchange: 1.430 against 1.407 ms.
+// Forms of the read-out tried when the merge loop was shortened (never committed; their code and every number:
+// profiles/README.md, round 11), each on top of the merge as it is now, which alone times 1.090 ms:
+//   - the read-out of all entries of a thread at once (the exchanges of both fields back to back, a field without an
+//     entry exchanging zero for zero at a spare word; the gtab reads of both entries in common group rounds): two
+//     round trips per pass instead of four, 3630 -> 3665 static vector instructions in the kernel and 370 more scalar
+//     ones and waits: 1.122 ms, alone 1.195 against 1.170.
+//   - the same with a branch per field (the compiler parts the two exchange pairs by a wait): 1.119 ms.
+//   - only the exchanges together, the entries evaluated one after the other as before: 1.103 ms.
+//   Why was not found.  What the common rounds do at run time and the counts above do not show: both entries' code
+//   runs for as many rounds as the slower entry needs, and every field without an entry makes two exchanges.
 #define KH_TUNE_SKM_UNION_COMPACT 0   // (read by no code: the previous commit's tests/test_gpu_skm_union_tail.py parses this line at import)
 template <u32 NT, u32 T, int KT>
 __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs, u32 first_claimed) {
@@ -725,6 +742,7 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs, 
             u32 hp = (u32)(((u64)h * T) >> 32);
             const u32 nch = (nj + (u32)E - 1u) / (u32)E;
             bool pend = nj != 0, won = false;
+            u32 mold = ~0u;   // the record this one is a copy of (a record merges at most once: it leaves the loop)
             while (__builtin_amdgcn_ballot_w64(pend)) {
                 if (pend) {
                     const u32 old = atomicCAS(&dd[hp], 0u, tid + 1u);
@@ -732,15 +750,11 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs, 
                         won = true;
                         pend = false;
                     } else {
-                        const uint4 o = stage[old - 1u];
-                        // the same bases, the same number of k-mers, a genome of the same half of the mask
-                        if (o.x == rx && o.y == ry && o.z == rz && SkmRec1::same_content(o.w, rw)) {
-                            const u32 bit = 1u << (tg & 31u);
-                            const u32 was = atomicOr(&rmask[old - 1u], bit);
-                            if (was & bit) {   // a second copy inside one genome: nj repeats
-                                atomicAdd(&dupc[tg], nj);
-                                rmask[tid] = 0u;   // (this record's own mask is unused: zero = "has counted repeats", should the slot be handed on below)
-                            }
+                        uint4 o = stage[old - 1u];   // (one 16-byte read: the opaque copy keeps the compiler from splitting it by use)
+                        asm volatile("" : "+v"(o.x), "+v"(o.y), "+v"(o.z), "+v"(o.w));
+                        // the same bases, the same number of k-mers, a genome of the same half of the mask: no branch per word
+                        if (((o.x ^ rx) | (o.y ^ ry) | (o.z ^ rz) | SkmRec1::content_diff(o.w, rw)) == 0u) {
+                            mold = old - 1u;
                             pend = false;
                         } else {
                             hp = (hp + 1u) & (T - 1u);
@@ -748,6 +762,12 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs, 
                     }
                 }
             }
+            // A copy adds its genome's bit to the mask of the record that stays: issued once, behind the loop (inside it,
+            // every iteration of the wave waited for the answer), and the answer is looked at behind the chunk
+            // numbering.  The loop is two dependent LDS round trips per iteration: the compare-and-swap, the 16-byte read.
+            const u32 bit = 1u << (tg & 31u);
+            u32 was = 0;
+            if (mold != ~0u) was = atomicOr(&rmask[mold], bit);
             // the wave's records take consecutive chunks in lane order (their loads in the expansion stay
             // coalesced); the wave's share comes from one returning LDS atomic
             const u32 mine = won ? (nch | (nj << 16)) : 0u;
@@ -762,6 +782,13 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs, 
                     for (u32 cc = 0; cc < (1u << SKM_OB); ++cc)
                         if (cc < nch) owner[cstart + cc] = (u16)((tid << SKM_OB) | cc);
                 }
+            }
+            // The OR's answer, behind the chunk numbering.  Safe to look at this late: only winners are entered in `dd`,
+            // so every OR goes to a winner's rmask word and nobody touches the word of a record that lost; the store
+            // below has one reader, the hand-over path behind barrier 2.
+            if (was & bit) {   // a second copy inside one genome: nj repeats
+                atomicAdd(&dupc[tg], nj);
+                rmask[tid] = 0u;   // (this record's own mask is unused: zero = "has counted repeats", should the slot be handed on below)
             }
             __builtin_amdgcn_s_setprio(0);
         }

@@ -487,9 +487,10 @@ __global__ __launch_bounds__(SKM2_UNT, SKM2_UNT == 1024 ? 8 : 6) void k_skm2_uni
                     const u32 old = atomicCAS(&dd[hp], 0u, tid + 1u);
                     if (old == 0u) { won = true; pend = false; }
                     else {
-                        const uint4 oa = stage[2 * (old - 1u)], ob = stage[2 * (old - 1u) + 1];
-                        if (oa.x == a0 && oa.y == a1 && oa.z == a2 && oa.w == a3 && ob.x == b0 && ob.y == b1 && ob.z == b2 &&
-                            SkmRec2::same_content(ob.w, b3)) {   // the same bases and number of k-mers, a genome of the same half
+                        uint4 oa = stage[2 * (old - 1u)], ob = stage[2 * (old - 1u) + 1];   // (two 16-byte reads, one wait: the opaque copy keeps the compiler from splitting them by use)
+                        asm volatile("" : "+v"(oa.x), "+v"(oa.y), "+v"(oa.z), "+v"(oa.w), "+v"(ob.x), "+v"(ob.y), "+v"(ob.z), "+v"(ob.w));
+                        if (((oa.x ^ a0) | (oa.y ^ a1) | (oa.z ^ a2) | (oa.w ^ a3) | (ob.x ^ b0) | (ob.y ^ b1) | (ob.z ^ b2) |
+                             SkmRec2::content_diff(ob.w, b3)) == 0u) {   // the same bases and number of k-mers, a genome of the same half: no branch per word
                             const u32 bit = 1u << (tg & 31u);
                             const u32 was = atomicOr(&rmask[old - 1u], bit);
                             if (was & bit) {

@@ -30,9 +30,11 @@ template <u32 Q_, u32 FINE_SHIFT_, u32 FINE_BITS_> struct SkmRecFmt {
     // halves walk one probe chain of the set of contents), the COMPARE ignores only the five low ones (the sixth, the mask
     // half, has to agree).
     static __host__ __device__ __forceinline__ u32 content_hash_word(u32 w) { return w & ~(((1u << TAG_BITS) - 1u) << TAG_SHIFT); }
-    static __host__ __device__ __forceinline__ bool same_content(u32 wa, u32 wb) {
-        return ((wa ^ wb) & ~(((1u << (TAG_BITS - 1)) - 1u) << TAG_SHIFT)) == 0u;
+    // (the last words' difference under the COMPARE rule, zero: the same; for callers that OR it with the other words')
+    static __host__ __device__ __forceinline__ u32 content_diff(u32 wa, u32 wb) {
+        return (wa ^ wb) & ~(((1u << (TAG_BITS - 1)) - 1u) << TAG_SHIFT);
     }
+    static __host__ __device__ __forceinline__ bool same_content(u32 wa, u32 wb) { return content_diff(wa, wb) == 0u; }
 };
 using SkmRec1 = SkmRecFmt<1, 12, 9>;    // 16 bytes, k <= 32:       fine 12..20, tag 21..26, n 27..31
 using SkmRec2 = SkmRecFmt<2, 10, 10>;   // 32 bytes, 33 <= k <= 63: fine 10..19, tag 20..25, n 26..31
