@@ -179,6 +179,37 @@ int kh_read_votes(kh_ctx *ctx, const uint8_t *reads, const uint64_t *read_off, u
                   int k, const kh_set *const *sets, int nsets, const kh_set *check /* may be NULL */,
                   uint64_t *tie_masks /* [nreads*nwords] */, double *votes /* [nreads*nsets] or NULL */,
                   uint32_t *unmatched /* [nreads] or NULL */);
+/* ---------------------------------------------------------------- merged mask index
+ * The union of nsets sets as ONE device-resident table: n distinct keys (mixed, ascending), per key the mask of the
+ * sets that hold it (mask_words = max(1, (nsets+63)/64) words, bit d%64 of word d/64 = "sets[d] holds the key", the
+ * numbering of kh_membership) and a directory of nbuckets = clamp(ceil(n / 4), 1, 2^31) equal-width buckets of the
+ * mixed key space in front (KHOICE_INDEX_BUCKET_KEYS, read per build, replaces the 4).  A lookup is one directory read
+ * and a bisection inside one bucket, whatever nsets is; it is exact for any distribution of the keys.  Any k from 1 to
+ * 64; only the keys of the sets are read; empty sets are fine, and all sets empty give a valid index with n = 0 in
+ * which every lookup misses.  The index keeps no reference to the sets: it outlives them.
+ * KH_E_ARG: nsets < 1, more than 1024 sets, a NULL set.  KH_E_KMISMATCH: sets of different k.  KH_E_NOMEM: the index
+ * does not fit. */
+typedef struct kh_index kh_index;
+int kh_index_build(kh_ctx *ctx, const kh_set *const *sets, int nsets, kh_index **out);
+void kh_index_free(kh_index *index);
+/* any output may be NULL */
+int kh_index_info(const kh_index *index, uint64_t *n, int *k, int *nsets, int *mask_words, uint64_t *nbuckets);
+/* HOST arrays in the index's storage order: keys[n*W] as kh_set_download gives them for the union of the sets (may be
+ * NULL), masks[n*mask_words] (may be NULL) */
+int kh_index_download(kh_ctx *ctx, const kh_index *index, uint64_t *keys /* as kh_set_download of the union */,
+                      uint64_t *masks /* [n*mask_words] */);
+/* The search of kh_membership against an index: for every key of `probe`, in the probe's STORAGE order (the order of
+ * kh_set_download, not dump order), the mask of the sets that hold it; zeros for a key the index lacks.
+ * KH_E_KMISMATCH: a probe of another k. */
+int kh_index_masks(kh_ctx *ctx, const kh_index *index, const kh_set *probe,
+                   uint64_t *masks_out /* [probe n * mask_words], probe's storage order */);
+/* kh_read_votes against the sets an index was built from (k and nsets are the index's): the same reads, outputs,
+ * batches and errors, the same numbers bit for bit, but one lookup per k-mer of a read instead of a search in every
+ * set.  KH_E_KMISMATCH: a check set of another k. */
+int kh_read_votes_index(kh_ctx *ctx, const uint8_t *reads, const uint64_t *read_off, uint64_t nreads, int on_device,
+                        const kh_index *index, const kh_set *check /* may be NULL */,
+                        uint64_t *tie_masks /* [nreads*mask_words] */, double *votes /* [nreads*nsets] or NULL */,
+                        uint32_t *unmatched /* [nreads] or NULL */);
 
 /* text form consumed at exp_type_1.smk:210-212: lines "c<TAB>n", c = 1..cmax */
 int kh_histogram_file(kh_ctx *ctx, const kh_set *set, uint32_t cmax, const char *path);
@@ -383,15 +414,21 @@ int kh_exp4_run(kh_ctx *ctx, int nseq, const uint8_t *const *seqs, const uint64_
 
 /* ---------------------------------------------------------------- fused experiment type 6
  * The device side of exp_type_6.smk:164-344 for one k and one read type: the rules of type 4 up to the last one, which
- * runs src/merge_lists.py with -r.  Two forms, the same outputs bit for bit:
- *   set form     builds, -cs{cs} unions and `set_counts 1` as in the set form of kh_exp4_run, then kh_read_votes for
- *                every pivot's reads against the unions of ALL groups (no check set: every k-mer of a read is in the
- *                database built from the same reads).
+ * runs src/merge_lists.py with -r.  Three forms, tried in this order, the same outputs bit for bit:
  *   bitmap form  k <= 12 (KHOICE_BMP_MAX_K: up to 13; KHOICE_NO_BMP: never), at most 1024 groups of at most 1023
  *                genomes, and the bitmaps and the table within the budget (KHOICE_BMP_MAX_BYTES): presence bitmaps of
  *                the genomes, the groups' presence rows transposed into a table of one mask per canonical code, and
  *                per window of a read one direct-addressed load of its mask; the fold of kh_read_votes unchanged.
- *                Where it does not apply the set form answers.
+ *   index form   any k: the builds, unions and `set_counts 1` of the set form, ONE merged mask index (kh_index_build)
+ *                over the groups' sets, and per window of a read one lookup in it (kh_read_votes_index without a
+ *                check set); the index is freed before the call returns.  KHOICE_EXP6_INDEX=1 takes the form whenever
+ *                it applies, =0 never; unset it is taken when windows * ngroups >= 0.53 * sum |sets| (windows: the
+ *                k-mers of all reads; sets: the groups' unions) and sum |sets| >= 3.6e6, the measured break-even
+ *                against the set form (profiles/exp6_index.json).  It declines when the index and the workspace of
+ *                its union are above a quarter of the free memory (KHOICE_INDEX_MAX_BYTES lowers that budget).
+ *   set form     builds, -cs{cs} unions and `set_counts 1` as in the set form of kh_exp4_run, then kh_read_votes for
+ *                every pivot's reads against the unions of ALL groups (no check set: every k-mer of a read is in the
+ *                database built from the same reads).  It answers wherever the other two do not apply.
  *   pivot_reads[p], pivot_read_off[p], pivot_nreads[p]   the reads of pivot p in the layout of kh_read_votes (host or
  *                                   device like seqs; the offsets always on the host)
  *   within_hist [ngroups * hist_len], distinct_per_seq [nseq]   as for kh_exp4_run; may be NULL

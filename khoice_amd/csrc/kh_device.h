@@ -42,7 +42,8 @@ __device__ __forceinline__ u32 wave_scan_max(u32 v) {
 
 // Does the set `sv` (distinct MIXED keys, ascending) hold the mixed key `key`?  top = kh_top32(key, k) << 32.  Mixed
 // keys are uniform, so the search starts from an interpolated window of +-(4 sqrt(n) + 64) records and falls back to
-// the whole set when the window misses.  Shared by k_membership (kh_kernels.hip) and k_read_masks (kh_reads.hip).
+// the whole set when the window misses.  Shared by k_membership (kh_kernels.hip), k_read_masks (kh_reads.hip) and, for
+// the check set, k_read_index (kh_index.hip).
 template <int W>
 __device__ __forceinline__ bool kh_set_holds(const KhSetView sv, const KmerKey<W> key, const u64 top) {
     if (!sv.n) return false;

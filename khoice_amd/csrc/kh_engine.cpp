@@ -233,7 +233,8 @@ static const char* kClsNames[KC_COUNT] = {"extract_hist", "bucket_plan", "extrac
                                           "remix", "copy_in", "union_tagged", "skm_scatter",
                                           "skm_regroup", "skm_union", "skm_big", "skm_pack", "skm_phased", "bmp_build",
                                           "bmp_readout", "bmp_pivot", "bmp_cross", "bmp_count", "bmp_present", "bmp_member", "skm_cross",
-                                          "read_masks", "read_fold", "bmp_group_masks", "read_lookup"};
+                                          "read_masks", "read_fold", "bmp_group_masks", "read_lookup",
+                                          "index_dir", "index_tag", "read_index", "index_member"};
 
 // ------------------------------------------------------------------------------ ctx API
 extern "C" int kh_device_count(void) {
@@ -1522,6 +1523,155 @@ extern "C" int kh_read_votes(kh_ctx* c, const uint8_t* reads, const uint64_t* re
         c->prof_end();
         return (int)KH_OK;
     });
+}
+
+// ------------------------------------------------------------------- merged mask index
+// The union of nsets sets with a mask per key and a bucket directory in front (kh_index.hip): one lookup
+// per key whatever nsets is.  Built from sorted sets by the n-ary union (the keys), k_index_dir (the directory) and
+// k_index_tag (the masks); the index owns all three arrays and keeps no reference to the sets.
+constexpr u64 KH_INDEX_BUCKET_KEYS = 4;   // B: keys per bucket of the directory (KHOICE_INDEX_BUCKET_KEYS overrides it, per build)
+static u64 index_bucket_keys() {
+    u64 b = KH_INDEX_BUCKET_KEYS;
+    if (const char* e = getenv("KHOICE_INDEX_BUCKET_KEYS")) b = std::max<u64>(1, strtoull(e, nullptr, 10));
+    return b;
+}
+static u32 index_buckets(u64 n, u64 bucket_keys) {
+    return (u32)std::min<u64>(1ull << 31, std::max<u64>(1, (n + bucket_keys - 1) / bucket_keys));
+}
+static KhIndexView index_view(const kh_index* ix) {
+    return KhIndexView{ix->n ? ix->keys->keys_ptr() : nullptr, reinterpret_cast<const u64*>(ix->masks->p),
+                       reinterpret_cast<const u64*>(ix->dir->p), ix->n, ix->nb, ix->mwords};
+}
+extern "C" void kh_index_free(kh_index* ix) {
+    if (!ix) return;
+    kh_set_free(ix->keys);
+    buf_unref(ix->masks);
+    buf_unref(ix->dir);
+    delete ix;
+}
+extern "C" int kh_index_build(kh_ctx* c, const kh_set* const* sets, int nsets, kh_index** out) {
+    if (!c || !out) return kh_fail(KH_E_ARG, "kh_index_build: NULL argument");
+    if (nsets < 1 || !sets) return kh_fail(KH_E_ARG, "kh_index_build: at least one set is needed (nsets = %d)", nsets);
+    if ((u32)nsets > KH_READS_MAX_SETS)
+        return kh_fail(KH_E_ARG, "kh_index_build: more than %u sets are not supported", KH_READS_MAX_SETS);
+    for (int i = 0; i < nsets; ++i) {
+        if (!sets[i]) return kh_fail(KH_E_ARG, "kh_index_build: NULL set");
+        if (sets[i]->k != sets[0]->k)
+            return kh_fail(KH_E_KMISMATCH, "kh_index_build: k differs (set %d has %d, asked %d)", i, sets[i]->k, sets[0]->k);
+    }
+    HIPCHK(hipSetDevice(c->dev));
+    struct Guard { kh_index* ix; ~Guard() { kh_index_free(ix); } } g{new kh_index{}};
+    kh_index* ix = g.ix;
+    ix->k = sets[0]->k;
+    ix->W = sets[0]->W;
+    ix->nsets = nsets;
+    ix->mwords = (u32)std::max(1, (nsets + 63) / 64);
+    u64 max_n = 0;
+    for (int i = 0; i < nsets; ++i) max_n = std::max<u64>(max_n, sets[i]->n);
+    {   // the keys: the existing n-ary union; its counters are dropped at once
+        kh_set* u = nullptr;
+        KHCHK(kh_union_sum(c, sets, nsets, 1, &u, nullptr, 0));
+        const int r = kh_set_counts(c, u, 1, &ix->keys);
+        kh_set_free(u);
+        KHCHK(r);
+    }
+    ix->n = ix->keys->n;
+    ix->nb = index_buckets(ix->n, index_bucket_keys());
+    ix->masks = c->buf_alloc(8 * ix->n * ix->mwords);
+    ix->dir = c->buf_alloc(8 * ((u64)ix->nb + 1));
+    if (!ix->masks || !ix->dir)
+        return kh_fail(KH_E_NOMEM, "kh_index_build: the index of %llu keys, %u mask words and %u buckets does not fit",
+                       (unsigned long long)ix->n, ix->mwords, ix->nb);
+    const KhIndexView v = index_view(ix);
+    c->prof_begin(KC_INDEX_DIR);
+    kh_launch_index_dir(ix->W, v, reinterpret_cast<u64*>(ix->dir->p), ix->k, c->st);
+    c->prof_end();
+    HIPCHK(hipGetLastError());
+    if (ix->n) {
+        std::vector<KhSetView> sv((size_t)nsets);
+        for (int i = 0; i < nsets; ++i) sv[i] = KhSetView{sets[i]->n ? sets[i]->keys_ptr() : nullptr, nullptr, sets[i]->n, 1, 0};
+        Tmp d_view, d_err;
+        TMP_ALLOC(d_view, c, sizeof(KhSetView) * sv.size());
+        TMP_ALLOC(d_err, c, 4);
+        HIPCHK(hipMemcpyAsync(d_view.b->p, sv.data(), sizeof(KhSetView) * sv.size(), hipMemcpyHostToDevice, c->st));
+        HIPCHK(hipMemsetAsync(d_err.b->p, 0, 4, c->st));
+        HIPCHK(hipMemsetAsync(ix->masks->p, 0, 8 * ix->n * ix->mwords, c->st));   // k_index_tag ORs into zeros
+        c->prof_begin(KC_INDEX_TAG);
+        kh_launch_index_tag(ix->W, v, reinterpret_cast<u64*>(ix->masks->p), d_view.as<KhSetView>(), (u32)nsets, max_n, ix->k,
+                            d_err.as<u32>(), c->st);
+        c->prof_end();
+        HIPCHK(hipGetLastError());
+        u32 err = 0;
+        HIPCHK(hipMemcpyAsync(&err, d_err.b->p, 4, hipMemcpyDeviceToHost, c->st));
+        HIPCHK(hipStreamSynchronize(c->st));
+        if (err) return kh_fail(KH_E_INTERNAL, "kh_index_build: a key of a set is missing from the union of the sets");
+    } else {
+        HIPCHK(hipStreamSynchronize(c->st));
+    }
+    *out = ix;
+    g.ix = nullptr;
+    return KH_OK;
+}
+extern "C" int kh_index_info(const kh_index* ix, uint64_t* n, int* k, int* nsets, int* mask_words, uint64_t* nbuckets) {
+    if (!ix) return kh_fail(KH_E_ARG, "index is NULL");
+    if (n) *n = ix->n;
+    if (k) *k = ix->k;
+    if (nsets) *nsets = ix->nsets;
+    if (mask_words) *mask_words = (int)ix->mwords;
+    if (nbuckets) *nbuckets = ix->nb;
+    return KH_OK;
+}
+extern "C" int kh_index_download(kh_ctx* c, const kh_index* ix, uint64_t* keys, uint64_t* masks) {
+    if (!c || !ix) return kh_fail(KH_E_ARG, "kh_index_download: NULL argument");
+    if (keys) KHCHK(kh_set_download(c, ix->keys, keys, nullptr));
+    if (masks && ix->n) {
+        HIPCHK(hipSetDevice(c->dev));
+        HIPCHK(hipMemcpyAsync(masks, ix->masks->p, 8 * ix->n * ix->mwords, hipMemcpyDeviceToHost, c->st));
+        HIPCHK(hipStreamSynchronize(c->st));
+    }
+    return KH_OK;
+}
+extern "C" int kh_index_masks(kh_ctx* c, const kh_index* ix, const kh_set* probe, uint64_t* masks_out) {
+    if (!c || !ix || !probe) return kh_fail(KH_E_ARG, "kh_index_masks: NULL argument");
+    if (probe->k != ix->k) return kh_fail(KH_E_KMISMATCH, "kh_index_masks: k differs (probe has %d, the index %d)", probe->k, ix->k);
+    if (!probe->n) return KH_OK;
+    if (!masks_out) return kh_fail(KH_E_ARG, "kh_index_masks: NULL argument");
+    HIPCHK(hipSetDevice(c->dev));
+    Tmp d_out;
+    TMP_ALLOC(d_out, c, 8 * probe->n * ix->mwords);
+    c->prof_begin(KC_INDEX_MEMBER);
+    kh_launch_index_member(ix->W, index_view(ix), probe->keys_ptr(), probe->n, ix->k, d_out.as<u64>(), c->st);
+    c->prof_end();
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(masks_out, d_out.b->p, 8 * probe->n * ix->mwords, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipStreamSynchronize(c->st));
+    return KH_OK;
+}
+// The votes of read_votes_batches with the masks from an index: what kh_read_votes_index and exp6_index share.
+static int read_votes_index(kh_ctx* c, const uint8_t* reads, const uint64_t* read_off, uint64_t nreads, int on_device,
+                            const kh_index* ix, const kh_set* check, uint64_t* tie_masks, double* votes, uint32_t* unmatched) {
+    const KhIndexView v = index_view(ix);
+    Tmp d_check;
+    return read_votes_batches(c, reads, read_off, nreads, on_device, ix->k, ix->nsets, tie_masks, votes, unmatched, [&](KhReadsJob& job) {
+        if (check && !d_check.b) {
+            const KhSetView cv{check->n ? check->keys_ptr() : nullptr, nullptr, check->n, 1, 0};
+            TMP_ALLOC(d_check, c, sizeof cv);
+            HIPCHK(hipMemcpyAsync(d_check.b->p, &cv, sizeof cv, hipMemcpyHostToDevice, c->st));
+        }
+        job.check = check ? d_check.as<KhSetView>() : nullptr;
+        c->prof_begin(KC_READ_INDEX);
+        kh_launch_read_index(ix->W, job, v, c->st);
+        c->prof_end();
+        return (int)KH_OK;
+    });
+}
+extern "C" int kh_read_votes_index(kh_ctx* c, const uint8_t* reads, const uint64_t* read_off, uint64_t nreads, int on_device,
+                                   const kh_index* ix, const kh_set* check, uint64_t* tie_masks, double* votes,
+                                   uint32_t* unmatched) {
+    if (!c || !read_off || !ix) return kh_fail(KH_E_ARG, "kh_read_votes_index: NULL argument");
+    if (check && check->k != ix->k)
+        return kh_fail(KH_E_KMISMATCH, "kh_read_votes_index: k differs (check set has %d, asked %d)", check->k, ix->k);
+    return read_votes_index(c, reads, read_off, nreads, on_device, ix, check, tie_masks, votes, unmatched);
 }
 
 // ------------------------------------------------------------------------------ transfer
@@ -4077,7 +4227,7 @@ extern "C" int kh_exp4_run(kh_ctx* c, int nseq, const uint8_t* const* seqs, cons
 // exp_type_6.smk:164-344 has the rules of type 4 up to the last one, which runs src/merge_lists.py with -r: per read the
 // votes over the groups' k-mer sets.  No pivot database: every k-mer of a read is in the database built from the same
 // reads, so the KeyError of :167 cannot happen and there is nothing to check against.
-struct Exp6In {   // the arguments of kh_exp6_run that both forms read
+struct Exp6In {   // the arguments of kh_exp6_run that every form reads
     int nseq; const uint8_t* const* seqs; const uint64_t* lens; int on_device;
     const int* group_of; int ngroups;
     int npivots; const uint8_t* const* pivot_reads; const uint64_t* const* pivot_read_off; const uint64_t* pivot_nreads;
@@ -4158,16 +4308,82 @@ static int exp6_bmp(kh_ctx* c, const Exp6In& in, const Exp6Out& out, bool* done)
     *done = true;
     return KH_OK;
 }
-// The set form: the genomes' plain builds, the -cs{cs} union of every group with its histogram and `set_counts 1`, as
-// exp4_sets makes them, then kh_read_votes per pivot's reads against those unions.
-static int exp6_sets(kh_ctx* c, const Exp6In& in, const Exp6Out& out) {
-    const int nseq = in.nseq, ngroups = in.ngroups;
-    SetBag plain, unions, gsets;
-    KHCHK(build_plain(c, nseq, in.seqs, in.lens, 0, nullptr, nullptr, in.on_device, in.k, &plain));
+// What the set form and the index form share: the genomes' plain builds, the -cs{cs} union of every group with its
+// histogram and `set_counts 1`, as exp4_sets makes them.  gsets.v[g] is what the votes are taken against.
+struct Exp6Sets { SetBag plain, unions, gsets; };
+static int exp6_group_sets(kh_ctx* c, const Exp6In& in, const Exp6Out& out, Exp6Sets* s) {
+    const int nseq = in.nseq;
+    KHCHK(build_plain(c, nseq, in.seqs, in.lens, 0, nullptr, nullptr, in.on_device, in.k, &s->plain));
     for (int i = 0; i < nseq; ++i)
-        if (out.distinct_per_seq) out.distinct_per_seq[i] = plain.v[i]->n;
-    KHCHK(group_unions(c, plain.v.data(), nseq, in.group_of, ngroups, in.cs, &unions, out.within_hist, in.hist_len));
-    KHCHK(group_ones(c, unions, &gsets));
+        if (out.distinct_per_seq) out.distinct_per_seq[i] = s->plain.v[i]->n;
+    KHCHK(group_unions(c, s->plain.v.data(), nseq, in.group_of, in.ngroups, in.cs, &s->unions, out.within_hist, in.hist_len));
+    return group_ones(c, s->unions, &s->gsets);
+}
+// The index form (kh_index.hip): ONE merged mask index over the groups' sets, then per pivot the batches of
+// read_votes_batches, whose masks k_read_index finds with one lookup per window.  No check set, as in the set form.
+// KHOICE_EXP6_INDEX=1 takes the form whenever it applies, =0 never; unset follows the rule below.  *done == false: the
+// form does not apply or was not chosen (nothing of it was launched), the set form answers:
+//   * more groups than kh_read_votes takes (the set form reports them);
+//   * the upper bound of the index, sum |sets| * (8 W + 8 mwords + 8 / B), plus the workspace of its union (the union's
+//     counters, and above one launch's fan-in the partial unions) is above a quarter of the free memory, the budget of
+//     reads_max_pos (KHOICE_INDEX_MAX_BYTES lowers it).
+// The rule: the set form's work grows with windows * ngroups searches, the index adds a build that grows with
+// sum |sets|, so the form is taken from windows * ngroups >= R * sum |sets| on.  Measured (tools/bench_exp6_index.py,
+// profiles/exp6_index.json, DESIGN.md §3 "Merged mask index"): at 10 groups x 5 genomes x 5 Mbp the index wins every
+// point from the ratio 0.5307 on (k = 63, 10 x 10 000 reads of 150 bases: 26 ms against 40 ms; 10 kb reads: 30 x) and
+// loses at 0.10 and 0.01; R is that ratio rounded down.  The same ratios at small inputs: up to sum |sets| = 1.6e5 a
+// call is 0.6 ms of launches and synchronisations either way and the index never wins, at 1.1e6 .. 1.5e6 it wins one
+// point of three, from 3.6e6 on all of them: below that size the rule does not hold and the set form stays.
+constexpr double KH_EXP6_INDEX_RATIO = 0.53;
+constexpr u64 KH_EXP6_INDEX_MIN_KEYS = 3600000;
+static int exp6_index(kh_ctx* c, const Exp6In& in, const Exp6Out& out, const SetBag& gsets, bool* done) {
+    *done = false;
+    const int ngroups = in.ngroups;
+    const char* sw = getenv("KHOICE_EXP6_INDEX");
+    const bool forced = sw && atoi(sw) != 0;
+    if (sw && !forced) return KH_OK;
+    if ((u32)ngroups > KH_READS_MAX_SETS) return KH_OK;
+    u64 total = 0;
+    for (const kh_set* s : gsets.v) total += s->n;
+    if (!forced) {
+        if (total < KH_EXP6_INDEX_MIN_KEYS) return KH_OK;
+        double windows = 0;
+        for (int p = 0; p < in.npivots; ++p) {
+            if (!in.pivot_read_off[p]) return KH_OK;        // (the set form's call reports it)
+            for (u64 i = 0; i < in.pivot_nreads[p]; ++i) {
+                const u64 a = in.pivot_read_off[p][i], b = in.pivot_read_off[p][i + 1];
+                if (b > a && b - 1 - a >= (u64)in.k) windows += (double)(b - 1 - a - (u64)in.k + 1);
+            }
+        }
+        if (windows * (double)ngroups < KH_EXP6_INDEX_RATIO * (double)total) return KH_OK;
+    }
+    {   // ---- the memory budget
+        const u64 W = in.k <= 32 ? 1 : 2, mwords = (u64)std::max(1, (ngroups + 63) / 64);
+        u64 budget = 1ull << 30;
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) budget = (free_b + c->pool.cached_bytes) / 4;
+        if (const char* e = getenv("KHOICE_INDEX_MAX_BYTES")) budget = std::min<u64>(budget, strtoull(e, nullptr, 10));
+        const u64 need = total * (8 * W + 8 * mwords) + 8 * (total / index_bucket_keys() + 2)       // keys, masks, dir
+                         + total * (4 + (ngroups > KH_MAX_INPUT_SETS ? 8 * W + 4 : 0))                // the union's workspace
+                         + 8ull * (total / 16 + 2 * (u64)ngroups + 64);                               // (its bounds and descriptors)
+        if (need > budget) return KH_OK;
+    }
+    struct Guard { kh_index* ix = nullptr; ~Guard() { kh_index_free(ix); } } g;
+    KHCHK(kh_index_build(c, gsets.v.data(), ngroups, &g.ix));
+    const u64 nwords = g.ix->mwords;
+    u64 r0 = 0;
+    for (int p = 0; p < in.npivots; ++p) {
+        if (!in.pivot_read_off[p]) return kh_fail(KH_E_ARG, "kh_read_votes: NULL argument");   // (as the set form's call says it)
+        KHCHK(read_votes_index(c, in.pivot_reads[p], in.pivot_read_off[p], in.pivot_nreads[p], in.on_device, g.ix, nullptr,
+                               out.tie_masks ? out.tie_masks + r0 * nwords : nullptr, nullptr, out.unmatched ? out.unmatched + r0 : nullptr));
+        r0 += in.pivot_nreads[p];
+    }
+    *done = true;
+    return KH_OK;
+}
+// The set form: kh_read_votes per pivot's reads against the groups' sets.
+static int exp6_sets(kh_ctx* c, const Exp6In& in, const Exp6Out& out, const SetBag& gsets) {
+    const int ngroups = in.ngroups;
     const u64 nwords = (u64)std::max(1, (ngroups + 63) / 64);
     u64 r0 = 0;
     for (int p = 0; p < in.npivots; ++p) {
@@ -4189,9 +4405,13 @@ extern "C" int kh_exp6_run(kh_ctx* c, int nseq, const uint8_t* const* seqs, cons
     const Exp6Out out{within_hist, tie_masks, unmatched, distinct_per_seq};
     HIPCHK(hipSetDevice(c->dev));
     bool done = false;
-    KHCHK(exp6_bmp(c, in, out, &done));
+    KHCHK(exp6_bmp(c, in, out, &done));       // the order of the forms: bitmaps, index, sets
     if (done) return KH_OK;
-    return exp6_sets(c, in, out);
+    Exp6Sets s;
+    KHCHK(exp6_group_sets(c, in, out, &s));
+    KHCHK(exp6_index(c, in, out, s.gsets, &done));
+    if (done) return KH_OK;
+    return exp6_sets(c, in, out, s.gsets);
 }
 
 // ------------------------------------------------------------------------------ fused experiment type 3

@@ -32,7 +32,8 @@ enum KernelClass {
     KC_EXTRACT_HIST = 0, KC_BUCKET_PLAN, KC_EXTRACT_SCATTER, KC_BUCKET_SORT, KC_RANGE_BOUNDS,
     KC_SETOP, KC_HISTOGRAM, KC_REMIX, KC_COPY_IN, KC_UNION_TAGGED, KC_SKM_SCATTER, KC_SKM_REGROUP, KC_SKM_UNION,
     KC_SKM_BIG, KC_SKM_PACK, KC_SKM_PHASED, KC_BMP_BUILD, KC_BMP_READOUT, KC_BMP_PIVOT, KC_BMP_CROSS, KC_BMP_COUNT,
-    KC_BMP_PRESENT, KC_BMP_MEMBER, KC_SKM_CROSS, KC_READ_MASKS, KC_READ_FOLD, KC_BMP_GROUP_MASKS, KC_READ_LOOKUP, KC_COUNT
+    KC_BMP_PRESENT, KC_BMP_MEMBER, KC_SKM_CROSS, KC_READ_MASKS, KC_READ_FOLD, KC_BMP_GROUP_MASKS, KC_READ_LOOKUP,
+    KC_INDEX_DIR, KC_INDEX_TAG, KC_READ_INDEX, KC_INDEX_MEMBER, KC_COUNT
 };
 struct ProfEvt { int cls; hipEvent_t a, b; };
 struct Stats {
@@ -86,6 +87,18 @@ struct kh_set {
     const u32* counts_ptr() const {
         return cb ? reinterpret_cast<const u32*>(static_cast<const u8*>(cb->p) + coff) : nullptr;
     }
+};
+
+// A merged mask index resident in HBM (kh_index.hip): the union of nsets sets as a set of its own, a mask of mwords words
+// per key and the bucket directory.  It holds no reference to the sets it was built from.
+struct kh_index {
+    int k, W, nsets;
+    u32 mwords;
+    u64 n;           // distinct keys
+    u32 nb;          // buckets of the directory
+    kh_set* keys;    // owned; n == keys->n
+    DevBuf* masks;   // [n][mwords] u64
+    DevBuf* dir;     // [nb + 1] u64
 };
 
 int kh_fail(int code, const char* fmt, ...);

@@ -471,6 +471,26 @@ void kh_launch_read_lookup(const KhReadsJob& job, const u64* table, hipStream_t 
 // votes [nreads][nsets] or null; unmatched [nreads] or null
 void kh_launch_read_fold(const KhReadsJob& job, const double* inv, u64* tie, double* votes, u32* unmatched, u32 grid,
                          hipStream_t st);
+// ---- merged mask index (kh_index.hip, kh_index_device.h): the union of nsets sorted sets, every key with the mask of
+// the sets that hold it, behind a bucket directory over the mixed key space.
+struct KhIndexView {
+    const void* keys;        // [n] distinct MIXED keys, ascending (nullptr when n == 0)
+    const u64* masks;        // [n][mwords]: bit d & 63 of word d >> 6 = sets[d] holds the key (the numbering of k_membership)
+    const u64* dir;          // [nb + 1]: dir[b] = first record whose kh_slot(key, k, nb) is at least b; dir[0] = 0, dir[nb] = n
+    u64 n;
+    u32 nb;                  // buckets, 1 .. 2^31
+    u32 mwords;              // max(1, (nsets + 63) / 64)
+};
+// dir of `v` from its keys: n + 1 threads, every entry written exactly once
+void kh_launch_index_dir(int W, const KhIndexView& v, u64* dir, int k, hipStream_t st);
+// masks of `v` (zeroed by the caller on the same stream) from the sets: bit d for every key of sets[d]; a key that the
+// index lacks sets *err (zeroed by the caller).  max_n: keys of the largest set
+void kh_launch_index_tag(int W, const KhIndexView& v, u64* masks, const KhSetView* sets, u32 nsets, u64 max_n, int k, u32* err,
+                         hipStream_t st);
+// out[i][mwords] = the mask of probe[i] (mixed keys, any order), zeros for a key the index lacks
+void kh_launch_index_member(int W, const KhIndexView& v, const void* probe, u64 n, int k, u64* out, hipStream_t st);
+// the masks of a batch of reads from the index: the contract of kh_launch_read_masks (job.sets is not read, job.check is)
+void kh_launch_read_index(int W, const KhReadsJob& job, const KhIndexView& v, hipStream_t st);
 void kh_launch_table_add(const void* keys, u64 n, int k, void* table, u32 cell_bytes, hipStream_t st);
 void kh_launch_table_hist(const void* table, u32 cell_bytes, u64 lo, u64 hi, u32 cs,
                           unsigned long long* hist, u32 hist_len, hipStream_t st);

@@ -105,6 +105,12 @@ def load_library(path: Optional[str] = None):
                                   u64p, C.c_uint32, C.POINTER(C.c_double), u64p, u64p, u64p]),
         "kh_read_votes": (C.c_int, [vp, vp, u64p, C.c_uint64, C.c_int, C.c_int, C.POINTER(vp), C.c_int, vp,
                                     u64p, C.POINTER(C.c_double), u32p]),
+        "kh_index_build": (C.c_int, [vp, C.POINTER(vp), C.c_int, C.POINTER(vp)]),
+        "kh_index_free": (None, [vp]),
+        "kh_index_info": (C.c_int, [vp, u64p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), u64p]),
+        "kh_index_download": (C.c_int, [vp, vp, vp, vp]),
+        "kh_index_masks": (C.c_int, [vp, vp, vp, vp]),
+        "kh_read_votes_index": (C.c_int, [vp, vp, u64p, C.c_uint64, C.c_int, vp, vp, u64p, C.POINTER(C.c_double), u32p]),
         "kh_exp6_run": (C.c_int, [vp, C.c_int, C.POINTER(vp), u64p, C.c_int, C.POINTER(C.c_int), C.c_int,
                                   C.c_int, C.POINTER(vp), C.POINTER(vp), u64p, C.c_int, C.c_uint32,
                                   u64p, C.c_uint32, u64p, u32p, u64p]),
@@ -135,6 +141,7 @@ ABI_SYMBOLS = [
     "kh_read_fasta", "kh_free_host", "kh_ingest_fasta", "kh_seqs_count", "kh_seqs_get", "kh_seqs_free",
     "kh_write_histogram_text", "kh_set_counts", "kh_union_sum", "kh_union_histogram", "kh_simple", "kh_histogram",
     "kh_histogram_file", "kh_membership", "kh_confusion_row", "kh_read_votes", "kh_exp6_run",
+    "kh_index_build", "kh_index_free", "kh_index_info", "kh_index_download", "kh_index_masks", "kh_read_votes_index",
     "kh_table_add_set", "kh_table_histogram", "kh_dump_sorted", "kh_set_free", "kh_set_info", "kh_set_counter_max",
     "kh_set_download",
     "kh_set_upload", "kh_set_device_ptrs", "kh_set_from_device", "kh_set_export_device",
@@ -251,6 +258,55 @@ class KmerSet:
         b = np.zeros(nparts + 1, dtype=np.uint64)
         _check(self._e._lib.kh_set_partition_bounds(self._e._ctx, self._h, nparts, _u64p(b)))
         return b
+
+
+class MaskIndex:
+    """A merged mask index resident in HBM (Engine.mask_index): the union of the sets it was built from, every key with
+    the mask of the sets that hold it.  It outlives those sets.  Owned by the library until close()."""
+
+    def __init__(self, engine: "Engine", handle: int):
+        self._e = engine
+        self._h = C.c_void_p(handle)
+
+    def close(self):
+        if self._h:
+            self._e._lib.kh_index_free(self._h)
+            self._h = None
+
+    free = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self):
+        n, k, ns, mw, nb = C.c_uint64(), C.c_int(), C.c_int(), C.c_int(), C.c_uint64()
+        _check(self._e._lib.kh_index_info(self._h, C.byref(n), C.byref(k), C.byref(ns), C.byref(mw), C.byref(nb)))
+        return {"n": n.value, "k": k.value, "nsets": ns.value, "mask_words": mw.value, "buckets": nb.value}
+
+    def download(self):
+        """(keys[n, W] uint64 as KmerSet.download gives them for the union of the sets, masks[n, mask_words] uint64:
+        bit d % 64 of word d // 64 = sets[d] holds the key), in the index's storage order."""
+        i = self.info()
+        keys = np.zeros((i["n"], words_per_key(i["k"])), dtype=np.uint64)
+        masks = np.zeros((i["n"], i["mask_words"]), dtype=np.uint64)
+        _check(self._e._lib.kh_index_download(self._e._ctx, self._h, keys.ctypes.data, masks.ctypes.data))
+        return keys, masks
+
+    def masks_of(self, probe: "KmerSet") -> np.ndarray:
+        """masks[len(probe), mask_words] of the probe's k-mers in ITS storage order (the order of probe.download());
+        zeros for a k-mer the index lacks."""
+        masks = np.zeros((len(probe), self.info()["mask_words"]), dtype=np.uint64)
+        _check(self._e._lib.kh_index_masks(self._e._ctx, self._h, probe._h, masks.ctypes.data))
+        return masks
 
 
 class DeviceTexts:
@@ -532,6 +588,31 @@ class Engine:
         _check(self._lib.kh_read_votes(self._ctx, ptr, _u64p(off), nreads, dev, k, arr, ns,
                                        check._h if check is not None else None,
                                        _u64p(res["tie_masks"]) if nreads else None, votes, unm))
+        return res
+
+    def mask_index(self, sets: Sequence[KmerSet]) -> MaskIndex:
+        """The merged mask index of `sets` (kh_index_build): one lookup per k-mer answers "which of the sets hold it"."""
+        arr = (C.c_void_p * max(1, len(sets)))(*[s._h for s in sets])
+        out = C.c_void_p()
+        _check(self._lib.kh_index_build(self._ctx, arr, len(sets), C.byref(out)))
+        return MaskIndex(self, out.value)
+
+    def read_votes_index(self, reads, offsets, index: MaskIndex, check: Optional[KmerSet] = None,
+                         want_votes: bool = False, want_unmatched: bool = False) -> dict:
+        """`read_votes` against the sets `index` was built from: the same dict, bit for bit, from one lookup per k-mer."""
+        ptr, off, dev, keep = self._reads_arg(reads, offsets)
+        i = index.info()
+        nreads, ns, nw = off.size - 1, i["nsets"], i["mask_words"]
+        res = {"tie_masks": np.zeros((nreads, nw), dtype=np.uint64)}
+        if want_votes:
+            res["votes"] = np.zeros((nreads, ns), dtype=np.float64)
+        if want_unmatched:
+            res["unmatched"] = np.zeros(nreads, dtype=np.uint32)
+        votes = res["votes"].ctypes.data_as(C.POINTER(C.c_double)) if want_votes and res["votes"].size else None
+        unm = res["unmatched"].ctypes.data_as(C.POINTER(C.c_uint32)) if want_unmatched and nreads else None
+        _check(self._lib.kh_read_votes_index(self._ctx, ptr, _u64p(off), nreads, dev, index._h,
+                                             check._h if check is not None else None,
+                                             _u64p(res["tie_masks"]) if nreads else None, votes, unm))
         return res
 
     def exp6_run(self, seqs: Sequence, group_of: Sequence[int], pivot_reads: Sequence, k: int, cs: int = 5000,
