@@ -512,8 +512,12 @@ struct SkmClaim1 {
 // compare-and-swap on `dd`, one 16-byte read of the staged record, compared without a branch per word); a copy's OR
 // into the survivor's mask is issued once behind the loop and waited for behind the chunk numbering.  With the compare
 // as an `&&` chain (three dependent reads) and the OR waited for inside the loop it made five: union 1.170 -> 1.090 ms,
-// B1->B2 7700 -> 7164 ticks per slot.  The read-out makes four per pass with both fields set (the exchange pair, the
-// gtab read, per entry) and was NOT brought down, see below.
+// B1->B2 7700 -> 7164 ticks per slot.  The read-out made four per pass with both fields set (the exchange pair, then
+// the gtab read of the mask's lowest genome, per entry) and makes two: the gtab entry it starts from is that of the
+// creator's OWN genome, known from `made`, fetched once per pass ahead of the exchanges (`eval_mask`).  That dependent
+// read was what the read-out cost: halving the vector instructions of an entry (52 -> 25: one index space for both
+// tables, the first group outside the loop, bin offsets in bytes) bought 0.008 ms of 1.088, a timing build that
+// evaluated nothing 0.101; what taking the read off the chain bought: profiles/README.md, round 12.
 //
 // MEASURED AND REJECTED.  Each was a compile-time switch of this kernel up to the commit "k_skm_union: read out a slot
 // during the next slot's merge interval", where the code can be found; every number: profiles/README.md, DESIGN.md §8.
@@ -544,15 +548,23 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs, 
     constexpr u32 T2SH = 25;   // 32 - log2(T2)
     constexpr int E = (int)SKM_UE;
     constexpr u64 EMPTY = ~0ull;   // never a canonical key: the reverse complement of the all-T k-mer is 0
-    // Table planes: keys (8-byte stride), low and high halves of the genome masks (4-byte stride).
+    // Table planes: keys (8-byte stride), low and high halves of the genome masks (4-byte stride).  ONE INDEX SPACE for
+    // both tables: entry i of the second table is entry T + i of each plane, so whoever knows an entry's joint index
+    // (the read-out, from `made`) addresses its masks without asking which table it is in.
+    // A word of `made`: two fields of 13 bits (0: no entry, else the entry's joint index + 1) and, above them, the
+    // operand number of the genome whose record the thread's chunk of that pass came from.
+    constexpr u32 MADE_FIELD_BITS = 13, MADE_FIELD = (1u << MADE_FIELD_BITS) - 1u, MADE_FIELDS = (1u << (2 * MADE_FIELD_BITS)) - 1u;
+    constexpr u32 MADE_OWN_SHIFT = 2 * MADE_FIELD_BITS;
+    static_assert(T + T2 <= MADE_FIELD, "a field of `made` holds a joint index + 1");
+    static_assert(KH_TAG_MAX_OPS <= (1 << (32 - MADE_OWN_SHIFT)), "a word of `made` holds an operand number above its fields");
     u8* p = lds_raw;
-    unsigned long long* tkey = reinterpret_cast<unsigned long long*>(p);   p += (size_t)T * 8;
-    u32* tmlo = reinterpret_cast<u32*>(p);                                 p += (size_t)T * 4;
-    u32* tmhi = reinterpret_cast<u32*>(p);                                 p += (size_t)T * 4;
-    unsigned long long* okey = reinterpret_cast<unsigned long long*>(p);   p += (size_t)T2 * 8;
-    u32* omlo = reinterpret_cast<u32*>(p);                                 p += (size_t)T2 * 4;
-    u32* omhi = reinterpret_cast<u32*>(p);                                 p += (size_t)T2 * 4;
-    uint4* gtab = reinterpret_cast<uint4*>(p);                             p += 1024;   // per operand: its group's mask (two halves), first bin << sshift
+    unsigned long long* tkey = reinterpret_cast<unsigned long long*>(p);   p += (size_t)(T + T2) * 8;
+    u32* tmlo = reinterpret_cast<u32*>(p);                                 p += (size_t)(T + T2) * 4;
+    u32* tmhi = reinterpret_cast<u32*>(p);                                 p += (size_t)(T + T2) * 4;
+    unsigned long long* const okey = tkey + T;
+    u32* const omlo = tmlo + T;
+    u32* const omhi = tmhi + T;
+    uint4* gtab = reinterpret_cast<uint4*>(p);                             p += 1024;   // per operand: its group's mask (two halves), first bin as a BYTE offset into hstripe
     u32* scratch = reinterpret_cast<u32*>(p);                              p += 128;
     u32* dupc = reinterpret_cast<u32*>(p);                                 p += 256;
     u32* hstripe = reinterpret_cast<u32*>(p);                              p += (size_t)SKM_HSTRIPE_WORDS * 4;
@@ -592,15 +604,16 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs, 
     SKM_MARK("init");
     // The read-out below is the twin of SkmReadout (kh_skm_device.h), kept in place: with the shared struct this kernel
     // had the same registers and 32 instructions fewer, and ran 1 % slower (1.431 -> 1.446 ms, three alternated runs
-    // each, the parent's spread 0.003).  The BIN RULE is shared: a change of it has to be made in both.  The zeroing
-    // of the masks as they are read is this kernel's alone: the kernels built on SkmReadout clear their planes.
+    // each, the parent's spread 0.003).  The BIN RULE is shared: a change of it has to be made in both; only the ORDER
+    // in which a mask's groups are counted differs (here the creator's own group first, there from the lowest bit up),
+    // and the group table here holds byte offsets.  The zeroing of the masks as they are read, the joint index of both
+    // tables and the genome carried in `made` are this kernel's alone: the kernels built on SkmReadout clear their planes.
     // (the mask planes, once: the first slot's first barrier comes before any mask is touched)
-    for (u32 i = tid; i < T / 2; i += NT) reinterpret_cast<uint4*>(tmlo)[i] = make_uint4(0u, 0u, 0u, 0u);   // (both planes of the main table)
-    if (tid < T2) { omlo[tid] = 0u; omhi[tid] = 0u; }
+    for (u32 i = tid; i < (T + T2) / 2; i += NT) reinterpret_cast<uint4*>(tmlo)[i] = make_uint4(0u, 0u, 0u, 0u);   // (both planes, both tables: they are adjacent)
     if (tid < (u32)KH_TAG_MAX_OPS) {
         const u32 g = jb.ginfo[tid], g0 = g & 0xffu, gn = (g >> 8) & 0xffu;
         const u64 gm = gn ? (gn >= 64u ? ~0ull : ((1ull << gn) - 1ull)) << g0 : 0ull;
-        gtab[tid] = make_uint4((u32)gm, (u32)(gm >> 32), (g >> 16) << sshift, 0u);
+        gtab[tid] = make_uint4((u32)gm, (u32)(gm >> 32), (g >> 16) << (sshift + 2u), 0u);
         dupc[tid] = 0;
     }
     if (tid < SKM_HSTRIPE_WORDS) hstripe[tid] = 0;
@@ -613,29 +626,46 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs, 
     const u32 tsh_sub = tsh_high ? tsh - 32u : tsh;
     // one distinct k-mer: popcount of its mask per group -> the group's bin; number of groups -> across bin
     // (returns true when the k-mer sits in exactly one group — nearly all do: those are counted per wave)
-    auto eval_mask = [&](u32 mlo, u32 mhi) -> bool {
-        const u32 lsel = lane & smask;
-        u32 ng = 0;
-        do {
-            const u32 first = mlo ? (u32)__builtin_ctz(mlo) : 32u + (u32)__builtin_ctz(mhi);
-            const uint4 g = gtab[first];
-            u32 c = (u32)__popc(mlo & g.x) + (u32)__popc(mhi & g.y);
+    // THE CREATOR'S OWN GROUP stands outside the loop.  Whoever created an entry ORed the mask of its own record into
+    // it, so the group of that record's genome (`own`, its operand number) is one of the mask's groups, and in which
+    // order the groups of a mask are counted makes no difference to the bins.  Its table entry `g` does not depend on
+    // the mask: the read-out fetches it together with the exchanges, one LDS round trip instead of two in a row.
+    // Nearly every k-mer sits in one group, and then no lane of the wave has bits outside that group's mask: one
+    // wave-uniform test, and the strip and the loop are not executed at all.  Otherwise the own group and the own bit
+    // are stripped (a tag outside every group has an empty group mask: its bit goes here, as the lowest bit does in
+    // the loop, which therefore ends) and the remaining groups are taken from the lowest bit up.
+    auto eval_mask = [&](u32 mlo, u32 mhi, const uint4 g, const u32 own) -> bool {
+        const u32 bsh = sshift + 2u;   // a bin's stripe in bytes
+        u8* const hlane = reinterpret_cast<u8*>(hstripe) + ((lane & smask) << 2);   // the lane's word of every stripe
+        auto count_group = [&](const uint4 gg) {
+            u32 c = (u32)__popc(mlo & gg.x) + (u32)__popc(mhi & gg.y);
             c = c < cs ? c : cs;
-            atomicAdd(&hstripe[g.z + (c << sshift) + lsel], 1u);
+            atomicAdd(reinterpret_cast<u32*>(hlane + (gg.z + (c << bsh))), 1u);
+        };
+        count_group(g);
+        if (!__builtin_amdgcn_ballot_w64(((mlo & ~g.x) | (mhi & ~g.y)) != 0u)) return true;   // (uniform) no lane has a second group
+        const u32 ob = 1u << (own & 31u);
+        mlo &= ~(g.x | (own < 32u ? ob : 0u));
+        mhi &= ~(g.y | (own < 32u ? 0u : ob));
+        u32 ng = 1;
+        while (mlo | mhi) {
+            const uint4 g2 = gtab[mlo ? (u32)__builtin_ctz(mlo) : 32u + (u32)__builtin_ctz(mhi)];
+            count_group(g2);
             const u32 keep_hi = mlo ? ~0u : mhi - 1u;   // (the lowest bit goes in any case: a tag outside every group cannot hang the loop)
-            mlo &= ~g.x & (mlo - 1u);
-            mhi &= ~g.y & keep_hi;
+            mlo &= ~g2.x & (mlo - 1u);
+            mhi &= ~g2.y & keep_hi;
             ++ng;
-        } while (mlo | mhi);
+        }
         if (ng == 1u) return true;
-        atomicAdd(&hstripe[((jb.abase + (ng < cs ? ng : cs)) << sshift) + lsel], 1u);
+        atomicAdd(&hstripe[((jb.abase + (ng < cs ? ng : cs)) << sshift) + (lane & smask)], 1u);
         return false;
     };
     u32 st_full = 0, st_exp = 0;   // fullest slot seen, k-mer instances expanded (uniform)
-    // ---- the read-out: every thread turns the entries it created (16-bit fields of `made`, per pass) into histogram bins.
+    // ---- the read-out: every thread turns the entries it created (13-bit fields of `made`, per pass) into histogram bins.
     // Invariant (the masks clean themselves): every non-zero mask has exactly one creator; it is read once, here, behind
     // the barrier after the insertion, and the read stores zero — so both planes of both tables are zero when
-    // the next insertion phase (next subset, next slot) begins.  A mask is only ever ORed into behind a
+    // the next insertion phase (next subset, next slot) begins; this holds word for word for the second table's
+    // entries, joint indices T .. T + T2 - 1 of the same planes.  A mask is only ever ORed into behind a
     // compare-and-swap that found its key or created it, and whoever created it recorded the place in `made`:
     // in the probe rounds (`mk`) or one key per lane (`where`, either table).  A key dropped under
     // KH_ERR_CAPACITY touched no mask; a slot handed on inserts nothing (C = 0); with R > 1 each subset's
@@ -645,29 +675,33 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs, 
     // interval nobody else touches the mask planes, gtab or hstripe (the merge works on the key plane, rmask, owner and
     // scratch[0]); dupc is added to from both sides, and additions commute.
     auto read_out = [&](u32 (&made)[SKM_PASSES][E / 2]) __attribute__((always_inline)) {
-        u32 ones = 0;   // keys that sit in exactly one group
+        u32 ones = 0;   // keys that sit in exactly one group, of the whole wave (uniform: a scalar register)
 #pragma unroll
         for (u32 pass = 0; pass < SKM_PASSES; ++pass) {
             u32 any = 0;
 #pragma unroll
-            for (int e = 0; e < E / 2; ++e) any |= made[pass][e];
+            for (int e = 0; e < E / 2; ++e) any |= made[pass][e] & MADE_FIELDS;
             if (!__builtin_amdgcn_ballot_w64(any != 0)) continue;
+            const u32 own = made[pass][0] >> MADE_OWN_SHIFT;   // the genome of the pass's record (0 where the thread had none)
+            const uint4 g = gtab[own];                         // (issued ahead of the exchanges, which it does not depend on)
 #pragma unroll
             for (int e = 0; e < E; ++e) {
-                const u32 f = (made[pass][e >> 1] >> (16 * (e & 1))) & 0xffffu;
-                if (f & 0x8000u) {
-                    const u32 at = f & 0x3fffu;
-                    const bool second = f & 0x4000u;
-                    const u32 mlo = atomicExch((second ? omlo : tmlo) + at, 0u);
-                    const u32 mhi = atomicExch((second ? omhi : tmhi) + at, 0u);
-                    if (eval_mask(mlo, mhi)) ++ones;
+                const u32 f = (made[pass][e >> 1] >> (MADE_FIELD_BITS * (e & 1))) & MADE_FIELD;
+                bool one = false;
+                if (f) {   // the joint index + 1: either table
+                    const u32 mlo = atomicExch(tmlo + f - 1u, 0u);
+                    const u32 mhi = atomicExch(tmhi + f - 1u, 0u);
+                    // (opaque copies made behind the exchanges: left to itself the compiler works on `g` ahead of them, for
+                    // both entries at once, and waits for it there: two round trips in a row again)
+                    uint4 ge = g;
+                    u32 owne = own;
+                    asm volatile("" : "+v"(ge.x), "+v"(ge.y), "+v"(ge.z), "+v"(owne));
+                    one = eval_mask(mlo, mhi, ge, owne);
                 }
+                ones += (u32)__builtin_popcountll(__builtin_amdgcn_ballot_w64(one));
             }
         }
-        if (__builtin_amdgcn_ballot_w64(ones != 0)) {
-            ones = wave_scan_add(ones);
-            if (lane == KH_WAVE - 1) atomicAdd(&hstripe[(jb.abase + 1u) << sshift], ones);
-        }
+        if (ones && lane == 0) atomicAdd(&hstripe[(jb.abase + 1u) << sshift], ones);
         SKM_MARK("readout_done");
     };
     // what a lean slot's insertion leaves for the read-out behind the next barrier 1 (all zero: nothing)
@@ -845,7 +879,7 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs, 
                 if (q) { clear_keys(); __syncthreads(); }
                 unsigned long long emptyv = EMPTY;   // (opaque: made here, or the compiler keeps the constant in two VGPRs across the loop and spills it)
                 asm volatile("" : "+v"(emptyv));
-                // entries this thread created, per pass: 16-bit fields (bit 15: set = valid, bit 14: second table)
+                // entries this thread created, per pass: two fields and the record's genome (the layout is at the table planes)
                 u32 made[SKM_PASSES][E / 2];
 #pragma unroll
                 for (u32 ps = 0; ps < SKM_PASSES; ++ps)
@@ -856,7 +890,7 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs, 
                     if (pass * NT >= C) break;   // uniform
                     const u32 c = pass * NT + c0;
                     u64 kreg[E];
-                    u32 slot_[E], act = 0, bits = 0, half = 0;
+                    u32 slot_[E], act = 0, bits = 0, half = 0, own = 0;
 #pragma unroll
                     for (int e = 0; e < E; ++e) { kreg[e] = EMPTY; slot_[e] = 0; }
                     if (c < C) {
@@ -866,6 +900,7 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs, 
                         const uint4 r0 = reg[ri];
                         bits = rmask[ri];
                         half = SkmRec1::half(r0.w);
+                        own = SkmRec1::tag(r0.w);   // (its bit is in `bits`: the record that stays keeps its own)
                         const u32 left = SkmRec1::n(r0.w) - first;
                         const u32 cnt = left < (u32)E ? left : (u32)E;
                         // The twin of skm1_expand<E> above, kept in place: through the shared expander (hash, kreg, slot_ and act
@@ -943,7 +978,7 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs, 
                                     u32* mp2 = level == 1 ? (khalf ? omhi : omlo) : kmp;
                                     u32 d = atomicOr(mp2 + S, kbits) & kbits;
                                     while (d) { atomicAdd(&dupc[khalf * 32u + (u32)__builtin_ctz(d)], 1u); d &= d - 1u; }
-                                    if (o2 == emptyv) where = 0x8000u | (level == 1 ? 0x4000u : 0u) | S;
+                                    if (o2 == emptyv) where = (level == 1 ? T : 0u) + S + 1u;
                                     mine = false;
                                 } else {
                                     ++probes;
@@ -989,11 +1024,11 @@ __global__ __launch_bounds__(NT, 8) void k_skm_union(const KhSkmJob jb, u32 cs, 
                     SKM_USTAMP(9);
                     SKM_MARK("rounds_done");
 #pragma unroll
-                    for (int e = 0; e < E; ++e) f16[e] = (mk >> e) & 1u ? (0x8000u | slot_[e]) : 0u;
+                    for (int e = 0; e < E; ++e) f16[e] = (mk >> e) & 1u ? slot_[e] + 1u : 0u;
                     serial_finish();
                     SKM_MARK("serial_done");
 #pragma unroll
-                    for (int e = 0; e < E / 2; ++e) made[pass][e] = f16[2 * e] | (f16[2 * e + 1] << 16);
+                    for (int e = 0; e < E / 2; ++e) made[pass][e] = f16[2 * e] | (f16[2 * e + 1] << MADE_FIELD_BITS) | (own << MADE_OWN_SHIFT);
                     {   // repeats inside a genome: the bit was set before this instance came
                         u32 d = 0;
 #pragma unroll
