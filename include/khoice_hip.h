@@ -211,11 +211,13 @@ int kh_read_votes_index(kh_ctx *ctx, const uint8_t *reads, const uint64_t *read_
                         uint64_t *tie_masks /* [nreads*mask_words] */, double *votes /* [nreads*nsets] or NULL */,
                         uint32_t *unmatched /* [nreads] or NULL */);
 
-/* text form consumed at exp_type_1.smk:210-212: lines "c<TAB>n", c = 1..cmax */
+/* text form consumed at exp_type_1.smk:210-212: lines "c<TAB>n", c = 1..cmax; counters above cmax are added to line
+ * cmax (kh_histogram with hist_len = cmax + 1).  KH_E_ARG: cmax = 0 or above 2^24 - 1; no file is written */
 int kh_histogram_file(kh_ctx *ctx, const kh_set *set, uint32_t cmax, const char *path);
 
 /* the same text from a histogram array in host memory (what kh_exp1_run returns): counters past
- * hist_len read 0 */
+ * hist_len read 0; entries of the array past cmax are not written and NOT added to line cmax (the array is taken as
+ * the histogram it is).  KH_E_ARG: cmax = 0 or above 2^24 - 1 */
 int kh_write_histogram_text(const char *path, const uint64_t *hist, uint32_t hist_len, uint32_t cmax);
 
 /* ---------------------------------------------------------------- K7: sorted dump
@@ -228,7 +230,12 @@ void kh_set_free(kh_set *set);
 int kh_set_info(const kh_set *set, uint64_t *n, int *k, int *words_per_key, int *has_counts,
                 uint32_t *uniform_count);
 /* saturation value the set's counters were produced with (kmc -cs, OUTPUT_PARAMS -cs, or the
- * kmc_tools default 255); `kmc_tools transform histogram` prints 2^(8*bytes(counter_max))-1 lines */
+ * kmc_tools default 255); `kmc_tools transform histogram` prints 2^(8*bytes(counter_max))-1 lines.
+ *   kh_build_batch / kh_build_fasta (cs), kh_union_sum (cs), kh_simple (cs)   cs
+ *   kh_set_counts (value)                                                     max(value, 255), not the input's
+ *   kh_load                                                                   what kh_save wrote
+ *   kh_set_upload, kh_set_from_device, kh_set_wrap_device                     255: these do NOT look at the counters
+ *                                                                             they are given, which may be larger */
 int kh_set_counter_max(const kh_set *set, uint32_t *counter_max);
 /* copy to host in storage order (NOT sorted by key): keys un-mixed, n*W words; counts n */
 int kh_set_download(kh_ctx *ctx, const kh_set *set, uint64_t *keys, uint32_t *counts);
@@ -262,7 +269,13 @@ int kh_sets_partition_bounds(kh_ctx *ctx, const kh_set *const *sets, int nsets, 
 
 /* ---------------------------------------------------------------- database files
  * `<prefix>.kmc_pre` + `<prefix>.kmc_suf` (names required by the Snakemake rules,
- * exp_type_1.smk:160-161); khoice_amd container format, written atomically. */
+ * exp_type_1.smk:160-161); khoice_amd container format ("Database files"), written atomically: each file
+ * through a temporary in the same directory and a rename; a failed save leaves no partial file.
+ * kh_load returns KH_E_IO for a file that cannot be opened and KH_E_FORMAT, before anything is allocated on the
+ * device, for a header that is not this format's (magic, version, k, words, mixing fingerprint, no counters with a
+ * uniform counter of 0), a suffix file whose size is not the header's, and a body whose keys do not ascend, are not
+ * distinct or lie outside the 2k-bit key space, or that holds a zero counter.  The message names the file and, for
+ * the body, the first offending record. */
 int kh_save(kh_ctx *ctx, const kh_set *set, const char *prefix);
 int kh_load(kh_ctx *ctx, const char *prefix, kh_set **out);
 

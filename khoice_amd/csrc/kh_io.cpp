@@ -312,6 +312,8 @@ extern "C" void kh_seqs_free(kh_seqs* s) {
 // ------------------------------------------------------------------------------ container
 // <prefix>.kmc_pre : KhFileHeader
 // <prefix>.kmc_suf : "KHAMDSUF" | n*W u64 mixed keys, ascending | n u32 counters (if any)
+// (pinned byte for byte by the independent reader and writer of tests/test_gpu_files.py; kh_load checks the header,
+// the size of the suffix file against it, and the body: verify_body)
 struct KhFileHeader {
     char magic[8];        // "KHAMDPRE"
     uint32_t version;     // 1
@@ -397,6 +399,35 @@ extern "C" int kh_save(kh_ctx* c, const kh_set* s, const char* prefix) {
     return fp.commit();
 }
 
+// What every consumer of a set bisects or merges on, checked on the arrays just read before anything goes to the
+// device: mixed keys ascending and distinct (high word first for W = 2), every key inside the 2k-bit key space, no
+// zero counter: what kh_set_upload refuses on the host path.  The key-space test is made on the stored (mixed) word:
+// the mixing is a bijection of [0, 4^k), so a word with a bit above 2k is the image of no k-mer, and for one-word
+// keys kh_unmix_host would mask such a bit away instead of showing it.
+static int verify_body(const char* suf, int k, const std::vector<uint8_t>& key_bytes, const std::vector<uint32_t>& counts) {
+    const int W = k <= 32 ? 1 : 2;
+    const uint64_t* keys = reinterpret_cast<const uint64_t*>(key_bytes.data());
+    const uint64_t n = key_bytes.size() / (8 * (size_t)W);
+    const uint64_t top_mask = W == 1 ? ~kh_mask(2 * k) : ~kh_mask(2 * k - 64);
+    for (uint64_t i = 0; i < n; ++i) {
+        const uint64_t* a = keys + i * W;
+        if (a[W - 1] & top_mask)
+            return kh_fail(KH_E_FORMAT, "%s: key of record %llu is not a %d-mer (bits above 2k are set)", suf,
+                           (unsigned long long)i, k);
+        if (i) {
+            const uint64_t* p = a - W;
+            const bool above = W == 1 ? p[0] < a[0] : (p[1] < a[1] || (p[1] == a[1] && p[0] < a[0]));
+            if (!above)
+                return kh_fail(KH_E_FORMAT, "%s: key of record %llu is not above the key of record %llu (keys must ascend "
+                                            "and be distinct)", suf, (unsigned long long)i, (unsigned long long)(i - 1));
+        }
+    }
+    for (uint64_t i = 0; i < counts.size(); ++i)
+        if (counts[i] == 0)
+            return kh_fail(KH_E_FORMAT, "%s: counter of record %llu is 0", suf, (unsigned long long)i);
+    return KH_OK;
+}
+
 extern "C" int kh_load(kh_ctx* c, const char* prefix, kh_set** out) {
     if (!c || !prefix || !out) return kh_fail(KH_E_ARG, "kh_load: NULL argument");
     if (hipSetDevice(c->dev) != hipSuccess) return kh_fail(KH_E_HIP, "hipSetDevice failed");
@@ -410,6 +441,8 @@ extern "C" int kh_load(kh_ctx* c, const char* prefix, kh_set** out) {
         return kh_fail(KH_E_FORMAT, "%s is not a khoice_amd database (was it written by KMC?)", pre.c_str());
     if (h.k < 1 || h.k > 64 || h.words != (h.k <= 32 ? 1u : 2u))
         return kh_fail(KH_E_FORMAT, "%s: inconsistent header", pre.c_str());
+    if (!h.has_counts && !h.uniform)   // every k-mer of a set without a counter array counts `uniform`, never 0
+        return kh_fail(KH_E_FORMAT, "%s: a database without counters whose uniform counter is 0", pre.c_str());
     if (h.mix_id != mix_fingerprint())
         return kh_fail(KH_E_FORMAT, "%s was written with a different key-mixing function", pre.c_str());
     FILE* fs = fopen(suf.c_str(), "rb");
@@ -443,6 +476,8 @@ extern "C" int kh_load(kh_ctx* c, const char* prefix, kh_set** out) {
     ok = ok && (counts.empty() || fread(counts.data(), 4, counts.size(), fs) == counts.size());
     fclose(fs);
     if (!ok) return kh_fail(KH_E_FORMAT, "%s is truncated or not a khoice_amd database", suf.c_str());
+    int r = verify_body(suf.c_str(), (int)h.k, keys, counts);
+    if (r != KH_OK) return r;
     return kh_set_from_mixed_host(c, (int)h.k, h.n, keys.data(), h.has_counts ? counts.data() : nullptr,
                                   h.uniform, h.counter_max ? h.counter_max : KH_KMC_DEFAULT_CS, out);
 }

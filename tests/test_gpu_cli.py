@@ -223,6 +223,35 @@ def test_cli_extras_filelist_cs_and_complex_operators(tmp_path):
     assert open(os.path.join(root, "d2.txt")).read() == O.dump_sorted_text(O.build(synth.fasta_bytes(recs[0]), k, ci=2), k)
 
 
+def test_histogram_line_tiers_follow_the_counter_ceiling(tmp_path):
+    """`transform histogram` prints 2^(8 * counter bytes) - 1 lines (hist_lines, kh_cli.cpp): 255 up to a ceiling of
+    255, 65535 up to 65535; `simple` without -cs takes the larger ceiling of its operands (do_simple).  The three-byte
+    tier (2^24 - 1 lines) is not run: 17 million lines for the same comparison."""
+    root = str(tmp_path)
+    k = 11
+    fasta = synth.fasta_bytes(synth.genome_records(9, 0, 400)) + b">rep\n" + b"ACGTTGCATTGACCGTAGGC" * 300 + b"\n"
+    open(os.path.join(root, "g.fa"), "wb").write(fasta)
+    os.makedirs(os.path.join(root, "tmp"))
+    assert max(O.build(fasta, k, cs=1 << 30).values()) >= 300
+    dbs = {}
+    for cs, lines in ((255, 255), (256, 65535), (65535, 65535)):
+        sh(f"kmc -fm -k{k} -ci1 -cs{cs} g.fa db{cs} tmp/ > /dev/null", root)
+        sh(f"kmc_tools transform db{cs} histogram h{cs}.txt", root)
+        dbs[cs] = O.build(fasta, k, cs=cs)
+        text = open(os.path.join(root, f"h{cs}.txt")).read()
+        assert text.count("\n") == lines, (cs, text.count("\n"))
+        assert text == O.histogram_text(dbs[cs], lines), cs
+    assert [max(dbs[cs].values()) for cs in (255, 256)] == [255, 256] and 300 <= max(dbs[65535].values()) < 65535
+    # no -cs on the command line: the larger ceiling of the two operands, so sums above 255 survive
+    sh("kmc_tools simple db65535 db255 intersect inter -ocsum", root)
+    sh("kmc_tools transform inter dump -s inter.txt", root)
+    sh("kmc_tools transform inter histogram inter.hist.txt", root)
+    want = O.intersect(dbs[65535], dbs[255], "sum", cs=65535)
+    assert 255 < max(want.values()) < 65535
+    assert open(os.path.join(root, "inter.txt")).read() == O.dump_sorted_text(want, k)
+    assert open(os.path.join(root, "inter.hist.txt")).read() == O.histogram_text(want, 65535)
+
+
 def test_concurrent_processes_share_the_gpu(tmp_path):
     """`snakemake --cores N` runs N rule processes at once: independent contexts on one GPU, and
     concurrent clients of one server, must all produce the same databases as serial runs."""
