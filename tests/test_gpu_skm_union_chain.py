@@ -4,23 +4,19 @@ The kernel leaves its mask planes zero by reading every mask with an exchange th
 them per slot.  That only matters from a workgroup's second slot on, and the other small tests have fewer slots than
 workgroups: here KHOICE_SKM_MEAN makes the slots small enough that every workgroup walks several, with chunk counts on both sides of a pass boundary, with a slot that is handed to k_skm_big in between, and
 with genomes repeated inside a group (repeat counters, mask bits already set).  Everything against the C restatement."""
-import re
-
 import numpy as np
 import pytest
 
 from khoice_amd import synth
-from oracle import c_oracle as CO
 from tests import util
 from tests.test_gpu_skm2_hashsets import handover_case
 from tests.test_gpu_skm_hashsets import deep_case, random_genomes, with_background
 
 pytestmark = pytest.mark.gpu
 
-KERNELS = ("skm_union", "skm_big", "union_tagged")
-COUNTERS = ("retries", "big_slots")
+KERNELS, COUNTERS = util.UNION_KERNELS, util.UNION_COUNTERS
 UNION_NT = 1024            # threads of k_skm_union = chunks of one pass
-NSLOTS = re.compile(r"\[skm\] k=\d+ .* nslots=(\d+) \|")
+NSLOTS = util.SKM_NSLOTS
 
 
 @pytest.fixture(scope="module")
@@ -43,20 +39,7 @@ def union_grid(eng):
     return 2 * eng.stats()["cus"]          # kh_skm_union_per_cu() workgroups per CU, persistent
 
 
-def run_checked(eng, capfd, seqs, group_of, k, cs=5000, hist_len=5001):
-    """One call against the oracle, a second that must give the same; -> (the [skm] line's nslots, what ran)."""
-    want = CO.exp1(seqs, group_of, k, cs=cs, hist_len=hist_len)
-    capfd.readouterr()
-    got, did = util.exp1_run_stats(eng, seqs, group_of, k, cs, hist_len, KERNELS, COUNTERS)
-    err = capfd.readouterr().err
-    util.exp1_same(got, want)
-    again, did2 = util.exp1_run_stats(eng, seqs, group_of, k, cs, hist_len, KERNELS, COUNTERS)
-    capfd.readouterr()
-    util.exp1_same(again, got)
-    assert did2 == did
-    found = NSLOTS.findall(err)
-    assert len(found) == 1, err
-    return int(found[0]), did, err
+run_checked = util.run_checked
 
 
 def mean_for(seqs, nslots):

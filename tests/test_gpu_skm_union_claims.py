@@ -75,13 +75,7 @@ def grid_of(eng, k):
     return union_grid(eng) if k <= 32 else 3 * eng.stats()["cus"]
 
 
-def fitted(seqs, k, n):
-    """(the texts, the last one cut by fewer than n bases; KHOICE_SKM_MEAN) for which nslots = ceil(positions / mean)
-    is exactly n."""
-    positions = sum(len(s) - k + 1 for s in seqs)
-    mean = positions // n
-    assert mean >= 64 and positions - n * mean < len(seqs[-1]) - k
-    return seqs[:-1] + [seqs[-1][:len(seqs[-1]) - (positions - n * mean)]], mean
+fitted = util.fitted
 
 
 # name -> (genome length, nslots as a function of the grid)

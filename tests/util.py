@@ -474,13 +474,18 @@ def memo_in(cache):
 
 SKM_SLOT = re.compile(r"\[skm\] k=(\d+) m=(\d+) .*slot: mean [\d.]+ max (\d+) cap (\d+) .*expanded: (\d+) k-mers \| "
                       r"errors (\d+) spilled (\d+) overfull slots (\d+)")
+SKM_PLAN = re.compile(r"\[skm\] k=\d+ m=\d+ w=(\d+) nmax=\d+ positions=(\d+) records=(\d+) .* nb1=(\d+) S=(\d+) nslots=(\d+) \| "
+                      r"coarse: mean \d+ max (\d+) cap (\d+) \|")
 
 
 def skm_line(err):
+    """The one [skm] line (KHOICE_SKM_DEBUG=1) of a call: how full the regions were, and the plan's geometry."""
     lines = SKM_SLOT.findall(err)
     assert len(lines) == 1, err
     k, m, slot_max, cap, expanded, errors, spilled, overfull = (int(x) for x in lines[0])
-    return dict(k=k, m=m, slot_max=slot_max, cap=cap, expanded=expanded, errors=errors, spilled=spilled, overfull=overfull)
+    w, positions, records, nb1, S, nslots, coarse_max, cap1 = (int(x) for x in SKM_PLAN.findall(err)[0])
+    return dict(k=k, m=m, slot_max=slot_max, cap=cap, expanded=expanded, errors=errors, spilled=spilled, overfull=overfull,
+                w=w, positions=positions, records=records, nb1=nb1, S=S, nslots=nslots, coarse_max=coarse_max, cap1=cap1)
 
 
 def exp1_run_stats(eng, seqs, group_of, k, cs, hist_len, kernels, counters):
@@ -499,6 +504,38 @@ def exp1_run_stats(eng, seqs, group_of, k, cs, hist_len, kernels, counters):
 def exp1_same(got, want):
     for f in ("within_hist", "across_hist", "distinct_per_seq"):
         assert got[f].shape == want[f].shape and (got[f] == want[f]).all(), f
+
+
+# what tests/test_gpu_skm_union_chain.py, tests/test_gpu_skm_union_claims.py and their followers share
+UNION_KERNELS = ("skm_union", "skm_big", "union_tagged")
+UNION_COUNTERS = ("retries", "big_slots")
+SKM_NSLOTS = re.compile(r"\[skm\] k=\d+ .* nslots=(\d+) \|")
+
+
+def run_checked(eng, capfd, seqs, group_of, k, cs=5000, hist_len=5001):
+    """One call against the oracle, a second that must give the same; -> (the [skm] line's nslots, what ran)."""
+    from oracle import c_oracle as CO
+    want = CO.exp1(seqs, group_of, k, cs=cs, hist_len=hist_len)
+    capfd.readouterr()
+    got, did = exp1_run_stats(eng, seqs, group_of, k, cs, hist_len, UNION_KERNELS, UNION_COUNTERS)
+    err = capfd.readouterr().err
+    exp1_same(got, want)
+    again, did2 = exp1_run_stats(eng, seqs, group_of, k, cs, hist_len, UNION_KERNELS, UNION_COUNTERS)
+    capfd.readouterr()
+    exp1_same(again, got)
+    assert did2 == did
+    found = SKM_NSLOTS.findall(err)
+    assert len(found) == 1, err
+    return int(found[0]), did, err
+
+
+def fitted(seqs, k, n):
+    """(the texts, the last one cut by fewer than n bases; KHOICE_SKM_MEAN) for which nslots = ceil(positions / mean)
+    is exactly n."""
+    positions = sum(len(s) - k + 1 for s in seqs)
+    mean = positions // n
+    assert mean >= 64 and positions - n * mean < len(seqs[-1]) - k
+    return seqs[:-1] + [seqs[-1][:len(seqs[-1]) - (positions - n * mean)]], mean
 
 
 def exp1_check(eng, capfd, seqs, group_of, k, expect, kernels, counters):
